@@ -21,12 +21,24 @@ if the node has fewer than N devices); under torch.distributed.run it uses the r
 independent: rank r runs its own block of trajectories, weak scaling, no data-path collective; RCCL is used only for the
 timing reduction and the end-of-run ATE all-reduce.
 
-Prints ONE JSON line on rank 0.  `value` is the first timed K-step window (the driver's contract); `repeats` holds the
-further windows (median / min / max).  `roofline` is for the dominant kernel (the longest single kernel of a step by HIP
-events on the library's stream).  `cpu_baseline` (rank 0, N = 1): the REFERENCE'S OWN SOURCE (oracle/_ref/lib_ref.so =
-/root/reference/include/msckf_mono/msckf.h compiled against oracle/ref_shim; `kind: "reference"`) timed on this box's
-host cores on a bounded sample of the same workload, the restatement's LEAN mode beside it; `ate_vs_ref_m` = RMS position
-difference between the HIP path and the CPU oracle on sampled trajectories at the end of the timed window.
+Prints ONE JSON line on rank 0.  `value` is the timed K-step window (the driver's contract), `ms_per_step` its milliseconds
+per step.  A plain run does only that: set-up, W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR) and the
+line.  The scenario holds at most SCENARIO_STEPS_MAX distinct steps: a longer timed run is cut into windows of that size,
+and before each further window every filter is initialised again and brought back to the first timed frame (untimed), so
+that every timed step is a real filter update on consistent inputs.
+
+`--full` adds everything else, as its own runs after the timed window: `repeats` (further windows: median / min / max),
+resident-input windows, `roofline` for the dominant kernel (the longest single kernel of a step by HIP events on the
+library's stream, from a profiled pass), the early-accept pass, the end-of-run ATE, the other BASELINE configurations
+(`other_configs`, default run only) and `cpu_baseline` (rank 0, N = 1): the REFERENCE'S OWN SOURCE (oracle/_ref/lib_ref.so =
+the reference's msckf.h compiled against oracle/ref_shim; `kind: "reference"`) timed on the host cores on a bounded sample
+of the same workload, the restatement's LEAN mode beside it; `ate_vs_ref_m` = RMS position difference between the HIP path
+and the CPU oracle on sampled trajectories at the end of the timed window.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step, as a caller of that path receives it, to
+DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the trajectories where all of them would exceed
+DUMP_BYTES_MAX): the IMU states, camera poses, covariances and gate statistics of the batch.  The inputs depend on the
+arguments only (seeded scenarios), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -44,6 +56,8 @@ K_IMU = 10
 PEAK_F32_TFLOPS = 157.3   # MI355X dense f32 (vector = f32-input MFMA) peak, MI355X_MICROARCH.md
 PEAK_F64_TFLOPS = 78.6
 PEAK_HBM_GBS = 8000.0
+SCENARIO_STEPS_MAX = 500      # distinct timed frames held in the scenario; longer timed runs are windows of this size
+DUMP_BYTES_MAX = 60 << 20     # --dump-outputs: at most this many bytes in all (the covariances dominate)
 CONFIGS = {
     # cfg2 has its own driver (run_cfg2): one double-precision filter through the per-call API
     "cfg2": dict(cid=2, N=10, F=50, B=1, iso=True, nseq=1, dtype="f64",
@@ -204,7 +218,8 @@ def device_clocks():
 
 
 def self_launch_if_needed(args):
-    """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: re-execute as N ranks, one per GPU, on this node."""
+    """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: run N ranks, one per GPU, on this node, as a child
+    torch.distributed.run process (this process may have opened the GPU to count the devices), and exit with its status."""
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is not None:
         if args.gpus > 1 and int(env_world) != args.gpus:
@@ -224,7 +239,9 @@ def self_launch_if_needed(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush(); sys.stderr.flush()
-    os.execvpe(sys.executable, cmd, dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")))
+    import subprocess
+    rc = subprocess.call(cmd, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")))
+    sys.exit(rc)
 
 
 def main():
@@ -254,7 +271,14 @@ def main():
                          "lockstep through msckf_hip_image_cycle_range (host bookkeeping per trajectory, batched device stages) instead of the resident scenario")
     ap.add_argument("--gate-early-accept", action="store_true",
                     help="exact early accept of the chi-square gate (msckf_hip_set_gate_early_accept); OFF for the headline number")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: repeat and resident-input windows, the profiled pass (roofline), the early-accept pass, "
+                         "ATE, CPU baselines, parity against the CPU oracle and the other BASELINE configurations (default run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     self_launch_if_needed(args)
     if args.config == "cfg2":
         return run_cfg2(args)
@@ -275,6 +299,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     K, W = args.steps, args.warmup
+    KW = min(K, SCENARIO_STEPS_MAX)  # distinct timed frames; the K timed steps are windows of at most KW of them
     fill = N_WIN                     # frames needed to reach the steady-state window
     est_ms = 0.7 * B_TRAJ / 64.0 * (N_WIN / 30.0) ** 2 * (F_TRK / 200.0)    # rough step time, only used to size the number of repeat windows
     R = args.repeats if args.repeats > 0 else int(min(48, max(3, np.ceil(250.0 / (K * est_ms)))))
@@ -282,7 +307,10 @@ def main():
     R2 = min(R, 3) if streamed else 0                       # resident-input windows beside the streamed ones
     extra = R2 + 1 + (0 if (args.gate_early_accept or args.no_early_accept_pass) else 1)
     W2 = max(W, 3)                           # untimed frames after the state reads that follow the first window (see below)
-    n_frames = fill + W + W2 + K * (R + 1 + extra)   # [fill | warmup | window 0 | one window straight after the state reads | re-warm | R - 1 timed windows | R2 resident windows | profiled | early-accept window]
+    if args.full:
+        n_frames = fill + W + W2 + KW * (R + 1 + extra)   # [fill | warmup | window 0 | one window straight after the state reads | re-warm | R - 1 timed windows | R2 resident windows | profiled | early-accept window]
+    else:
+        n_frames = fill + W + KW                          # [fill | warmup | timed window]
     rendezvous_only = bool(os.environ.get("BENCH_RENDEZVOUS_ONLY"))   # test hook, see below
     t_gen = time.time()
     trajs = [] if rendezvous_only else make_trajectories(c, rank, n_frames)
@@ -297,7 +325,7 @@ def main():
     backend = os.environ.get("BENCH_DIST_BACKEND", "nccl")
     if os.environ.get("BENCH_DEVICE_OVERRIDE") is not None:
         local_rank = int(os.environ["BENCH_DEVICE_OVERRIDE"])
-    if torch.cuda.is_available():
+    if torch.cuda.is_available() and not (rendezvous_only and backend == "gloo"):   # (the hook's ranks need no device: one box may have fewer)
         torch.cuda.set_device(local_rank)
     red_dev = "cuda" if backend == "nccl" else "cpu"
     dist = None
@@ -364,12 +392,60 @@ def main():
     f = fill + W
     run_timed_path = bt.run_frames_streamed if streamed else bt.run_frames
     if streamed:                     # page-lock the frames that will be streamed (set-up, like every other allocation)
-        bt.scenario_pin(0, f + K * (R + 1) + W2)
-    run_timed_path(0, fill)          # window fill (untimed), on the path that is timed: the staging ring wraps several times
-    run_timed_path(fill, f)          # W warm-up steps (untimed)
+        bt.scenario_pin(0, (f + KW * (R + 1) + W2) if args.full else (f + KW))
+
+    def bring_to(frame):
+        """every filter from its initial state through frames [0, frame) on the timed path (untimed): window fill, warm-up, and
+        the frames of a timed window that is to be run again"""
+        for b, tr in enumerate(trajs):
+            bt.initialize(b, tr.cfg, tr.imu0)
+        run_timed_path(0, fill)      # window fill (untimed), on the path that is timed: the staging ring wraps several times
+        run_timed_path(fill, frame)  # W warm-up steps (untimed)
+        bt.sync()
+    run_timed_path(0, fill)
+    run_timed_path(fill, f)
     bt.sync()
     bt.imu_state(0); bt.last_stats(0, strict=False)   # first device-to-host reads of the process (the runtime sets its read path up lazily): not inside a timed window
-    elapsed = timed(f, f + K, streamed=streamed)   # ---- THE timed region: exactly K steps -> `value`
+    # ---- THE timed region: exactly K steps -> `value`; beyond SCENARIO_STEPS_MAX, windows of KW steps over the same frames,
+    # each from the same filter states (bring_to between them, untimed)
+    elapsed, done = 0.0, 0
+    while done < K:
+        n = min(KW, K - done)
+        if done:
+            bring_to(f)
+        elapsed += timed(f, f + n, streamed=streamed)
+        done += n
+    dumped = batch_outputs(bt, B_TRAJ) if (args.dump_outputs and rank == 0) else None
+    if not args.full:
+        if rank == 0:
+            value = world * B_TRAJ * K / elapsed
+            out = {
+                "metric": "filter updates/sec (%d-cam window, %d feats)" % (N_WIN, F_TRK), "value": value, "unit": "updates/s",
+                "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f32" if c["dtype"] == "f32" else "f32 (measurement Jacobian stored as f16)", "data": "synthetic",
+                "config": {"workload": c["workload"], "name": args.config,
+                           "cam_window": N_WIN, "tracks_per_update": F_TRK, "trajectories_per_gpu": B_TRAJ, "imu_per_update": K_IMU,
+                           "parallelism": "replicated trajectories, %d per rank" % B_TRAJ,
+                           "noise": "isotropic (f_u = f_v)" if c["iso"] else ("anisotropic (EuRoC f_u != f_v): " + ("the reference's literal R_n = Q_1^T R_o Q_1 on the device" if args.aniso_mode == 0 else "rows pre-whitened by 1/sigma (GLS)")),
+                           "sequences": c["nseq"], "gate_early_accept": bool(args.gate_early_accept), "streams": args.streams,
+                           "host_affinity": pin_cpus or None},
+                "inputs": ("uploaded per frame inside the timed region (SURVEY.md 8d): page-locked host memory -> staging ring on a copy stream, "
+                           "compact work-lists, %d sets" % args.ring) if streamed else "resident in HBM before the timed region (--no-upload-pass)",
+                "timed_windows": {"steps_each": KW, "windows": -(-K // KW),
+                                  "note": "windows after the first restart every filter from its initial state through the same frames (untimed)"},
+                "scenario_gen_s": t_gen, "scenario_upload_s": t_up,
+                "note": "plain run: the timed steps only; --full adds repeats, roofline, ATE, CPU baselines and the other configurations",
+            }
+            if dumped is not None:
+                out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    if K > KW and K % KW:
+        bring_to(f + KW)             # the measurements below continue from the end of a whole window
+    K = KW                           # the further windows of --full are KW steps each
     f_end_timed = f + K
     sample = sorted(set(int(x) for x in np.linspace(0, B_TRAJ - 1, 8)))
     p_dev_sample = {b: bt.imu_state(b)[13:16].copy() for b in sample}   # positions at the end of the timed window
@@ -383,7 +459,7 @@ def main():
     # that the two conventions stay comparable: repeats.first_after_reads)
     el_after_reads = timed(f, f + K, streamed=streamed); f += K
     run_timed_path(f, f + W2); bt.sync(); f += W2
-    rep = [elapsed]
+    rep = []
     for _ in range(R - 1):           # further windows of the same size: spread of the measurement
         rep.append(timed(f, f + K, streamed=streamed)); f += K
     res_rep = []
@@ -474,9 +550,9 @@ def main():
 
     if rank == 0:
         updates = world * B_TRAJ * K
-        value = updates / elapsed
-        ms_per_step = 1e3 * elapsed / K
-        rep_vals = [updates / e for e in rep]
+        value = world * B_TRAJ * args.steps / elapsed
+        ms_per_step = 1e3 * elapsed / args.steps
+        rep_vals = [value] + [updates / e for e in rep]
         res_vals = [updates / e for e in res_rep]
         # a stage timer is an event pair around the stage's launches: the pair's own reading (marker packets) is measured
         # separately and taken off, so that a single-kernel stage reads what rocprofv3's kernel trace reads for that kernel
@@ -528,7 +604,7 @@ def main():
         whole_frac = f_update * value / 1e12 / world / PEAK_F32_TFLOPS
         out = {
             "metric": "filter updates/sec (%d-cam window, %d feats)" % (N_WIN, F_TRK), "value": value, "unit": "updates/s",
-            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "n_gpus": world, "steps": args.steps, "warmup": W, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32" if c["dtype"] == "f32" else "f32 (measurement Jacobian stored as f16)", "data": "synthetic",
             "config": {"workload": c["workload"], "name": args.config,
                        "cam_window": N_WIN, "tracks_per_update": F_TRK, "trajectories_per_gpu": B_TRAJ, "imu_per_update": K_IMU,
@@ -545,7 +621,7 @@ def main():
             # value_suspect = window 0 fell below 0.93 x the median of the run's windows (a slow window, DESIGN.md 9, reached `value`)
             "repeats_median": float(np.median(rep_vals)), "repeats_min_over_median": float(np.min(rep_vals) / np.median(rep_vals)),
             "value_over_repeats_median": float(rep_vals[0] / np.median(rep_vals)), "value_suspect": bool(rep_vals[0] < 0.93 * np.median(rep_vals)),
-            "repeats": {"windows": len(rep_vals), "steps_each": K, "values": rep_vals, "median": float(np.median(rep_vals)),
+            "repeats": {"windows": len(rep_vals), "steps_each": K, "steps_first": args.steps, "values": rep_vals, "median": float(np.median(rep_vals)),
                         "min": float(np.min(rep_vals)), "max": float(np.max(rep_vals)),
                         "first_after_reads": updates / el_after_reads,
                         "note": "value = windows[0] (the contract's K timed steps); the others are the same measurement on later frames, after the "
@@ -599,6 +675,8 @@ def main():
             out["cpu_baseline_note"] = ("not run at this size: one update of the reference's algorithm on a 60-camera / 500-track window builds a "
                                         "~28 000 x 28 000 Q (minutes and > 3 GB per filter); parity at this geometry is held by the -m gpu tests")
         # BASELINE.json's other configurations, shortened, in the same line (the default run only: cfg3, one GPU)
+        if dumped is not None:
+            out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
         if args.config == "cfg3" and world == 1 and streamed and not args.no_other_configs and args.trajectories <= 0:
             bt.close()
             out["other_configs"] = run_other_configs()
@@ -627,7 +705,7 @@ def run_other_configs():
     for name, extra in specs:
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-other-configs"] + extra, capture_output=True, text=True, timeout=300)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-other-configs"] + extra, capture_output=True, text=True, timeout=300)
             j = json.loads(r.stdout.strip().splitlines()[-1])
             rf = j.get("roofline") or {}
             if name == "cfg2":
@@ -708,6 +786,22 @@ def run_cycle(args):
         win.append(time.perf_counter() - t1)
     bt.sync(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t_all
+    dumped = batch_outputs(bt, B) if args.dump_outputs else None
+    if not args.full:
+        out = {
+            "metric": "filter updates/sec (%d-cam window, %d feats)" % (N, F), "value": B * K / elapsed, "unit": "updates/s", "n_gpus": 1, "steps": K, "warmup": W,
+            "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": c["workload"] + "; the ASL runner's per-image cycle WITH pruneRedundantStates for the batch in lockstep",
+                       "name": args.config, "cam_window": N, "tracks_per_update": F, "trajectories_per_gpu": B, "prune_redundant": True,
+                       "noise": "anisotropic (EuRoC f_u != f_v), literal route" if args.aniso_mode == 0 else "anisotropic, rows pre-whitened"},
+            "scenario_gen_s": t_gen,
+            "note": "plain run: the timed images only; --full adds the stage timers and the per-filter parity run",
+        }
+        if dumped is not None:
+            out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
+        bt.close()
+        print(json.dumps(out))
+        return
     # the same K images once more with the library's stage timers (HIP events around the device stages): what the device part costs
     bt.profile_enable(True)
     ncam = [bt.num_cam_states(b) for b in allb]
@@ -742,6 +836,8 @@ def run_cycle(args):
         "parity": {"per_filter_calls_bit_identical": same, "trajectories": [0, B - 1]},
         "roofline": None, "cpu_baseline": None, "scenario_gen_s": t_gen,
     }
+    if dumped is not None:
+        out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
     print(json.dumps(out))
 
 
@@ -788,7 +884,8 @@ def run_cfg2(args):
             lines.append(str(len(ids)) + " " + " ".join("%r %r %d" % (float(z[0]), float(z[1]), i) for z, i in zip(obs, ids)))
     text = "\n".join(lines) + "\n"
     runs = []
-    for _ in range(max(1, args.repeats if args.repeats > 0 else 5)):       # every run replays the whole sequence: fill + warm-up untimed, K frames timed
+    n_runs = max(1, args.repeats if args.repeats > 0 else 5) if args.full else 1
+    for _ in range(n_runs):          # every run replays the whole sequence: fill + warm-up untimed, K frames timed
         r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
         if r.returncode:
             raise SystemExit("cfg2 driver failed (%d): %s" % (r.returncode, r.stderr[-2000:]))
@@ -797,6 +894,22 @@ def run_cfg2(args):
     frame_us = np.array(first["frame_us"])
     value = len(frame_us) / (frame_us.sum() * 1e-6)
     rep_vals = [len(x["frame_us"]) / (sum(x["frame_us"]) * 1e-6) for x in runs]
+    dumped = {"imu_state": np.array(first["imu"]), "trace_P": np.array([first["trace_P"]]), "num_cam_states": np.array([float(first["n_cam"])])}
+    if not args.full:
+        out = {
+            "metric": "filter updates/sec (%d-cam window, %d feats)" % (N, F), "value": value, "unit": "updates/s", "n_gpus": 1, "steps": K, "warmup": W,
+            "ms_per_step": 1e3 / value, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": c["workload"], "name": "cfg2", "cam_window": N, "tracks_per_update": F, "trajectories_per_gpu": 1, "imu_per_update": K_IMU,
+                       "parallelism": "one trajectory, one stream: every call of the reference's API is a call into libmsckf_hip.so",
+                       "noise": "isotropic (f_u = f_v)"},
+            "latency_us": {"per_update_mean": float(frame_us.mean()), "per_update_median": float(np.median(frame_us)), "per_update_max": float(frame_us.max()),
+                           "stage_mean": first["stage_us"]},
+            "note": "plain run: one run of the timed frames; --full adds repeats, stage timers, the CPU baseline and parity",
+        }
+        if args.dump_outputs:
+            out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
+        print(json.dumps(out))
+        return
 
     # ---- the same frames through the C-ABI with the library's HIP-event stage timers (which kernel dominates, executed FLOP)
     f = capi.MSCKF(capi.F64, n_cap=N + 3, f_cap=max(F, 64), m_cap=N + 3)
@@ -888,7 +1001,45 @@ def run_cfg2(args):
         "parity": {"shim_run_vs_oracle_state_rel": err_state, "capi_run_vs_oracle": err_capi,
                    "trace_P_rel": abs(first["trace_P"] - trP) / trP, "bar": 1e-6},
     }
+    if args.dump_outputs:
+        out["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
     print(json.dumps(out))
+
+
+def batch_outputs(bt, B, budget=DUMP_BYTES_MAX):
+    """What a caller of the batched path reads back after the last step, per trajectory: IMU state (29), camera poses
+    (n_cap x 7, zero past the window), window size, covariance (D x D, zero-padded to the largest window) and the gate
+    statistics of the last update.  When all B covariances exceed `budget`, a fixed seeded sample of the trajectories."""
+    ncam = np.array([bt.num_cam_states(b) for b in range(B)])
+    D = 15 + 6 * int(ncam.max())
+    per = 4 * D * D + 8 * (29 + 7 * bt.n_cap + 9)
+    if B * per <= budget:
+        idx = np.arange(B)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(B, max(1, budget // per), replace=False))
+    cov = np.zeros((len(idx), D, D), np.float32)
+    cams = np.zeros((len(idx), bt.n_cap, 7))
+    for i, b in enumerate(idx):
+        P = bt.covariance(int(b))
+        cov[i, :P.shape[0], :P.shape[1]] = P
+        poses = bt.cam_states(int(b))[0]
+        cams[i, :len(poses)] = poses
+    stats = np.array([[bt.last_stats(int(b), strict=False)[k] for k in ("n_tracks", "n_motion_rejected", "n_tri_rejected", "n_gate_rejected", "n_passed", "m_rows", "r_rows")]
+                      for b in idx], dtype=np.float64)
+    return {"trajectory_index": idx.astype(np.float64), "imu_state": np.stack([bt.imu_state(int(b)) for b in idx]),
+            "cam_poses": cams, "num_cam_states": ncam[idx].astype(np.float64), "covariance": cov, "gate_stats": stats}
+
+
+def write_outputs(dirpath, arrays):
+    """DIR/<name>.npy for every array (float32 stays float32, everything else float64) -> {name: shape}"""
+    os.makedirs(dirpath, exist_ok=True)
+    shapes = {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        arr = arr if arr.dtype == np.float32 else np.asarray(arr, dtype=np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
 
 
 def pmc_block(kernel):

@@ -3,7 +3,7 @@
 cd /root/repo
 O=gpurun_out/${TAG:-ab}; mkdir -p $O
 P=msckf_mono_amd/lib_ab/libmsckf_hip_prev.so
-BA="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-early-accept-pass --repeats 6 ${AB_ARGS:-}"
+BA="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-early-accept-pass --repeats 6 --full ${AB_ARGS:-}"
 for i in 1 2; do
   for v in prev cur; do
     if [ $v = prev ]; then export MSCKF_HIP_LIB=$P; else unset MSCKF_HIP_LIB; fi

@@ -1,6 +1,6 @@
 # WRITE_SIZE / FETCH_SIZE of the per-track kernel (separate passes), previous library (msckf_mono_amd/lib_ab/libmsckf_hip_prev.so) and current one
 cd /tmp && export TMPDIR=/tmp
-CM="--steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1"
+CM="--steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1 --full"
 for v in prev cur; do
   if [ $v = prev ]; then export MSCKF_HIP_LIB=/root/repo/msckf_mono_amd/lib_ab/libmsckf_hip_prev.so; else unset MSCKF_HIP_LIB; fi
   for c in WRITE_SIZE FETCH_SIZE; do

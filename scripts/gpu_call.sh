@@ -43,7 +43,7 @@ if has lit_timers; then
 fi
 if has pause; then python scripts/pause_probe.py 2>&1 | tail -6 | tee $O/pause_probe.txt; fi
 if has ab_env; then   # A/B inside one lease: AB_ENV="VAR=val" (the alternative) against the default, alternating, twice each
-  BA="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-early-accept-pass --repeats 6 ${AB_ARGS:-}"
+  BA="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-early-accept-pass --repeats 6 --full ${AB_ARGS:-}"
   for i in 1 2; do
     env $AB_ENV python bench.py $BA > $O/bench_alt$i.json 2> $O/bench_alt$i.err; summ bench_alt$i
     python bench.py $BA > $O/bench_def$i.json 2> $O/bench_def$i.err; summ bench_def$i
@@ -51,7 +51,7 @@ if has ab_env; then   # A/B inside one lease: AB_ENV="VAR=val" (the alternative)
 fi
 if has feat_pmc; then   # instruction / issue counters of the per-track kernel only (two PMC passes), default library and with AB_ENV set
   cd /tmp && export TMPDIR=/tmp
-  CM="--steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1"
+  CM="--steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1 --full"
   for v in def alt; do
     E=""; if [ $v = alt ]; then E="$AB_ENV"; fi
     env $E rocprofv3 --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVES --kernel-trace -d /tmp/f1$v -o r -- python /root/repo/bench.py $CM > /tmp/f1$v.log 2>&1
@@ -61,13 +61,13 @@ if has feat_pmc; then   # instruction / issue counters of the per-track kernel o
   done
   cd /root/repo
 fi
-if has bench; then python bench.py > $O/bench.json 2> $O/bench.err; summ bench; fi
-if has cfg4; then python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs > $O/bench_cfg4.json 2> $O/bench_cfg4.err; summ bench_cfg4; fi
+if has bench; then python bench.py --full > $O/bench.json 2> $O/bench.err; summ bench; fi
+if has cfg4; then python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err; summ bench_cfg4; fi
 if has cfgs; then
-  python bench.py --config cfg2 --steps 20 --warmup 5 --no-other-configs > $O/bench_cfg2.json 2>/dev/null
-  python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs > $O/bench_cfg4.json 2>/dev/null
-  python bench.py --config cfg4 --steps 20 --warmup 5 --no-cpu-baseline --no-early-accept-pass --no-other-configs --aniso-mode 1 > $O/bench_cfg4_whitened.json 2>/dev/null
-  python bench.py --config cfg5 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs > $O/bench_cfg5.json 2>/dev/null
+  python bench.py --config cfg2 --steps 20 --warmup 5 --no-other-configs --full > $O/bench_cfg2.json 2>/dev/null
+  python bench.py --config cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs --full > $O/bench_cfg4.json 2>/dev/null
+  python bench.py --config cfg4 --steps 20 --warmup 5 --no-cpu-baseline --no-early-accept-pass --no-other-configs --full --aniso-mode 1 > $O/bench_cfg4_whitened.json 2>/dev/null
+  python bench.py --config cfg5 --steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-other-configs --full > $O/bench_cfg5.json 2>/dev/null
   summ bench_cfg2 bench_cfg4 bench_cfg4_whitened bench_cfg5
 fi
 if has sweep; then python scripts/sweep_variants.py --steps 20 --windows 5 "streams=4,streamed=0" "streams=4,streamed=1" "streams=1,streamed=0" > $O/sweep.txt 2>&1; cut -c1-250 $O/sweep.txt; fi
@@ -83,7 +83,7 @@ fi
 if has lit_profile || has cfg2_profile; then
   cd /tmp && export TMPDIR=/tmp
   if has lit_profile; then
-    C4="--config cfg4 --steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1"
+    C4="--config cfg4 --steps 6 --warmup 2 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --no-other-configs --repeats 1 --streams 1 --full"
     rocprofv3 --kernel-trace --stats -d /tmp/q1 -o r -- python /root/repo/bench.py $C4 > /tmp/c1.log 2>&1
     python /root/repo/scripts/rocpd_summary.py $(find /tmp/q1 -name "*.db" | head -1) /root/repo/$O/kernel_stats_cfg4_literal.md > /dev/null
     ROCPD_TAIL=6 python /root/repo/scripts/rocpd_summary.py $(find /tmp/q1 -name "*.db" | head -1) /root/repo/$O/kernel_stats_cfg4_literal_tail6.md > /dev/null

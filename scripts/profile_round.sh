@@ -8,7 +8,7 @@ mkdir -p $OUT
 export PMC_TAG=$TAG PMC_COMMIT=${PMC_COMMIT:-unknown}
 export PMC_CSRC_HASH=$(python -c 'import bench; print(bench.csrc_hash())')
 cd /tmp && export TMPDIR=/tmp
-COMMON="--steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --repeats 1 --streams 1"
+COMMON="--steps 10 --warmup 3 --no-cpu-baseline --no-early-accept-pass --no-upload-pass --repeats 1 --streams 1 --full"
 rocprofv3 --kernel-trace --stats -d /tmp/p1 -o r -- python /root/repo/bench.py $COMMON > /tmp/b1.log 2>&1
 DB=$(find /tmp/p1 -name "*.db" | head -1); tail -1 /tmp/b1.log > $OUT/bench_profiled.json
 ROCPD_TAIL=20 python /root/repo/scripts/rocpd_summary.py $DB $OUT/kernel_stats_tail20.md > /dev/null

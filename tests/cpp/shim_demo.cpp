@@ -2,7 +2,7 @@
 // sequence of datasets/asl_msckf.cpp:227-294 on a small scene; prints the state so the pytest wrapper can compare it
 // with the oracle fed the same numbers (read from stdin).  Two builds: WITHOUT Eigen (pod_types.h stand-ins, compiled by
 // the test itself) and the branch a maintainer builds -- <Eigen/Dense> + the reference's own <msckf_mono/types.h>, against
-// oracle/ref_shim's Eigen surface (tests/cpp/Makefile, built where /root/reference exists, the binary travels).  A copy of
+// oracle/ref_shim's Eigen surface (oracle/Makefile: oracle/_ref/shim_demo_eigen, built where the reference tree exists).  A copy of
 // the filter taken mid-run (MSCKF is copyable, msckf.h:31-67) finishes the run as well and must print the same state.
 //   input : cam12 noise29 params8 imu29, then frames: "F K" K*7 readings, n_cur (x y id)*, n_new (x y id)*
 #include <cstdio>

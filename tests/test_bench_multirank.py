@@ -16,7 +16,7 @@ def test_two_ranks_on_one_gpu():
     gloo; the driver's node gives every rank its own GPU and RCCL)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_DIST_BACKEND="gloo", BENCH_DEVICE_OVERRIDE="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -46,7 +46,7 @@ def test_cfg4_monte_carlo_mode_reports_per_sequence_ate():
     """bench.py --config cfg4: 5 synthetic sequences x noise seeds, EuRoC intrinsics (anisotropic noise), per-sequence ATE
     through shard.ate_local / ate_allreduce, the CPU oracle's ATE beside the HIP path's on sampled trajectories."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg4", "--steps", "4", "--warmup", "1", "--repeats", "1",
-           "--no-early-accept-pass", "--no-upload-pass", "--cpu-seconds", "5"]
+           "--no-early-accept-pass", "--no-upload-pass", "--cpu-seconds", "5", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -64,7 +64,7 @@ def test_cfg2_single_trajectory_latency_config_runs():
     """bench.py --config cfg2 (BASELINE.json configs[1]: 10-camera window, 50 tracks, double, ONE trajectory): a C++ caller over
     the drop-in shim, one propagate() + getImuState() per IMU sample, the reference's stage names; the reference's own source
     in double on one core beside it; the state at the end of the run against the oracle at 1e-6."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "10", "--warmup", "3", "--repeats", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg2", "--steps", "10", "--warmup", "3", "--repeats", "2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -85,7 +85,7 @@ def test_eight_rank_rehearsal_on_one_device():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BENCH_DIST_BACKEND="gloo", BENCH_DEVICE_OVERRIDE="0", BENCH_SAME_SEEDS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--trajectories", "8", "--steps", "3", "--warmup", "1", "--repeats", "2",
-           "--no-cpu-baseline", "--no-early-accept-pass"]
+           "--no-cpu-baseline", "--no-early-accept-pass", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -94,3 +94,44 @@ def test_eight_rank_rehearsal_on_one_device():
     assert d["n_gpus"] == 8 and d["ranks_seen"] == list(range(8)) and d["ranks_bit_identical_for_equal_seeds"] is True
     assert abs(d["value"] - 8 * 8 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
     assert d["config"]["host_affinity"] is None or len(d["config"]["host_affinity"]) == 5
+
+
+def _plain(args, tmp, name):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp / name)],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), tmp / name
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full): the result line's headline fields, K timed steps behind
+    ms_per_step, nothing of what --full adds, and --dump-outputs: what the timed path computed, float32 / float64, under
+    64 MB, identical from run to run.  A run longer than the scenario's SCENARIO_STEPS_MAX distinct steps times its steps
+    in windows, each from the same filter states: the last step's outputs are those of a run of one window."""
+    import numpy as np
+    import bench
+    d, a = _plain(["--gpus", "1", "--steps", "5", "--warmup", "2"], tmp_path, "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["unit"] == "updates/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 64 * 5 / (d["ms_per_step"] * 5e-3)) / d["value"] < 1e-6
+    assert not set(d) & {"roofline", "repeats", "cpu_baseline", "other_configs", "ate_m", "resident_inputs"}
+    files = sorted(p.name for p in a.iterdir())
+    assert files == sorted(n + ".npy" for n in d["dumped_outputs"]) and "covariance.npy" in files and "imu_state.npy" in files
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 64 << 20
+    arrs = {p.stem: np.load(p) for p in a.iterdir()}
+    assert all(x.dtype in (np.float32, np.float64) for x in arrs.values())
+    assert arrs["imu_state"].shape == (64, 29) and np.all(np.isfinite(arrs["covariance"])) and np.all(arrs["gate_stats"][:, 4] > 0)
+    _, b = _plain(["--gpus", "1", "--steps", "5", "--warmup", "2"], tmp_path, "b")
+    for n, x in arrs.items():
+        assert np.array_equal(x, np.load(b / (n + ".npy"))), n
+    # windows: 2 x SCENARIO_STEPS_MAX steps = two windows over the same frames, against one window (8 trajectories)
+    m = bench.SCENARIO_STEPS_MAX
+    d1, one = _plain(["--steps", str(m), "--warmup", "1", "--trajectories", "8"], tmp_path, "one")
+    d2, two = _plain(["--steps", str(2 * m), "--warmup", "1", "--trajectories", "8"], tmp_path, "two")
+    assert d1["timed_windows"]["windows"] == 1 and d2["timed_windows"]["windows"] == 2 and d2["steps"] == 2 * m
+    for n in d1["dumped_outputs"]:
+        assert np.array_equal(np.load(one / (n + ".npy")), np.load(two / (n + ".npy"))), n

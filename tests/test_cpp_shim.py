@@ -21,15 +21,16 @@ def test_shim_compiles_without_eigen(tmp_path):
 
 
 def test_shim_eigen_branch_compiles_against_the_reference_types():
-    """The branch a maintainer would build (with <Eigen/Dense> and the reference's own types.h): compile-only, against
-    the minimal Eigen surface of oracle/ref_shim (Eigen itself is not installed here)."""
-    ref_inc = "/root/reference/include"
-    if not os.path.exists(os.path.join(ref_inc, "msckf_mono", "types.h")):
-        pytest.skip("reference tree not present on this machine")
-    src = os.path.join(ROOT, "tests", "cpp", "shim_eigen_check.cpp")
-    out = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                          "-I" + os.path.join(ROOT, "oracle", "ref_shim"), "-I" + ref_inc, src], capture_output=True, text=True)
+    """The branch a maintainer would build (with <Eigen/Dense> and the reference's own types.h), against the minimal Eigen
+    surface of oracle/ref_shim (Eigen itself is not installed here): oracle/Makefile compiles tests/cpp/shim_eigen_check.cpp
+    into oracle/_ref/shim_eigen_check.o at build time (where the reference tree is; the object travels like lib_ref.so).
+    Held: the object is there (make rebuilds it when the shim or the check source changes) and holds the instantiating
+    function."""
+    obj = os.path.join(ROOT, "oracle", "_ref", "shim_eigen_check.o")
+    assert os.path.exists(obj), "oracle/_ref/shim_eigen_check.o missing: __graft_entry__.build() compiles it"
+    out = subprocess.run(["nm", "-C", obj], capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
+    assert "use_all_members()" in out.stdout
 
 
 def _run_shim_demo(exe, po, N=6, F=8, nf=12, traj=21, isotropic=True):
@@ -98,11 +99,11 @@ def test_shim_runs_like_the_asl_runner(tmp_path, oracle_lib):
 @pytest.mark.gpu
 def test_shim_eigen_branch_runs(oracle_lib):
     """The branch a maintainer builds -- <Eigen/Dense> and the reference's own <msckf_mono/types.h> (here over
-    oracle/ref_shim's Eigen surface: Eigen is not installed) -- as an executable: built by tests/cpp/Makefile where
-    /root/reference exists (__graft_entry__.build()), it travels to the GPU box like oracle/_ref/; same run, same
-    assertions as the Eigen-free build."""
-    exe = os.path.join(ROOT, "tests", "cpp", "_built", "shim_demo_eigen")
+    oracle/ref_shim's Eigen surface: Eigen is not installed) -- as an executable: built by oracle/Makefile into
+    oracle/_ref/shim_demo_eigen where the reference tree exists (__graft_entry__.build()), it travels with oracle/_ref/;
+    same run, same assertions as the Eigen-free build."""
+    exe = os.path.join(ROOT, "oracle", "_ref", "shim_demo_eigen")
     if not os.path.exists(exe):
-        pytest.skip("tests/cpp/_built/shim_demo_eigen not built (needs /root/reference at build time)")
+        pytest.skip("oracle/_ref/shim_demo_eigen not built (needs the reference tree at build time)")
     _run_shim_demo(exe, oracle_lib)
     _run_shim_demo(exe, oracle_lib, N=8, F=16, nf=14, traj=22, isotropic=False)
