@@ -18,6 +18,9 @@
  *   cam12    c_u c_v f_u f_v b | q_CI(w,x,y,z) | p_C_I(3)                               types.h:48-55
  *   noise29  u_var_prime v_var_prime | diag(Q_imu)(12) | diag(initial_imu_covar)(15)   types.h:86-92
  *            (every caller of the reference passes diagonal matrices: asl_msckf.cpp:86-108)
+ *   uv2      u_var_prime v_var_prime                                                   types.h:87-88
+ *   Q144     Q_imu, 12 x 12 column-major; noise order n_g n_wg n_a n_wa (calcG)         types.h:90
+ *   P0_225   initial_imu_covar, 15 x 15 column-major; error-state order th b_g v b_a p  types.h:91
  *   params8  max_gn_cost_norm min_rcond translation_threshold redundancy_angle_thresh
  *            redundancy_distance_thresh min_track_length max_track_length max_cam_states types.h:94-99
  *   imu29    q_IG(4) b_g(3) v_I_G(3) b_a(3) p_I_G(3) g(3) q_IG_null(4) v_I_G_null(3) p_I_G_null(3)
@@ -71,6 +74,14 @@ const char* msckf_hip_last_error(void);
 /* MSCKF::initialize(camera, noise_params, msckf_params, imu_state)                   msckf.h:72-97  */
 int msckf_hip_initialize(msckf_hip_handle h, int b, const double* cam12, const double* noise29,
                          const double* params8, const double* imu29);
+/* The same with the whole Q_imu and initial_imu_covar (msckf.h:86, :134) instead of their diagonals.  Q_imu is kept as its
+ * symmetric part (Q + Q^T) / 2 -- exact: msckf.h:143 symmetrises Phi (P_II + G Q G^T dT) Phi^T, so only the symmetric part
+ * of G Q G^T reaches the covariance.  initial_imu_covar becomes P_II as given and must be symmetric to 1e-12 of its largest
+ * entry.  Non-finite entries or an asymmetric initial_imu_covar: -EINVAL (reason in msckf_hip_last_error()).  With every
+ * off-diagonal entry of both matrices zero this is msckf_hip_initialize on the diagonals, bit for bit; a later
+ * msckf_hip_initialize of the same b drops the full Q_imu again.  No positive-definiteness check (the reference has none). */
+int msckf_hip_initialize_full(msckf_hip_handle h, int b, const double* cam12, const double* uv2, const double* Q144,
+                              const double* P0_225, const double* params8, const double* imu29);
 /* MSCKF::propagate(imuReading&), K consecutive readings fused into one launch        msckf.h:101-145 */
 int msckf_hip_propagate(msckf_hip_handle h, int b, const double* readings7, int K);
 /* MSCKF::augmentState(state_id, time)                                                msckf.h:148-212 */

@@ -12,7 +12,9 @@
 //   * one filter = one batch handle with B = 1; capacities come from MSCKFParams (override with
 //     MSCKF_SHIM_N_CAP / MSCKF_SHIM_F_CAP / MSCKF_SHIM_M_CAP at compile time; the track capacity per update also at run
 //     time, before the filter is initialized: environment MSCKF_SHIM_F_CAP or MSCKF<S>::setTrackCapacity(n));
-//   * Q_imu / initial_imu_covar are read through their diagonals (every caller passes .asDiagonal());
+//   * Q_imu / initial_imu_covar are taken whole (msckf_hip_initialize_full); Q_imu is kept as its symmetric part, which is
+//     all that reaches the covariance (msckf.h:143), and initial_imu_covar must be symmetric -- an asymmetric one is refused
+//     (lastError() == -EINVAL).  Without Eigen (pod_types.h) through the *_diag arrays or the whole-matrix members;
 //   * u_var_prime != v_var_prime (EuRoC intrinsics): the reference's R_o_j = A_j^T R_j A_j / R_n = Q_1^T R_o Q_1 construction
 //     runs on the device, see include/msckf_hip.h (msckf_hip_set_anisotropic_noise);
 //   * capacities: a window or a track list beyond the handle's capacity does not abort the caller (the reference has no
@@ -100,21 +102,34 @@ class MSCKF {
     double cam[12] = {(double)camera.c_u, (double)camera.c_v, (double)camera.f_u, (double)camera.f_v, (double)camera.b,
                       (double)camera.q_CI.w(), (double)camera.q_CI.x(), (double)camera.q_CI.y(), (double)camera.q_CI.z(),
                       (double)camera.p_C_I(0), (double)camera.p_C_I(1), (double)camera.p_C_I(2)};
-    double noise[29];
+    double noise[29], Q[144], P0[225];   // Q_imu / initial_imu_covar column-major
     noise[0] = (double)noise_params.u_var_prime; noise[1] = (double)noise_params.v_var_prime;
 #ifdef MSCKF_SHIM_EIGEN
-    for (int i = 0; i < 12; ++i) noise[2 + i] = (double)noise_params.Q_imu(i, i);
-    for (int i = 0; i < 15; ++i) noise[14 + i] = (double)noise_params.initial_imu_covar(i, i);
+    for (int j = 0; j < 12; ++j) for (int i = 0; i < 12; ++i) Q[i + 12 * j] = (double)noise_params.Q_imu(i, j);
+    for (int j = 0; j < 15; ++j) for (int i = 0; i < 15; ++i) P0[i + 15 * j] = (double)noise_params.initial_imu_covar(i, j);
+    const bool full = true;    // with no off-diagonal entry the same as msckf_hip_initialize, bit for bit
 #else
-    for (int i = 0; i < 12; ++i) noise[2 + i] = (double)noise_params.Q_imu_diag[i];
-    for (int i = 0; i < 15; ++i) noise[14 + i] = (double)noise_params.initial_imu_covar_diag[i];
+    const bool qm = any_nonzero(&noise_params.Q_imu[0][0], 144), pm = any_nonzero(&noise_params.initial_imu_covar[0][0], 225);
+    bool full = false;
+    for (int j = 0; j < 12; ++j)
+      for (int i = 0; i < 12; ++i) {
+        Q[i + 12 * j] = qm ? (double)noise_params.Q_imu[i][j] : (i == j ? (double)noise_params.Q_imu_diag[i] : 0.0);
+        full = full || (i != j && Q[i + 12 * j] != 0);
+      }
+    for (int j = 0; j < 15; ++j)
+      for (int i = 0; i < 15; ++i) {
+        P0[i + 15 * j] = pm ? (double)noise_params.initial_imu_covar[i][j] : (i == j ? (double)noise_params.initial_imu_covar_diag[i] : 0.0);
+        full = full || (i != j && P0[i + 15 * j] != 0);
+      }
 #endif
+    for (int i = 0; i < 12; ++i) noise[2 + i] = Q[i + 12 * i];
+    for (int i = 0; i < 15; ++i) noise[14 + i] = P0[i + 15 * i];
     double prm[8] = {(double)msckf_params.max_gn_cost_norm, (double)msckf_params.min_rcond, (double)msckf_params.translation_threshold,
                      (double)msckf_params.redundancy_angle_thresh, (double)msckf_params.redundancy_distance_thresh,
                      (double)msckf_params.min_track_length, (double)msckf_params.max_track_length, (double)msckf_params.max_cam_states};
     double imu[29];
     pack_imu(imu_state, imu);
-    rc_ = msckf_hip_initialize(h_, 0, cam, noise, prm, imu);
+    rc_ = full ? msckf_hip_initialize_full(h_, 0, cam, noise, Q, P0, prm, imu) : msckf_hip_initialize(h_, 0, cam, noise, prm, imu);
     report("initialize");
   }
   // msckf.h:101
@@ -245,6 +260,7 @@ class MSCKF {
     for (size_t i = 0; i < m.size(); ++i) { buf_[2 * i] = (double)m[i](0); buf_[2 * i + 1] = (double)m[i](1); }
     for (size_t i = 0; i < ids.size(); ++i) ids_[i] = (uint64_t)ids[i];
   }
+  static bool any_nonzero(const _S* a, int n) { for (int i = 0; i < n; ++i) if (a[i] != 0) return true; return false; }
   template <class V> static void set3(V& v, const double* p) { v(0) = (_S)p[0]; v(1) = (_S)p[1]; v(2) = (_S)p[2]; }
   template <class Q> static void setq(Q& q, const double* p) { q.w() = (_S)p[0]; q.x() = (_S)p[1]; q.y() = (_S)p[2]; q.z() = (_S)p[3]; }
   static void pack_imu(const imuState<_S>& s, double* x) {

@@ -52,10 +52,15 @@ template <typename S> struct imuState {
   Point<S> p_I_G, p_I_G_null; Vector3<S> v_I_G, b_g, b_a, g, v_I_G_null; Quaternion<S> q_IG, q_IG_null;
 };
 template <typename S> struct imuReading { GyroscopeReading<S> omega; AccelerometerReading<S> a; S dT = 0; };
+// Q_imu / initial_imu_covar (types.h:90-91): either through their diagonals (*_diag; every caller of the reference passes
+// diagonal matrices, asl_msckf.cpp:86-108) or whole, row i column j at [i][j].  A whole member with any non-zero entry is
+// used in place of its *_diag array; a non-zero off-diagonal entry in either takes msckf_hip_initialize_full.
 template <typename S> struct noiseParams {
   S u_var_prime = 0, v_var_prime = 0;
-  S Q_imu_diag[12] = {};            // the reference's 12x12 Q_imu is diagonal in every caller (asl_msckf.cpp:86-90)
+  S Q_imu_diag[12] = {};
   S initial_imu_covar_diag[15] = {};
+  S Q_imu[12][12] = {};
+  S initial_imu_covar[15][15] = {};
 };
 template <typename S> struct MSCKFParams {
   S max_gn_cost_norm = 0, min_rcond = 0, translation_threshold = 0;

@@ -21,7 +21,7 @@ _up = C.POINTER(C.c_uint64)
 
 # every symbol include/msckf_hip.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [
-    "msckf_hip_create", "msckf_hip_destroy", "msckf_hip_last_error", "msckf_hip_initialize", "msckf_hip_propagate",
+    "msckf_hip_create", "msckf_hip_destroy", "msckf_hip_last_error", "msckf_hip_initialize", "msckf_hip_initialize_full", "msckf_hip_propagate",
     "msckf_hip_augment_state", "msckf_hip_update", "msckf_hip_add_features", "msckf_hip_marginalize",
     "msckf_hip_prune_empty_states", "msckf_hip_prune_redundant_states", "msckf_hip_finish",
     "msckf_hip_get_num_cam_states", "msckf_hip_get_imu_state", "msckf_hip_get_cam_states", "msckf_hip_get_map",
@@ -86,6 +86,18 @@ def pack_config(cfg):
     return cam, noise, params
 
 
+def full_noise(cfg):
+    """(Q_imu 12 x 12, initial_imu_covar 15 x 15) of a config that carries "Q_imu" and/or "P0" (a missing one is the diagonal
+    matrix of "Q_imu_diag" / "P0_diag"), or None for a config with neither: msckf_hip_initialize_full's matrices."""
+    if "Q_imu" not in cfg and "P0" not in cfg:
+        return None
+    Q = np.asarray(cfg["Q_imu"], dtype=np.float64) if "Q_imu" in cfg else np.diag(np.asarray(cfg["Q_imu_diag"], dtype=np.float64))
+    P0 = np.asarray(cfg["P0"], dtype=np.float64) if "P0" in cfg else np.diag(np.asarray(cfg["P0_diag"], dtype=np.float64))
+    if Q.shape != (12, 12) or P0.shape != (15, 15):
+        raise ValueError("Q_imu must be 12 x 12 and P0 15 x 15")
+    return Q, P0
+
+
 class Batch:
     """A batch of B independent filters resident on one GPU."""
 
@@ -108,9 +120,17 @@ class Batch:
 
     # ---- reference API, per trajectory
     def initialize(self, b, cfg, imu29):
+        """MSCKF::initialize; a config with "Q_imu" (12 x 12) and/or "P0" (15 x 15) goes through msckf_hip_initialize_full"""
         cam, noise, params = pack_config(cfg)
-        a, pa = _d(cam); n, pn = _d(noise); p, pp = _d(params); s, ps = _d(imu29)
-        _chk(self.L.msckf_hip_initialize(self.h, b, pa, pn, pp, ps))
+        a, pa = _d(cam); p, pp = _d(params); s, ps = _d(imu29)
+        fn = full_noise(cfg)
+        if fn is None:
+            n, pn = _d(noise)
+            _chk(self.L.msckf_hip_initialize(self.h, b, pa, pn, pp, ps))
+            return
+        uv, puv = _d(noise[:2])
+        Q, pq = _d(np.asfortranarray(fn[0]).ravel(order="F")); P0, pp0 = _d(np.asfortranarray(fn[1]).ravel(order="F"))
+        _chk(self.L.msckf_hip_initialize_full(self.h, b, pa, puv, pq, pp0, pp, ps))
 
     def propagate(self, b, readings):
         r, p = _d(np.asarray(readings).reshape(-1, 7))
@@ -354,6 +374,13 @@ class MSCKF:
 
     def __init__(self, dtype=F32, n_cap=32, f_cap=256, m_cap=32, device=0):
         self.batch = Batch(1, n_cap, f_cap, m_cap, dtype, device)
+        self._device = device
+
+    def copy(self):
+        """value semantics of the reference object (msckf.h:31-67): a new filter with this one's state (msckf_hip_copy_state)"""
+        c = MSCKF(self.batch.dtype, self.batch.n_cap, self.batch.f_cap, self.batch.m_cap, self._device)
+        c.batch.copy_state_from(self.batch)
+        return c
 
     def initialize(self, cfg, imu29):
         self.batch.initialize(0, cfg, imu29)

@@ -5,6 +5,7 @@
 //                                  (reference: types.h:69-76 imuState)
 //   cam  [B][n_cap][CAM_STRIDE]    q_CG(w,x,y,z) p_C_G                       (types.h:57-67 camState)
 //   prm  [B][PRM_STRIDE]           Camera / noiseParams / MSCKFParams scalars (types.h:48-99)
+//   qf   [B][QF_STRIDE]            full process noise: upper triangle of (Q_imu + Q_imu^T) / 2 row by row, flag
 //   P    [B][ld*ld]                full symmetric covariance, column-major, IMU block first, camera
 //                                  slot s at rows/cols 15+6s..  (reference keeps three blocks,
 //                                  msckf.h:52-54, and re-assembles them on every use :166-174)
@@ -22,6 +23,12 @@ constexpr int CAM_STRIDE = 8;
 constexpr int PRM_STRIDE = 48;
 constexpr int DG_STRIDE = 28; // per-slot Gram block: 21 (upper 6x6) + 6 (h^T r) + pad
 constexpr int RD_STRIDE = 7;  // imuReading: omega(3) a(3) dT   (types.h:78-84)
+// full Q_imu of a trajectory (msckf_hip_initialize_full): the 78 entries (i, j), i <= j, of its symmetric part at
+// qf_index(i, j), then QF_FLAG = 1 when an off-diagonal entry is non-zero (k_propagate's full-Q instantiation runs it), else 0
+// (the 12 diagonal entries at PRM_Q are used, as for msckf_hip_initialize)
+constexpr int QF_STRIDE = 80;
+constexpr int QF_FLAG = 78;
+__host__ __device__ constexpr int qf_index(int i, int j) { return i * (23 - i) / 2 + j; }   // i <= j < 12
 
 enum {  // offsets into imu[]
   IQ = 0, IBG = 4, IV = 7, IBA = 10, IP = 13, IG = 16, IQN = 19, IVN = 23, IPN = 26
@@ -133,6 +140,7 @@ struct Dev {
   // prune
   int* keep; int* nkeep;
   LitBufs lit;
+  S* qf;   // [B][QF_STRIDE] full process noise and its flag (last: the offsets of every other member stay as they were)
 };
 
 // first observation of track t of the launch's i-th trajectory in trk_slots / trk_obs
@@ -396,7 +404,9 @@ __device__ __forceinline__ double lam_hat(const double* Lam, const double* /*Dg*
 }
 
 // ---------------------------------------------------------------- launch entry points (one per .hip file)
-template <class S> void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment = false);
+// qroute: 0 no trajectory of [b0, b0 + nb) carries a full Q_imu (the diagonal kernel alone, over the range), 1 some do (both
+// instantiations over the range, each skips the other's trajectories), 2 all do (the full-Q instantiation alone)
+template <class S> void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute);
 template <class S> void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st);
 template <class S> void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop = nullptr, int drop_const = -1);
 template <class S> void launch_feature(const Dev<S>& d, int b0, int nb, hipStream_t st);

@@ -7,7 +7,8 @@
 //
 // Design (not a translation): K queued IMU samples are fused into one launch; the 15x15 blocks live in
 // LDS, Phi_total = Phi_K...Phi_1 is accumulated so the only O(N) part, P_IC <- Phi P_IC, touches HBM once
-// per image instead of once per IMU sample; G Q G^T is applied in its closed block-diagonal form;
+// per image instead of once per IMU sample; G Q G^T is applied in its closed block-diagonal form (a full Q_imu: in closed
+// 3x3 blocks, by an instantiation of its own);
 // augmentation uses the 6 non-zero 3x3 blocks of J instead of two dense (D+6) x D GEMMs and never
 // computes the unused determinant of msckf.h:176.
 #include "dev_common.h"
@@ -89,6 +90,12 @@ __device__ __forceinline__ void imu_rk(const S* st, V3<S> g, V3<S> om, V3<S> ac,
 //   C  the sequential chains P_II <- sym(Phi (P_II + G Q G^T dT) Phi^T) (:134,143) and Phi_total = Phi_K ... Phi_1 advance
 //      together, one 15 x 15 element per thread
 //   D  P_IC <- Phi_total P_IC for all camera columns, both halves of the symmetric storage    (:144)
+// QM selects the process-noise term: 0 a diagonal Q_imu (PRM_Q) for every trajectory of the launch; 1 the same, but the
+// trajectories with a full Q_imu (qf flag set) are left to a QM = 2 launch over the same range, which runs only those.  A
+// trajectory's bits therefore do not depend on which others share its launch (one workgroup per trajectory; QM 0 and 1 run
+// the same arithmetic).  QM = 2: G Q G^T with the whole symmetric Q (calcG :892-903, G_th = -I, G_bg = G_ba = I,
+// G_v = -C^T): block (a, b) = G_a Q_ab G_b^T, i.e. (v, v) = C^T Q_vv C, (v, b) = -C^T Q_vb and (a, v) = -Q_av C for a, b != v
+// (signs: G_th = -I), the rest +-Q_ab; waves 1-3 write it as a 12 x 12 table per sample in place of the compact one.
 #ifdef MSCKF_ABLATE
 // phase timers of the -DMSCKF_ABLATE build (scripts/chol_phases.py): shader-clock cycles of workgroup 0, thread 0:
 // 0 load, 1 state chain, 2 Phi series, 3 P_II / Phi_total chains, 4 write back + P_IC, 5 launches
@@ -166,23 +173,28 @@ template <> struct Mfs<float> {    // v_mfma_f32_16x16x4_f32: C/D row = 4 g + r
   static __device__ __forceinline__ int crow(int g, int r) { return 4 * g + r; }
 };
 
-template <class S, bool AUGMENT>
+template <class S, bool AUGMENT, int QM>
 __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  constexpr bool FULLQ = QM == 2;
+  if (QM != 0 && (d.qf[(long)b * QF_STRIDE + QF_FLAG] != S(0)) != FULLQ) return;   // the other instantiation's trajectory
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
 #ifdef MSCKF_ABLATE
   long long pcyc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ptl = clock64();
 #endif
   __shared__ S sState[(PG + 1) * SST];
   __shared__ S sPhi[PG * 225];
-  __shared__ S sQt[PG * 32];        // G Q G^T dT of the group's samples, compact: [0,15) diagonal, [15,24) the C^T Qa C block, 31 = 0
+  // G Q G^T dT of the group's samples.  Diagonal Q, compact: [0,15) diagonal, [15,24) the C^T Qa C block, 31 = 0.  Full Q:
+  // rows / columns 0..11 row-major (the position rows 12..14 of G are zero), 144 = 0
+  constexpr int QT = FULLQ ? 145 : 32;
+  __shared__ S sQt[PG * QT];
   __shared__ S sTot[225];
   __shared__ S sPii[225];
   __shared__ S sNull[12];          // q_null v_null p_null used by the next sample
   __shared__ S sG[4];
   __shared__ S sRd[PG * RD_STRIDE];  // the group's IMU samples, staged once (the state chain is one thread: a global
                                       // read per sample would put a memory round trip on every step of the chain)
-  __shared__ S sQ[12];
+  __shared__ S sQ[FULLQ ? 144 : 12];   // diagonal of Q_imu, or the whole symmetric Q_imu (row-major)
   __shared__ S sRk[PG * 16];         // RK maps M_s of the group's samples (column-major 4 x 4)
   __shared__ S sDv[PG * 3];          // velocity increments of the group's samples
   S* imu = d.imu + (long)b * IMU_STRIDE;
@@ -210,7 +222,11 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
   }
   if (tid < 16) sState[tid] = imu[tid];                 // q b_g v b_a p
   if (tid < 3) sG[tid] = imu[IG + tid];
-  if (tid >= 64 && tid < 64 + 12) sQ[tid - 64] = prm[PRM_Q + tid - 64];
+  if (!FULLQ) { if (tid >= 64 && tid < 64 + 12) sQ[tid - 64] = prm[PRM_Q + tid - 64]; }
+  else if (tid >= 64 && tid < 64 + 144) {
+    const int i = (tid - 64) / 12, j = (tid - 64) % 12;
+    sQ[tid - 64] = d.qf[(long)b * QF_STRIDE + (i <= j ? qf_index(i, j) : qf_index(j, i))];
+  }
   if (tid >= 32 && tid < 32 + 10) sNull[tid - 32] = imu[IQN + (tid - 32)];
   for (int e = tid; e < 225; e += 256) {
     const int i = e / 15, j = e % 15;
@@ -375,7 +391,38 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
           Phi[(12 + i) * 15 + j] = A2.m[i][j] - e2v[i] * s3[j];
         }
       }
-    } else if (tid >= 64) {
+    } else if (FULLQ && tid >= 64) {
+      // waves 1-3 meanwhile: G Q G^T dT of every sample of the group for a full Q (calcG :892-903), rows / columns 0..11.
+      // Entry (i, j) is computed as (min, max): the table is symmetric to the bit.
+      for (int e = tid - 64; e < G * QT; e += 192) {
+        const int s = e / QT, q = e % QT;
+        S val = 0;
+        if (q < 144) {
+          const int i = min(q / 12, q % 12), j = max(q / 12, q % 12), a = i / 3, bb = j / 3, ii = i % 3, jj = j % 3;
+          const S dT = sRd[s * RD_STRIDE + 6];
+          if (a != 2 && bb != 2) {
+            val = ((a == 0) != (bb == 0) ? -sQ[i * 12 + j] : sQ[i * 12 + j]) * dT;           // G_th = -I, G_bg = G_ba = I
+          } else {
+            const M3<S> C = q2rot(ldq(sState + s * SST));
+            S sm = 0;
+            if (a == 2 && bb == 2) {                                                        // C^T Q_vv C
+              for (int k = 0; k < 3; ++k) {
+                S t = 0;
+                for (int l = 0; l < 3; ++l) t += sQ[(6 + k) * 12 + 6 + l] * C.m[l][jj];
+                sm += C.m[k][ii] * t;
+              }
+            } else if (a == 2) {                                                            // (v, ba) = -C^T Q_v,ba
+              for (int k = 0; k < 3; ++k) sm -= C.m[k][ii] * sQ[(6 + k) * 12 + j];
+            } else {                                                                        // (th, v) = Q_th,v C, (bg, v) = -Q_bg,v C
+              for (int l = 0; l < 3; ++l) sm += sQ[i * 12 + 6 + l] * C.m[l][jj];
+              if (a == 1) sm = -sm;
+            }
+            val = sm * dT;
+          }
+        }
+        sQt[e] = val;
+      }
+    } else if (!FULLQ && tid >= 64) {
       // waves 1-3 meanwhile: G Q G^T dT = diag(Qw, Qbg, C^T Qa C, Qba, 0) dT of every sample of the group   (calcG :899-902, Q diagonal)
       for (int e = tid - 64; e < G * 32; e += 192) {
         const int s = e >> 5, q = e & 31;
@@ -403,17 +450,18 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
     // (Phi Y)^T = Y^T Phi^T = mma(A = Y regs, B = aPhi) -- the transpose comes out of the matrix core with the same products
     // summed in the same order, so the symmetrisation of :143 is a register add and both halves get the same bits.  No
     // barrier and no LDS traffic inside the chain besides the four reads of Phi and the process-noise term (table sQt,
-    // filled by waves 1-3 during phase B).
+    // filled by waves 1-3 during phase B; QT entries per sample).
     {
       typedef Mfs<S> MF;
       const int g = lane >> 4, c = lane & 15;
       if (w < 2) {
         const S* qt = sQt;
-        int qidx[4];   // where this lane's four elements find their process-noise term in a sample's compact table
+        int qidx[4];   // where this lane's four elements find their process-noise term in a sample's table
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int i = MF::crow(g, r), bi = i / 3;
-          qidx[r] = (bi != c / 3 || bi >= 4) ? 31 : (bi == 2 ? 15 + (i - 6) * 3 + (c - 6) : (i == c ? i : 31));
+          if (FULLQ) qidx[r] = (i < 12 && c < 12) ? i * 12 + c : 144;
+          else qidx[r] = (bi != c / 3 || bi >= 4) ? 31 : (bi == 2 ? 15 + (i - 6) * 3 + (c - 6) : (i == c ? i : 31));
         }
         if (w == 0) {
 #pragma unroll
@@ -431,7 +479,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
             for (int kk = 0; kk < 4; ++kk) Y = MF::mma(Mreg[kk], aPhi[kk], Y);
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) { Pn = MF::mma(aPhi[kk], Y[kk], Pn); Pt = MF::mma(Y[kk], aPhi[kk], Pt); }
-            qt += 32;
+            qt += QT;
 #pragma unroll
             for (int r = 0; r < 4; ++r) Mreg[r] = (Pn[r] + Pt[r]) / S(2) + (s + 1 < G ? qt[qidx[r]] : S(0));
           } else {
@@ -550,12 +598,18 @@ __global__ __launch_bounds__(1024) void k_prune_inplace(Dev<S> d, int b0, const 
   if (tid == 0) d.ncam[b] = nk;
 }
 
+template <class S, int QM>
+static void launch_propagate_q(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment) {
+  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true, QM>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K);
+  else hipLaunchKernelGGL((k_propagate<S, false, QM>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K);
+}
 template <class S>
-void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment) {
+void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute) {
   if (nb <= 0) return;
   if (K <= 0) { if (then_augment) launch_augment<S>(d, b0, nb, st); return; }
-  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K);
-  else hipLaunchKernelGGL((k_propagate<S, false>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K);
+  if (qroute == 0) { launch_propagate_q<S, 0>(d, b0, nb, readings, rd_stride, K, st, then_augment); return; }
+  if (qroute == 1) launch_propagate_q<S, 1>(d, b0, nb, readings, rd_stride, K, st, then_augment);   // disjoint trajectories: same stream, either order
+  launch_propagate_q<S, 2>(d, b0, nb, readings, rd_stride, K, st, then_augment);
 }
 template <class S>
 void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st) {
@@ -574,8 +628,8 @@ void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* dr
   else hipLaunchKernelGGL((k_prune_inplace<S, 2, 12>), grid, dim3(1024), 0, st, d, b0, drop, drop_const, use_keep);
 }
 
-template void launch_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, bool);
-template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool);
+template void launch_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, bool, int);
+template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool, int);
 template void launch_augment<float>(const Dev<float>&, int, int, hipStream_t);
 template void launch_augment<double>(const Dev<double>&, int, int, hipStream_t);
 template void launch_prune<float>(const Dev<float>&, int, int, hipStream_t, const int*, int);

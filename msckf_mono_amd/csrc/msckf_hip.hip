@@ -93,6 +93,7 @@ struct BatchBase {
   bool h16 = false;   // dtype MSCKF_HIP_F16H_F32P: fp16 measurement Jacobian, f32 state and covariance
   std::vector<HostTraj> traj;
   virtual int init(int b, const double* cam, const double* noise, const double* params, const double* imu) = 0;
+  virtual int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) = 0;
   virtual int propagate(int b0, int nb, const double* rd, int K, bool mirror = false) = 0;
   virtual int augment(int b0, int nb) = 0;
   virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
@@ -251,6 +252,13 @@ struct Batch : BatchBase {
   // (marginalize, the batched calls) invalidates it; the next getter reads the device and re-validates.
   std::vector<S> h_imu; std::vector<char> h_imu_ok;
   std::vector<char> h_lit;   // [B] trajectory runs the literal route
+  std::vector<char> h_qfull; // [B] trajectory carries a full Q_imu (its qf flag): k_propagate's full-Q instantiation runs it
+  // launch_propagate's qroute for [b0, b0 + nb): 0 no trajectory with a full Q_imu, 1 some, 2 all
+  int qroute(int b0, int nb) const {
+    int n = 0;
+    for (int b = b0; b < b0 + nb; ++b) n += h_qfull[b] ? 1 : 0;
+    return n == 0 ? 0 : (n == nb ? 2 : 1);
+  }
   int n_lit = 0;
   // single-call staging on device
   S* d_rd = nullptr; int rd_cap = 0;               // [B][rd_cap][7]
@@ -322,7 +330,7 @@ struct Batch : BatchBase {
       HIPCHK(hipStreamCreateWithFlags(&sty[i], hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&ev_fa[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_fb[i], hipEventDisableTiming));
     }
-    h_ncam.assign(B, 0); h_uv.assign((size_t)2 * B, 0.0); h_lit.assign(B, 0); h_imu.assign((size_t)B * IMU_STRIDE, S(0)); h_imu_ok.assign(B, 0);
+    h_ncam.assign(B, 0); h_uv.assign((size_t)2 * B, 0.0); h_lit.assign(B, 0); h_qfull.assign(B, 0); h_imu.assign((size_t)B * IMU_STRIDE, S(0)); h_imu_ok.assign(B, 0);
     d.B = B; d.n_cap = n_cap; d.f_cap = f_cap; d.m_cap = m_cap;
     d.n6cap = 6 * n_cap;
     d.ld = ((15 + 6 * n_cap + 15) / 16) * 16;
@@ -337,6 +345,7 @@ struct Batch : BatchBase {
     const size_t TF = Bz * f_cap;
     int rc = 0;
     rc |= dalloc(&d.imu, Bz * IMU_STRIDE); rc |= dalloc(&d.cam, Bz * n_cap * CAM_STRIDE); rc |= dalloc(&d.prm, Bz * PRM_STRIDE);
+    rc |= dalloc(&d.qf, Bz * QF_STRIDE);
     rc |= dalloc(&d.P, Bz * pl); rc |= dalloc(&P_spare, Bz * pl); d.Pout = nullptr; d.fuse_drop = nullptr; d.ncam_defer = 0;
     if (const char* e = getenv("MSCKF_HIP_FUSE_PRUNE")) fuse_prune = atoi(e) != 0;
     if (const char* e = getenv("MSCKF_HIP_TEST_FAIL_UPLOAD")) test_fail_upload = atoi(e);   // test hook: the upload of this frame fails
@@ -551,11 +560,43 @@ struct Batch : BatchBase {
     return 0;
   }
   int init(int b, const double* cam, const double* noise, const double* params, const double* imu) override {
+    return init_core(b, cam, noise, nullptr, nullptr, params, imu);
+  }
+  // MSCKF::initialize with the whole noiseParams::Q_imu (12 x 12) and initial_imu_covar (15 x 15), column-major (types.h:90-91).
+  // Q_imu enters the filter only through G Q_imu G^T in Phi (P_II + G Q_imu G^T dT) Phi^T, which msckf.h:143 symmetrises:
+  // with X = G Q_imu G^T, (Phi (P + X dT) Phi^T + its transpose) / 2 = Phi (P + (X + X^T) / 2 dT) Phi^T for symmetric P_II, and
+  // (X + X^T) / 2 = G ((Q_imu + Q_imu^T) / 2) G^T -- only the symmetric part of Q_imu ever reaches P, so that is what is stored.
+  // initial_imu_covar is P_II as it is (msckf.h:86): it must be symmetric.  No off-diagonal entry anywhere: exactly init().
+  int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) override {
+    POISON_GUARD();
+    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
+    double pmax = 0;
+    for (int i = 0; i < 144; ++i) if (!std::isfinite(Q144[i])) return fail(-EINVAL, "Q_imu has a non-finite entry");
+    for (int i = 0; i < 225; ++i) { if (!std::isfinite(P0_225[i])) return fail(-EINVAL, "initial_imu_covar has a non-finite entry"); pmax = std::max(pmax, std::fabs(P0_225[i])); }
+    for (int j = 0; j < 15; ++j)
+      for (int i = 0; i < j; ++i)
+        if (std::fabs(P0_225[i + 15 * j] - P0_225[j + 15 * i]) > 1e-12 * pmax) return fail(-EINVAL, "initial_imu_covar is not symmetric (to 1e-12 of its largest entry)");
+    double noise[29], qs[QF_STRIDE] = {0};
+    noise[0] = uv2[0]; noise[1] = uv2[1];
+    for (int i = 0; i < 12; ++i) noise[2 + i] = Q144[i + 12 * i];
+    for (int i = 0; i < 15; ++i) noise[14 + i] = P0_225[i + 15 * i];
+    bool full = false;
+    for (int i = 0; i < 12; ++i)
+      for (int j = i; j < 12; ++j) {
+        qs[qf_index(i, j)] = i == j ? Q144[i + 12 * i] : (Q144[i + 12 * j] + Q144[j + 12 * i]) / 2;
+        if (i != j && (S)qs[qf_index(i, j)] != S(0)) full = true;
+      }
+    return init_core(b, cam, noise, full ? qs : nullptr, P0_225, params, imu);
+  }
+  // q78: upper triangle of the symmetric Q_imu (qf_index), null = diagonal Q_imu (noise[2..13]); P0: the whole
+  // initial_imu_covar (column-major), null = its diagonal noise[14..28]
+  int init_core(int b, const double* cam, const double* noise, const double* q78, const double* P0, const double* params, const double* imu) {
     POISON_GUARD();
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     if (!(noise[0] > 0) || !(noise[1] > 0)) return fail(-EINVAL, "u_var_prime / v_var_prime must be positive");
     DEVICE_ENTER();
-    S prm[PRM_STRIDE] = {0}, st_imu[IMU_STRIDE] = {0};
+    S prm[PRM_STRIDE] = {0}, st_imu[IMU_STRIDE] = {0}, qf[QF_STRIDE] = {0};
+    if (q78) { for (int i = 0; i < QF_FLAG; ++i) qf[i] = (S)q78[i]; qf[QF_FLAG] = 1; }
     for (int i = 0; i < 12; ++i) prm[i] = (S)cam[i];
     prm[PRM_UVAR] = (S)noise[0]; prm[PRM_VVAR] = (S)noise[1];
     for (int i = 0; i < 12; ++i) prm[PRM_Q + i] = (S)noise[2 + i];
@@ -566,9 +607,12 @@ struct Batch : BatchBase {
     for (int i = 0; i < 4; ++i) st_imu[IQN + i] = st_imu[IQ + i];        // msckf.h:83-85
     for (int i = 0; i < 3; ++i) { st_imu[IVN + i] = st_imu[IV + i]; st_imu[IPN + i] = st_imu[IP + i]; }
     std::vector<S> P((size_t)d.ld * d.ld, S(0));
-    for (int i = 0; i < 15; ++i) P[(size_t)i * d.ld + i] = (S)noise[14 + i];
+    if (P0) { for (int j = 0; j < 15; ++j) for (int i = 0; i < 15; ++i) P[(size_t)j * d.ld + i] = (S)P0[i + 15 * j]; }
+    else for (int i = 0; i < 15; ++i) P[(size_t)i * d.ld + i] = (S)noise[14 + i];
     std::copy(st_imu, st_imu + IMU_STRIDE, h_imu.begin() + (size_t)b * IMU_STRIDE); h_imu_ok[b] = 1;
     HIPCHK(hipMemcpyAsync(d.prm + (size_t)b * PRM_STRIDE, prm, sizeof(prm), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d.qf + (size_t)b * QF_STRIDE, qf, sizeof(qf), hipMemcpyHostToDevice, st));   // (a diagonal Q_imu clears the flag)
+    h_qfull[b] = q78 ? 1 : 0;
     HIPCHK(hipMemcpyAsync(d.imu + (size_t)b * IMU_STRIDE, st_imu, sizeof(st_imu), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d.P + (size_t)b * d.ld * d.ld, P.data(), P.size() * sizeof(S), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d.ncam + b, 0, sizeof(int), st));
@@ -668,7 +712,7 @@ struct Batch : BatchBase {
       HIPCHK(hipMemcpyAsync(d_rd, tmp, cnt * sizeof(S), hipMemcpyHostToDevice, st));
       rc = stage_release();
       if (rc) return rc;
-      launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, then_augment && k0 + kk >= K);
+      launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, then_augment && k0 + kk >= K, qroute(b0, nb));
       HIPCHK(hipGetLastError());
     }
     return 0;
@@ -1120,9 +1164,10 @@ struct Batch : BatchBase {
     auto cp = [&](void* dst, const void* sp, size_t bytes) { return hipMemcpyAsync(dst, sp, bytes, hipMemcpyDeviceToDevice, st); };
     HIPCHK(cp(d.imu, o->d.imu, Bz * IMU_STRIDE * sizeof(S))); HIPCHK(cp(d.cam, o->d.cam, Bz * n_cap * CAM_STRIDE * sizeof(S)));
     HIPCHK(cp(d.prm, o->d.prm, Bz * PRM_STRIDE * sizeof(S))); HIPCHK(cp(d.P, o->d.P, Bz * pl * sizeof(S)));
+    HIPCHK(cp(d.qf, o->d.qf, Bz * QF_STRIDE * sizeof(S)));
     HIPCHK(cp(d.ncam, o->d.ncam, Bz * sizeof(int))); HIPCHK(cp(d.n_resid, o->d.n_resid, Bz * sizeof(long long)));
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
-    traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok;
+    traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
     compress_route = o->compress_route; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; nstreams = o->nstreams;
     overlap_feature = o->overlap_feature; d.gain_fused_s = o->d.gain_fused_s; fuse_prune = o->fuse_prune;
     HIPCHK(hipStreamSynchronize(st));
@@ -1518,7 +1563,7 @@ int Batch<S>::run_frames(int f0, int f1) {
       // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
       {
         StageRange r("imu_prop+msckf_augment_state");
-        stage_begin(0, q); launch_propagate<S>(v, b0, nb, sc_rd + (cell0 + b0) * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof); stage_end(0, q);
+        stage_begin(0, q); launch_propagate<S>(v, b0, nb, sc_rd + (cell0 + b0) * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
         if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
       }
       if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
@@ -1617,7 +1662,7 @@ int Batch<S>::run_frames_streamed(int f0, int f1) {
       v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
       v.P = curP; v.ncam_defer = pending ? 1 : 0;
       const bool fuse = fuse_prune && !prof && !overlap_feature && d.joseph == 0 && f + 1 < f1;   // as in run_frames
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof); stage_end(0, q);
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
       if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
       v.ncam_defer = 0;
       if (fuse) { v.Pout = spare; v.fuse_drop = (const int*)(reinterpret_cast<int*>(blk + pk_drop) + b0); }
@@ -2383,6 +2428,11 @@ int msckf_hip_destroy(msckf_hip_handle h) { delete H(h); return 0; }
 
 int msckf_hip_initialize(msckf_hip_handle h, int b, const double* cam12, const double* noise29, const double* params8, const double* imu29) {
   return H(h)->init(b, cam12, noise29, params8, imu29);
+}
+int msckf_hip_initialize_full(msckf_hip_handle h, int b, const double* cam12, const double* uv2, const double* Q144, const double* P0_225,
+                              const double* params8, const double* imu29) {
+  if (!h || !cam12 || !uv2 || !Q144 || !P0_225 || !params8 || !imu29) return fail(-EINVAL, "null argument");
+  return H(h)->init_full(b, cam12, uv2, Q144, P0_225, params8, imu29);
 }
 int msckf_hip_propagate(msckf_hip_handle h, int b, const double* readings7, int K) { StageRange r("imu_prop"); return H(h)->propagate(b, 1, readings7, K, true); }
 int msckf_hip_augment_state(msckf_hip_handle h, int b, int state_id, double time) {

@@ -99,14 +99,16 @@ def camera_extrinsics():
     return rot_to_quat(R), -R.T @ T_CAM_IMU[:3, 3]
 
 
-def filter_config(N, isotropic=True, feature_px=7.0, gn_px=7.0):
-    """Filter parameters: the effective EuRoC set of SURVEY.md section 5 with max_cam_states = N-1."""
+def filter_config(N, isotropic=True, feature_px=7.0, gn_px=7.0, Q_imu=None, P0=None):
+    """Filter parameters: the effective EuRoC set of SURVEY.md section 5 with max_cam_states = N-1.
+    Q_imu (12 x 12) / P0 (15 x 15): whole noiseParams::Q_imu / initial_imu_covar (types.h:90-91) in place of the diagonal
+    ones; "Q_imu_diag" / "P0_diag" then hold their diagonals."""
     f_u, f_v, c_u, c_v = EUROC_INTRINSICS
     if isotropic:
         f_v = f_u
     q_CI, p_C_I = camera_extrinsics()
     w_var, dbg_var, a_var, dba_var = 1e-4, 3.6733e-5, 1e-2, 7e-2
-    return dict(
+    cfg = dict(
         c_u=c_u, c_v=c_v, f_u=f_u, f_v=f_v, b=0.0, q_CI=q_CI, p_C_I=p_C_I,
         u_var_prime=(feature_px / f_u) ** 2, v_var_prime=(feature_px / f_v) ** 2,
         Q_imu_diag=[w_var] * 3 + [dbg_var] * 3 + [a_var] * 3 + [dba_var] * 3,
@@ -114,6 +116,13 @@ def filter_config(N, isotropic=True, feature_px=7.0, gn_px=7.0):
         max_gn_cost_norm=(gn_px / f_u) ** 2, min_rcond=3e-12, translation_threshold=0.1,
         redundancy_angle_thresh=0.005, redundancy_distance_thresh=0.05,
         min_track_length=3, max_track_length=1000, max_cam_states=N - 1)
+    if Q_imu is not None:
+        cfg["Q_imu"] = np.array(Q_imu, dtype=np.float64).reshape(12, 12)
+        cfg["Q_imu_diag"] = list(np.diag(cfg["Q_imu"]))
+    if P0 is not None:
+        cfg["P0"] = np.array(P0, dtype=np.float64).reshape(15, 15)
+        cfg["P0_diag"] = list(np.diag(cfg["P0"]))
+    return cfg
 
 
 # ------------------------------------------------------------------ analytic trajectory
@@ -193,8 +202,16 @@ class Trajectory:
         sa = imu_noise_scale * np.sqrt(q[6] / self.dT)
         C_IG = np.swapaxes(gt["R_GI"], -1, -2)
         a_body = np.einsum("nij,nj->ni", C_IG, gt["a"] - GRAVITY)
-        om = gt["omega"] + self.b_g + sg * rng.normal(3 * n_imu).reshape(n_imu, 3)
-        ac = a_body + self.b_a + sa * rng.normal(3 * n_imu).reshape(n_imu, 3)
+        if "Q_imu" in self.cfg:
+            # correlated gyro / accelerometer white noise: the [omega, a] block of Q_imu (noise order n_g n_wg n_a n_wa)
+            sel = [0, 1, 2, 6, 7, 8]
+            L = np.linalg.cholesky(np.asarray(self.cfg["Q_imu"], dtype=np.float64)[np.ix_(sel, sel)])
+            n6 = (imu_noise_scale / np.sqrt(self.dT)) * (rng.normal(6 * n_imu).reshape(n_imu, 6) @ L.T)
+            om = gt["omega"] + self.b_g + n6[:, :3]
+            ac = a_body + self.b_a + n6[:, 3:]
+        else:
+            om = gt["omega"] + self.b_g + sg * rng.normal(3 * n_imu).reshape(n_imu, 3)
+            ac = a_body + self.b_a + sa * rng.normal(3 * n_imu).reshape(n_imu, 3)
         self.readings = np.concatenate([om, ac, np.full((n_imu, 1), self.dT)], 1)   # [n_imu, 7]
         # frame k happens at time t0 + (k+1)*10*dT, i.e. after IMU samples [10k, 10k+10)
         self.frame_times = t0 + (np.arange(n_frames) + 1) * IMU_PER_FRAME * self.dT
