@@ -150,7 +150,8 @@ int msckf_hip_marginalize_range(msckf_hip_handle h, int b0, int nb);
 int msckf_hip_drop_oldest_range(msckf_hip_handle h, int b0, int nb, int n_drop);
 /* The ASL runner's per-image cycle (datasets/asl_msckf.cpp:269-294: augmentState, update, addFeatures, marginalize,
  * pruneRedundantStates :289, pruneEmptyStates) for trajectories b0 .. b0 + nb - 1 IN LOCKSTEP: the feature bookkeeping of every
- * trajectory (msckf.h:215-332, 453-534, 685-717, 1049-1098) runs on the host as in the per-filter entries, every device stage is one
+ * trajectory (msckf.h:215-332, 453-534, 685-717, 1049-1098) runs on the host through the same steps as the per-filter entries
+ * (msckf_mono_amd/csrc/host_lists.h states each rule once; the two callers differ only in their device calls), every device stage is one
  * launch sequence over the range and every read-back (poses for findRedundantCamStates, triangulated points, pruned states' poses)
  * one copy + one wait for the whole range.  Same results per trajectory as msckf_hip_augment_state / _update / _add_features /
  * _marginalize / _prune_redundant_states / _prune_empty_states called filter by filter, bit for bit.  IMU samples go in beforehand

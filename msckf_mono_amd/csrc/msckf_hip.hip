@@ -30,10 +30,13 @@
 #include <pthread.h>
 #include <sched.h>
 #include "dev_common.h"
+#include "host_lists.h"
 
 
 namespace {
 using namespace msckf;
+using namespace msckf_lists;
+static_assert(TRK_MOTION_OK == ST_MOTION_OK && TRK_TRI_VALID == ST_TRI_VALID && TRK_MOTION_SKIPPED == ST_MOTION_SKIPPED, "host_lists.h reads the feature kernel's status bits");
 
 thread_local std::string g_err;
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
@@ -68,25 +71,6 @@ struct StageRange {
     if (e_ != hipSuccess) return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-struct CamMeta { int state_id; double time; int last_correlated_id; std::vector<uint64_t> tracked; };
-struct PrunedState { int state_id; double time; int last_correlated_id; double pose[7]; };   // camState at the moment it was pruned (msckf.h:631,714)
-struct Track { uint64_t id; std::vector<double> obs; std::vector<int> cam_ids; bool initialized = false; double p_f_G[3] = {0, 0, 0}; };
-struct TrackToResid { uint64_t id; std::vector<double> obs; std::vector<int> slots; };
-struct HostTraj {
-  bool initialized = false;
-  int max_cam_states = 0, min_track_length = 0, max_track_length = 0;
-  double redundancy_angle_thresh = 0, redundancy_distance_thresh = 0;
-  std::vector<CamMeta> cams;
-  std::vector<Track> tracks;
-  std::vector<uint64_t> tracked_ids;
-  std::vector<TrackToResid> to_resid;
-  std::vector<PrunedState> pruned;
-  std::vector<double> map;   // xyz triples of the last marginalize
-  int map_pending = 0;       // > 0: the last marginalize()'s triangulated points of this many tracks are still on the device
-                             // (read back when somebody asks -- getMap(), pruneRedundantStates(), a copy -- or dropped by the next marginalize())
-  int wl_F = 0;              // tracks in the device work-list of this trajectory
-};
-
 struct BatchBase {
   virtual ~BatchBase() {}
   int B = 0, n_cap = 0, f_cap = 0, m_cap = 0, dtype = 0, device = 0;
@@ -100,15 +84,13 @@ struct BatchBase {
   virtual int marginalize(int b0, int nb) = 0;
   virtual int set_given_positions(int b, int F, const double* pf3) = 0;   // mode-1 work-list: stored p_f_G per track
   virtual int feature_only(int b, int* status, double* pf3, int cap) = 0;  // checkMotion + triangulation of the work-list
-  virtual int marginalize_given(int b) = 0;                               // second update of pruneRedundantStates
   virtual int prune_keep(int b, const std::vector<int>& keep) = 0;
   // range forms for the batched image cycle (host_image_cycle): one copy / one launch for trajectories b0 .. b0 + nb - 1
-  struct WorkList { std::vector<int> M, slots; std::vector<double> obs; };                     // one trajectory's tracks to residualize (set_tracks' arguments)
   virtual int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) = 0;           // every trajectory's list in one pinned block, two copies
   virtual int cams_range(int b0, int nb, double* poses7) = 0;                                  // [nb][n_cap][7], one read + one wait
   virtual int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) = 0;   // [nb][f_cap], [nb][f_cap][3]; launch = false: only read what the last launch left
   virtual int set_given_range(int b0, int nb, const double* pf3) = 0;                          // [nb][f_cap][3]
-  virtual int marginalize_given_range(int b0, int nb) = 0;
+  virtual int marginalize_given_range(int b0, int nb) = 0;                                     // second update of pruneRedundantStates
   virtual int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) = 0; // keep[i]: ascending slots of trajectory b0 + i
   virtual int drop_oldest(int b0, int nb, int n) = 0;
   virtual int get_ncam(int b, int* n) = 0;
@@ -766,7 +748,7 @@ struct Batch : BatchBase {
     traj[b].wl_F = F;
     return 0;
   }
-  int set_tracks_range(int b0, int nb, const std::vector<BatchBase::WorkList>& wl) override {
+  int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) override {
     if (chk_range(b0, nb) || (int)wl.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
     DEVICE_ENTER();
     for (int i = 0; i < nb; ++i) {
@@ -916,17 +898,6 @@ struct Batch : BatchBase {
     HIPCHK(hipStreamSynchronize(st));
     for (int t = 0; t < F; ++t) { status[t] = stt[t]; for (int k = 0; k < 3; ++k) pf3[3 * t + k] = (double)pf[4 * t + k]; }
     return F;
-  }
-  int marginalize_given(int b) override {
-    POISON_GUARD();
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    use_single_worklists();
-    Dev<S> v = view(b);
-    v.mode = 1;
-    launch_update(v, b, 1, st);
-    HIPCHK(hipGetLastError());
-    return 0;
   }
   int prune_keep(int b, const std::vector<int>& keep) override {
     POISON_GUARD();
@@ -1718,125 +1689,14 @@ int Batch<S>::run_frames_streamed(int f0, int f1) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// host bookkeeping shared by both dtypes (restates msckf.h:215-332, 685-717, 765-807, 1469-1485)
+// host bookkeeping shared by both dtypes (restates msckf.h:215-332, 685-717, 765-807, 1469-1485): the list work is
+// host_lists.h, free of device calls; here are the drivers that put the device calls between its steps
 // -------------------------------------------------------------------------------------------------
-void remove_tracked_feature(HostTraj& t, uint64_t fid, std::vector<int>& slots) {
-  slots.clear();
-  for (size_t c = 0; c < t.cams.size(); ++c) {
-    auto& ids = t.cams[c].tracked;
-    auto it = std::find(ids.begin(), ids.end(), fid);
-    if (it != ids.end()) { ids.erase(it); slots.push_back((int)c); }
-  }
-}
-
-// key -> int table without a heap node per key (open addressing, power-of-two capacity, one instance per host thread reused
-// from call to call): the bookkeeping below makes a few hundred to a few thousand look-ups per image and trajectory, and a
-// std::unordered_map's allocations were most of their cost
-struct FlatIndex {
-  std::vector<uint64_t> key; std::vector<int> val; unsigned shift = 64; size_t mask = 0;
-  void reset(size_t n) {
-    size_t cap = 16; unsigned lg = 4;
-    while (cap < 2 * n + 2) { cap <<= 1; ++lg; }
-    if (key.size() < cap) key.resize(cap);
-    val.assign(cap, -1);
-    mask = cap - 1; shift = 64 - lg;
-  }
-  size_t slot(uint64_t k) const { return (size_t)((k * 0x9E3779B97F4A7C15ull) >> shift) & mask; }
-  // keeps the FIRST value given for a key (std::find returns the first occurrence); returns the value held
-  int insert_first(uint64_t k, int v) {
-    for (size_t s = slot(k);; s = (s + 1) & mask) {
-      if (val[s] < 0) { key[s] = k; val[s] = v; return v; }
-      if (key[s] == k) return val[s];
-    }
-  }
-  int find(uint64_t k) const {
-    for (size_t s = slot(k);; s = (s + 1) & mask) {
-      if (val[s] < 0) return -1;
-      if (key[s] == k) return val[s];
-    }
-  }
-};
-
-// update(), msckf.h:215-300, with the reference's results and none of its quadratic searches.  The reference looks every tracked
-// feature up in the incoming ids by linear search (:226), removes an ended feature from every camera state's list by linear
-// search + erase (removeTrackedFeature :1469-1485) and erases the ended tracks one by one (:283-298): O(tracked x incoming) +
-// O(ended x cameras x tracked) per image -- 43 us of the single filter's 286 us at 50 features per image (round-5 verdict), tens of
-// milliseconds per filter at the benchmark's 200.  Here: one table of the incoming ids (first occurrence, as std::find
-// returns), one table "ended feature -> camera slots that list it" built from the lists as they stand after this image's
-// registrations, ONE stable filter pass per camera list and per track list.  Every list ends in the order the reference leaves it.
 int host_update(BatchBase* B, int b, const double* meas, const uint64_t* ids, int n) {
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
   if (t.cams.empty()) return fail(-EINVAL, "update() before augmentState() (msckf.h:238 dereferences cam_states_.end()-1)");
-  t.to_resid.clear();
-  static thread_local FlatIndex first, where;
-  first.reset((size_t)n);
-  for (int k = 0; k < n; ++k) first.insert_first(ids[k], k);                  // keeps the first occurrence (std::find, :226)
-  // pass 1 (:224-247): register this image's observation; which tracks end here
-  const size_t nt = t.tracked_ids.size();
-  static thread_local std::vector<char> ended;
-  ended.assign(nt, 0);
-  size_t n_ended = 0;
-  for (size_t i = 0; i < nt; ++i) {
-    const uint64_t fid = t.tracked_ids[i];
-    Track& tr = t.tracks[i];
-    const int k = first.find(fid);
-    const bool valid = k >= 0;
-    if (valid) {
-      tr.obs.push_back(meas[2 * (size_t)k]); tr.obs.push_back(meas[2 * (size_t)k + 1]);
-      t.cams.back().tracked.push_back(fid);
-      tr.cam_ids.push_back(t.cams.back().state_id);
-    }
-    if (!valid || tr.obs.size() / 2 >= (size_t)t.max_track_length) { ended[i] = 1; ++n_ended; }
-  }
-  if (!n_ended) return 0;
-  // pass 2 (:249-265 + removeTrackedFeature): the camera slots that list an ended feature, in camera order
-  where.reset(n_ended);
-  std::vector<std::vector<int>> slots_of(n_ended);
-  {
-    int e = 0;
-    for (size_t i = 0; i < nt; ++i) if (ended[i]) where.insert_first(t.tracked_ids[i], e++);
-  }
-  for (size_t c = 0; c < t.cams.size(); ++c) {
-    auto& lst = t.cams[c].tracked;
-    size_t w = 0;
-    for (size_t r = 0; r < lst.size(); ++r) {
-      const int e = where.find(lst[r]);
-      if (e >= 0 && (slots_of[e].empty() || slots_of[e].back() != (int)c)) { slots_of[e].push_back((int)c); continue; }   // first occurrence in this list leaves it
-      lst[w++] = lst[r];
-    }
-    lst.resize(w);
-  }
-  {
-    int e = 0;
-    for (size_t i = 0; i < nt; ++i) {
-      if (!ended[i]) continue;
-      Track& tr = t.tracks[i];
-      std::vector<int>& slots = slots_of[e++];
-      if (slots.size() >= (size_t)t.min_track_length) {
-        TrackToResid r;
-        r.id = tr.id; r.obs = std::move(tr.obs); r.slots = std::move(slots);   // (the track is erased below: its observations move, they are not copied)
-        t.to_resid.push_back(std::move(r));
-      }
-    }
-  }
-  // pass 3 (:283-298): last_correlated_id of the camera states an ended track leaves empty, then the tracks themselves
-  for (size_t i = 0; i < nt; ++i) {
-    if (!ended[i] || t.tracks[i].cam_ids.empty()) continue;
-    const int last_id = t.tracks[i].cam_ids.back();
-    for (int idx : t.tracks[i].cam_ids)
-      for (auto& cs : t.cams)
-        if (cs.state_id == idx) { if (cs.tracked.empty()) cs.last_correlated_id = last_id; break; }
-  }
-  {
-    size_t w = 0;
-    for (size_t i = 0; i < nt; ++i) {
-      if (ended[i]) continue;
-      if (w != i) { t.tracks[w] = std::move(t.tracks[i]); t.tracked_ids[w] = t.tracked_ids[i]; }
-      ++w;
-    }
-    t.tracks.resize(w); t.tracked_ids.resize(w);
-  }
+  update_lists(t, meas, ids, n);
   return 0;
 }
 
@@ -1844,40 +1704,23 @@ int host_add_features(BatchBase* B, int b, const double* meas, const uint64_t* i
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
   if (t.cams.empty()) return fail(-EINVAL, "addFeatures() before augmentState() (msckf.h:320)");
-  static thread_local FlatIndex known;
-  known.reset(t.tracked_ids.size() + (size_t)n);
-  for (size_t i = 0; i < t.tracked_ids.size(); ++i) known.insert_first(t.tracked_ids[i], (int)i);
-  for (int i = 0; i < n; ++i) {
-    if (known.find(ids[i]) >= 0)
-      return fail(-EEXIST, "added new feature that was already being tracked");   // msckf.h:328-329 prints and returns
-    known.insert_first(ids[i], (int)t.tracked_ids.size());
-    Track tr; tr.id = ids[i];
-    tr.obs.push_back(meas[2 * i]); tr.obs.push_back(meas[2 * i + 1]);
-    t.cams.back().tracked.push_back(ids[i]);
-    tr.cam_ids.push_back(t.cams.back().state_id);
-    t.tracks.push_back(std::move(tr));
-    t.tracked_ids.push_back(ids[i]);
-  }
+  if (add_features_lists(t, meas, ids, n)) return fail(-EEXIST, "added new feature that was already being tracked");
   return 0;
 }
 
-int resolve_map(BatchBase* B, int b);
+int set_tracks(BatchBase* B, int b, const WorkList& wl) { return B->set_tracks(b, (int)wl.M.size(), wl.M.data(), wl.slots.data(), wl.obs.data()); }
+
 int host_marginalize(BatchBase* B, int b) {
   HostTraj& t = B->traj[b];
   t.map.clear(); t.map_pending = 0;
-  if (t.to_resid.empty()) { int z = 0; int rc = B->set_tracks(b, 0, &z, &z, nullptr); return rc ? rc : B->clear_stats(b); }
-  const int F = (int)t.to_resid.size();
-  std::vector<int> M(F), slots; std::vector<double> obs;
-  for (int i = 0; i < F; ++i) {
-    M[i] = (int)t.to_resid[i].slots.size();
-    slots.insert(slots.end(), t.to_resid[i].slots.begin(), t.to_resid[i].slots.end());
-    obs.insert(obs.end(), t.to_resid[i].obs.begin(), t.to_resid[i].obs.end());
-  }
-  int rc = B->set_tracks(b, F, M.data(), slots.data(), obs.data());
+  WorkList wl;
+  build_worklist(t.to_resid, wl);
+  int rc = set_tracks(B, b, wl);
   if (rc) return rc;
+  if (wl.M.empty()) return B->clear_stats(b);
   rc = B->marginalize(b, 1);
   if (rc) return rc;
-  t.map_pending = F;      // map_ (msckf.h:371) is read back when it is asked for: no wait for the device inside marginalize()
+  t.map_pending = (int)wl.M.size();   // map_ (msckf.h:371) is read back when it is asked for: no wait for the device inside marginalize()
   return 0;
 }
 
@@ -1890,79 +1733,35 @@ int resolve_map(BatchBase* B, int b) {
   std::vector<double> info((size_t)F * 8);
   const int rc = B->track_info(b, info.data(), F);
   if (rc < 0) return rc;
-  for (int i = 0; i < F; ++i)
-    if (info[8 * i] != 0 && info[8 * i + 1] != 0) { t.map.push_back(info[8 * i + 5]); t.map.push_back(info[8 * i + 6]); t.map.push_back(info[8 * i + 7]); }
+  // track_info's rows (motion passed or skipped, triangulation valid, ..., xyz) back as what append_map reads
+  std::vector<int> status(F); std::vector<double> pf((size_t)F * 3);
+  for (int i = 0; i < F; ++i) {
+    status[i] = (info[8 * i] != 0 ? ST_MOTION_OK : 0) | (info[8 * i + 1] != 0 ? ST_TRI_VALID : 0);
+    std::copy(&info[8 * i + 5], &info[8 * i + 5] + 3, &pf[3 * (size_t)i]);
+  }
+  append_map(t, status.data(), pf.data(), F);
   return 0;
 }
 
 int host_prune_empty(BatchBase* B, int b) {
   HostTraj& t = B->traj[b];
-  const int max_states = t.max_cam_states, num = (int)t.cams.size();
-  if (num < max_states) return 0;
-  if (!t.cams.front().tracked.empty()) return 0;
-  int last_to_remove = num - max_states - 1;
-  for (int i = 1; i < num - max_states; i++)
-    if (!t.cams[i].tracked.empty()) { last_to_remove = i - 1; break; }
+  const int last_to_remove = plan_prune_empty(t);
   if (last_to_remove < 0) return 0;
-  std::vector<int> keep;
   // pruned_states_ keeps the whole camState (msckf.h:714; read by asl_msckf.cpp:409-424): poses come back once, here
+  const int num = (int)t.cams.size();
   std::vector<double> poses((size_t)num * 7);
   int rc = B->get_cams_known(b, poses.data(), num);
   if (rc) return rc;
-  for (int i = 0; i <= last_to_remove; ++i) {
-    PrunedState ps{t.cams[i].state_id, t.cams[i].time, t.cams[i].last_correlated_id, {0}};
-    std::copy(&poses[7 * (size_t)i], &poses[7 * (size_t)i] + 7, ps.pose);
-    t.pruned.push_back(ps);
-  }
-  for (int i = last_to_remove + 1; i < num; ++i) keep.push_back(i);
-  rc = B->prune_keep(b, keep);
+  Retirement ret;
+  retire_plan_leading(t, poses.data(), last_to_remove, ret);
+  rc = B->prune_keep(b, ret.keep);
   if (rc) return rc;
-  t.cams.erase(t.cams.begin(), t.cams.begin() + last_to_remove + 1);
+  retire_commit(t, ret);
   return 0;
 }
 
-// findRedundantCamStates, msckf.h:1049-1098 (poses: n x 7 = q_CG(w,x,y,z) p_C_G)
-static void find_redundant(const HostTraj& t, const std::vector<double>& poses, std::vector<int>& rm) {
-  const int n = (int)t.cams.size();
-  if (n < 5) return;
-  auto qp = [&](int i) { return &poses[7 * i]; };
-  int kf = 0;
-  const int prot = n - 3;
-  int next = 1;
-  while (next != prot) {
-    const double* a = qp(kf); const double* c = qp(next);
-    const double dx = c[4] - a[4], dy = c[5] - a[5], dz = c[6] - a[6];
-    const double distance = std::sqrt(dx * dx + dy * dy + dz * dz);
-    // Eigen angularDistance: d = kf_q * conj(cam_q); 2*atan2(|vec(d)|, |d.w|)
-    const double aw = a[0], ax = a[1], ay = a[2], az = a[3], bw = c[0], bx = -c[1], by = -c[2], bz = -c[3];
-    const double dw = aw * bw - ax * bx - ay * by - az * bz;
-    const double vx = aw * bx + ax * bw + ay * bz - az * by, vy = aw * by + ay * bw + az * bx - ax * bz, vz = aw * bz + az * bw + ax * by - ay * bx;
-    const double angle = 2 * std::atan2(std::sqrt(vx * vx + vy * vy + vz * vz), std::fabs(dw));
-    if (distance < t.redundancy_distance_thresh && angle < t.redundancy_angle_thresh) rm.push_back(t.cams[next].state_id);
-    else kf = next;
-    ++next;
-    if (n - (int)rm.size() <= t.max_cam_states) break;
-  }
-  const int over = (n - (int)rm.size()) - t.max_cam_states;
-  for (int i = 0; i < over; i++)
-    if (std::find(rm.begin(), rm.end(), t.cams[i].state_id) == rm.end()) rm.push_back(t.cams[i].state_id);
-  if (rm.size() < 2) rm.clear();
-  std::sort(rm.begin(), rm.end());
-}
-
-static void erase_involved(Track& tr, const std::vector<int>& involved) {
-  for (int cam_id : involved) {
-    auto it = std::find(tr.cam_ids.begin(), tr.cam_ids.end(), cam_id);
-    if (it != tr.cam_ids.end()) {
-      const size_t idx = (size_t)(it - tr.cam_ids.begin());
-      tr.cam_ids.erase(it);
-      tr.obs.erase(tr.obs.begin() + 2 * idx, tr.obs.begin() + 2 * idx + 2);
-    }
-  }
-}
-
-// MSCKF::pruneRedundantStates, msckf.h:453-682: keyframe selection and observation surgery on the host, the
-// triangulation of not-yet-initialized features and the second measurement update on the device.
+// MSCKF::pruneRedundantStates, msckf.h:453-682: keyframe selection and observation surgery on the host (host_lists.h),
+// the triangulation of not-yet-initialized features and the second measurement update on the device.
 int host_prune_redundant(BatchBase* B, int b) {
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
@@ -1973,97 +1772,40 @@ int host_prune_redundant(BatchBase* B, int b) {
   if (rc) return rc;
   rc = B->get_cams_known(b, poses.data(), n);
   if (rc) return rc;
-  std::vector<int> rm;
-  find_redundant(t, poses, rm);
-  auto involved_of = [&](const Track& tr) {
-    std::vector<int> inv;
-    for (int cam_id : rm) if (std::find(tr.cam_ids.begin(), tr.cam_ids.end(), cam_id) != tr.cam_ids.end()) inv.push_back(cam_id);
-    return inv;
-  };
-  auto slot_of = [&](int cam_id) { for (int i = 0; i < n; ++i) if (t.cams[i].state_id == cam_id) return i; return -1; };
+  RedundantPlan plan;
+  WorkList wl;
   // ---- first loop :466-534
-  std::vector<size_t> cand;   // not-yet-initialized features with >= 2 involved states: need motion check + triangulation
-  for (size_t i = 0; i < t.tracks.size(); ++i) {
-    Track& tr = t.tracks[i];
-    std::vector<int> inv = involved_of(tr);
-    if (inv.empty()) continue;
-    if (inv.size() == 1) { erase_involved(tr, inv); continue; }
-    if (!tr.initialized) cand.push_back(i);
-  }
-  if (!cand.empty()) {
-    if ((int)cand.size() > B->f_cap) return fail(-E2BIG, "more candidate features than f_cap");
-    std::vector<int> M, slots; std::vector<double> obs;
-    for (size_t ci : cand) {
-      const Track& tr = t.tracks[ci];
-      int m = 0;
-      for (int p = 0; p < n; ++p) {                                           // feature_associated_cam_states in cam order (:490-495)
-        auto it = std::find(tr.cam_ids.begin(), tr.cam_ids.end(), t.cams[p].state_id);
-        if (it == tr.cam_ids.end()) continue;
-        const size_t k = (size_t)(it - tr.cam_ids.begin());
-        slots.push_back(p); obs.push_back(tr.obs[2 * k]); obs.push_back(tr.obs[2 * k + 1]); ++m;
-      }
-      M.push_back(m);
-    }
-    rc = B->set_tracks(b, (int)cand.size(), M.data(), slots.data(), obs.data());
+  if (redundant_select(t, poses.data(), B->f_cap, plan, wl)) return fail(-E2BIG, "more candidate features than f_cap");
+  if (plan.rm.empty()) return 0;
+  if (!wl.M.empty()) {
+    rc = set_tracks(B, b, wl);
     if (rc) return rc;
-    std::vector<int> status(cand.size()); std::vector<double> pf(3 * cand.size());
-    rc = B->feature_only(b, status.data(), pf.data(), (int)cand.size());
+    const int C = (int)wl.M.size();
+    std::vector<int> status(C); std::vector<double> pf(3 * (size_t)C);
+    rc = B->feature_only(b, status.data(), pf.data(), C);
     if (rc < 0) return rc;
-    for (size_t c = 0; c < cand.size(); ++c) {
-      Track& tr = t.tracks[cand[c]];
-      const bool ok = (status[c] & ST_MOTION_OK) && (status[c] & ST_TRI_VALID);
-      if (!ok) erase_involved(tr, involved_of(tr));                           // :496-524
-      else { tr.initialized = true; for (int k = 0; k < 3; ++k) tr.p_f_G[k] = pf[3 * c + k]; t.map.insert(t.map.end(), &pf[3 * c], &pf[3 * c] + 3); }
-    }
+    redundant_apply_candidates(t, plan, status.data(), pf.data());
   }
   // ---- second loop :545-607
-  {
-    std::vector<int> M, slots; std::vector<double> obs, pf;
-    std::vector<size_t> used;
-    for (size_t i = 0; i < t.tracks.size(); ++i) {
-      Track& tr = t.tracks[i];
-      std::vector<int> inv = involved_of(tr);
-      if (inv.empty()) continue;
-      for (int cam_id : inv) {
-        const size_t k = (size_t)(std::find(tr.cam_ids.begin(), tr.cam_ids.end(), cam_id) - tr.cam_ids.begin());
-        slots.push_back(slot_of(cam_id)); obs.push_back(tr.obs[2 * k]); obs.push_back(tr.obs[2 * k + 1]);
-      }
-      M.push_back((int)inv.size());
-      for (int k = 0; k < 3; ++k) pf.push_back(tr.p_f_G[k]);
-      used.push_back(i);
-    }
-    const int F = (int)M.size();
-    if (F > B->f_cap) return fail(-E2BIG, "more features than f_cap");
-    if (F > 0) {
-      rc = B->set_tracks(b, F, M.data(), slots.data(), obs.data());
-      if (rc) return rc;
-      rc = B->set_given_positions(b, F, pf.data());
-      if (rc) return rc;
-      rc = B->marginalize_given(b);
-      if (rc) return rc;
-    }
-    for (size_t i : used) erase_involved(t.tracks[i], involved_of(t.tracks[i]));
-  }
-  // ---- prune the removed camera states :616-681
-  std::vector<int> keep;
-  std::vector<CamMeta> kept;
-  if (!rm.empty()) {                                  // poses as corrected by the second update (msckf.h:614 precedes :631)
-    rc = B->get_cams_known(b, poses.data(), n);
+  std::vector<double> pfin(3 * (size_t)B->f_cap);
+  if (redundant_second_update(t, plan, B->f_cap, wl, pfin.data())) return fail(-E2BIG, "more features than f_cap");
+  if (!wl.M.empty()) {
+    rc = set_tracks(B, b, wl);
+    if (rc) return rc;
+    rc = B->set_given_positions(b, (int)wl.M.size(), pfin.data());
+    if (rc) return rc;
+    rc = B->marginalize_given_range(b, 1);
     if (rc) return rc;
   }
-  for (int i = 0; i < n; ++i) {
-    if (std::find(rm.begin(), rm.end(), t.cams[i].state_id) != rm.end()) {
-      PrunedState ps{t.cams[i].state_id, t.cams[i].time, t.cams[i].last_correlated_id, {0}};
-      std::copy(&poses[7 * (size_t)i], &poses[7 * (size_t)i] + 7, ps.pose);
-      t.pruned.push_back(ps);
-    }
-    else { keep.push_back(i); kept.push_back(t.cams[i]); }
-  }
-  if ((int)keep.size() != n) {
-    rc = B->prune_keep(b, keep);
-    if (rc) return rc;
-    t.cams = kept;
-  }
+  redundant_finish(t, plan);
+  // ---- prune the removed camera states :616-681, poses as corrected by the second update (msckf.h:614 precedes :631)
+  rc = B->get_cams_known(b, poses.data(), n);
+  if (rc) return rc;
+  Retirement ret;
+  retire_plan_ids(t, poses.data(), plan.rm, ret);
+  rc = B->prune_keep(b, ret.keep);
+  if (rc) return rc;
+  retire_commit(t, ret);
   return 0;
 }
 
@@ -2088,11 +1830,13 @@ int host_finish(BatchBase* B, int b) {
 // -------------------------------------------------------------------------------------------------
 // One image of the ASL runner's loop (asl_msckf.cpp:269-294) for trajectories b0 .. b0 + nb - 1 of a batch IN LOCKSTEP:
 //   augmentState -> update -> addFeatures -> marginalize -> [pruneRedundantStates] -> [pruneEmptyStates]
-// The bookkeeping of every trajectory (msckf.h:215-332, 453-534, 685-717, 1049-1098) runs on the host exactly as in the
-// per-filter entries above -- same functions --, the device work of a stage goes out as ONE launch sequence over the range
-// (the kernels index trajectories; a run of trajectories with nothing to do is skipped) and what a stage needs back -- poses for
-// findRedundantCamStates, triangulated points of not-yet-initialized features, poses of the states about to be pruned --
-// comes back in one read and one wait per stage for the whole range, instead of one per filter.
+// The bookkeeping of every trajectory runs on the host through the same functions as the per-filter entries above --
+// host_update, host_add_features, and the steps of host_lists.h: build_worklist, append_map, redundant_select /
+// _apply_candidates / _second_update / _finish, plan_prune_empty, retire_plan_* / retire_commit --, the device work of a stage
+// goes out as ONE launch sequence over the range (the kernels index trajectories; a run of trajectories with nothing to do is
+// skipped) and what a stage needs back -- poses for findRedundantCamStates, triangulated points of not-yet-initialized
+// features, poses of the states about to be pruned -- comes back in one read and one wait per stage for the whole range,
+// instead of one per filter.
 // Same arithmetic per trajectory as the per-filter calls (tests/test_gpu_parity.py: bit for bit).
 // -------------------------------------------------------------------------------------------------
 // the bookkeeping of the trajectories of a range is independent: spread over host threads (created per call: tens of microseconds
@@ -2121,6 +1865,18 @@ template <class Fn> static int for_runs(const std::vector<char>& on, int b0, Fn 
     if (rc) return rc;
     i = j;
   }
+  return 0;
+}
+static bool any_of(const std::vector<char>& on) { for (char c : on) if (c) return true; return false; }
+
+// retire what every trajectory of the range planned: one prune launch for the range, then the host lists
+static int prune_retired_range(BatchBase* B, int b0, const std::vector<Retirement>& ret) {
+  const int nb = (int)ret.size();
+  std::vector<std::vector<int>> keep(nb);
+  for (int i = 0; i < nb; ++i) keep[i] = ret[i].keep;
+  const int rc = B->prune_keep_range(b0, nb, keep);
+  if (rc) return rc;
+  for (int i = 0; i < nb; ++i) retire_commit(B->traj[b0 + i], ret[i]);
   return 0;
 }
 
@@ -2160,20 +1916,10 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
   }
   tick(1);
   // ---- marginalize :336-449
-  std::vector<char> has(nb, 0);
   {
-    std::vector<BatchBase::WorkList> wl(nb);
-    parallel_for(nb, [&](int i) {
-      const HostTraj& t = B->traj[b0 + i];
-      const int F = (int)t.to_resid.size();
-      wl[i].M.assign(F, 0);
-      for (int k = 0; k < F; ++k) {
-        wl[i].M[k] = (int)t.to_resid[k].slots.size();
-        wl[i].slots.insert(wl[i].slots.end(), t.to_resid[k].slots.begin(), t.to_resid[k].slots.end());
-        wl[i].obs.insert(wl[i].obs.end(), t.to_resid[k].obs.begin(), t.to_resid[k].obs.end());
-      }
-      return 0;
-    });
+    std::vector<char> has(nb, 0);
+    std::vector<WorkList> wl(nb);
+    parallel_for(nb, [&](int i) { build_worklist(B->traj[b0 + i].to_resid, wl[i]); return 0; });
     tick(2);
     rc = B->set_tracks_range(b0, nb, wl);
     if (rc) return rc;
@@ -2191,9 +1937,8 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
   // ---- pruneRedundantStates :453-682
   if (flags & 1) {
     std::vector<char> act(nb, 0);
-    bool any = false;
-    for (int i = 0; i < nb; ++i) { act[i] = B->traj[b0 + i].cams.size() >= 20; any |= act[i] != 0; }   // :455
-    if (any) {
+    for (int i = 0; i < nb; ++i) act[i] = B->traj[b0 + i].cams.size() >= 20;   // :455
+    if (any_of(act)) {
       std::vector<int> status((size_t)nb * f_cap);
       std::vector<double> pf((size_t)nb * f_cap * 3), poses((size_t)nb * n_cap * 7);
       // what resolve_map() fetches per filter: the points of the marginalize just launched (the work-lists are reused below)
@@ -2201,138 +1946,53 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
       if (rc) return rc;
       rc = B->cams_range(b0, nb, poses.data());
       if (rc) return rc;
-      std::vector<std::vector<int>> rm(nb);
-      std::vector<std::vector<size_t>> cand(nb);
+      std::vector<RedundantPlan> plan(nb);    // (a trajectory that is not active keeps an empty plan: every step skips it)
       std::vector<char> has_cand(nb, 0), has_upd(nb, 0);
-      auto involved_of = [&](int i, const Track& tr) {
-        std::vector<int> inv;
-        for (int cam_id : rm[i]) if (std::find(tr.cam_ids.begin(), tr.cam_ids.end(), cam_id) != tr.cam_ids.end()) inv.push_back(cam_id);
-        return inv;
-      };
+      WorkList wl;
+      // first loop :466-534
       for (int i = 0; i < nb; ++i) {
         if (!act[i]) continue;
         HostTraj& t = B->traj[b0 + i];
-        const int F = t.map_pending; t.map_pending = 0;
-        for (int k = 0; k < F; ++k) {
-          const int sx = status[(size_t)i * f_cap + k];
-          if (((sx & ST_MOTION_SKIPPED) || (sx & ST_MOTION_OK)) && (sx & ST_TRI_VALID)) t.map.insert(t.map.end(), &pf[((size_t)i * f_cap + k) * 3], &pf[((size_t)i * f_cap + k) * 3] + 3);
-        }
-        const int n = (int)t.cams.size();
-        std::vector<double> pz(&poses[(size_t)i * n_cap * 7], &poses[(size_t)i * n_cap * 7] + (size_t)n * 7);
-        find_redundant(t, pz, rm[i]);
-        if (rm[i].empty()) continue;                   // no camera state to remove: both loops over the tracks find nothing involved
-        // first loop :466-534
-        for (size_t k = 0; k < t.tracks.size(); ++k) {
-          Track& tr = t.tracks[k];
-          std::vector<int> inv = involved_of(i, tr);
-          if (inv.empty()) continue;
-          if (inv.size() == 1) { erase_involved(tr, inv); continue; }
-          if (!tr.initialized) cand[i].push_back(k);
-        }
-        if ((int)cand[i].size() > f_cap) return fail(-E2BIG, "more candidate features than f_cap");
-        if (!cand[i].empty()) {
-          std::vector<int> M, slots; std::vector<double> obs;
-          for (size_t ci : cand[i]) {
-            const Track& tr = t.tracks[ci];
-            int m = 0;
-            for (int p2 = 0; p2 < n; ++p2) {
-              auto it = std::find(tr.cam_ids.begin(), tr.cam_ids.end(), t.cams[p2].state_id);
-              if (it == tr.cam_ids.end()) continue;
-              const size_t k = (size_t)(it - tr.cam_ids.begin());
-              slots.push_back(p2); obs.push_back(tr.obs[2 * k]); obs.push_back(tr.obs[2 * k + 1]); ++m;
-            }
-            M.push_back(m);
-          }
-          rc = B->set_tracks(b0 + i, (int)cand[i].size(), M.data(), slots.data(), obs.data());
-          if (rc) return rc;
-          has_cand[i] = 1;
-        }
+        append_map(t, &status[(size_t)i * f_cap], &pf[(size_t)i * f_cap * 3], t.map_pending);
+        t.map_pending = 0;
+        if (redundant_select(t, &poses[(size_t)i * n_cap * 7], f_cap, plan[i], wl)) return fail(-E2BIG, "more candidate features than f_cap");
+        if (wl.M.empty()) continue;
+        rc = set_tracks(B, b0 + i, wl);
+        if (rc) return rc;
+        has_cand[i] = 1;
       }
       // checkMotion + initializePosition of the not-yet-initialized features, every trajectory's in one launch per run
-      {
-        bool anyc = false;
-        for (int i = 0; i < nb; ++i) anyc |= has_cand[i] != 0;
-        if (anyc) {
-          // (feature_only_range launches over the runs; the read-back covers the whole range once)
-          rc = for_runs(has_cand, b0, [&](int s0, int n) { return B->feature_only_range(s0, n, status.data() + (size_t)(s0 - b0) * f_cap, pf.data() + (size_t)(s0 - b0) * f_cap * 3, true); });
-          if (rc) return rc;
-          for (int i = 0; i < nb; ++i) {
-            if (!has_cand[i]) continue;
-            HostTraj& t = B->traj[b0 + i];
-            for (size_t c = 0; c < cand[i].size(); ++c) {
-              Track& tr = t.tracks[cand[i][c]];
-              const int sx = status[(size_t)i * f_cap + c];
-              const double* pc = &pf[((size_t)i * f_cap + c) * 3];
-              const bool ok = (sx & ST_MOTION_OK) && (sx & ST_TRI_VALID);
-              if (!ok) erase_involved(tr, involved_of(i, tr));                      // :496-524
-              else { tr.initialized = true; for (int k = 0; k < 3; ++k) tr.p_f_G[k] = pc[k]; t.map.insert(t.map.end(), pc, pc + 3); }
-            }
-          }
-        }
+      if (any_of(has_cand)) {
+        // (feature_only_range launches over the runs; the read-back covers the whole range once)
+        rc = for_runs(has_cand, b0, [&](int s0, int n) { return B->feature_only_range(s0, n, status.data() + (size_t)(s0 - b0) * f_cap, pf.data() + (size_t)(s0 - b0) * f_cap * 3, true); });
+        if (rc) return rc;
+        for (int i = 0; i < nb; ++i)
+          if (has_cand[i]) redundant_apply_candidates(B->traj[b0 + i], plan[i], &status[(size_t)i * f_cap], &pf[(size_t)i * f_cap * 3]);
       }
       // second loop :545-607: the work-lists of the second update
-      std::vector<std::vector<size_t>> used(nb);
       std::vector<double> pfin((size_t)nb * f_cap * 3, 0.0);
       for (int i = 0; i < nb; ++i) {
-        if (!act[i] || rm[i].empty()) continue;
-        HostTraj& t = B->traj[b0 + i];
-        const int n = (int)t.cams.size();
-        auto slot_of = [&](int cam_id) { for (int q = 0; q < n; ++q) if (t.cams[q].state_id == cam_id) return q; return -1; };
-        std::vector<int> M, slots; std::vector<double> obs;
-        for (size_t k = 0; k < t.tracks.size(); ++k) {
-          Track& tr = t.tracks[k];
-          std::vector<int> inv = involved_of(i, tr);
-          if (inv.empty()) continue;
-          for (int cam_id : inv) {
-            const size_t q = (size_t)(std::find(tr.cam_ids.begin(), tr.cam_ids.end(), cam_id) - tr.cam_ids.begin());
-            slots.push_back(slot_of(cam_id)); obs.push_back(tr.obs[2 * q]); obs.push_back(tr.obs[2 * q + 1]);
-          }
-          for (int q = 0; q < 3; ++q) pfin[((size_t)i * f_cap + M.size()) * 3 + q] = tr.p_f_G[q];
-          M.push_back((int)inv.size());
-          used[i].push_back(k);
-          if ((int)M.size() > f_cap) return fail(-E2BIG, "more features than f_cap");
-        }
-        if (!M.empty()) {
-          rc = B->set_tracks(b0 + i, (int)M.size(), M.data(), slots.data(), obs.data());
-          if (rc) return rc;
-          has_upd[i] = 1;
-        }
+        if (redundant_second_update(B->traj[b0 + i], plan[i], f_cap, wl, &pfin[(size_t)i * f_cap * 3])) return fail(-E2BIG, "more features than f_cap");
+        if (wl.M.empty()) continue;
+        rc = set_tracks(B, b0 + i, wl);
+        if (rc) return rc;
+        has_upd[i] = 1;
       }
-      {
-        bool anyu = false;
-        for (int i = 0; i < nb; ++i) anyu |= has_upd[i] != 0;
-        if (anyu) {
-          rc = B->set_given_range(b0, nb, pfin.data());
-          if (rc) return rc;
-          rc = for_runs(has_upd, b0, [&](int s0, int n) { return B->marginalize_given_range(s0, n); });
-          if (rc) return rc;
-        }
+      if (any_of(has_upd)) {
+        rc = B->set_given_range(b0, nb, pfin.data());
+        if (rc) return rc;
+        rc = for_runs(has_upd, b0, [&](int s0, int n) { return B->marginalize_given_range(s0, n); });
+        if (rc) return rc;
       }
-      for (int i = 0; i < nb; ++i) {
-        HostTraj& t = B->traj[b0 + i];
-        for (size_t k : used[i]) erase_involved(t.tracks[k], involved_of(i, t.tracks[k]));
-      }
-      // prune the removed camera states :616-681 (poses as corrected by the second update: :614 precedes :631)
       bool anyrm = false;
-      for (int i = 0; i < nb; ++i) anyrm |= !rm[i].empty();
+      for (int i = 0; i < nb; ++i) { redundant_finish(B->traj[b0 + i], plan[i]); anyrm |= !plan[i].rm.empty(); }
+      // prune the removed camera states :616-681 (poses as corrected by the second update: :614 precedes :631)
       if (anyrm) {
         rc = B->cams_range(b0, nb, poses.data());
         if (rc) return rc;
-        std::vector<std::vector<int>> keep(nb);
-        for (int i = 0; i < nb; ++i) {
-          HostTraj& t = B->traj[b0 + i];
-          const int n = (int)t.cams.size();
-          std::vector<CamMeta> kept;
-          for (int q = 0; q < n; ++q) {
-            if (!rm[i].empty() && std::find(rm[i].begin(), rm[i].end(), t.cams[q].state_id) != rm[i].end()) {
-              PrunedState ps{t.cams[q].state_id, t.cams[q].time, t.cams[q].last_correlated_id, {0}};
-              std::copy(&poses[((size_t)i * n_cap + q) * 7], &poses[((size_t)i * n_cap + q) * 7] + 7, ps.pose);
-              t.pruned.push_back(ps);
-            } else { keep[i].push_back(q); kept.push_back(t.cams[q]); }
-          }
-          if ((int)keep[i].size() != n) t.cams = kept;
-        }
-        rc = B->prune_keep_range(b0, nb, keep);
+        std::vector<Retirement> ret(nb);
+        for (int i = 0; i < nb; ++i) retire_plan_ids(B->traj[b0 + i], &poses[(size_t)i * n_cap * 7], plan[i].rm, ret[i]);
+        rc = prune_retired_range(B, b0, ret);
         if (rc) return rc;
       }
     }
@@ -2342,33 +2002,14 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
   if (flags & 2) {
     std::vector<int> last(nb, -1);
     bool any = false;
-    for (int i = 0; i < nb; ++i) {
-      const HostTraj& t = B->traj[b0 + i];
-      const int max_states = t.max_cam_states, num = (int)t.cams.size();
-      if (num < max_states || !t.cams.front().tracked.empty()) continue;
-      int last_to_remove = num - max_states - 1;
-      for (int q = 1; q < num - max_states; q++)
-        if (!t.cams[q].tracked.empty()) { last_to_remove = q - 1; break; }
-      last[i] = last_to_remove;
-      any |= last_to_remove >= 0;
-    }
+    for (int i = 0; i < nb; ++i) { last[i] = plan_prune_empty(B->traj[b0 + i]); any |= last[i] >= 0; }
     if (any) {
       std::vector<double> poses((size_t)nb * n_cap * 7);
       rc = B->cams_range(b0, nb, poses.data());    // pruned_states_ keeps the whole camState (msckf.h:714)
       if (rc) return rc;
-      std::vector<std::vector<int>> keep(nb);
-      for (int i = 0; i < nb; ++i) {
-        HostTraj& t = B->traj[b0 + i];
-        const int num = (int)t.cams.size();
-        for (int q = 0; q <= last[i]; ++q) {
-          PrunedState ps{t.cams[q].state_id, t.cams[q].time, t.cams[q].last_correlated_id, {0}};
-          std::copy(&poses[((size_t)i * n_cap + q) * 7], &poses[((size_t)i * n_cap + q) * 7] + 7, ps.pose);
-          t.pruned.push_back(ps);
-        }
-        for (int q = last[i] + 1; q < num; ++q) keep[i].push_back(q);
-        if (last[i] >= 0) t.cams.erase(t.cams.begin(), t.cams.begin() + last[i] + 1);
-      }
-      rc = B->prune_keep_range(b0, nb, keep);
+      std::vector<Retirement> ret(nb);
+      for (int i = 0; i < nb; ++i) retire_plan_leading(B->traj[b0 + i], &poses[(size_t)i * n_cap * 7], last[i], ret[i]);
+      rc = prune_retired_range(B, b0, ret);
       if (rc) return rc;
     }
   }

@@ -183,9 +183,9 @@ def test_batched_image_cycle_with_prune_redundant_equals_per_filter_calls_and_or
     for a BATCH of trajectories in lockstep -- host bookkeeping per trajectory, every device stage one launch sequence over
     the range, every read-back one copy for the range.  (1) bit for bit the per-filter API (augmentState / update /
     addFeatures / marginalize / pruneRedundantStates / pruneEmptyStates called filter by filter on a second handle): state,
-    camera states and their ids, covariance, pruned states, after every image; (2) against the oracle running the same
-    cycle: 1e-6 in double after every image, free-running; in float the two free-running filters are compared at the end (2e-2)
-    when they selected the same keyframes."""
+    camera states and their ids, covariance, map, pruned states, after every image, camera-state metadata at the end;
+    (2) against the oracle running the same cycle: 1e-6 in double after every image, free-running; in float the two
+    free-running filters are compared at the end (2e-2) when they selected the same keyframes."""
     N, F, nf, B = 26, 12, 40, 5
     cd, pd, tol = (capi.F64, po.F64, 1e-6) if prec == "f64" else (capi.F32, po.F32, 1e-3)
     cfg = sc.filter_config(N)
@@ -225,11 +225,14 @@ def test_batched_image_cycle_with_prune_redundant_equals_per_filter_calls_and_or
             assert np.array_equal(big.imu_state(b), one.imu_state(b)), (k, b)
             assert np.array_equal(big.cam_states(b)[0], one.cam_states(b)[0]), (k, b)
             assert np.array_equal(big.covariance(b), one.covariance(b)), (k, b)
+            assert np.array_equal(big.get_map(b), one.get_map(b)), (k, b)
             if prec == "f64":
                 e = _errs(big, b, o)
                 assert H.worst(e) < tol, (k, b, e)
     assert pruned_any >= B          # every trajectory pruned redundant states at least once
     for b in range(B):
+        for mb, mo in zip(big.cam_meta(b), one.cam_meta(b)):    # times, tracked counts, last_correlated ids
+            assert np.array_equal(mb, mo), b
         assert np.array_equal(big.pruned_state_ids(b), one.pruned_state_ids(b))
         assert np.array_equal(big.pruned_states(b), one.pruned_states(b))
         if prec == "f64":
@@ -239,6 +242,68 @@ def test_batched_image_cycle_with_prune_redundant_equals_per_filter_calls_and_or
             # keyframes (threshold decisions on float poses may flip) the filters stay together
             e = _errs(big, b, oracles[b])
             assert H.worst(e) < 2e-2, (b, e)
+    one.close(); big.close()
+
+
+def test_prune_redundant_over_f_cap_is_the_same_error_on_both_paths(capi):
+    """pruneRedundantStates meeting more tracks than f_cap: msckf_hip_image_cycle_range and, on a second handle fed the same
+    images filter by filter, msckf_hip_prune_redundant_states(0) refuse with the same -E2BIG at the same image, and the
+    other trajectory of the range handle is what its per-filter twin is.
+    The scenario (found with the oracle on the CPU): trajectory 0 has dense tracks (every track spans the window) and the
+    redundancy thresholds of the test above, so the first selection -- image 21, states 1 and 2 of a 22-state window --
+    finds 60 not-yet-initialized tracks that saw both states, against f_cap = 16; marginalize() never has more than the
+    F = 12 tracks that end per image.  Trajectory 1 keeps the default thresholds, under which no state is ever selected
+    (pruneRedundantStates is a no-op for it), so its twin is well defined whichever capacity check trips."""
+    N, F, nf, f_cap = 26, 12, 24, 16
+    cfg = sc.filter_config(N)
+    cfg["max_cam_states"] = 20
+    cfg["redundancy_distance_thresh"] = 0.25
+    cfg["redundancy_angle_thresh"] = 0.25
+    trs = [sc.Trajectory(2, 70, N, F, nf, cfg=cfg, dense_tracks=True), sc.Trajectory(2, 71, N, F, nf)]
+    sts = [tr.stream() for tr in trs]
+    one, big = capi.Batch(2, 40, f_cap, 40, capi.F64), capi.Batch(2, 40, f_cap, 40, capi.F64)
+    for b, tr in enumerate(trs):
+        one.initialize(b, tr.cfg, tr.imu0); big.initialize(b, tr.cfg, tr.imu0)
+
+    def same(b, k):
+        assert big.num_cam_states(b) == one.num_cam_states(b), (k, b)
+        assert np.array_equal(big.cam_states(b)[1], one.cam_states(b)[1]), (k, b)
+        assert np.array_equal(big.cam_states(b)[0], one.cam_states(b)[0]), (k, b)
+        assert np.array_equal(big.imu_state(b), one.imu_state(b)), (k, b)
+        assert np.array_equal(big.covariance(b), one.covariance(b)), (k, b)
+        assert np.array_equal(big.get_map(b), one.get_map(b)), (k, b)
+        for mb, mo in zip(big.cam_meta(b), one.cam_meta(b)):
+            assert np.array_equal(mb, mo), (k, b)
+        assert np.array_equal(big.pruned_states(b), one.pruned_states(b)), (k, b)
+
+    for k in range(nf):
+        err_big = err_one = None
+        big.propagate_range(0, 2, np.stack([tr.imu_for_frame(k) for tr in trs]))
+        try:
+            big.image_cycle_range(0, 2, [k] * 2, [tr.frame_times[k] for tr in trs], [sts[b][k]["cur"] for b in range(2)], [sts[b][k]["new"] for b in range(2)])
+        except capi.HipError as e:
+            err_big = str(e)
+        for b, tr in enumerate(trs):
+            one.propagate_range(b, 1, tr.imu_for_frame(k))
+            one.augment_state(b, k, tr.frame_times[k])
+            one.update(b, sts[b][k]["cur"][0], sts[b][k]["cur"][1])
+            one.add_features(b, sts[b][k]["new"][0], sts[b][k]["new"][1])
+            one.marginalize(b)
+            try:
+                one.prune_redundant_states(b)
+            except capi.HipError as e:
+                assert b == 0, (k, str(e))
+                err_one = str(e)
+        print("image %d: range %r, per filter %r" % (k, err_big, err_one))
+        assert err_big == err_one, k
+        if err_one:
+            break
+        for b in range(2):
+            one.prune_empty_states(b)
+            same(b, k)
+    assert err_one is not None and "(-7)" in err_one and "f_cap" in err_one, (k, err_one)     # -E2BIG
+    assert k == 21
+    same(1, k)
     one.close(); big.close()
 
 
