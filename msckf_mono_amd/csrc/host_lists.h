@@ -54,6 +54,13 @@ inline void remove_tracked_feature(HostTraj& t, uint64_t fid, std::vector<int>& 
   }
 }
 
+// augmentState's host half (msckf.h:148-149): the new camera state joins the window and map_ is cleared -- the points of the
+// previous marginalize() still on the device belong to the map just cleared
+inline void begin_image(HostTraj& t, int state_id, double time) {
+  t.cams.push_back(CamMeta{state_id, time, -1, {}});
+  t.map.clear(); t.map_pending = 0;
+}
+
 // key -> int table without a heap node per key (open addressing, power-of-two capacity, one instance per host thread reused
 // from call to call): the bookkeeping below makes a few hundred to a few thousand look-ups per image and trajectory, and a
 // std::unordered_map's allocations were most of their cost

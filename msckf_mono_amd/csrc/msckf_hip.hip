@@ -5,6 +5,9 @@
 // (msckf.h:215-332, 685-717, 1469-1485) -- and turns it into positional work-lists for the device.
 // Everything numerical (msckf.h:101-212, 336-449, 905-1423) runs in the HIP kernels of kernels_*.hip; there
 // is no CPU fallback: if no HIP device is usable msckf_hip_create fails.
+// What one frame of a scenario enqueues -- run_frames on resident inputs, run_frames_streamed on uploaded ones -- is
+// Batch<S>::enqueue_frame; the rules for a work-list are Batch<S>::check_worklist; the per-filter entries are the range
+// entries with nb = 1.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -81,16 +84,13 @@ struct BatchBase {
   virtual int propagate(int b0, int nb, const double* rd, int K, bool mirror = false) = 0;
   virtual int augment(int b0, int nb) = 0;
   virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
-  virtual int marginalize(int b0, int nb) = 0;
-  virtual int set_given_positions(int b, int F, const double* pf3) = 0;   // mode-1 work-list: stored p_f_G per track
-  virtual int feature_only(int b, int* status, double* pf3, int cap) = 0;  // checkMotion + triangulation of the work-list
-  virtual int prune_keep(int b, const std::vector<int>& keep) = 0;
-  // range forms for the batched image cycle (host_image_cycle): one copy / one launch for trajectories b0 .. b0 + nb - 1
+  virtual int marginalize(int b0, int nb, int mode = 0) = 0;   // mode 1: the second update of pruneRedundantStates (stored p_f_G per track, set_given_range)
+  // range forms (one copy / one launch for trajectories b0 .. b0 + nb - 1): the batched image cycle (host_image_cycle), and
+  // the per-filter entries with nb = 1
   virtual int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) = 0;           // every trajectory's list in one pinned block, two copies
   virtual int cams_range(int b0, int nb, double* poses7) = 0;                                  // [nb][n_cap][7], one read + one wait
-  virtual int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) = 0;   // [nb][f_cap], [nb][f_cap][3]; launch = false: only read what the last launch left
+  virtual int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) = 0;   // checkMotion + triangulation of the work-lists: [nb][f_cap], [nb][f_cap][3]; launch = false: only read what the last launch left
   virtual int set_given_range(int b0, int nb, const double* pf3) = 0;                          // [nb][f_cap][3]
-  virtual int marginalize_given_range(int b0, int nb) = 0;                                     // second update of pruneRedundantStates
   virtual int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) = 0; // keep[i]: ascending slots of trajectory b0 + i
   virtual int drop_oldest(int b0, int nb, int n) = 0;
   virtual int get_ncam(int b, int* n) = 0;
@@ -392,33 +392,42 @@ struct Batch : BatchBase {
   // pinned staging area of at least `bytes`, safe to overwrite (the previous asynchronous copy out of it has finished)
   int stage_acquire(size_t bytes, unsigned char** out) {
     stage_cur = (stage_cur + 1) % NSTG;
-    const int k = stage_cur;
-    if (stage_busy[k]) { HIPCHK(hipEventSynchronize(ev_stage[k])); stage_busy[k] = false; }
-    if (bytes > h_stage_bytes[k]) {
-      if (h_stage[k]) HIPCHK(hipHostFree(h_stage[k]));
-      h_stage[k] = nullptr; h_stage_bytes[k] = 0;
-      const size_t nb = std::max<size_t>(bytes, 1 << 12);
-      HIPCHK(hipHostMalloc((void**)&h_stage[k], nb, hipHostMallocDefault));
-      h_stage_bytes[k] = nb;
-    }
-    *out = h_stage[k];
-    return 0;
+    const int rc = stage_grow(stage_cur, bytes, true);
+    *out = h_stage[stage_cur];
+    return rc;
   }
   int stage_release() { HIPCHK(hipEventRecord(ev_stage[stage_cur], st)); stage_busy[stage_cur] = true; return 0; }
+  // slot k of the ring at least `bytes`; wait: first for the copy still in flight out of it (a slot that is re-allocated is
+  // always waited for)
+  int stage_grow(int k, size_t bytes, bool wait) {
+    const bool grow = bytes > h_stage_bytes[k];
+    if ((wait || grow) && stage_busy[k]) { HIPCHK(hipEventSynchronize(ev_stage[k])); stage_busy[k] = false; }
+    if (!grow) return 0;
+    if (h_stage[k]) HIPCHK(hipHostFree(h_stage[k]));
+    h_stage[k] = nullptr; h_stage_bytes[k] = 0;
+    const size_t nb = std::max<size_t>(bytes, 1 << 12);
+    HIPCHK(hipHostMalloc((void**)&h_stage[k], nb, hipHostMallocDefault));
+    h_stage_bytes[k] = nb;
+    return 0;
+  }
   // every slot of the ring at least `bytes` (a commit walks the ring once per frame: without this each slot would be freed and
   // re-allocated as the frames grow)
   int stage_reserve(size_t bytes) {
-    for (int k = 0; k < NSTG; ++k) {
-      if (bytes <= h_stage_bytes[k]) continue;
-      if (stage_busy[k]) { HIPCHK(hipEventSynchronize(ev_stage[k])); stage_busy[k] = false; }
-      if (h_stage[k]) HIPCHK(hipHostFree(h_stage[k]));
-      h_stage[k] = nullptr; h_stage_bytes[k] = 0;
-      const size_t nb = std::max<size_t>(bytes, 1 << 12);
-      HIPCHK(hipHostMalloc((void**)&h_stage[k], nb, hipHostMallocDefault));
-      h_stage_bytes[k] = nb;
-    }
+    for (int k = 0; k < NSTG; ++k) { const int rc = stage_grow(k, bytes, false); if (rc) return rc; }
     return 0;
   }
+  // copy on st + wait: what the getters and setters of single values do
+  int read_back(void* dst, const void* src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  int write_dev(void* dst, const void* src, size_t bytes) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  static size_t al256(size_t x) { return (x + 255) / 256 * 256; }   // sections of a streamed frame block
   void use_single_worklists() {
     d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
     d.wl_stride_n = wl_ib; d.wl_stride_f = wl_ib; d.wl_stride_o = wl_ib;
@@ -450,6 +459,35 @@ struct Batch : BatchBase {
     unsigned long long seen = 0;
     for (int k = 0; k < M; ++k) { const unsigned long long bit = 1ull << (s[k] & 63); if (s[k] >= 0 && s[k] < 64 && (seen & bit)) return true; seen |= bit; }
     return false;
+  }
+  // The rules for one trajectory's work-list (set_tracks, set_tracks_range, scenario_set), checked before anything of it is
+  // staged or written: the number of tracks, then every track's length, then track by track its slots' range and repetition
+  int check_worklist(int F, const int* M, const int* slots) const {
+    if (F < 0 || F > f_cap) return fail(-E2BIG, "more tracks than f_cap");
+    for (int t = 0; t < F; ++t) if (M[t] > m_cap || M[t] < 0) return fail(-E2BIG, "track longer than m_cap");
+    size_t o = 0;
+    for (int t = 0; t < F; o += M[t++]) {
+      for (int k = 0; k < M[t]; ++k) if (slots[o + k] < 0 || slots[o + k] >= n_cap) return fail(-EINVAL, "camera slot out of range");
+      if (repeated_slot(slots + o, M[t])) return fail(-EINVAL, "camera slot repeated within a track");
+    }
+    return 0;
+  }
+  // the device's padded single-call layout of one work-list, the F rows in use (all that is written): I = [F, 0, 0, 0 | M[f4] |
+  // F rows of m_cap slots], O = F rows of m_cap coordinate pairs
+  void pack_worklist(int* I, S* O, int F, const int* M, const int* slots, const double* obs) const {
+    std::memset(I, 0, (4 + (size_t)wl_f4 + (size_t)F * m_cap) * sizeof(int));
+    std::memset(O, 0, (size_t)F * m_cap * 2 * sizeof(S));
+    I[0] = F;
+    int* hM = I + 4; int* hS = I + 4 + wl_f4;
+    size_t o = 0;
+    for (int t = 0; t < F; o += M[t++]) {
+      hM[t] = M[t];
+      for (int k = 0; k < M[t]; ++k) {
+        hS[(size_t)t * m_cap + k] = slots[o + k];
+        O[((size_t)t * m_cap + k) * 2] = (S)obs[2 * (o + k)];
+        O[((size_t)t * m_cap + k) * 2 + 1] = (S)obs[2 * (o + k) + 1];
+      }
+    }
   }
   int chk(int b) const { return (b < 0 || b >= B) ? -EINVAL : 0; }
   // A run_frames / run_frames_streamed call that failed after some of its frames were enqueued leaves the slices at different
@@ -515,8 +553,7 @@ struct Batch : BatchBase {
       S out5[5];
       const int rc = derive_noise(b, out5);
       if (rc) return rc;
-      HIPCHK(hipMemcpyAsync(d.prm + (size_t)b * PRM_STRIDE + PRM_WU, out5, sizeof(out5), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
+      if (const int rc = write_dev(d.prm + (size_t)b * PRM_STRIDE + PRM_WU, out5, sizeof(out5))) return rc;
     }
     return 0;
   }
@@ -524,12 +561,10 @@ struct Batch : BatchBase {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     if (!d.lit.info) { for (int i = 0; i < 8; ++i) out8[i] = 0; return 0; }
     DEVICE_ENTER();
-    HIPCHK(hipMemcpyAsync(out8, d.lit.info + (size_t)b * 8, 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(out8, d.lit.info + (size_t)b * 8, 8 * sizeof(int))) return rc;
     if (d.lit.tim) {     // MSCKF_HIP_LITERAL_TIMERS=1 (profiling runs): phase durations of the last launch in microseconds on stderr
       long long t[LIT_TIM_SLOTS];
-      HIPCHK(hipMemcpyAsync(t, d.lit.tim + (size_t)b * LIT_TIM_SLOTS, sizeof(t), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      if (const int rc = read_back(t, d.lit.tim + (size_t)b * LIT_TIM_SLOTS, sizeof(t))) return rc;
       std::fprintf(stderr, "[k_literal b=%d] us: explicit rows %.0f Gram %.0f sweep %.0f kept %.0f handed-through rows %.0f basis products %.0f Z fill %.0f eliminate %.0f store %.0f total %.0f\n", b,
                    (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01, (t[4] - t[3]) * 0.01, (t[5] - t[4]) * 0.01, (t[6] - t[5]) * 0.01,
                    (t[8] - t[6]) * 0.01, (t[10] - t[8]) * 0.01, (t[11] - t[10]) * 0.01, (t[9] - t[11]) * 0.01, (t[9] - t[0]) * 0.01);
@@ -716,31 +751,18 @@ struct Batch : BatchBase {
   }
   int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    if (F < 0 || F > f_cap) return fail(-E2BIG, "more tracks than f_cap");
+    int rc = check_worklist(F, M, slots);
+    if (rc) return rc;
     DEVICE_ENTER();
-    for (int t = 0; t < F; ++t) if (M[t] > m_cap || M[t] < 0) return fail(-E2BIG, "track longer than m_cap");
-    { size_t o = 0; for (int t = 0; t < F; ++t) { if (repeated_slot(slots + o, M[t])) return fail(-EINVAL, "camera slot repeated within a track"); o += M[t]; } }
     // only the F rows in use travel, as the device holds them: [n, 0, 0, 0 | M[f4] | F rows of slots] in one copy, F rows of
     // coordinates in a second one, both out of one pinned block
     const size_t nI = 4 + (size_t)wl_f4 + (size_t)F * m_cap, nO = (size_t)F * m_cap * 2;
     const size_t offO = ((nI * sizeof(int) + 15) / 16) * 16;
     unsigned char* raw = nullptr;
-    int rc = stage_acquire(offO + nO * sizeof(S) + 16, &raw);
+    rc = stage_acquire(offO + nO * sizeof(S) + 16, &raw);
     if (rc) return rc;
-    int* hI = reinterpret_cast<int*>(raw); int* hM = hI + 4; int* hS = hI + 4 + wl_f4; S* hO = reinterpret_cast<S*>(raw + offO);
-    std::memset(raw, 0, offO + nO * sizeof(S));
-    hI[0] = F;
-    size_t o = 0;
-    for (int t = 0; t < F; ++t) {
-      hM[t] = M[t];
-      for (int k = 0; k < M[t]; ++k) {
-        if (slots[o + k] < 0 || slots[o + k] >= n_cap) return fail(-EINVAL, "camera slot out of range");
-        hS[(size_t)t * m_cap + k] = slots[o + k];
-        hO[((size_t)t * m_cap + k) * 2] = (S)obs[2 * (o + k)];
-        hO[((size_t)t * m_cap + k) * 2 + 1] = (S)obs[2 * (o + k) + 1];
-      }
-      o += M[t];
-    }
+    int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + offO);
+    pack_worklist(hI, hO, F, M, slots, obs);
     HIPCHK(hipMemcpyAsync(wl_i + (size_t)b * wl_ib, hI, (F ? nI : 4) * sizeof(int), hipMemcpyHostToDevice, st));
     if (F) HIPCHK(hipMemcpyAsync(wl_obs + (size_t)b * wl_ib * 2, hO, nO * sizeof(S), hipMemcpyHostToDevice, st));
     rc = stage_release();
@@ -750,19 +772,8 @@ struct Batch : BatchBase {
   }
   int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) override {
     if (chk_range(b0, nb) || (int)wl.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
+    for (int i = 0; i < nb; ++i) { const int rc = check_worklist((int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data()); if (rc) return rc; }
     DEVICE_ENTER();
-    for (int i = 0; i < nb; ++i) {
-      const int F = (int)wl[i].M.size();
-      if (F > f_cap) return fail(-E2BIG, "more tracks than f_cap");
-      size_t o = 0;
-      for (int t = 0; t < F; ++t) {
-        const int m = wl[i].M[t];
-        if (m > m_cap || m < 0) return fail(-E2BIG, "track longer than m_cap");
-        if (repeated_slot(wl[i].slots.data() + o, m)) return fail(-EINVAL, "camera slot repeated within a track");
-        for (int k = 0; k < m; ++k) if (wl[i].slots[o + k] < 0 || wl[i].slots[o + k] >= n_cap) return fail(-EINVAL, "camera slot out of range");
-        o += m;
-      }
-    }
     // the device's padded single-call layout for the whole range: [nb][wl_ib] ints ([n, 0, 0, 0 | M[f4] | f_cap rows of slots]) and
     // [nb][wl_ib * 2] coordinates, out of one pinned block, two copies
     const size_t nI = (size_t)nb * wl_ib, nO = (size_t)nb * wl_ib * 2;
@@ -771,25 +782,8 @@ struct Batch : BatchBase {
     int rc = stage_acquire(offO + nO * sizeof(S) + 16, &raw);
     if (rc) return rc;
     int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + offO);
-    const long ib = wl_ib; const int f4 = wl_f4, mc = m_cap;
     parallel_for(nb, [&](int i) {
-      int* I = hI + (size_t)i * ib; S* O = hO + (size_t)i * ib * 2;
-      const int F = (int)wl[i].M.size();
-      std::memset(I, 0, (size_t)(4 + f4 + (size_t)F * mc) * sizeof(int));
-      std::memset(O, 0, (size_t)F * mc * 2 * sizeof(S));
-      I[0] = F;
-      int* hM = I + 4; int* hS = I + 4 + f4;
-      size_t o = 0;
-      for (int t = 0; t < F; ++t) {
-        const int m = wl[i].M[t];
-        hM[t] = m;
-        for (int k = 0; k < m; ++k) {
-          hS[(size_t)t * mc + k] = wl[i].slots[o + k];
-          O[((size_t)t * mc + k) * 2] = (S)wl[i].obs[2 * (o + k)];
-          O[((size_t)t * mc + k) * 2 + 1] = (S)wl[i].obs[2 * (o + k) + 1];
-        }
-        o += m;
-      }
+      pack_worklist(hI + (size_t)i * wl_ib, hO + (size_t)i * wl_ib * 2, (int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data(), wl[i].obs.data());
       return 0;
     });
     HIPCHK(hipMemcpyAsync(wl_i + (size_t)b0 * wl_ib, hI, nI * sizeof(int), hipMemcpyHostToDevice, st));
@@ -812,10 +806,15 @@ struct Batch : BatchBase {
     HIPCHK(hipMemsetAsync(d.stats + (size_t)b * STAT_STRIDE + STAT_ERR, 0, sizeof(int), st));
     return 0;
   }
-  // every slice ran the same frames: all but the last of a call carry their prune on the downdate and flip the buffers
+  // Frame f of a call over [.., f1): does its prune ride on the downdate (the covariance lands, pruned, in the other buffer and
+  // the next frame's k_propagate commits the window size)?  Never the call's last frame: it prunes with its own launch, so that
+  // ncam is final when the call returns.  The frame step and commit_buffer_parity both ask here.
+  bool fuse_frame(int f, int f1) const { return fuse_prune && !prof && !overlap_feature && d.joseph == 0 && f + 1 < f1; }
+  // every slice ran the same frames; each fused one flipped the buffers
   void commit_buffer_parity(int f0, int f1) {
-    const bool fuse = fuse_prune && !prof && !overlap_feature && d.joseph == 0;
-    if (fuse && f1 - f0 >= 2 && ((f1 - f0 - 1) & 1)) std::swap(d.P, P_spare);
+    int flips = 0;
+    for (int f = f0; f < f1; ++f) flips += fuse_frame(f, f1) ? 1 : 0;
+    if (flips & 1) std::swap(d.P, P_spare);
   }
   // compression route of an update's launches (k_feature publishes B^ only for the information form): the handle's choice,
   // except that a batch with a trajectory on the literal anisotropic route always takes the information form (that route hands
@@ -865,69 +864,25 @@ struct Batch : BatchBase {
     }
     stage_begin(5, q); launch_kalman<S>(v, b0, nb, q); stage_end(5, q);
   }
-  int marginalize(int b0, int nb) override {
+  int marginalize(int b0, int nb, int mode) override {
     POISON_GUARD();
     if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
     DEVICE_ENTER();
     use_single_worklists();
-    launch_update(view(b0), b0, nb, st);
+    Dev<S> v = view(b0);
+    v.mode = mode;
+    launch_update(v, b0, nb, st);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  int set_given_positions(int b, int F, const double* pf3) override {
-    if (chk(b) || F > f_cap) return fail(-EINVAL, "bad arguments");
-    DEVICE_ENTER();
-    std::vector<S> tmp((size_t)std::max(F, 1) * 4, S(0));
-    for (int t = 0; t < F; ++t) for (int k = 0; k < 3; ++k) tmp[4 * t + k] = (S)pf3[3 * t + k];
-    HIPCHK(hipMemcpyAsync(d_pfin + (size_t)b * f_cap * 4, tmp.data(), tmp.size() * sizeof(S), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-  }
-  int feature_only(int b, int* status, double* pf3, int cap) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    use_single_worklists();
-    const int F = traj[b].wl_F;
-    if (F > cap) return fail(-E2BIG, "output buffer too small");
-    if (F == 0) return 0;
-    launch_feature<S>(view(b), b, 1, st);
-    HIPCHK(hipGetLastError());
-    std::vector<int> stt(F); std::vector<S> pf((size_t)F * 4);
-    HIPCHK(hipMemcpyAsync(stt.data(), d.trk_status + (size_t)b * f_cap, F * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(pf.data(), d.trk_pf + (size_t)b * f_cap * 4, (size_t)F * 4 * sizeof(S), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int t = 0; t < F; ++t) { status[t] = stt[t]; for (int k = 0; k < 3; ++k) pf3[3 * t + k] = (double)pf[4 * t + k]; }
-    return F;
-  }
-  int prune_keep(int b, const std::vector<int>& keep) override {
-    POISON_GUARD();
-    DEVICE_ENTER();
-    const int nk = (int)keep.size();
-    // the list goes through the pinned ring like every other input: no wait for the stream in the middle of the image's chain
-    // (the update before it, k_prune and the state read after it are one uninterrupted queue)
-    unsigned char* raw = nullptr;
-    int rc = stage_acquire(((size_t)nk + 1) * sizeof(int), &raw);
-    if (rc) return rc;
-    int* hk = reinterpret_cast<int*>(raw);
-    hk[0] = nk; for (int i = 0; i < nk; ++i) hk[1 + i] = keep[i];
-    if (nk) HIPCHK(hipMemcpyAsync(d.keep + (size_t)b * n_cap, hk + 1, nk * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d.nkeep + b, hk, sizeof(int), hipMemcpyHostToDevice, st));
-    rc = stage_release();
-    if (rc) return rc;
-    launch_prune<S>(d, b, 1, st);
-    h_ncam[b] = nk;
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  // ---- range forms (host_image_cycle)
+  // ---- range forms (host_image_cycle; the per-filter entries with nb = 1)
   int cams_range(int b0, int nb, double* poses7) override {
     POISON_GUARD();
     if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
     DEVICE_ENTER();
     const size_t per = (size_t)n_cap * CAM_STRIDE;
     std::vector<S> tmp(per * nb);
-    HIPCHK(hipMemcpyAsync(tmp.data(), d.cam + (size_t)b0 * per, tmp.size() * sizeof(S), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(tmp.data(), d.cam + (size_t)b0 * per, tmp.size() * sizeof(S))) return rc;
     for (int i = 0; i < nb; ++i)
       for (int c = 0; c < n_cap; ++c)
         for (int k = 0; k < 7; ++k) poses7[((size_t)i * n_cap + c) * 7 + k] = (double)tmp[(size_t)i * per + (size_t)c * CAM_STRIDE + k];
@@ -957,22 +912,13 @@ struct Batch : BatchBase {
     HIPCHK(hipMemcpyAsync(d_pfin + (size_t)b0 * f_cap * 4, tmp, cnt * sizeof(S), hipMemcpyHostToDevice, st));
     return stage_release();
   }
-  int marginalize_given_range(int b0, int nb) override {
-    POISON_GUARD();
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
-    use_single_worklists();
-    Dev<S> v = view(b0);
-    v.mode = 1;
-    launch_update(v, b0, nb, st);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
   int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) override {
     POISON_GUARD();
     if (chk_range(b0, nb) || (int)keep.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
     DEVICE_ENTER();
-    // [nb][n_cap] slots + [nb] counts through the pinned ring, two copies, one launch (a trajectory that keeps everything is a no-op there)
+    // [nb][n_cap] slots + [nb] counts through the pinned ring, two copies, one launch (a trajectory that keeps everything is a no-op
+    // there).  Like every other input: no wait for the stream in the middle of an image's chain (the update before it, k_prune and
+    // the state read after it are one uninterrupted queue)
     const size_t nI = (size_t)nb * n_cap + nb;
     unsigned char* raw = nullptr;
     int rc = stage_acquire(nI * sizeof(int), &raw);
@@ -1000,9 +946,7 @@ struct Batch : BatchBase {
     POISON_GUARD();
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
-    HIPCHK(hipMemcpyAsync(n, d.ncam + b, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return read_back(n, d.ncam + b, sizeof(int));
   }
   int get_imu(int b, double* o) override {
     POISON_GUARD();
@@ -1010,8 +954,7 @@ struct Batch : BatchBase {
     S* tmp = h_imu.data() + (size_t)b * IMU_STRIDE;
     if (!h_imu_ok[b]) {
       DEVICE_ENTER();
-      HIPCHK(hipMemcpyAsync(tmp, d.imu + (size_t)b * IMU_STRIDE, IMU_STRIDE * sizeof(S), hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
+      if (const int rc = read_back(tmp, d.imu + (size_t)b * IMU_STRIDE, IMU_STRIDE * sizeof(S))) return rc;
       h_imu_ok[b] = 1;
     }
     for (int i = 0; i < 29; ++i) o[i] = (double)tmp[i];
@@ -1022,8 +965,7 @@ struct Batch : BatchBase {
     DEVICE_ENTER();
     S tmp[IMU_STRIDE] = {0};
     for (int i = 0; i < 29; ++i) tmp[i] = (S)in[i];
-    HIPCHK(hipMemcpyAsync(d.imu + (size_t)b * IMU_STRIDE, tmp, sizeof(tmp), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = write_dev(d.imu + (size_t)b * IMU_STRIDE, tmp, sizeof(tmp))) return rc;
     std::copy(tmp, tmp + IMU_STRIDE, h_imu.begin() + (size_t)b * IMU_STRIDE); h_imu_ok[b] = 1;
     return 0;
   }
@@ -1060,9 +1002,7 @@ struct Batch : BatchBase {
     DEVICE_ENTER();
     S tmp[CAM_STRIDE] = {0};
     for (int k = 0; k < 7; ++k) tmp[k] = (S)in[k];
-    HIPCHK(hipMemcpyAsync(d.cam + ((size_t)b * n_cap + slot) * CAM_STRIDE, tmp, sizeof(tmp), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return write_dev(d.cam + ((size_t)b * n_cap + slot) * CAM_STRIDE, tmp, sizeof(tmp));
   }
   int get_cov(int b, double* P, int ldo) override {
     POISON_GUARD();
@@ -1072,8 +1012,7 @@ struct Batch : BatchBase {
     const int D = 15 + 6 * n;
     if (ldo < D) return fail(-EINVAL, "ld smaller than D");
     std::vector<S> tmp((size_t)d.ld * d.ld);
-    HIPCHK(hipMemcpyAsync(tmp.data(), d.P + (size_t)b * d.ld * d.ld, tmp.size() * sizeof(S), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(tmp.data(), d.P + (size_t)b * d.ld * d.ld, tmp.size() * sizeof(S))) return rc;
     for (int j = 0; j < D; ++j) for (int i = 0; i < D; ++i) P[(size_t)j * ldo + i] = (double)tmp[(size_t)j * d.ld + i];
     return 0;
   }
@@ -1093,24 +1032,19 @@ struct Batch : BatchBase {
   int get_nres(int b, long long* n) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
-    HIPCHK(hipMemcpyAsync(n, d.n_resid + b, sizeof(long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return read_back(n, d.n_resid + b, sizeof(long long));
   }
   int set_nres(int b, long long n) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
-    HIPCHK(hipMemcpyAsync(d.n_resid + b, &n, sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return write_dev(d.n_resid + b, &n, sizeof(long long));
   }
   int stats(int b, int* out) override {
     POISON_GUARD();
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
     int tmp[STAT_STRIDE];
-    HIPCHK(hipMemcpyAsync(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
     for (int i = 0; i < 7; ++i) out[i] = tmp[i];
     if (tmp[STAT_ERR] & STAT_ERR_NCAP) return fail(-EOVERFLOW, "camera-state capacity n_cap exceeded in augmentState");
     if (tmp[STAT_ERR] & STAT_ERR_PIVOT)
@@ -1148,16 +1082,13 @@ struct Batch : BatchBase {
   int error_flags(int b, int* flags) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
-    HIPCHK(hipMemcpyAsync(flags, d.stats + (size_t)b * STAT_STRIDE + STAT_ERR, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    return read_back(flags, d.stats + (size_t)b * STAT_STRIDE + STAT_ERR, sizeof(int));
   }
   int track_info(int b, double* out, int cap) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     DEVICE_ENTER();
     int tmp[STAT_STRIDE];
-    HIPCHK(hipMemcpyAsync(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
     const int F = tmp[STAT_NTRACKS];
     if (F > cap) return fail(-E2BIG, "output buffer too small");
     std::vector<int> stt(std::max(F, 1)); std::vector<S> gm(std::max(F, 1)), pf((size_t)std::max(F, 1) * 4);
@@ -1183,8 +1114,7 @@ struct Batch : BatchBase {
     const int D = 15 + 6 * n;
     if (D > cap) return fail(-E2BIG, "output buffer too small");
     std::vector<S> tmp(D);
-    HIPCHK(hipMemcpyAsync(tmp.data(), d.dx + (size_t)b * d.ld, D * sizeof(S), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = read_back(tmp.data(), d.dx + (size_t)b * d.ld, D * sizeof(S))) return rc;
     for (int i = 0; i < D; ++i) out[i] = (double)tmp[i];
     return D;
   }
@@ -1220,28 +1150,19 @@ struct Batch : BatchBase {
     rc |= sc_dalloc(&sc_rd, h_rd.size()); rc |= sc_dalloc(&sc_n, h_n.size()); rc |= sc_dalloc(&sc_M, h_M.size());
     rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size());
     if (rc) return rc;
-    {   // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
-      auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-      pk_rd = 0; pk_n = al(pk_rd + Bz * K * RD_STRIDE * sizeof(S)); pk_drop = al(pk_n + Bz * sizeof(int));
-      pk_M = al(pk_drop + Bz * sizeof(int)); pk_off = al(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al(pk_off + Bz * f_cap * sizeof(int));
-    }
+    // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
+    pk_rd = 0; pk_n = al256(pk_rd + Bz * K * RD_STRIDE * sizeof(S)); pk_drop = al256(pk_n + Bz * sizeof(int));
+    pk_M = al256(pk_drop + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
     sc_frames = n_frames; sc_K = K;
     return 0;
   }
   int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) override {
     if (f < 0 || f >= sc_frames || chk(b)) return fail(-EINVAL, "scenario cell out of range");
-    if (F < 0 || F > f_cap) return fail(-E2BIG, "more tracks than f_cap");
+    { const int rc = check_worklist(F, M, slots); if (rc) return rc; }   // before the staged cell is touched
     if (n_drop < 0) return fail(-EINVAL, "negative n_drop");
     const size_t cell = (size_t)f * B + b;
     size_t tot = 0;
-    {   // validate before touching the staged cell (same rules as set_tracks)
-      for (int t = 0; t < F; ++t) {
-        if (M[t] > m_cap || M[t] < 0) return fail(-E2BIG, "track longer than m_cap");
-        for (int k = 0; k < M[t]; ++k) if (slots[tot + k] < 0 || slots[tot + k] >= n_cap) return fail(-EINVAL, "camera slot out of range");
-        if (repeated_slot(slots + tot, M[t])) return fail(-EINVAL, "camera slot repeated within a track");
-        tot += M[t];
-      }
-    }
+    for (int t = 0; t < F; ++t) tot += M[t];
     for (int k = 0; k < sc_K; ++k) for (int c = 0; c < RD_STRIDE; ++c) h_rd[(cell * sc_K + k) * RD_STRIDE + c] = (S)rd[k * RD_STRIDE + c];
     h_n[cell] = F; h_drop[cell] = n_drop;
     for (int t = 0; t < f_cap; ++t) h_M[cell * f_cap + t] = t < F ? M[t] : 0;
@@ -1253,6 +1174,15 @@ struct Batch : BatchBase {
     committed = false;               // offsets move: the resident copy and the frame's page-locked block are stale until the next commit
     unpin_frame(f);                  // (its chunk is released with the last of its frames: patch -> commit -> stream cycles do not grow)
     return 0;
+  }
+  // the compact cells of frame f, trajectory after trajectory, as one contiguous block: slots to hs, coordinates to ho
+  void gather_frame(int f, int* hs, S* ho) const {
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+      const size_t cell = (size_t)f * B + b, n = c_slots[cell].size();
+      if (n) { std::memcpy(hs + o, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * o, c_obs[cell].data(), 2 * n * sizeof(S)); }
+      o += n;
+    }
   }
   // H2D of everything staged.  The host copy is kept, so cells may be patched with scenario_set and committed again.
   int scen_commit() override {
@@ -1300,12 +1230,7 @@ struct Batch : BatchBase {
       int rc = stage_acquire(nf * (sizeof(int) + 2 * sizeof(S)), &raw);
       if (rc) return rc;
       int* hs = reinterpret_cast<int*>(raw); S* ho = reinterpret_cast<S*>(raw + nf * sizeof(int));
-      size_t o = 0;
-      for (size_t b = 0; b < Bz; ++b) {
-        const size_t cell = (size_t)f * Bz + b, n = c_slots[cell].size();
-        if (n) { std::memcpy(hs + o, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * o, c_obs[cell].data(), 2 * n * sizeof(S)); }
-        o += n;
-      }
+      gather_frame(f, hs, ho);
       HIPCHK(hipMemcpyAsync(sc_slots + fr_base[f], hs, nf * sizeof(int), hipMemcpyHostToDevice, st));
       HIPCHK(hipMemcpyAsync(sc_obs + 2 * fr_base[f], ho, 2 * nf * sizeof(S), hipMemcpyHostToDevice, st));
       rc = stage_release();
@@ -1321,13 +1246,12 @@ struct Batch : BatchBase {
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     DEVICE_ENTER();
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t Bz = B;
     size_t need = 0, maxb = sg_bytes;
     std::vector<int> todo;
     for (int f = f0; f < f1; ++f) {
       const size_t nf = fr_base[f + 1] - fr_base[f];
-      const size_t off_obs = al(pk_slots + nf * sizeof(int)), bytes = al(off_obs + 2 * nf * sizeof(S));
+      const size_t off_obs = al256(pk_slots + nf * sizeof(int)), bytes = al256(off_obs + 2 * nf * sizeof(S));
       maxb = std::max(maxb, bytes);
       if (pinf[f].p) continue;
       pinf[f].bytes = bytes; pinf[f].off_obs = off_obs;
@@ -1352,13 +1276,7 @@ struct Batch : BatchBase {
         std::memcpy(blk + pk_drop, h_drop.data() + c0, Bz * sizeof(int));
         std::memcpy(blk + pk_M, h_M.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
         std::memcpy(blk + pk_off, h_off.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
-        int* hs = reinterpret_cast<int*>(blk + pk_slots); S* ho = reinterpret_cast<S*>(blk + pinf[f].off_obs);
-        size_t e = 0;
-        for (size_t b = 0; b < Bz; ++b) {
-          const size_t cell = c0 + b, n = c_slots[cell].size();
-          if (n) { std::memcpy(hs + e, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * e, c_obs[cell].data(), 2 * n * sizeof(S)); }
-          e += n;
-        }
+        gather_frame(f, reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs));
         pinf[f].p = blk; pinf[f].chunk = ci;
         o += pinf[f].bytes;
       }
@@ -1384,21 +1302,104 @@ struct Batch : BatchBase {
     ring = depth; up_mode = mode;
     return 0;
   }
-  // streams of the nh slices of a run
-  int slice_streams(int nh, hipStream_t* qs) {
-    for (int i = 0; i < nh; ++i) qs[i] = stx[i];
-    return 0;
+  // ---- the frame loop of a scenario (run_frames, run_frames_streamed)
+  // Trajectories are independent, so the batch may be cut into slices that run the same kernel sequence on separate streams:
+  // the latency-bound stages of one slice (gain solve, Cholesky, propagate: one workgroup per trajectory) overlap with the
+  // chip-filling stages of the others.  One host thread per slice enqueues that slice's kernels for all frames of the call
+  // (~13 launches per frame and slice would otherwise serialise on one thread and make more than two slices launch-bound).
+  // Stage profiling forces a single stream.
+  int n_slices() const { return prof ? 1 : std::max(1, std::min(nstreams, B)); }
+  // slice hh of nh on its enqueue thread: trajectories [b0, b0 + nb) on stream q.  A frame whose prune rides on the downdate
+  // leaves the covariance in the other buffer (curP / spare) and the new window size for the next k_propagate to commit (pending)
+  struct Slice { int hh, b0, nb; hipStream_t q; S* curP; S* spare; bool pending; };
+  Slice begin_slice(int hh, int nh) {
+    (void)hipSetDevice(device);
+    (void)hipGetLastError();
+    const int b0 = (int)((long)B * hh / nh);
+    return Slice{hh, b0, (int)((long)B * (hh + 1) / nh) - b0, stx[hh], d.P, P_spare, false};
   }
-  int fork_slices(int nh, hipStream_t* qs, hipStream_t extra = nullptr) {
+  // where a frame's inputs are on the device, for a slice that starts at trajectory b0: per-trajectory arrays already offset
+  // to b0, slots / obs the frame's compact entries (tracks find theirs through off)
+  struct FrameIn { const S* rd; const int* n; const int* M; const int* off; const int* slots; const S* obs; const int* drop; };
+  FrameIn resident_frame(int f, int b0) const {
+    const size_t c = (size_t)f * B + b0;
+    return FrameIn{sc_rd + c * sc_K * RD_STRIDE, sc_n + c, sc_M + c * f_cap, sc_off + c * f_cap, sc_slots + fr_base[f], sc_obs + 2 * fr_base[f], sc_drop + c};
+  }
+  FrameIn staged_frame(int f, int k, int b0) const {   // frame f as uploaded into staging set k
+    unsigned char* blk = sg_blk[k];
+    return FrameIn{reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, reinterpret_cast<int*>(blk + pk_n) + b0,
+                   reinterpret_cast<int*>(blk + pk_M) + (size_t)b0 * f_cap, reinterpret_cast<int*>(blk + pk_off) + (size_t)b0 * f_cap,
+                   reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs), reinterpret_cast<int*>(blk + pk_drop) + b0};
+  }
+  // THE frame step: frame f of a call over [f0, f1) for slice s, inputs at `in` -- propagate + augmentState, the update, the
+  // prune (on the downdate or with its own launch, fuse_frame), the host mirror of the window size.
+  // may_overlap (resident inputs only): k_feature reads only what the previous frame's prune left behind -- camera states and
+  // P blocks of slots below the newest one, the constant gravity vector -- unless a track observes the camera this frame's
+  // augmentState adds.  When none does (host mirror of the window sizes, slots known since scenario_set) and the handle asks
+  // for it (set_feature_overlap) it runs on a side stream concurrently with the latency-bound propagate + augment.
+  void enqueue_frame(Slice& s, int f, int f0, int f1, const FrameIn& in, bool may_overlap) {
+    const int b0 = s.b0, nb = s.nb, hh = s.hh;
+    hipStream_t q = s.q;
+    const size_t cell0 = (size_t)f * B;
+    Dev<S> v = d;
+    v.P = s.curP; v.ncam_defer = s.pending ? 1 : 0;
+    const bool fuse = fuse_frame(f, f1);
+    v.trk_n = in.n; v.trk_M = in.M; v.trk_off = in.off; v.trk_slots = in.slots; v.trk_obs = in.obs;
+    v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
+    bool early = may_overlap && overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
+    for (int b = b0; b < b0 + nb && early; ++b) {
+      const int n_after = std::min(h_ncam[b] + 1, n_cap);
+      early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2;
+    }
+    if (early) {
+      (void)hipEventRecord(ev_fa[hh], q);
+      (void)hipStreamWaitEvent(sty[hh], ev_fa[hh], 0);
+      Dev<S> v2 = v; v2.ncam_bias = 1;
+      v2.compress = update_compress(v2.compress);
+      launch_feature<S>(v2, b0, nb, sty[hh]);
+      (void)hipEventRecord(ev_fb[hh], sty[hh]);
+    }
+    // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
+    {
+      StageRange r("imu_prop+msckf_augment_state");
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
+      if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
+    }
+    if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
+    v.ncam_defer = 0;
+    if (fuse) { v.Pout = s.spare; v.fuse_drop = in.drop; }
+    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1); }
+    if (fuse) std::swap(s.curP, s.spare);
+    else {
+      StageRange r("msckf_prune_empty_states");
+      stage_begin(6, q);
+      launch_prune<S>(v, b0, nb, q, in.drop, 0);
+      stage_end(6, q);
+    }
+    s.pending = fuse;
+    for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment, then drop n_drop (clamped as k_make_keep does)
+      if (h_ncam[b] < n_cap) h_ncam[b]++;
+      h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
+    }
+  }
+  // fork: the slices' streams (and the copy stream of a streamed run) start after what is queued on st
+  int fork_slices(int nh, hipStream_t extra = nullptr) {
     if (nh <= 1 && !extra) return 0;
     HIPCHK(hipEventRecord(ev_fork, st));
-    for (int i = 0; i < nh; ++i) if (qs[i] != st) HIPCHK(hipStreamWaitEvent(qs[i], ev_fork, 0));
+    for (int i = 1; i < nh; ++i) HIPCHK(hipStreamWaitEvent(stx[i], ev_fork, 0));
     if (extra) HIPCHK(hipStreamWaitEvent(extra, ev_fork, 0));
     return 0;
   }
-  int join_slices(int nh, hipStream_t* qs) {
+  // the end of a call whose frames are enqueued: st waits for the slices (and the copy stream); a launch error of any slice
+  // (slice_rc: hipGetLastError is per host thread, a failed launch must not vanish with its thread) makes the handle
+  // unusable; otherwise the covariance buffer that is current now becomes the handle's
+  int finish_slices(int nh, const int* slice_rc, int f0, int f1, hipStream_t extra = nullptr) {
+    for (int i = 1; i < nh; ++i)
+      if (hipEventRecord(ev_join[i], stx[i]) != hipSuccess || hipStreamWaitEvent(st, ev_join[i], 0) != hipSuccess) return poison(-EIO, "joining the slices' streams failed");
+    if (extra && (hipEventRecord(ev_join[1], extra) != hipSuccess || hipStreamWaitEvent(st, ev_join[1], 0) != hipSuccess)) return poison(-EIO, "joining the copy stream failed");
     for (int i = 0; i < nh; ++i)
-      if (qs[i] != st) { HIPCHK(hipEventRecord(ev_join[i], qs[i])); HIPCHK(hipStreamWaitEvent(st, ev_join[i], 0)); }
+      if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
+    commit_buffer_parity(f0, f1);
     return 0;
   }
   int sync() override {
@@ -1485,78 +1486,14 @@ int Batch<S>::run_frames(int f0, int f1) {
   if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
   if (!committed) return fail(-EINVAL, "scenario not committed");
   DEVICE_ENTER();
-  // Trajectories are independent, so the batch may be cut into slices that run the same kernel sequence on
-  // separate streams: the latency-bound stages of one slice (gain solve, Cholesky, propagate: one workgroup per
-  // trajectory) overlap with the chip-filling stages of the others.  Stage profiling forces a single stream.
-  const int nh = prof ? 1 : std::max(1, std::min(nstreams, B));
-  hipStream_t qs[MAXS];
-  int rc = slice_streams(nh, qs);
+  const int nh = n_slices();
+  const int rc = fork_slices(nh);
   if (rc) return rc;
-  rc = fork_slices(nh, qs);
-  if (rc) return rc;
-  // one host thread per slice enqueues that slice's kernels for all frames: ~13 launches per frame and slice would
-  // otherwise serialise on one thread and make more than two slices launch-bound
   int slice_rc[MAXS] = {0};
   auto enqueue = [&](int hh) {
-    (void)hipSetDevice(device);
-    (void)hipGetLastError();
-    hipStream_t q = qs[hh];
-    const int b0 = (int)((long)B * hh / nh);
-    const int nb = (int)((long)B * (hh + 1) / nh) - b0;
-    S* curP = d.P; S* spare = P_spare;   // a frame whose prune rides on the downdate leaves the covariance in the other buffer
-    bool pending = false;                // ... and the new window size for the next k_propagate to commit
-    for (int f = f0; f < f1; ++f) {
-      const size_t cell0 = (size_t)f * B;
-      Dev<S> v = d;
-      v.P = curP; v.ncam_defer = pending ? 1 : 0;
-      // the call's last frame prunes with its own launch: ncam must be final when run_frames returns
-      const bool fuse = fuse_prune && !prof && !overlap_feature && d.joseph == 0 && f + 1 < f1;
-      v.trk_n = sc_n + cell0 + b0; v.trk_M = sc_M + (cell0 + b0) * f_cap; v.trk_off = sc_off + (cell0 + b0) * f_cap;
-      v.trk_slots = sc_slots + fr_base[f]; v.trk_obs = sc_obs + 2 * fr_base[f];
-      v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
-      // k_feature reads only what the previous frame's prune left behind -- camera states and P blocks of slots below the
-      // newest one, the constant gravity vector -- unless a track observes the camera this frame's augmentState adds.
-      // When none does (host mirror of the window sizes, slots known since scenario_set) it runs on a side stream
-      // concurrently with the latency-bound propagate + augment of the same frame.
-      bool early = overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
-      for (int b = b0; b < b0 + nb && early; ++b) {
-        const int n_after = std::min(h_ncam[b] + 1, n_cap);
-        early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2;
-      }
-      if (early) {
-        (void)hipEventRecord(ev_fa[hh], q);
-        (void)hipStreamWaitEvent(sty[hh], ev_fa[hh], 0);
-        Dev<S> v2 = v; v2.ncam_bias = 1;
-        v2.compress = update_compress(v2.compress);
-        launch_feature<S>(v2, b0, nb, sty[hh]);
-        (void)hipEventRecord(ev_fb[hh], sty[hh]);
-      }
-      // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
-      {
-        StageRange r("imu_prop+msckf_augment_state");
-        stage_begin(0, q); launch_propagate<S>(v, b0, nb, sc_rd + (cell0 + b0) * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
-        if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
-      }
-      if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
-      v.ncam_defer = 0;
-      if (fuse) { v.Pout = spare; v.fuse_drop = (const int*)(sc_drop + cell0 + b0); }
-      { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1); }
-      if (fuse) { std::swap(curP, spare); pending = true; }
-      else {
-        StageRange r("msckf_prune_empty_states");
-        stage_begin(6, q);
-        launch_prune<S>(v, b0, nb, q, (const int*)(sc_drop + cell0 + b0), 0);
-        stage_end(6, q);
-        pending = false;
-      }
-      for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment, then drop n_drop (clamped as k_make_keep does)
-        if (h_ncam[b] < n_cap) h_ncam[b]++;
-        h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
-      }
-    }
-    // hipGetLastError is per host thread: a failed launch of this slice must not vanish with the thread
-    const hipError_t e = hipGetLastError();
-    slice_rc[hh] = (int)e;
+    Slice s = begin_slice(hh, nh);
+    for (int f = f0; f < f1; ++f) enqueue_frame(s, f, f0, f1, resident_frame(f, s.b0), true);
+    slice_rc[hh] = (int)hipGetLastError();
   };
   if (nh == 1) enqueue(0);
   else {
@@ -1564,12 +1501,7 @@ int Batch<S>::run_frames(int f0, int f1) {
     enqueue(0);
     workers.wait();
   }
-  rc = join_slices(nh, qs);
-  if (rc) return poison(rc, "joining the slices' streams failed");
-  for (int i = 0; i < nh; ++i)
-    if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
-  commit_buffer_parity(f0, f1);
-  return 0;
+  return finish_slices(nh, slice_rc, f0, f1);
 }
 
 // run_frames with the inputs handed over per frame, as the reference's callers do (asl_msckf.cpp:227-284: IMU samples and
@@ -1598,12 +1530,9 @@ int Batch<S>::run_frames_streamed(int f0, int f1) {
       for (int i = 0; i < MAXS; ++i) HIPCHK(hipEventCreateWithFlags(&ev_use[k][i], hipEventDisableTiming));
     }
   }
-  const int nh = prof ? 1 : std::max(1, std::min(nstreams, B));
+  const int nh = n_slices();
   const int R = ring, mode = up_mode;
-  hipStream_t qs[MAXS];
-  int rc = slice_streams(nh, qs);
-  if (rc) return rc;
-  rc = fork_slices(nh, qs, stc);
+  const int rc = fork_slices(nh, stc);
   if (rc) return rc;
   // up_rdy = frames whose block may be read (mode 0: the copy has completed; mode 1: copy + event record are enqueued --
   // an event must be recorded before a wait on it is enqueued); use_enq[s] = frames whose "consumed" record is enqueued.
@@ -1613,43 +1542,14 @@ int Batch<S>::run_frames_streamed(int f0, int f1) {
   std::atomic<int> failed{0};
   int slice_rc[MAXS] = {0};
   auto slice = [&](int hh) {
-    (void)hipSetDevice(device);
-    (void)hipGetLastError();
-    hipStream_t q = qs[hh];
-    const int b0 = (int)((long)B * hh / nh);
-    const int nb = (int)((long)B * (hh + 1) / nh) - b0;
-    S* curP = d.P; S* spare = P_spare;
-    bool pending = false;
+    Slice s = begin_slice(hh, nh);
     for (int f = f0; f < f1; ++f) {
       while (up_rdy.load(std::memory_order_acquire) <= f && !failed.load()) std::this_thread::yield();
       if (failed.load()) break;
       const int k = (f - f0) % R;
-      unsigned char* blk = sg_blk[k];
-      if (mode == 1) (void)hipStreamWaitEvent(q, ev_up[k], 0);
-      Dev<S> v = d;
-      v.trk_n = reinterpret_cast<int*>(blk + pk_n) + b0; v.trk_M = reinterpret_cast<int*>(blk + pk_M) + (size_t)b0 * f_cap;
-      v.trk_off = reinterpret_cast<int*>(blk + pk_off) + (size_t)b0 * f_cap;
-      v.trk_slots = reinterpret_cast<int*>(blk + pk_slots); v.trk_obs = reinterpret_cast<S*>(blk + pinf[f].off_obs);
-      v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
-      v.P = curP; v.ncam_defer = pending ? 1 : 0;
-      const bool fuse = fuse_prune && !prof && !overlap_feature && d.joseph == 0 && f + 1 < f1;   // as in run_frames
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
-      if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
-      v.ncam_defer = 0;
-      if (fuse) { v.Pout = spare; v.fuse_drop = (const int*)(reinterpret_cast<int*>(blk + pk_drop) + b0); }
-      launch_update(v, b0, nb, q, false, 1);
-      if (fuse) { std::swap(curP, spare); pending = true; }
-      else {
-        stage_begin(6, q);
-        launch_prune<S>(v, b0, nb, q, (const int*)(reinterpret_cast<int*>(blk + pk_drop) + b0), 0);
-        stage_end(6, q);
-        pending = false;
-      }
-      (void)hipEventRecord(ev_use[k][hh], q);
-      for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size
-        if (h_ncam[b] < n_cap) h_ncam[b]++;
-        h_ncam[b] -= std::max(0, std::min(h_drop[(size_t)f * B + b], h_ncam[b]));
-      }
+      if (mode == 1) (void)hipStreamWaitEvent(s.q, ev_up[k], 0);
+      enqueue_frame(s, f, f0, f1, staged_frame(f, k, s.b0), false);
+      (void)hipEventRecord(ev_use[k][hh], s.q);
       use_enq[hh].store(f + 1, std::memory_order_release);
     }
     slice_rc[hh] = (int)hipGetLastError();
@@ -1675,17 +1575,10 @@ int Batch<S>::run_frames_streamed(int f0, int f1) {
     if (rc_up) failed.store(1);
     up_rdy.store(f + 1, std::memory_order_release);
   }
-  if (rc_up) failed.store(1);
   workers.wait();
   if (repin) (void)pthread_setaffinity_np(pthread_self(), sizeof(old_mask), &old_mask);
   if (rc_up) return poison(rc_up, "input upload failed");
-  rc = join_slices(nh, qs);
-  if (rc) return poison(rc, "joining the slices' streams failed");
-  if (hipEventRecord(ev_join[1], stc) != hipSuccess || hipStreamWaitEvent(st, ev_join[1], 0) != hipSuccess) return poison(-EIO, "joining the copy stream failed");
-  for (int i = 0; i < nh; ++i)
-    if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
-  commit_buffer_parity(f0, f1);
-  return 0;
+  return finish_slices(nh, slice_rc, f0, f1, stc);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -1743,6 +1636,17 @@ int resolve_map(BatchBase* B, int b) {
   return 0;
 }
 
+// retire what every trajectory of the range planned: one prune launch for the range, then the host lists
+static int prune_retired_range(BatchBase* B, int b0, const std::vector<Retirement>& ret) {
+  const int nb = (int)ret.size();
+  std::vector<std::vector<int>> keep(nb);
+  for (int i = 0; i < nb; ++i) keep[i] = ret[i].keep;
+  const int rc = B->prune_keep_range(b0, nb, keep);
+  if (rc) return rc;
+  for (int i = 0; i < nb; ++i) retire_commit(B->traj[b0 + i], ret[i]);
+  return 0;
+}
+
 int host_prune_empty(BatchBase* B, int b) {
   HostTraj& t = B->traj[b];
   const int last_to_remove = plan_prune_empty(t);
@@ -1752,12 +1656,9 @@ int host_prune_empty(BatchBase* B, int b) {
   std::vector<double> poses((size_t)num * 7);
   int rc = B->get_cams_known(b, poses.data(), num);
   if (rc) return rc;
-  Retirement ret;
-  retire_plan_leading(t, poses.data(), last_to_remove, ret);
-  rc = B->prune_keep(b, ret.keep);
-  if (rc) return rc;
-  retire_commit(t, ret);
-  return 0;
+  std::vector<Retirement> ret(1);
+  retire_plan_leading(t, poses.data(), last_to_remove, ret[0]);
+  return prune_retired_range(B, b, ret);
 }
 
 // MSCKF::pruneRedundantStates, msckf.h:453-682: keyframe selection and observation surgery on the host (host_lists.h),
@@ -1780,10 +1681,9 @@ int host_prune_redundant(BatchBase* B, int b) {
   if (!wl.M.empty()) {
     rc = set_tracks(B, b, wl);
     if (rc) return rc;
-    const int C = (int)wl.M.size();
-    std::vector<int> status(C); std::vector<double> pf(3 * (size_t)C);
-    rc = B->feature_only(b, status.data(), pf.data(), C);
-    if (rc < 0) return rc;
+    std::vector<int> status(B->f_cap); std::vector<double> pf(3 * (size_t)B->f_cap);
+    rc = B->feature_only_range(b, 1, status.data(), pf.data(), true);
+    if (rc) return rc;
     redundant_apply_candidates(t, plan, status.data(), pf.data());
   }
   // ---- second loop :545-607
@@ -1792,21 +1692,18 @@ int host_prune_redundant(BatchBase* B, int b) {
   if (!wl.M.empty()) {
     rc = set_tracks(B, b, wl);
     if (rc) return rc;
-    rc = B->set_given_positions(b, (int)wl.M.size(), pfin.data());
+    rc = B->set_given_range(b, 1, pfin.data());
     if (rc) return rc;
-    rc = B->marginalize_given_range(b, 1);
+    rc = B->marginalize(b, 1, 1);
     if (rc) return rc;
   }
   redundant_finish(t, plan);
   // ---- prune the removed camera states :616-681, poses as corrected by the second update (msckf.h:614 precedes :631)
   rc = B->get_cams_known(b, poses.data(), n);
   if (rc) return rc;
-  Retirement ret;
-  retire_plan_ids(t, poses.data(), plan.rm, ret);
-  rc = B->prune_keep(b, ret.keep);
-  if (rc) return rc;
-  retire_commit(t, ret);
-  return 0;
+  std::vector<Retirement> ret(1);
+  retire_plan_ids(t, poses.data(), plan.rm, ret[0]);
+  return prune_retired_range(B, b, ret);
 }
 
 int host_finish(BatchBase* B, int b) {
@@ -1869,17 +1766,6 @@ template <class Fn> static int for_runs(const std::vector<char>& on, int b0, Fn 
 }
 static bool any_of(const std::vector<char>& on) { for (char c : on) if (c) return true; return false; }
 
-// retire what every trajectory of the range planned: one prune launch for the range, then the host lists
-static int prune_retired_range(BatchBase* B, int b0, const std::vector<Retirement>& ret) {
-  const int nb = (int)ret.size();
-  std::vector<std::vector<int>> keep(nb);
-  for (int i = 0; i < nb; ++i) keep[i] = ret[i].keep;
-  const int rc = B->prune_keep_range(b0, nb, keep);
-  if (rc) return rc;
-  for (int i = 0; i < nb; ++i) retire_commit(B->traj[b0 + i], ret[i]);
-  return 0;
-}
-
 int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const double* times,
                      const double* upd_meas, const uint64_t* upd_ids, const int* upd_n,
                      const double* new_meas, const uint64_t* new_ids, const int* new_n, int flags) {
@@ -1897,11 +1783,7 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
   // ---- augmentState :148-212
   int rc = B->augment(b0, nb);
   if (rc) return rc;
-  for (int i = 0; i < nb; ++i) {
-    HostTraj& t = B->traj[b0 + i];
-    t.cams.push_back(CamMeta{state_ids[i], times ? times[i] : 0.0, -1, {}});
-    t.map.clear(); t.map_pending = 0;
-  }
+  for (int i = 0; i < nb; ++i) begin_image(B->traj[b0 + i], state_ids[i], times ? times[i] : 0.0);
   tick(0);
   // ---- update :215-300, addFeatures :302-332 (host)
   {
@@ -1981,7 +1863,7 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
       if (any_of(has_upd)) {
         rc = B->set_given_range(b0, nb, pfin.data());
         if (rc) return rc;
-        rc = for_runs(has_upd, b0, [&](int s0, int n) { return B->marginalize_given_range(s0, n); });
+        rc = for_runs(has_upd, b0, [&](int s0, int n) { return B->marginalize(s0, n, 1); });
         if (rc) return rc;
       }
       bool anyrm = false;
@@ -2083,9 +1965,7 @@ int msckf_hip_augment_state(msckf_hip_handle h, int b, int state_id, double time
   StageRange r("msckf_augment_state");
   int rc = B->augment(b, 1);
   if (rc) return rc;
-  B->traj[b].cams.push_back(CamMeta{state_id, time, -1, {}});
-  B->traj[b].map.clear();   // msckf.h:149
-  B->traj[b].map_pending = 0;   // (the points of the previous marginalize() still on the device belong to the map just cleared)
+  begin_image(B->traj[b], state_id, time);
   return 0;
 }
 int msckf_hip_update(msckf_hip_handle h, int b, const double* meas2, const uint64_t* ids, int n) {
@@ -2208,7 +2088,7 @@ int msckf_hip_last_deltax(msckf_hip_handle h, int b, double* dx, int cap) { retu
 int msckf_hip_set_tracks(msckf_hip_handle h, int b, int F, const int* M, const int* slots, const double* obs2) { return H(h)->set_tracks(b, F, M, slots, obs2); }
 int msckf_hip_propagate_range(msckf_hip_handle h, int b0, int nb, const double* readings7, int K) { return H(h)->propagate(b0, nb, readings7, K); }
 int msckf_hip_augment_range(msckf_hip_handle h, int b0, int nb) { return H(h)->augment(b0, nb); }
-int msckf_hip_marginalize_range(msckf_hip_handle h, int b0, int nb) { return H(h)->marginalize(b0, nb); }
+int msckf_hip_marginalize_range(msckf_hip_handle h, int b0, int nb) { return H(h)->marginalize(b0, nb, 0); }
 int msckf_hip_drop_oldest_range(msckf_hip_handle h, int b0, int nb, int n_drop) { return H(h)->drop_oldest(b0, nb, n_drop); }
 
 int msckf_hip_scenario_alloc(msckf_hip_handle h, int n_frames, int K) { return H(h)->scen_alloc(n_frames, K); }

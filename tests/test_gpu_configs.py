@@ -410,3 +410,31 @@ def test_failed_streamed_run_makes_the_handle_unusable(capi, monkeypatch):
     for b in range(B):
         assert np.array_equal(good.imu_state(b), ref.imu_state(b)) and np.array_equal(good.covariance(b), ref.covariance(b))
     good.close(); ref.close()
+
+
+def test_streamed_run_under_the_stage_timers_equals_the_resident_run(capi, cfg3_trajs):
+    """With the stage timers on (msckf_hip_profile_enable: one stream, augmentState and the prune as launches of their own)
+    run_frames_streamed goes through the same frame step as run_frames: same bits for every trajectory, and profile_read
+    counts the same number of launches per stage -- one propagate, augment, update sequence and prune per frame."""
+    c = CFG3
+    B, nf = 8, 33
+
+    def run(streamed):
+        bt = _resident_batch(capi, cfg3_trajs[:B], c["N"], c["F"], nf, 32, capi.F32, streams=3)
+        bt.profile_enable(True)
+        go = bt.run_frames_streamed if streamed else bt.run_frames
+        go(0, 20); go(20, nf); bt.sync()
+        prof = bt.profile_read()
+        bt.profile_enable(False)
+        snap = _snapshot(bt, B)
+        bt.close()
+        return snap, {stage: cnt for stage, (ms, cnt) in prof.items()}
+
+    ref, ref_cnt = run(False)
+    snap, cnt = run(True)
+    for stage in ("propagate", "augment", "feature", "select", "prune"):
+        assert ref_cnt[stage] == nf, (stage, ref_cnt)
+    assert cnt == ref_cnt, (cnt, ref_cnt)
+    for b in range(B):
+        for x, y in zip(snap[b], ref[b]):
+            assert np.array_equal(x, y), b

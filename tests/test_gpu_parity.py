@@ -858,3 +858,71 @@ def test_cfg5_geometry_runs_and_stays_consistent(capi):
         assert np.all(np.isfinite(P)) and np.array_equal(P, P.T) and np.all(np.diag(P) > 0)
         assert np.linalg.norm(bt.imu_state(b)[13:16] - trs[b].gt_frames["p"][nf - 1]) < 0.1
         assert bt.last_stats(b)["n_passed"] > 0.9 * F
+
+
+def test_work_list_rules_are_the_same_on_set_tracks_and_scenario_set(capi):
+    """The rules for a work-list -- at most f_cap tracks, a track at most m_cap long, every camera slot in [0, n_cap), no slot
+    twice within a track -- are stated once in the library.  Each single violation raises with the SAME code and message on
+    msckf_hip_set_tracks and on msckf_hip_scenario_set, before anything is staged or written: the valid list given afterwards
+    produces the same bits as on a handle that never saw a bad list."""
+    N, F, nf = 8, 24, 12
+    tr = sc.Trajectory(2, 7, N, F, nf)
+    k = nf - 1
+    fr = tr.frames[k]
+    assert len(fr["M"]) > 0 and max(fr["M"]) <= N - 1
+    bad_lists = [   # (M, slots, code, message)
+        ([2] * (F + 1), [0, 1] * (F + 1), -7, "more tracks than f_cap"),
+        ([N], list(range(N)), -7, "track longer than m_cap"),
+        ([3], [0, -1, 2], -22, "camera slot out of range"),
+        ([3], [0, N, 2], -22, "camera slot out of range"),
+        ([3], [0, 1, 1], -22, "camera slot repeated within a track"),
+    ]
+
+    def give_bad_lists(call):
+        said = []
+        for M, slots, code, msg in bad_lists:
+            with pytest.raises(capi.HipError, match=r"\(%d\): %s$" % (code, msg)) as ei:
+                call(M, slots, np.zeros((len(slots), 2)))
+            said.append(str(ei.value))
+        return said
+
+    def per_call(with_bad):
+        bt = capi.Batch(1, N, F, N - 1, capi.F64)          # n_cap > m_cap: a track can be too long with every slot valid
+        bt.initialize(0, tr.cfg, tr.imu0)
+        for j in range(k):
+            H.device_frame(bt, 0, tr, j, N)
+        bt.propagate_range(0, 1, tr.imu_for_frame(k)); bt.augment_range(0, 1)
+        said = give_bad_lists(lambda M, s, o: bt.set_tracks(0, M, s, o)) if with_bad else None
+        bt.set_tracks(0, fr["M"], fr["slots"], fr["obs"]); bt.marginalize_range(0, 1)
+        out = bt.imu_state(0), bt.cam_states(0)[0], bt.covariance(0), bt.last_stats(0)
+        bt.close()
+        return out, said
+
+    def resident(with_bad):
+        bt = capi.Batch(1, N, F, N - 1, capi.F64)
+        bt.initialize(0, tr.cfg, tr.imu0)
+        bt.scenario_alloc(nf, sc.IMU_PER_FRAME)
+
+        def cell(j):
+            f = tr.frames[j]
+            bt.scenario_set(j, 0, tr.imu_for_frame(j), f["M"], f["slots"], f["obs"], 1 if f["Nw"] == N else 0)
+        for j in range(nf):
+            cell(j)
+        said = give_bad_lists(lambda M, s, o: bt.scenario_set(k, 0, tr.imu_for_frame(k), M, s, o, 0)) if with_bad else None
+        if with_bad:
+            cell(k)
+        bt.scenario_commit()
+        bt.run_frames(0, nf); bt.sync()
+        out = bt.imu_state(0), bt.cam_states(0)[0], bt.covariance(0), bt.last_stats(0)
+        bt.close()
+        return out, said
+
+    said_by = []
+    for run in (per_call, resident):
+        fresh, _ = run(False)
+        after, said = run(True)
+        assert fresh[3]["n_passed"] > 0 and fresh[3] == after[3]
+        for x, y in zip(fresh[:3], after[:3]):
+            assert np.array_equal(x, y), run.__name__
+        said_by.append(said)
+    assert said_by[0] == said_by[1]
