@@ -5,44 +5,40 @@
 // (msckf.h:215-332, 685-717, 1469-1485) -- and turns it into positional work-lists for the device.
 // Everything numerical (msckf.h:101-212, 336-449, 905-1423) runs in the HIP kernels of kernels_*.hip; there
 // is no CPU fallback: if no HIP device is usable msckf_hip_create fails.
-// What one frame of a scenario enqueues -- run_frames on resident inputs, run_frames_streamed on uploaded ones -- is
-// Batch<S>::enqueue_frame; the rules for a work-list are Batch<S>::check_worklist; the per-filter entries are the range
-// entries with nb = 1.
+// A handle is a BatchCore -- everything that is the same for float and double: streams, staging, the frame loops run_frames /
+// run_frames_streamed, the work-list rules BatchCore::check_worklist -- with the typed half Batch<S> on top: the device
+// buffers, the launches, the conversions between S and double.  What one frame of a scenario enqueues is
+// Batch<S>::enqueue_frame; the per-filter entries are the range entries with nb = 1.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
+#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <dlfcn.h>
 #include <cstring>
-#include <string>
-#include <vector>
-#include <chrono>
-#include <unordered_map>
-#include <unordered_set>
-
-#include "../../include/msckf_hip.h"
-#include <atomic>
-#include <condition_variable>
+#include <dlfcn.h>
 #include <functional>
 #include <mutex>
+#include <string>
 #include <thread>
+#include <utility>
+#include <vector>
 #include <pthread.h>
 #include <sched.h>
+
+#include "../../include/msckf_hip.h"
 #include "dev_common.h"
 #include "host_lists.h"
-
 
 namespace {
 using namespace msckf;
 using namespace msckf_lists;
 static_assert(TRK_MOTION_OK == ST_MOTION_OK && TRK_TRI_VALID == ST_TRI_VALID && TRK_MOTION_SKIPPED == ST_MOTION_SKIPPED, "host_lists.h reads the feature kernel's status bits");
-
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 // rocTX ranges under the reference's stage names (asl_msckf.cpp:229-296: imu_prop, msckf_augment_state, msckf_update,
 // msckf_add_features, msckf_marginalize, msckf_prune_redundant, msckf_prune_empty_states) around the host side of every stage,
@@ -68,71 +64,16 @@ struct StageRange {
   ~StageRange() { if (on) roctx().pop(); }
 };
 
+// the text behind msckf_hip_last_error(), per calling thread
+thread_local std::string g_err;
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
+
 #define HIPCHK(expr)                                                                         \
   do {                                                                                       \
     hipError_t e_ = (expr);                                                                  \
     if (e_ != hipSuccess) return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-struct BatchBase {
-  virtual ~BatchBase() {}
-  int B = 0, n_cap = 0, f_cap = 0, m_cap = 0, dtype = 0, device = 0;
-  bool h16 = false;   // dtype MSCKF_HIP_F16H_F32P: fp16 measurement Jacobian, f32 state and covariance
-  std::vector<HostTraj> traj;
-  virtual int init(int b, const double* cam, const double* noise, const double* params, const double* imu) = 0;
-  virtual int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) = 0;
-  virtual int propagate(int b0, int nb, const double* rd, int K, bool mirror = false) = 0;
-  virtual int augment(int b0, int nb) = 0;
-  virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
-  virtual int marginalize(int b0, int nb, int mode = 0) = 0;   // mode 1: the second update of pruneRedundantStates (stored p_f_G per track, set_given_range)
-  // range forms (one copy / one launch for trajectories b0 .. b0 + nb - 1): the batched image cycle (host_image_cycle), and
-  // the per-filter entries with nb = 1
-  virtual int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) = 0;           // every trajectory's list in one pinned block, two copies
-  virtual int cams_range(int b0, int nb, double* poses7) = 0;                                  // [nb][n_cap][7], one read + one wait
-  virtual int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) = 0;   // checkMotion + triangulation of the work-lists: [nb][f_cap], [nb][f_cap][3]; launch = false: only read what the last launch left
-  virtual int set_given_range(int b0, int nb, const double* pf3) = 0;                          // [nb][f_cap][3]
-  virtual int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) = 0; // keep[i]: ascending slots of trajectory b0 + i
-  virtual int drop_oldest(int b0, int nb, int n) = 0;
-  virtual int get_ncam(int b, int* n) = 0;
-  virtual int ncam_host(int b) const = 0;   // the window size from the host's own count (kept through every entry that changes it): no device read
-  virtual int get_imu(int b, double* o) = 0;
-  virtual int set_imu(int b, const double* in) = 0;
-  virtual int get_cams(int b, double* o, int cap, int* n) = 0;
-  virtual int get_cams_known(int b, double* o, int n) = 0;   // n known to the caller: cameras + (into the host copy) the IMU state, one wait
-  virtual int set_cam(int b, int slot, const double* in) = 0;
-  virtual int get_cov(int b, double* P, int ldo) = 0;
-  virtual int set_cov(int b, const double* P, int D) = 0;
-  virtual int get_nres(int b, long long* n) = 0;
-  virtual int set_nres(int b, long long n) = 0;
-  virtual int stats(int b, int* out) = 0;
-  virtual int track_info(int b, double* out, int cap) = 0;
-  virtual int deltax(int b, double* out, int cap) = 0;
-  virtual int scen_alloc(int n_frames, int K) = 0;
-  virtual int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) = 0;
-  virtual int scen_commit() = 0;
-  virtual int run_frames(int f0, int f1) = 0;
-  virtual int run_frames_streamed(int f0, int f1) = 0;
-  virtual int scen_pin(int f0, int f1) = 0;
-  virtual int set_upload_ring(int depth, int mode) = 0;
-  virtual int sync() = 0;
-  virtual int prof_enable(int on) = 0;
-  virtual int prof_read(double* ms, int* cnt, int cap) = 0;
-  virtual int prof_event_overhead(double* ms) = 0;
-  virtual int set_streams(int n) = 0;
-  virtual int set_host_affinity(const int* cpus, int n) = 0;
-  virtual int set_gate_early(int on) = 0;
-  virtual int set_compression(int route) = 0;
-  virtual int set_cov_update(int form) = 0;
-  virtual int set_feature_overlap(int on) = 0;
-  virtual int clear_stats(int b) = 0;
-  virtual int clear_errors(int b) = 0;
-  virtual int set_aniso(int mode, double tol) = 0;
-  virtual int error_flags(int b, int* flags) = 0;
-  virtual int copy_from(BatchBase* src) = 0;
-  virtual int lit_info(int b, int* out8) = 0;
-};
-
-int resolve_map(BatchBase* B, int b);   // (defined with the host-side bookkeeping below)
 constexpr int NSTAGE = 11;   // 0..7: msckf_hip_profile_read; 8 k_lit_pre, 9 k_lit_gamma, 10 k_literal (msckf_hip_profile_read_ex)
 
 // Persistent enqueue threads of a batch (one per slice of run_frames / run_frames_streamed): a K-frame window is a few
@@ -193,14 +134,15 @@ struct Workers {
   }
 };
 
-template <class S>
-struct Batch : BatchBase {
-  Dev<S> d{};
+struct BatchCore {
+  int B = 0, n_cap = 0, f_cap = 0, m_cap = 0, dtype = 0, device = 0;
+  bool h16 = false;   // dtype MSCKF_HIP_F16H_F32P: fp16 measurement Jacobian, f32 state and covariance
+  size_t esz = 0;     // sizeof(S) of the typed half (set with the handle's dtype): element size of every buffer the core only moves as bytes
+  std::vector<HostTraj> traj;
   hipStream_t st = nullptr;
   static constexpr int MAXS = 8;     // run_frames can run up to MAXS slices of the batch concurrently
   hipStream_t stx[MAXS] = {nullptr}; // stx[0] == st
   hipEvent_t ev_fork = nullptr, ev_join[MAXS] = {nullptr};
-  int nstreams = 1;
   std::vector<void*> allocs;
   // pinned host staging of the per-call inputs (single-filter API): filled, copied asynchronously, reused only after
   // ev_stage says the previous copy has left it -- the calls themselves do not wait for the device
@@ -213,26 +155,25 @@ struct Batch : BatchBase {
   // slot its work-list touches: run_frames overlaps k_feature with propagate + augment when no track sees the newest camera
   std::vector<int> h_ncam, h_maxslot;
   hipStream_t sty[MAXS] = {nullptr}; hipEvent_t ev_fa[MAXS] = {nullptr}, ev_fb[MAXS] = {nullptr};
-  S* P_spare = nullptr;   // second covariance buffer: target of a downdate that carries the frame's prune (Dev::Pout)
-  int fuse_prune = 1;     // run_frames: prune rides on the downdate (MSCKF_HIP_FUSE_PRUNE=0: separate k_prune_inplace launch)
+  // the settings a copy of the handle takes over (copy_from assigns the group; the knobs inside Dev<S> and the anisotropic-noise
+  // mode travel with the typed half).  What follows the group stays with its own handle.
+  struct Knobs {
+    int nstreams = 1;
+    int fuse_prune = 1;        // run_frames: prune rides on the downdate (MSCKF_HIP_FUSE_PRUNE=0: separate k_prune_inplace launch)
+    int overlap_feature = 0;   // measured on MI355X at cfg3: 100 k -> 82 k updates/s with the overlap on (k_feature floods the CUs the
+                               // latency-bound propagate/augment workgroups need); kept selectable, off by default
+    int compress_route = -1;   // -1 default, 0 Householder TSQR, != 0 information form + blocked matrix-core Cholesky
+  } knobs;
   int small_update = 84;     // windows of at most this many camera columns (6 x cameras) take the one-launch update k_update_small; MSCKF_HIP_SMALL_UPDATE=0 switches it off
-  int overlap_feature = 0;   // measured on MI355X at cfg3: 100 k -> 82 k updates/s with the overlap on (k_feature floods the CUs the
-                             // latency-bound propagate/augment workgroups need); kept selectable, off by default
-  int compress_route = -1;   // -1 default, 0 Householder TSQR, != 0 information form + blocked matrix-core Cholesky
   int test_fail_upload = -1;  // test hook (MSCKF_HIP_TEST_FAIL_UPLOAD): run_frames_streamed pretends that this frame's copy failed
   // anisotropic pixel noise (u_var' != v_var'): 0 = the reference's construction R_o_j = A_j^T R_j A_j, R_n = Q_1^T R_o Q_1 on
   // the device (kernels_literal.hip; default), 1 = rows pre-whitened by 1/sigma (generalized least squares, unit noise)
   int aniso_mode = 0;
   int lit_route = 0;         // 0 the compact route; 1 the sweep over the dense stack (tests, A/B)
   double lit_tol = -1;       // zero-tail tolerance of the literal route; < 0: 1e-10 (double) / 8e-4 (float: H_x is float-rounded)
+  bool info_form = false;    // the information form's buffers exist (Dev::trk_B; set by the typed half's create)
   std::vector<double> h_uv;  // [B][2] u_var', v_var' as initialize() got them
-  // Host mirror of the IMU state for the single-filter API: getImuState() is called once per IMU sample by the reference's
-  // runner (asl_msckf.cpp:231) and must be synchronously available on the host (SURVEY.md 8b); between two images only
-  // propagate() changes it, and propogateImuStateRK (msckf.h:1425-1467) is a few hundred FLOP -- so msckf_hip_propagate
-  // advances this copy with the reference's own RK sequence while the device advances the state the filter uses, and
-  // msckf_hip_get_imu_state answers from it without a device round trip.  Any other device-side change of the state
-  // (marginalize, the batched calls) invalidates it; the next getter reads the device and re-validates.
-  std::vector<S> h_imu; std::vector<char> h_imu_ok;
+  std::vector<char> h_imu_ok;   // [B] the typed half's host copy of the IMU state is current (see Batch<S>::h_imu)
   std::vector<char> h_lit;   // [B] trajectory runs the literal route
   std::vector<char> h_qfull; // [B] trajectory carries a full Q_imu (its qf flag): k_propagate's full-Q instantiation runs it
   // launch_propagate's qroute for [b0, b0 + nb): 0 no trajectory with a full Q_imu, 1 some, 2 all
@@ -242,22 +183,23 @@ struct Batch : BatchBase {
     return n == 0 ? 0 : (n == nb ? 2 : 1);
   }
   int n_lit = 0;
-  // single-call staging on device
-  S* d_rd = nullptr; int rd_cap = 0;               // [B][rd_cap][7]
-  S* d_pfin = nullptr;                              // [B][f_cap][4] stored feature positions (mode 1)
+  // the device arrays of plain integers, as the typed half's create allocated them (Dev::ncam, ::n_resid, ::stats)
+  int* dv_ncam = nullptr; long long* dv_nres = nullptr; int* dv_stats = nullptr;
+  int rd_cap = 0;   // samples per trajectory that the single-call staging of propagate holds
+  void* h_rb = nullptr;   // page-locked landing area of the single-filter state read (get_cams_known): [n_cap][CAM_STRIDE] + [IMU_STRIDE] scalars
   // single-call work-lists: per trajectory ONE block of ints [n, 0, 0, 0 | M[f4] | slots[f_cap][m_cap]] (wl_ib ints; one copy per
   // set_tracks instead of three) and the observations [2 wl_ib] (the kernels index both with the same stride)
-  int* wl_i = nullptr; long wl_ib = 0; int wl_f4 = 0; S* wl_obs = nullptr;
-  S* h_rb = nullptr;           // page-locked landing area of the single-filter state read (get_cams_known): [n_cap][CAM_STRIDE] + [IMU_STRIDE]
+  int* wl_i = nullptr; long wl_ib = 0; int wl_f4 = 0;
   // scenario.  Work-lists are COMPACT: a cell (frame, trajectory) holds sum M_j (slot, observation) entries, track t of the
   // cell starts at off[cell][t] counted from the frame's first entry (Dev::trk_off) -- not [f_cap][m_cap] padded rows (1.9x
   // the payload at cfg3's track lengths, on the host, in HBM and in every per-frame upload).
+  // h_rd / sc_rd ([frames][B][K][RD_STRIDE]) and c_obs / sc_obs (coordinate pairs) hold scalars of esz bytes.
   int sc_frames = 0, sc_K = 0;
   bool committed = false;
-  S* sc_rd = nullptr; int* sc_n = nullptr; int* sc_M = nullptr; int* sc_off = nullptr; int* sc_drop = nullptr;
-  int* sc_slots = nullptr; S* sc_obs = nullptr; size_t sc_total = 0;      // sum over all cells
-  std::vector<S> h_rd; std::vector<int> h_n, h_M, h_off, h_drop;
-  std::vector<std::vector<int>> c_slots; std::vector<std::vector<S>> c_obs;   // per cell
+  unsigned char* sc_rd = nullptr; int* sc_n = nullptr; int* sc_M = nullptr; int* sc_off = nullptr; int* sc_drop = nullptr;
+  int* sc_slots = nullptr; unsigned char* sc_obs = nullptr; size_t sc_total = 0;      // sum over all cells
+  std::vector<unsigned char> h_rd; std::vector<int> h_n, h_M, h_off, h_drop;
+  std::vector<std::vector<int>> c_slots; std::vector<std::vector<unsigned char>> c_obs;   // per cell
   std::vector<size_t> fr_base;                                             // [frames + 1] first entry of a frame in sc_slots / sc_obs
   std::vector<void*> sc_allocs;
   // streamed inputs (run_frames_streamed): frame f's block [rd | n | drop | M | off | slots | obs] is copied from page-locked
@@ -280,6 +222,11 @@ struct Batch : BatchBase {
     }
     pinf[f] = PinFrame();
   }
+  void unpin_host() {
+    for (auto& q : pin_chunks) if (q.p) hipHostFree(q.p);
+    pin_chunks.clear();
+    for (auto& pf : pinf) pf = PinFrame();
+  }
   size_t pk_rd = 0, pk_n = 0, pk_drop = 0, pk_M = 0, pk_off = 0, pk_slots = 0;   // section offsets (256-byte aligned); obs follows the frame's slots
   Workers workers;   // enqueue threads of the slices
   // profiling
@@ -288,16 +235,16 @@ struct Batch : BatchBase {
   size_t ev_used[NSTAGE] = {0};
   double prof_ms[NSTAGE] = {0}; int prof_cnt[NSTAGE] = {0};
 
-  template <class T> int dalloc(T** p, size_t count) {
+  // `count` zeroed elements of `elem` bytes on the device, freed with the handle
+  template <class T> int dalloc(T** p, size_t count, size_t elem = sizeof(T)) {
     void* q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), st));
+    HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * elem));
+    HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * elem, st));
     allocs.push_back(q);
     *p = (T*)q;
     return 0;
   }
-  // (flush_pending: the IMU samples of propagate() calls that have not reached the device yet, see propagate())
-#define DEVICE_ENTER() do { HIPCHK(hipSetDevice(device)); if (pend_b >= 0) { const int rc_p_ = flush_pending(); if (rc_p_) return rc_p_; } } while (0)
+  // the device's tables, streams and events, host mirrors, the knobs the environment sets; then the typed half's buffers
   int create() {
     HIPCHK(hipSetDevice(device));
     feature_device_setup(); qr_device_setup(); kalman_device_setup(); gram_device_setup(); literal_device_setup();   // per device: constant tables, dynamic-LDS limits
@@ -312,67 +259,15 @@ struct Batch : BatchBase {
       HIPCHK(hipStreamCreateWithFlags(&sty[i], hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&ev_fa[i], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_fb[i], hipEventDisableTiming));
     }
-    h_ncam.assign(B, 0); h_uv.assign((size_t)2 * B, 0.0); h_lit.assign(B, 0); h_qfull.assign(B, 0); h_imu.assign((size_t)B * IMU_STRIDE, S(0)); h_imu_ok.assign(B, 0);
-    d.B = B; d.n_cap = n_cap; d.f_cap = f_cap; d.m_cap = m_cap;
-    d.n6cap = 6 * n_cap;
-    d.ld = ((15 + 6 * n_cap + 15) / 16) * 16;
-    d.ldR = ((6 * n_cap + 1 + 63) / 64) * 64;
-    // 6 n_cap + 1 <= 384 (n_cap <= 63): the compression kernels' column capacity; it also bounds everything indexed by a state
-    // column or a camera slot further down (k_prune_inplace keeps ceil(ld / 16) x ceil(ld / 256) <= 25 x 2 elements per thread: ld <= 400; 6-bit slot fields of trk_first)
-    if (d.ldR / 64 > 6) return fail(-ENOTSUP, "n_cap too large: 6*n_cap+1 must be <= 384 (at most 63 camera states)");
-    int nch = 1;
-    while (nch < 8 && (long)B * nch * 2 <= 256) nch *= 2;    // TSQR route: chunks x trajectories ~ one workgroup per CU
-    d.nchunk = nch;
-    const size_t Bz = B, pl = (size_t)d.ld * d.ld, nl = (size_t)d.n6cap * d.n6cap, dn = (size_t)d.ld * d.n6cap;
-    const size_t TF = Bz * f_cap;
-    int rc = 0;
-    rc |= dalloc(&d.imu, Bz * IMU_STRIDE); rc |= dalloc(&d.cam, Bz * n_cap * CAM_STRIDE); rc |= dalloc(&d.prm, Bz * PRM_STRIDE);
-    rc |= dalloc(&d.qf, Bz * QF_STRIDE);
-    rc |= dalloc(&d.P, Bz * pl); rc |= dalloc(&P_spare, Bz * pl); d.Pout = nullptr; d.fuse_drop = nullptr; d.ncam_defer = 0;
-    if (const char* e = getenv("MSCKF_HIP_FUSE_PRUNE")) fuse_prune = atoi(e) != 0;
+    h_ncam.assign(B, 0); h_uv.assign((size_t)2 * B, 0.0); h_lit.assign(B, 0); h_qfull.assign(B, 0); h_imu_ok.assign(B, 0);
+    traj.assign(B, HostTraj());
+    if (const char* e = getenv("MSCKF_HIP_FUSE_PRUNE")) knobs.fuse_prune = atoi(e) != 0;
     if (const char* e = getenv("MSCKF_HIP_TEST_FAIL_UPLOAD")) test_fail_upload = atoi(e);   // test hook: the upload of this frame fails
     if (const char* e = getenv("MSCKF_HIP_LITERAL_ROUTE")) lit_route = atoi(e);   // A/B runs and tests: 1 = the sweep over the dense stack
-    rc |= dalloc(&d.ncam, Bz); rc |= dalloc(&d.n_resid, Bz);
-    rc |= dalloc(&d.trk_status, TF); rc |= dalloc(&d.trk_pf, TF * 4); rc |= dalloc(&d.trk_gamma, TF);
-    d.h16 = h16 ? 1 : 0; d.trk_Hx = nullptr; d.trk_Hx16 = nullptr;
-    if (h16) rc |= dalloc(&d.trk_Hx16, TF * m_cap * 12); else rc |= dalloc(&d.trk_Hx, TF * m_cap * 12);
-    rc |= dalloc(&d.trk_V, TF * 2 * m_cap * 4); rc |= dalloc(&d.trk_Zf, TF * 3 * (size_t)d.ldR);
-    rc |= dalloc(&d.trk_ro, TF * 2 * m_cap); rc |= dalloc(&d.trk_first, TF);
-    rc |= dalloc(&d.row_start, Bz * (f_cap + 1)); rc |= dalloc(&d.trk_order, TF); rc |= dalloc(&d.stats, Bz * STAT_STRIDE);
-    rc |= dalloc(&d.Rbuf, Bz * d.nchunk * (size_t)d.n6cap * d.ldR);
-    // information-form compression (kernels_gram.hip + kernels_chol.hip)
-    d.compress = (d.ldR <= 384 && f_cap <= 1024) ? 3 : 0;   // blocked matrix-core Cholesky (kernels_chol.hip), two levels beyond 192 columns
-    d.Mp = nullptr; d.Mp2 = nullptr;
-    if (d.n6cap > 192) rc |= dalloc(&d.Mp2, Bz * 24 * 256);
-    if (d.compress) {
-      if (d.ldR > 192) rc |= dalloc(&d.Mp, Bz * 12 * 256);
-      rc |= dalloc(&d.trk_B, TF * 3 * (size_t)d.ldR); rc |= dalloc(&d.trk_rw, TF * 2 * m_cap); rc |= dalloc(&d.trk_inv, TF * n_cap);
-      rc |= dalloc(&d.Dg, Bz * n_cap * DG_STRIDE);
-      d.lam_part = d.ldR <= 192 ? (long)(Bz * (size_t)d.ldR * d.ldR) : 0;     // up to four copies of Lam^ for the split-K SYRK (windows up to 31 cameras)
-      d.gram_parts = 3;   // P = 4 (sixteen workgroups per trajectory) measured: k_gram 56 -> 54 us, the Cholesky's extra load round 64 -> 66 us
-      rc |= dalloc(&d.Lam, Bz * (size_t)d.ldR * d.ldR * (d.lam_part ? 4 : 1));
-    }
-    rc |= dalloc(&d.PHt, Bz * dn); rc |= dalloc(&d.Smat, Bz * nl); rc |= dalloc(&d.Linv, Bz * nl); rc |= dalloc(&d.W, Bz * dn);
-    rc |= dalloc(&d.K, Bz * dn); rc |= dalloc(&d.A, Bz * pl); rc |= dalloc(&d.AP, Bz * pl); rc |= dalloc(&d.X, Bz * pl); rc |= dalloc(&d.dx, Bz * d.ld);
-    rc |= dalloc(&d.keep, Bz * n_cap); rc |= dalloc(&d.nkeep, Bz); rc |= dalloc(&d.ncam_upd, Bz); rc |= dalloc(&d.nres_upd, Bz);
-    rc |= dalloc(&d_pfin, TF * 4); d.trk_pfin = d_pfin; d.mode = 0; d.joseph = 0; d.ncam_bias = 0;
-    { const char* e = getenv("MSCKF_HIP_FUSED_S"); d.gain_fused_s = e ? atoi(e) : 2; }
-    { const char* e = getenv("MSCKF_HIP_FEATURE_PAIR"); d.feat_pair = e ? atoi(e) : 1; }
-    { const char* e = getenv("MSCKF_HIP_SMALL_UPDATE"); if (e) small_update = atoi(e); }
-    rc |= dalloc(&d.gain_bar, Bz * 32);   // 0: the S GEMM as a launch of its own (A/B runs)
-    rd_cap = 64;
-    rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE);
-    HIPCHK(hipHostMalloc((void**)&h_rb, ((size_t)n_cap * CAM_STRIDE + IMU_STRIDE) * sizeof(S), hipHostMallocDefault));
-    wl_f4 = (f_cap + 3) & ~3; wl_ib = (4 + wl_f4 + (long)f_cap * m_cap + 3) & ~3L;
-    rc |= dalloc(&wl_i, Bz * wl_ib); rc |= dalloc(&wl_obs, Bz * wl_ib * 2);
-    if (rc) return rc;
-    use_single_worklists();
-    if (feature_lds_bytes(m_cap, sizeof(S)) > 160 * 1024) return fail(-EINVAL, "m_cap too large for the feature kernel's LDS budget");
-    traj.assign(B, HostTraj());
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    if (const char* e = getenv("MSCKF_HIP_SMALL_UPDATE")) small_update = atoi(e);
+    return alloc();
   }
-  ~Batch() override {
+  virtual ~BatchCore() {
     hipSetDevice(device);
     if (st) hipStreamSynchronize(st);
     for (void* p : allocs) hipFree(p);
@@ -389,6 +284,30 @@ struct Batch : BatchBase {
     for (int i = 0; i < NSTG; ++i) if (h_stage[i]) hipHostFree(h_stage[i]);
     if (st) hipStreamDestroy(st);
   }
+  // ---- what the head of an entry checks
+  int chk(int b) const { return (b < 0 || b >= B) ? -EINVAL : 0; }
+  int chk_range(int b0, int nb) const { return (b0 < 0 || nb < 0 || b0 + nb > B) ? -EINVAL : 0; }
+  // A run_frames / run_frames_streamed call that failed after some of its frames were enqueued leaves the slices at different
+  // frames: which covariance buffer is current (the fused prune flips them per frame) and whether a window size is still
+  // deferred differ per slice, and nothing can put that right.  The handle refuses further work instead of answering from a
+  // stale buffer; the caller destroys it.
+  bool poisoned = false;
+  int poison(int rc, const std::string& msg) {
+    (void)hipDeviceSynchronize();
+    poisoned = true;
+    return fail(rc, msg + " -- frames of this call were already enqueued: the filter states of this handle are undefined, destroy it");
+  }
+  // `if (int rc = guard()) return rc;` at the head of an entry that must not answer from a poisoned handle
+  int guard() const { return poisoned ? fail(-EIO, "handle unusable after a failed run_frames call (destroy it)") : 0; }
+  // `if (int rc = enter()) return rc;` before an entry's first device call: this handle's device is current, and the IMU samples
+  // of propagate() calls that have not reached the device yet (see propagate()) are on their way
+  int enter() {
+    HIPCHK(hipSetDevice(device));
+    return pend_b >= 0 ? flush_pending() : 0;
+  }
+  // the same after the check of the entry's trajectory index, or of its range
+  int enter_traj(int b) { return chk(b) ? fail(-EINVAL, "trajectory index out of range") : enter(); }
+  int enter_range(int b0, int nb) { return chk_range(b0, nb) ? fail(-EINVAL, "trajectory range out of bounds") : enter(); }
   // pinned staging area of at least `bytes`, safe to overwrite (the previous asynchronous copy out of it has finished)
   int stage_acquire(size_t bytes, unsigned char** out) {
     stage_cur = (stage_cur + 1) % NSTG;
@@ -428,17 +347,6 @@ struct Batch : BatchBase {
     return 0;
   }
   static size_t al256(size_t x) { return (x + 255) / 256 * 256; }   // sections of a streamed frame block
-  void use_single_worklists() {
-    d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
-    d.wl_stride_n = wl_ib; d.wl_stride_f = wl_ib; d.wl_stride_o = wl_ib;
-  }
-  // Dev view whose work-list pointers start at trajectory b0 (kernels index work-lists by b - b0)
-  Dev<S> view(int b0) const {
-    Dev<S> v = d;
-    v.trk_n += (long)b0 * d.wl_stride_n; v.trk_M += (long)b0 * d.wl_stride_f;
-    v.trk_slots += (long)b0 * d.wl_stride_o; v.trk_obs += 2 * (long)b0 * d.wl_stride_o;
-    return v;
-  }
   // ---- profiling helpers
   void stage_begin(int s, hipStream_t q) {
     if (!prof) return;
@@ -472,6 +380,558 @@ struct Batch : BatchBase {
     }
     return 0;
   }
+  void invalidate_imu(int b0, int nb) { for (int b = b0; b < b0 + nb && b < B; ++b) h_imu_ok[b] = 0; }
+  // Single-filter API (the shim's propagate(), one call per IMU sample, msckf.h:101): while the host copy of the IMU state is
+  // valid it answers getImuState(), so the samples need not reach the device one by one -- they wait here and go as ONE copy +
+  // ONE k_propagate launch when anything else touches the device (enter() at the head of every other entry).  Ten calls per
+  // image were ten pinned-memory copies and ten launches (~6 us of host time each) for the same device-side result.
+  std::vector<double> pend_rd; int pend_b = -1;
+  int flush_pending(bool then_augment = false) {
+    if (pend_b < 0) return 0;
+    const int b = pend_b; pend_b = -1;
+    std::vector<double> rd; rd.swap(pend_rd);
+    if (hipSetDevice(device) != hipSuccess) { h_imu_ok[b] = 0; return fail(-EIO, "hipSetDevice failed"); }
+    const int rc = propagate_device(b, 1, rd.data(), (int)(rd.size() / RD_STRIDE), then_augment);
+    if (rc) h_imu_ok[b] = 0;   // the samples are gone and the device never saw them: the host copy is ahead of the filter, drop it (getImuState() re-reads the device)
+    return rc;
+  }
+  int propagate(int b0, int nb, const double* rd, int K, bool mirror = false) {
+    if (int rc = guard()) return rc;
+    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
+    if (K < 0) return fail(-EINVAL, "negative sample count");
+    if (mirror && nb == 1 && h_imu_ok[b0]) {
+      if (pend_b >= 0 && pend_b != b0) { const int rc = flush_pending(); if (rc) return rc; }   // first: a failure here must not leave b0's host copy advanced with nothing queued
+      mirror_advance(b0, rd, K);
+      pend_b = b0; pend_rd.insert(pend_rd.end(), rd, rd + (size_t)K * RD_STRIDE);
+      return 0;
+    }
+    if (!(mirror && nb == 1)) invalidate_imu(b0, nb);
+    if (int rc = enter()) return rc;
+    return propagate_device(b0, nb, rd, K);
+  }
+  // ---- the device's integer arrays
+  // last_stats of a marginalize() that had nothing to residualize (the reference returns early, msckf.h:337)
+  int clear_stats(int b) {
+    if (int rc = enter_traj(b)) return rc;
+    HIPCHK(hipMemsetAsync(dv_stats + (size_t)b * STAT_STRIDE, 0, sizeof(int) * STAT_ERR, st));
+    return 0;
+  }
+  int clear_errors(int b) {
+    if (int rc = enter_traj(b)) return rc;
+    HIPCHK(hipMemsetAsync(dv_stats + (size_t)b * STAT_STRIDE + STAT_ERR, 0, sizeof(int), st));
+    return 0;
+  }
+  // the window size from the host's own count (kept through every entry that changes it): no device read.  A poisoned handle's
+  // count is not to be trusted (its slices may have stopped at different frames)
+  int ncam_host(int b) const {
+    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
+    return poisoned ? guard() : h_ncam[b];
+  }
+  int get_ncam(int b, int* n) {
+    if (int rc = guard()) return rc;
+    if (int rc = enter_traj(b)) return rc;
+    return read_back(n, dv_ncam + b, sizeof(int));
+  }
+  int get_nres(int b, long long* n) {
+    if (int rc = enter_traj(b)) return rc;
+    return read_back(n, dv_nres + b, sizeof(long long));
+  }
+  int set_nres(int b, long long n) {
+    if (int rc = enter_traj(b)) return rc;
+    return write_dev(dv_nres + b, &n, sizeof(long long));
+  }
+  int stats(int b, int* out) {
+    if (int rc = guard()) return rc;
+    if (int rc = enter_traj(b)) return rc;
+    int tmp[STAT_STRIDE];
+    if (const int rc = read_back(tmp, dv_stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
+    for (int i = 0; i < 7; ++i) out[i] = tmp[i];
+    if (tmp[STAT_ERR] & STAT_ERR_NCAP) return fail(-EOVERFLOW, "camera-state capacity n_cap exceeded in augmentState");
+    if (tmp[STAT_ERR] & STAT_ERR_PIVOT)
+      return fail(-EDOM, "non-positive pivot in the factorization of S = T_H P T_H^T + R_n: the covariance lost positive definiteness "
+                         "(msckf_hip_set_covariance_update(h, 1) selects the reference's Joseph form)");
+    return 0;
+  }
+  int error_flags(int b, int* flags) {
+    if (int rc = enter_traj(b)) return rc;
+    return read_back(flags, dv_stats + (size_t)b * STAT_STRIDE + STAT_ERR, sizeof(int));
+  }
+  // ---- scenario
+  void free_scenario_device() {
+    for (void* q : sc_allocs) {                                  // a previous scenario is replaced, not leaked
+      hipFree(q);
+      allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end());
+    }
+    sc_allocs.clear();
+    sc_rd = nullptr; sc_n = sc_M = sc_off = sc_drop = sc_slots = nullptr; sc_obs = nullptr; sc_total = 0;
+  }
+  template <class T> int sc_dalloc(T** p, size_t count, size_t elem = sizeof(T)) {
+    const size_t mark = allocs.size();
+    const int rc = dalloc(p, count, elem);
+    sc_allocs.insert(sc_allocs.end(), allocs.begin() + mark, allocs.end());
+    return rc;
+  }
+  int scen_alloc(int n_frames, int K) {
+    if (n_frames <= 0 || K <= 0) return fail(-EINVAL, "bad scenario size");
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    free_scenario_device();
+    sc_frames = 0; committed = false;
+    unpin_host();
+    const size_t Bz = B, FB = (size_t)n_frames * Bz;
+    h_rd.assign(FB * K * RD_STRIDE * esz, 0); h_n.assign(FB, 0); h_M.assign(FB * f_cap, 0); h_off.assign(FB * f_cap, 0);
+    h_drop.assign(FB, 0); h_maxslot.assign(FB, -1);
+    c_slots.assign(FB, std::vector<int>()); c_obs.assign(FB, std::vector<unsigned char>());
+    fr_base.assign((size_t)n_frames + 1, 0);
+    pinf.assign((size_t)n_frames, PinFrame());
+    int rc = 0;
+    rc |= sc_dalloc(&sc_rd, FB * K * RD_STRIDE, esz); rc |= sc_dalloc(&sc_n, h_n.size()); rc |= sc_dalloc(&sc_M, h_M.size());
+    rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size());
+    if (rc) return rc;
+    // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
+    pk_rd = 0; pk_n = al256(pk_rd + Bz * K * RD_STRIDE * esz); pk_drop = al256(pk_n + Bz * sizeof(int));
+    pk_M = al256(pk_drop + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
+    sc_frames = n_frames; sc_K = K;
+    return 0;
+  }
+  // the compact cells of frame f, trajectory after trajectory, as one contiguous block: slots to hs, coordinates to ho
+  void gather_frame(int f, int* hs, unsigned char* ho) const {
+    size_t o = 0;
+    for (int b = 0; b < B; ++b) {
+      const size_t cell = (size_t)f * B + b, n = c_slots[cell].size();
+      if (n) { std::memcpy(hs + o, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * o * esz, c_obs[cell].data(), 2 * n * esz); }
+      o += n;
+    }
+  }
+  // H2D of everything staged.  The host copy is kept, so cells may be patched with scenario_set and committed again.
+  int scen_commit() {
+    if (sc_frames <= 0) return fail(-EINVAL, "no scenario allocated");
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t Bz = B;
+    size_t total = 0;
+    for (int f = 0; f < sc_frames; ++f) {
+      fr_base[f] = total;
+      size_t in_frame = 0;
+      for (size_t b = 0; b < Bz; ++b) {
+        const size_t cell = (size_t)f * Bz + b;
+        size_t o = in_frame;
+        for (int t = 0; t < f_cap; ++t) { h_off[cell * f_cap + t] = (int)o; o += h_M[cell * f_cap + t]; }
+        in_frame += c_slots[cell].size();
+      }
+      if (in_frame > 0x7fffffffu) return fail(-E2BIG, "a frame's work-lists exceed 2^31 observations");
+      total += in_frame;
+    }
+    fr_base[sc_frames] = total;
+    if (total != sc_total || !sc_slots) {          // patched cells may have changed the compact size
+      for (void* q : {(void*)sc_slots, (void*)sc_obs})
+        if (q) { hipFree(q); allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end()); sc_allocs.erase(std::remove(sc_allocs.begin(), sc_allocs.end(), q), sc_allocs.end()); }
+      sc_slots = nullptr; sc_obs = nullptr;
+      int rc = sc_dalloc(&sc_slots, total); rc |= sc_dalloc(&sc_obs, 2 * total, esz);
+      if (rc) return rc;
+      sc_total = total;
+    }
+    HIPCHK(hipMemcpyAsync(sc_rd, h_rd.data(), h_rd.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc_n, h_n.data(), h_n.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc_M, h_M.data(), h_M.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc_off, h_off.data(), h_off.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc_drop, h_drop.data(), h_drop.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    {   // size the pinned staging ring once, for the largest frame
+      size_t mx = 0;
+      for (int f = 0; f < sc_frames; ++f) mx = std::max(mx, fr_base[f + 1] - fr_base[f]);
+      const int rc = stage_reserve(mx * (sizeof(int) + 2 * esz));
+      if (rc) return rc;
+    }
+    for (int f = 0; f < sc_frames; ++f) {            // one frame at a time through the pinned staging area (bounded host memory)
+      const size_t nf = fr_base[f + 1] - fr_base[f];
+      if (!nf) continue;
+      unsigned char* raw = nullptr;
+      int rc = stage_acquire(nf * (sizeof(int) + 2 * esz), &raw);
+      if (rc) return rc;
+      int* hs = reinterpret_cast<int*>(raw); unsigned char* ho = raw + nf * sizeof(int);
+      gather_frame(f, hs, ho);
+      HIPCHK(hipMemcpyAsync(sc_slots + fr_base[f], hs, nf * sizeof(int), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(sc_obs + 2 * fr_base[f] * esz, ho, 2 * nf * esz, hipMemcpyHostToDevice, st));
+      rc = stage_release();
+      if (rc) return rc;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    committed = true;
+    return 0;
+  }
+  // page-locked per-frame blocks for run_frames_streamed, frames [f0, f1) that do not have one yet; also sizes the device
+  // staging ring.  Called by run_frames_streamed itself; call it beforehand to keep the pinning out of a timed region.
+  int scen_pin(int f0, int f1) {
+    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (!committed) return fail(-EINVAL, "scenario not committed");
+    if (int rc = enter()) return rc;
+    const size_t Bz = B;
+    size_t need = 0, maxb = sg_bytes;
+    std::vector<int> todo;
+    for (int f = f0; f < f1; ++f) {
+      const size_t nf = fr_base[f + 1] - fr_base[f];
+      const size_t off_obs = al256(pk_slots + nf * sizeof(int)), bytes = al256(off_obs + 2 * nf * esz);
+      maxb = std::max(maxb, bytes);
+      if (pinf[f].p) continue;
+      pinf[f].bytes = bytes; pinf[f].off_obs = off_obs;
+      need += bytes; todo.push_back(f);
+    }
+    if (!todo.empty()) {
+      unsigned char* chunk = nullptr;
+      if (hipHostMalloc((void**)&chunk, need, hipHostMallocDefault) != hipSuccess) {
+        for (int f : todo) pinf[f] = PinFrame();
+        return fail(-ENOMEM, "could not page-lock the frames to stream (run_frames on the resident scenario is unaffected)");
+      }
+      int ci = -1;
+      for (size_t q = 0; q < pin_chunks.size(); ++q) if (!pin_chunks[q].p) { ci = (int)q; break; }
+      if (ci < 0) { pin_chunks.push_back(PinChunk()); ci = (int)pin_chunks.size() - 1; }
+      pin_chunks[ci].p = chunk; pin_chunks[ci].live = (int)todo.size();
+      size_t o = 0;
+      for (int f : todo) {
+        unsigned char* blk = chunk + o;
+        const size_t c0 = (size_t)f * Bz;
+        std::memcpy(blk + pk_rd, h_rd.data() + c0 * sc_K * RD_STRIDE * esz, Bz * sc_K * RD_STRIDE * esz);
+        std::memcpy(blk + pk_n, h_n.data() + c0, Bz * sizeof(int));
+        std::memcpy(blk + pk_drop, h_drop.data() + c0, Bz * sizeof(int));
+        std::memcpy(blk + pk_M, h_M.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
+        std::memcpy(blk + pk_off, h_off.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
+        gather_frame(f, reinterpret_cast<int*>(blk + pk_slots), blk + pinf[f].off_obs);
+        pinf[f].p = blk; pinf[f].chunk = ci;
+        o += pinf[f].bytes;
+      }
+    }
+    if (maxb > sg_bytes || !sg_blk[0]) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (stc) HIPCHK(hipStreamSynchronize(stc));
+      for (int k = 0; k < RING_MAX; ++k) { if (sg_blk[k]) hipFree(sg_blk[k]); sg_blk[k] = nullptr; }
+      for (int k = 0; k < RING_MAX; ++k) HIPCHK(hipMalloc((void**)&sg_blk[k], maxb));
+      sg_bytes = maxb;
+    }
+    return 0;
+  }
+  int set_upload_ring(int depth, int mode) {
+    if (depth < 2 || depth > RING_MAX || mode < 0 || mode > 1) return fail(-EINVAL, "ring depth 2..8; mode 0 host hand-over, 1 device-side event waits");
+    ring = depth; up_mode = mode;
+    return 0;
+  }
+  // ---- the frame loop of a scenario (run_frames, run_frames_streamed)
+  // Trajectories are independent, so the batch may be cut into slices that run the same kernel sequence on separate streams:
+  // the latency-bound stages of one slice (gain solve, Cholesky, propagate: one workgroup per trajectory) overlap with the
+  // chip-filling stages of the others.  One host thread per slice enqueues that slice's kernels for all frames of the call
+  // (~13 launches per frame and slice would otherwise serialise on one thread and make more than two slices launch-bound).
+  // Stage profiling forces a single stream.
+  int n_slices() const { return prof ? 1 : std::max(1, std::min(knobs.nstreams, B)); }
+  // slice hh of nh on its enqueue thread: trajectories [b0, b0 + nb) on stream q.  A frame whose prune rides on the downdate
+  // leaves the covariance in the other buffer (flipped: the slice's current one is the handle's spare) and the new window size
+  // for the next k_propagate to commit (pending)
+  struct Slice { int hh, b0, nb; hipStream_t q; bool flipped, pending; };
+  Slice begin_slice(int hh, int nh) {
+    (void)hipSetDevice(device);
+    (void)hipGetLastError();
+    const int b0 = (int)((long)B * hh / nh);
+    return Slice{hh, b0, (int)((long)B * (hh + 1) / nh) - b0, stx[hh], false, false};
+  }
+  // fork: the slices' streams (and the copy stream of a streamed run) start after what is queued on st
+  int fork_slices(int nh, hipStream_t extra = nullptr) {
+    if (nh <= 1 && !extra) return 0;
+    HIPCHK(hipEventRecord(ev_fork, st));
+    for (int i = 1; i < nh; ++i) HIPCHK(hipStreamWaitEvent(stx[i], ev_fork, 0));
+    if (extra) HIPCHK(hipStreamWaitEvent(extra, ev_fork, 0));
+    return 0;
+  }
+  // the end of a call whose frames are enqueued: st waits for the slices (and the copy stream); a launch error of any slice
+  // (slice_rc: hipGetLastError is per host thread, a failed launch must not vanish with its thread) makes the handle
+  // unusable; otherwise the covariance buffer that is current now becomes the handle's
+  int finish_slices(int nh, const int* slice_rc, int f0, int f1, hipStream_t extra = nullptr) {
+    for (int i = 1; i < nh; ++i)
+      if (hipEventRecord(ev_join[i], stx[i]) != hipSuccess || hipStreamWaitEvent(st, ev_join[i], 0) != hipSuccess) return poison(-EIO, "joining the slices' streams failed");
+    if (extra && (hipEventRecord(ev_join[1], extra) != hipSuccess || hipStreamWaitEvent(st, ev_join[1], 0) != hipSuccess)) return poison(-EIO, "joining the copy stream failed");
+    for (int i = 0; i < nh; ++i)
+      if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
+    commit_buffer_parity(f0, f1);
+    return 0;
+  }
+  int run_frames(int f0, int f1) {
+    if (int rc = guard()) return rc;
+    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (!committed) return fail(-EINVAL, "scenario not committed");
+    if (int rc = enter()) return rc;
+    const int nh = n_slices();
+    const int rc = fork_slices(nh);
+    if (rc) return rc;
+    int slice_rc[MAXS] = {0};
+    auto enqueue = [&](int hh) {
+      Slice s = begin_slice(hh, nh);
+      for (int f = f0; f < f1; ++f) enqueue_frame(s, f, f0, f1, -1);
+      slice_rc[hh] = (int)hipGetLastError();
+    };
+    if (nh == 1) enqueue(0);
+    else {
+      workers.start(nh - 1, [&](int idx) { enqueue(idx + 1); });
+      enqueue(0);
+      workers.wait();
+    }
+    return finish_slices(nh, slice_rc, f0, f1);
+  }
+  // run_frames with the inputs handed over per frame, as the reference's callers do (asl_msckf.cpp:227-284: IMU samples and
+  // the image's tracks arrive with the image): frame f's block -- IMU samples + compact work-list, what the frame really
+  // holds, not a padded maximum -- goes from page-locked host memory into staging set f % ring on a copy stream, up to
+  // ring - 1 frames ahead of the kernels that consume it.  Hand-over (up_mode 0): the uploading thread waits for its copy on
+  // the HOST and publishes the frame number; a slice's enqueue thread launches frame f only after that, and the uploader
+  // reuses a set only after every slice's "consumed" event of frame f - ring has completed -- no stream ever waits for
+  // another stream's event on the device (those waits cost 0.15-0.25 ms per frame with two staging sets).  up_mode 1 keeps
+  // the device-side hipStreamWaitEvent protocol, for comparison.
+  int run_frames_streamed(int f0, int f1) {
+    if (int rc = guard()) return rc;
+    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (!committed) return fail(-EINVAL, "scenario not committed");
+    if (int rc = enter()) return rc;
+    {
+      bool all = sg_blk[0] != nullptr;
+      for (int f = f0; f < f1 && all; ++f) all = pinf[f].p != nullptr;
+      if (!all) { int rc = scen_pin(f0, f1); if (rc) return rc; }
+    }
+    if (!stc) {
+      HIPCHK(hipStreamCreateWithFlags(&stc, hipStreamNonBlocking));
+      for (int k = 0; k < RING_MAX; ++k) {
+        HIPCHK(hipEventCreateWithFlags(&ev_up[k], hipEventDisableTiming));
+        for (int i = 0; i < MAXS; ++i) HIPCHK(hipEventCreateWithFlags(&ev_use[k][i], hipEventDisableTiming));
+      }
+    }
+    const int nh = n_slices();
+    const int R = ring, mode = up_mode;
+    const int rc = fork_slices(nh, stc);
+    if (rc) return rc;
+    // up_rdy = frames whose block may be read (mode 0: the copy has completed; mode 1: copy + event record are enqueued --
+    // an event must be recorded before a wait on it is enqueued); use_enq[s] = frames whose "consumed" record is enqueued.
+    std::atomic<int> up_rdy{f0};
+    std::atomic<int> use_enq[MAXS];
+    for (int i = 0; i < MAXS; ++i) use_enq[i].store(f0);
+    std::atomic<int> failed{0};
+    int slice_rc[MAXS] = {0};
+    auto slice = [&](int hh) {
+      Slice s = begin_slice(hh, nh);
+      for (int f = f0; f < f1; ++f) {
+        while (up_rdy.load(std::memory_order_acquire) <= f && !failed.load()) std::this_thread::yield();
+        if (failed.load()) break;
+        const int k = (f - f0) % R;
+        if (mode == 1) (void)hipStreamWaitEvent(s.q, ev_up[k], 0);
+        enqueue_frame(s, f, f0, f1, k);
+        (void)hipEventRecord(ev_use[k][hh], s.q);
+        use_enq[hh].store(f + 1, std::memory_order_release);
+      }
+      slice_rc[hh] = (int)hipGetLastError();
+    };
+    // the uploading (calling) thread on its own core for the duration of the call, when a list of cores was given
+    cpu_set_t old_mask; bool repin = false;
+    if (!workers.cpus.empty() && workers.cpus[0] >= 0 && pthread_getaffinity_np(pthread_self(), sizeof(old_mask), &old_mask) == 0) {
+      cpu_set_t one; CPU_ZERO(&one); CPU_SET(workers.cpus[0], &one);
+      (void)pthread_setaffinity_np(pthread_self(), sizeof(one), &one); repin = true;
+    }
+    workers.start(nh, slice);
+    int rc_up = 0;
+    for (int f = f0; f < f1 && !rc_up; ++f) {
+      const int k = (f - f0) % R;
+      if (f - f0 >= R)
+        for (int i = 0; i < nh && !rc_up; ++i) {   // the set is free again once every slice has consumed frame f - R
+          while (use_enq[i].load(std::memory_order_acquire) <= f - R) std::this_thread::yield();
+          const hipError_t e = mode == 0 ? hipEventSynchronize(ev_use[k][i]) : hipStreamWaitEvent(stc, ev_use[k][i], 0);
+          if (e != hipSuccess) rc_up = -EIO;
+        }
+      if (!rc_up && (f == test_fail_upload || hipMemcpyAsync(sg_blk[k], pinf[f].p, pinf[f].bytes, hipMemcpyHostToDevice, stc) != hipSuccess)) rc_up = -EIO;
+      if (!rc_up && (mode == 0 ? hipStreamSynchronize(stc) : hipEventRecord(ev_up[k], stc)) != hipSuccess) rc_up = -EIO;
+      if (rc_up) failed.store(1);
+      up_rdy.store(f + 1, std::memory_order_release);
+    }
+    workers.wait();
+    if (repin) (void)pthread_setaffinity_np(pthread_self(), sizeof(old_mask), &old_mask);
+    if (rc_up) return poison(rc_up, "input upload failed");
+    return finish_slices(nh, slice_rc, f0, f1, stc);
+  }
+  int sync() {
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  int set_feature_overlap(int on) { knobs.overlap_feature = on ? 1 : 0; return 0; }
+  int set_compression(int route) {
+    if (route < -1 || route > 3) return fail(-EINVAL, "route: -1 default, 0 Householder TSQR, 1..3 information form (blocked matrix-core Cholesky; 1 and 2 named retired factorizations)");
+    if (route >= 1 && !info_form) return fail(-ENOTSUP, "information form not available for this window size (6 n_cap + 1 > 384 or f_cap > 1024)");
+    knobs.compress_route = route;
+    return 0;
+  }
+  int set_host_affinity(const int* cpus, int n) {
+    std::lock_guard<std::mutex> lk(workers.m);
+    workers.cpus.assign(cpus, cpus + std::max(n, 0));
+    return 0;
+  }
+  int set_streams(int n) {
+    if (n < 1 || n > MAXS) return fail(-EINVAL, "1 to 8 streams");
+    knobs.nstreams = n;
+    return 0;
+  }
+  int prof_enable(int on) {
+    prof = on != 0;
+    for (int s = 0; s < NSTAGE; ++s) { ev_used[s] = 0; prof_ms[s] = 0; prof_cnt[s] = 0; }
+    return 0;
+  }
+  // what an event pair with NOTHING between its records measures on this stream (the marker packets themselves): the stage
+  // timers of prof_read hold one such pair per launch, so a single-kernel stage reads kernel time + this
+  int prof_event_overhead(double* ms) {
+    if (int rc = enter()) return rc;
+    hipEvent_t a, b2;
+    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b2));
+    HIPCHK(hipStreamSynchronize(st));
+    double tot = 0; const int reps = 64;
+    for (int i = 0; i < reps; ++i) {
+      HIPCHK(hipEventRecord(a, st)); HIPCHK(hipEventRecord(b2, st));
+      HIPCHK(hipEventSynchronize(b2));
+      float t = 0; HIPCHK(hipEventElapsedTime(&t, a, b2));
+      tot += t;
+    }
+    hipEventDestroy(a); hipEventDestroy(b2);
+    *ms = tot / reps;
+    return 0;
+  }
+  int prof_read(double* ms, int* cnt, int cap) {
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < NSTAGE; ++s) {
+      for (size_t i = 0; i < ev_used[s]; ++i) {
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, ev_pool[s][i].first, ev_pool[s][i].second));
+        prof_ms[s] += t; prof_cnt[s]++;
+      }
+      ev_used[s] = 0;
+      if (s < cap) { ms[s] = prof_ms[s]; cnt[s] = prof_cnt[s]; }
+    }
+    return 0;
+  }
+
+  // ---- the typed steps (Batch<S>, msckf_hip.hip): everything that launches a kernel or converts between S and double
+  virtual int alloc() = 0;   // create()'s typed part: Dev<S> and every device buffer
+  virtual int init_core(int b, const double* cam, const double* noise, const double* q78, const double* P0, const double* params, const double* imu) = 0;
+  virtual int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) = 0;
+  virtual void mirror_advance(int b, const double* rd, int K) = 0;   // propagate()'s K samples on the host copy of the IMU state
+  virtual int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment = false) = 0;
+  virtual int augment(int b0, int nb) = 0;
+  virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
+  virtual int marginalize(int b0, int nb, int mode = 0) = 0;   // mode 1: the second update of pruneRedundantStates (stored p_f_G per track, set_given_range)
+  // range forms (one copy / one launch for trajectories b0 .. b0 + nb - 1): the batched image cycle (host_image_cycle), and
+  // the per-filter entries with nb = 1
+  virtual int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) = 0;           // every trajectory's list in one pinned block, two copies
+  virtual int cams_range(int b0, int nb, double* poses7) = 0;                                  // [nb][n_cap][7], one read + one wait
+  virtual int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) = 0;   // checkMotion + triangulation of the work-lists: [nb][f_cap], [nb][f_cap][3]; launch = false: only read what the last launch left
+  virtual int set_given_range(int b0, int nb, const double* pf3) = 0;                          // [nb][f_cap][3]
+  virtual int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) = 0; // keep[i]: ascending slots of trajectory b0 + i
+  virtual int drop_oldest(int b0, int nb, int n) = 0;
+  virtual int get_imu(int b, double* o) = 0;
+  virtual int set_imu(int b, const double* in) = 0;
+  virtual int get_cams(int b, double* o, int cap, int* n) = 0;
+  virtual int get_cams_known(int b, double* o, int n) = 0;   // n known to the caller: cameras + (into the host copy) the IMU state, one wait
+  virtual int set_cam(int b, int slot, const double* in) = 0;
+  virtual int get_cov(int b, double* P, int ldo) = 0;
+  virtual int set_cov(int b, const double* P, int D) = 0;
+  virtual int track_info(int b, double* out, int cap) = 0;
+  virtual int deltax(int b, double* out, int cap) = 0;
+  virtual int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) = 0;
+  // THE frame step of run_frames / run_frames_streamed: frame f of a call over [f0, f1) for slice s, inputs in staging set
+  // `staged` of the upload ring, or (staged < 0) resident
+  virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
+  virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
+  virtual int set_gate_early(int on) = 0;
+  virtual int set_cov_update(int form) = 0;
+  virtual int set_aniso(int mode, double tol) = 0;
+  virtual int copy_from(BatchCore* src) = 0;
+  virtual int lit_info(int b, int* out8) = 0;
+};
+
+int resolve_map(BatchCore* B, int b);   // (defined with the host-side bookkeeping below)
+
+template <class S>
+struct Batch : BatchCore {
+  Dev<S> d{};
+  S* P_spare = nullptr;   // second covariance buffer: target of a downdate that carries the frame's prune (Dev::Pout)
+  // Host mirror of the IMU state for the single-filter API: getImuState() is called once per IMU sample by the reference's
+  // runner (asl_msckf.cpp:231) and must be synchronously available on the host (SURVEY.md 8b); between two images only
+  // propagate() changes it, and propogateImuStateRK (msckf.h:1425-1467) is a few hundred FLOP -- so msckf_hip_propagate
+  // advances this copy with the reference's own RK sequence while the device advances the state the filter uses, and
+  // msckf_hip_get_imu_state answers from it without a device round trip.  Any other device-side change of the state
+  // (marginalize, the batched calls) invalidates it (h_imu_ok); the next getter reads the device and re-validates.
+  std::vector<S> h_imu;
+  // single-call staging on device
+  S* d_rd = nullptr;                                // [B][rd_cap][7]
+  S* d_pfin = nullptr;                              // [B][f_cap][4] stored feature positions (mode 1)
+  S* wl_obs = nullptr;         // the observations of the single-call work-lists: [B][2 wl_ib], beside the core's wl_i
+
+  int alloc() override {
+    h_imu.assign((size_t)B * IMU_STRIDE, S(0));
+    d.B = B; d.n_cap = n_cap; d.f_cap = f_cap; d.m_cap = m_cap;
+    d.n6cap = 6 * n_cap;
+    d.ld = ((15 + 6 * n_cap + 15) / 16) * 16;
+    d.ldR = ((6 * n_cap + 1 + 63) / 64) * 64;
+    // 6 n_cap + 1 <= 384 (n_cap <= 63): the compression kernels' column capacity; it also bounds everything indexed by a state
+    // column or a camera slot further down (k_prune_inplace keeps ceil(ld / 16) x ceil(ld / 256) <= 25 x 2 elements per thread: ld <= 400; 6-bit slot fields of trk_first)
+    if (d.ldR / 64 > 6) return fail(-ENOTSUP, "n_cap too large: 6*n_cap+1 must be <= 384 (at most 63 camera states)");
+    int nch = 1;
+    while (nch < 8 && (long)B * nch * 2 <= 256) nch *= 2;    // TSQR route: chunks x trajectories ~ one workgroup per CU
+    d.nchunk = nch;
+    const size_t Bz = B, pl = (size_t)d.ld * d.ld, nl = (size_t)d.n6cap * d.n6cap, dn = (size_t)d.ld * d.n6cap;
+    const size_t TF = Bz * f_cap;
+    int rc = 0;
+    rc |= dalloc(&d.imu, Bz * IMU_STRIDE); rc |= dalloc(&d.cam, Bz * n_cap * CAM_STRIDE); rc |= dalloc(&d.prm, Bz * PRM_STRIDE);
+    rc |= dalloc(&d.qf, Bz * QF_STRIDE);
+    rc |= dalloc(&d.P, Bz * pl); rc |= dalloc(&P_spare, Bz * pl); d.Pout = nullptr; d.fuse_drop = nullptr; d.ncam_defer = 0;
+    rc |= dalloc(&d.ncam, Bz); rc |= dalloc(&d.n_resid, Bz);
+    rc |= dalloc(&d.trk_status, TF); rc |= dalloc(&d.trk_pf, TF * 4); rc |= dalloc(&d.trk_gamma, TF);
+    d.h16 = h16 ? 1 : 0; d.trk_Hx = nullptr; d.trk_Hx16 = nullptr;
+    if (h16) rc |= dalloc(&d.trk_Hx16, TF * m_cap * 12); else rc |= dalloc(&d.trk_Hx, TF * m_cap * 12);
+    rc |= dalloc(&d.trk_V, TF * 2 * m_cap * 4); rc |= dalloc(&d.trk_Zf, TF * 3 * (size_t)d.ldR);
+    rc |= dalloc(&d.trk_ro, TF * 2 * m_cap); rc |= dalloc(&d.trk_first, TF);
+    rc |= dalloc(&d.row_start, Bz * (f_cap + 1)); rc |= dalloc(&d.trk_order, TF); rc |= dalloc(&d.stats, Bz * STAT_STRIDE);
+    rc |= dalloc(&d.Rbuf, Bz * d.nchunk * (size_t)d.n6cap * d.ldR);
+    // information-form compression (kernels_gram.hip + kernels_chol.hip)
+    d.compress = (d.ldR <= 384 && f_cap <= 1024) ? 3 : 0;   // blocked matrix-core Cholesky (kernels_chol.hip), two levels beyond 192 columns
+    d.Mp = nullptr; d.Mp2 = nullptr;
+    if (d.n6cap > 192) rc |= dalloc(&d.Mp2, Bz * 24 * 256);
+    if (d.compress) {
+      if (d.ldR > 192) rc |= dalloc(&d.Mp, Bz * 12 * 256);
+      rc |= dalloc(&d.trk_B, TF * 3 * (size_t)d.ldR); rc |= dalloc(&d.trk_rw, TF * 2 * m_cap); rc |= dalloc(&d.trk_inv, TF * n_cap);
+      rc |= dalloc(&d.Dg, Bz * n_cap * DG_STRIDE);
+      d.lam_part = d.ldR <= 192 ? (long)(Bz * (size_t)d.ldR * d.ldR) : 0;     // up to four copies of Lam^ for the split-K SYRK (windows up to 31 cameras)
+      d.gram_parts = 3;   // P = 4 (sixteen workgroups per trajectory) measured: k_gram 56 -> 54 us, the Cholesky's extra load round 64 -> 66 us
+      rc |= dalloc(&d.Lam, Bz * (size_t)d.ldR * d.ldR * (d.lam_part ? 4 : 1));
+    }
+    rc |= dalloc(&d.PHt, Bz * dn); rc |= dalloc(&d.Smat, Bz * nl); rc |= dalloc(&d.Linv, Bz * nl); rc |= dalloc(&d.W, Bz * dn);
+    rc |= dalloc(&d.K, Bz * dn); rc |= dalloc(&d.A, Bz * pl); rc |= dalloc(&d.AP, Bz * pl); rc |= dalloc(&d.X, Bz * pl); rc |= dalloc(&d.dx, Bz * d.ld);
+    rc |= dalloc(&d.keep, Bz * n_cap); rc |= dalloc(&d.nkeep, Bz); rc |= dalloc(&d.ncam_upd, Bz); rc |= dalloc(&d.nres_upd, Bz);
+    rc |= dalloc(&d_pfin, TF * 4); d.trk_pfin = d_pfin; d.mode = 0; d.joseph = 0; d.ncam_bias = 0;
+    { const char* e = getenv("MSCKF_HIP_FUSED_S"); d.gain_fused_s = e ? atoi(e) : 2; }
+    { const char* e = getenv("MSCKF_HIP_FEATURE_PAIR"); d.feat_pair = e ? atoi(e) : 1; }
+    rc |= dalloc(&d.gain_bar, Bz * 32);   // 0: the S GEMM as a launch of its own (A/B runs)
+    rd_cap = 64;
+    rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE);
+    HIPCHK(hipHostMalloc(&h_rb, ((size_t)n_cap * CAM_STRIDE + IMU_STRIDE) * sizeof(S), hipHostMallocDefault));
+    wl_f4 = (f_cap + 3) & ~3; wl_ib = (4 + wl_f4 + (long)f_cap * m_cap + 3) & ~3L;
+    rc |= dalloc(&wl_i, Bz * wl_ib); rc |= dalloc(&wl_obs, Bz * wl_ib * 2);
+    dv_ncam = d.ncam; dv_nres = d.n_resid; dv_stats = d.stats; info_form = d.trk_B != nullptr;
+    if (rc) return rc;
+    use_single_worklists();
+    if (feature_lds_bytes(m_cap, sizeof(S)) > 160 * 1024) return fail(-EINVAL, "m_cap too large for the feature kernel's LDS budget");
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  void use_single_worklists() {
+    d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
+    d.wl_stride_n = wl_ib; d.wl_stride_f = wl_ib; d.wl_stride_o = wl_ib;
+  }
+  // Dev view whose work-list pointers start at trajectory b0 (kernels index work-lists by b - b0)
+  Dev<S> view(int b0) const {
+    Dev<S> v = d;
+    v.trk_n += (long)b0 * d.wl_stride_n; v.trk_M += (long)b0 * d.wl_stride_f;
+    v.trk_slots += (long)b0 * d.wl_stride_o; v.trk_obs += 2 * (long)b0 * d.wl_stride_o;
+    return v;
+  }
   // the device's padded single-call layout of one work-list, the F rows in use (all that is written): I = [F, 0, 0, 0 | M[f4] |
   // F rows of m_cap slots], O = F rows of m_cap coordinate pairs
   void pack_worklist(int* I, S* O, int F, const int* M, const int* slots, const double* obs) const {
@@ -489,19 +949,6 @@ struct Batch : BatchBase {
       }
     }
   }
-  int chk(int b) const { return (b < 0 || b >= B) ? -EINVAL : 0; }
-  // A run_frames / run_frames_streamed call that failed after some of its frames were enqueued leaves the slices at different
-  // frames: which covariance buffer is current (the fused prune flips them per frame) and whether a window size is still
-  // deferred differ per slice, and nothing can put that right.  The handle refuses further work instead of answering from a
-  // stale buffer; the caller destroys it.
-  bool poisoned = false;
-  int poison(int rc, const std::string& msg) {
-    (void)hipDeviceSynchronize();
-    poisoned = true;
-    return fail(rc, msg + " -- frames of this call were already enqueued: the filter states of this handle are undefined, destroy it");
-  }
-#define POISON_GUARD() do { if (poisoned) return fail(-EIO, "handle unusable after a failed run_frames call (destroy it)"); } while (0)
-  int chk_range(int b0, int nb) const { return (b0 < 0 || nb < 0 || b0 + nb > B) ? -EINVAL : 0; }
 
   // The five derived noise parameters PRM_WU .. PRM_LIT of trajectory b for the batch's anisotropic-noise mode
   // (dev_common.h); allocates the literal route's work space when the first trajectory needs it.
@@ -544,7 +991,7 @@ struct Batch : BatchBase {
   }
   int set_aniso(int mode, double tol) override {
     if (mode < 0 || mode > 1) return fail(-EINVAL, "mode: 0 the reference's R_n = Q_1^T R_o Q_1 on the device, 1 pre-whitened rows");
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     aniso_mode = mode; lit_tol = tol;
     d.lit.tol = tol >= 0 ? tol : (sizeof(S) == 4 ? 8e-4 : 1e-10);
     d.lit.route = lit_route;
@@ -560,7 +1007,7 @@ struct Batch : BatchBase {
   int lit_info(int b, int* out8) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     if (!d.lit.info) { for (int i = 0; i < 8; ++i) out8[i] = 0; return 0; }
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     if (const int rc = read_back(out8, d.lit.info + (size_t)b * 8, 8 * sizeof(int))) return rc;
     if (d.lit.tim) {     // MSCKF_HIP_LITERAL_TIMERS=1 (profiling runs): phase durations of the last launch in microseconds on stderr
       long long t[LIT_TIM_SLOTS];
@@ -576,16 +1023,13 @@ struct Batch : BatchBase {
     }
     return 0;
   }
-  int init(int b, const double* cam, const double* noise, const double* params, const double* imu) override {
-    return init_core(b, cam, noise, nullptr, nullptr, params, imu);
-  }
   // MSCKF::initialize with the whole noiseParams::Q_imu (12 x 12) and initial_imu_covar (15 x 15), column-major (types.h:90-91).
   // Q_imu enters the filter only through G Q_imu G^T in Phi (P_II + G Q_imu G^T dT) Phi^T, which msckf.h:143 symmetrises:
   // with X = G Q_imu G^T, (Phi (P + X dT) Phi^T + its transpose) / 2 = Phi (P + (X + X^T) / 2 dT) Phi^T for symmetric P_II, and
   // (X + X^T) / 2 = G ((Q_imu + Q_imu^T) / 2) G^T -- only the symmetric part of Q_imu ever reaches P, so that is what is stored.
   // initial_imu_covar is P_II as it is (msckf.h:86): it must be symmetric.  No off-diagonal entry anywhere: exactly init().
   int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     double pmax = 0;
     for (int i = 0; i < 144; ++i) if (!std::isfinite(Q144[i])) return fail(-EINVAL, "Q_imu has a non-finite entry");
@@ -607,11 +1051,11 @@ struct Batch : BatchBase {
   }
   // q78: upper triangle of the symmetric Q_imu (qf_index), null = diagonal Q_imu (noise[2..13]); P0: the whole
   // initial_imu_covar (column-major), null = its diagonal noise[14..28]
-  int init_core(int b, const double* cam, const double* noise, const double* q78, const double* P0, const double* params, const double* imu) {
-    POISON_GUARD();
+  int init_core(int b, const double* cam, const double* noise, const double* q78, const double* P0, const double* params, const double* imu) override {
+    if (int rc = guard()) return rc;
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     if (!(noise[0] > 0) || !(noise[1] > 0)) return fail(-EINVAL, "u_var_prime / v_var_prime must be positive");
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     S prm[PRM_STRIDE] = {0}, st_imu[IMU_STRIDE] = {0}, qf[QF_STRIDE] = {0};
     if (q78) { for (int i = 0; i < QF_FLAG; ++i) qf[i] = (S)q78[i]; qf[QF_FLAG] = 1; }
     for (int i = 0; i < 12; ++i) prm[i] = (S)cam[i];
@@ -685,37 +1129,11 @@ struct Batch : BatchBase {
     for (int i = 0; i < 4; ++i) x[IQN + i] = x[IQ + i];
     for (int i = 0; i < 3; ++i) { x[IVN + i] = x[IV + i]; x[IPN + i] = x[IP + i]; }
   }
-  void invalidate_imu(int b0, int nb) { for (int b = b0; b < b0 + nb && b < B; ++b) h_imu_ok[b] = 0; }
-  // Single-filter API (the shim's propagate(), one call per IMU sample, msckf.h:101): while the host copy of the IMU state is
-  // valid it answers getImuState(), so the samples need not reach the device one by one -- they wait here and go as ONE copy +
-  // ONE k_propagate launch when anything else touches the device (DEVICE_ENTER at the head of every other entry).  Ten calls per
-  // image were ten pinned-memory copies and ten launches (~6 us of host time each) for the same device-side result.
-  std::vector<double> pend_rd; int pend_b = -1;
-  int flush_pending(bool then_augment = false) {
-    if (pend_b < 0) return 0;
-    const int b = pend_b; pend_b = -1;
-    std::vector<double> rd; rd.swap(pend_rd);
-    if (hipSetDevice(device) != hipSuccess) { h_imu_ok[b] = 0; return fail(-EIO, "hipSetDevice failed"); }
-    const int rc = propagate_device(b, 1, rd.data(), (int)(rd.size() / RD_STRIDE), then_augment);
-    if (rc) h_imu_ok[b] = 0;   // the samples are gone and the device never saw them: the host copy is ahead of the filter, drop it (getImuState() re-reads the device)
-    return rc;
-  }
-  int propagate(int b0, int nb, const double* rd, int K, bool mirror) override {
-    POISON_GUARD();
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    if (K < 0) return fail(-EINVAL, "negative sample count");
-    if (mirror && nb == 1 && h_imu_ok[b0]) {
-      if (pend_b >= 0 && pend_b != b0) { const int rc = flush_pending(); if (rc) return rc; }   // first: a failure here must not leave b0's host copy advanced with nothing queued
-      for (int k = 0; k < K; ++k) host_rk(h_imu.data() + (size_t)b0 * IMU_STRIDE, rd + (size_t)k * RD_STRIDE);
-      pend_b = b0; pend_rd.insert(pend_rd.end(), rd, rd + (size_t)K * RD_STRIDE);
-      return 0;
-    }
-    if (!(mirror && nb == 1)) invalidate_imu(b0, nb);
-    DEVICE_ENTER();
-    return propagate_device(b0, nb, rd, K);
+  void mirror_advance(int b, const double* rd, int K) override {
+    for (int k = 0; k < K; ++k) host_rk(h_imu.data() + (size_t)b * IMU_STRIDE, rd + (size_t)k * RD_STRIDE);
   }
   // then_augment: augmentState follows for the same trajectories -- k_propagate's fused variant on the last chunk (as run_frames)
-  int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment = false) {
+  int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment) override {
     for (int k0 = 0; k0 < K; k0 += rd_cap) {
       const int kk = std::min(rd_cap, K - k0);
       const size_t cnt = (size_t)nb * kk * RD_STRIDE;
@@ -735,14 +1153,14 @@ struct Batch : BatchBase {
     return 0;
   }
   int augment(int b0, int nb) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
     HIPCHK(hipSetDevice(device));
     if (pend_b >= 0 && pend_b == b0 && nb == 1 && !pend_rd.empty()) {     // the image's IMU samples are still here: one launch for both
       const int rc = flush_pending(true);
       if (rc) return rc;
     } else {
-      DEVICE_ENTER();
+      if (int rc = enter()) return rc;
       launch_augment<S>(d, b0, nb, st);
     }
     for (int b = b0; b < b0 + nb; ++b) if (h_ncam[b] < n_cap) h_ncam[b]++;
@@ -753,7 +1171,7 @@ struct Batch : BatchBase {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     int rc = check_worklist(F, M, slots);
     if (rc) return rc;
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     // only the F rows in use travel, as the device holds them: [n, 0, 0, 0 | M[f4] | F rows of slots] in one copy, F rows of
     // coordinates in a second one, both out of one pinned block
     const size_t nI = 4 + (size_t)wl_f4 + (size_t)F * m_cap, nO = (size_t)F * m_cap * 2;
@@ -773,7 +1191,7 @@ struct Batch : BatchBase {
   int set_tracks_range(int b0, int nb, const std::vector<WorkList>& wl) override {
     if (chk_range(b0, nb) || (int)wl.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
     for (int i = 0; i < nb; ++i) { const int rc = check_worklist((int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data()); if (rc) return rc; }
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     // the device's padded single-call layout for the whole range: [nb][wl_ib] ints ([n, 0, 0, 0 | M[f4] | f_cap rows of slots]) and
     // [nb][wl_ib * 2] coordinates, out of one pinned block, two copies
     const size_t nI = (size_t)nb * wl_ib, nO = (size_t)nb * wl_ib * 2;
@@ -793,25 +1211,12 @@ struct Batch : BatchBase {
     for (int i = 0; i < nb; ++i) traj[b0 + i].wl_F = (int)wl[i].M.size();
     return 0;
   }
-  // last_stats of a marginalize() that had nothing to residualize (the reference returns early, msckf.h:337)
-  int clear_stats(int b) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    HIPCHK(hipMemsetAsync(d.stats + (size_t)b * STAT_STRIDE, 0, sizeof(int) * STAT_ERR, st));
-    return 0;
-  }
-  int clear_errors(int b) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    HIPCHK(hipMemsetAsync(d.stats + (size_t)b * STAT_STRIDE + STAT_ERR, 0, sizeof(int), st));
-    return 0;
-  }
   // Frame f of a call over [.., f1): does its prune ride on the downdate (the covariance lands, pruned, in the other buffer and
   // the next frame's k_propagate commits the window size)?  Never the call's last frame: it prunes with its own launch, so that
   // ncam is final when the call returns.  The frame step and commit_buffer_parity both ask here.
-  bool fuse_frame(int f, int f1) const { return fuse_prune && !prof && !overlap_feature && d.joseph == 0 && f + 1 < f1; }
+  bool fuse_frame(int f, int f1) const { return knobs.fuse_prune && !prof && !knobs.overlap_feature && d.joseph == 0 && f + 1 < f1; }
   // every slice ran the same frames; each fused one flipped the buffers
-  void commit_buffer_parity(int f0, int f1) {
+  void commit_buffer_parity(int f0, int f1) override {
     int flips = 0;
     for (int f = f0; f < f1; ++f) flips += fuse_frame(f, f1) ? 1 : 0;
     if (flips & 1) std::swap(d.P, P_spare);
@@ -822,7 +1227,7 @@ struct Batch : BatchBase {
   // asks here.
   int update_compress(int base) const {
     int cmp = base;
-    if (compress_route >= 0) cmp = (compress_route && d.trk_B) ? 3 : 0;
+    if (knobs.compress_route >= 0) cmp = (knobs.compress_route && d.trk_B) ? 3 : 0;
     if (n_lit > 0 && !cmp) cmp = d.compress;
     return cmp;
   }
@@ -865,9 +1270,8 @@ struct Batch : BatchBase {
     stage_begin(5, q); launch_kalman<S>(v, b0, nb, q); stage_end(5, q);
   }
   int marginalize(int b0, int nb, int mode) override {
-    POISON_GUARD();
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
+    if (int rc = guard()) return rc;
+    if (int rc = enter_range(b0, nb)) return rc;
     use_single_worklists();
     Dev<S> v = view(b0);
     v.mode = mode;
@@ -877,9 +1281,8 @@ struct Batch : BatchBase {
   }
   // ---- range forms (host_image_cycle; the per-filter entries with nb = 1)
   int cams_range(int b0, int nb, double* poses7) override {
-    POISON_GUARD();
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
+    if (int rc = guard()) return rc;
+    if (int rc = enter_range(b0, nb)) return rc;
     const size_t per = (size_t)n_cap * CAM_STRIDE;
     std::vector<S> tmp(per * nb);
     if (const int rc = read_back(tmp.data(), d.cam + (size_t)b0 * per, tmp.size() * sizeof(S))) return rc;
@@ -889,9 +1292,8 @@ struct Batch : BatchBase {
     return 0;
   }
   int feature_only_range(int b0, int nb, int* status, double* pf3, bool launch) override {
-    POISON_GUARD();
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
+    if (int rc = guard()) return rc;
+    if (int rc = enter_range(b0, nb)) return rc;
     if (launch) { use_single_worklists(); launch_feature<S>(view(b0), b0, nb, st); HIPCHK(hipGetLastError()); }
     std::vector<int> stt((size_t)nb * f_cap); std::vector<S> pf((size_t)nb * f_cap * 4);
     HIPCHK(hipMemcpyAsync(stt.data(), d.trk_status + (size_t)b0 * f_cap, stt.size() * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -901,8 +1303,7 @@ struct Batch : BatchBase {
     return 0;
   }
   int set_given_range(int b0, int nb, const double* pf3) override {
-    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
+    if (int rc = enter_range(b0, nb)) return rc;
     const size_t cnt = (size_t)nb * f_cap * 4;
     unsigned char* raw = nullptr;
     int rc = stage_acquire(cnt * sizeof(S), &raw);
@@ -913,9 +1314,9 @@ struct Batch : BatchBase {
     return stage_release();
   }
   int prune_keep_range(int b0, int nb, const std::vector<std::vector<int>>& keep) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     if (chk_range(b0, nb) || (int)keep.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     // [nb][n_cap] slots + [nb] counts through the pinned ring, two copies, one launch (a trajectory that keeps everything is a no-op
     // there).  Like every other input: no wait for the stream in the middle of an image's chain (the update before it, k_prune and
     // the state read after it are one uninterrupted queue)
@@ -940,20 +1341,20 @@ struct Batch : BatchBase {
     HIPCHK(hipGetLastError());
     return 0;
   }
-  int drop_oldest(int b0, int nb, int n) override;
-  int ncam_host(int b) const override { return (b < 0 || b >= B) ? -EINVAL : (poisoned ? -EIO : h_ncam[b]); }   // a poisoned handle's count is not to be trusted (its slices may have stopped at different frames)
-  int get_ncam(int b, int* n) override {
-    POISON_GUARD();
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    return read_back(n, d.ncam + b, sizeof(int));
+  int drop_oldest(int b0, int nb, int n) override {
+    if (int rc = guard()) return rc;
+    if (int rc = enter_range(b0, nb)) return rc;
+    launch_prune<S>(d, b0, nb, st, nullptr, std::max(n, 0));
+    for (int b = b0; b < b0 + nb; ++b) h_ncam[b] -= std::max(0, std::min(n, h_ncam[b]));
+    HIPCHK(hipGetLastError());
+    return 0;
   }
   int get_imu(int b, double* o) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     S* tmp = h_imu.data() + (size_t)b * IMU_STRIDE;
     if (!h_imu_ok[b]) {
-      DEVICE_ENTER();
+      if (int rc = enter()) return rc;
       if (const int rc = read_back(tmp, d.imu + (size_t)b * IMU_STRIDE, IMU_STRIDE * sizeof(S))) return rc;
       h_imu_ok[b] = 1;
     }
@@ -961,8 +1362,7 @@ struct Batch : BatchBase {
     return 0;
   }
   int set_imu(int b, const double* in) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
+    if (int rc = enter_traj(b)) return rc;
     S tmp[IMU_STRIDE] = {0};
     for (int i = 0; i < 29; ++i) tmp[i] = (S)in[i];
     if (const int rc = write_dev(d.imu + (size_t)b * IMU_STRIDE, tmp, sizeof(tmp))) return rc;
@@ -970,7 +1370,7 @@ struct Batch : BatchBase {
     return 0;
   }
   int get_cams(int b, double* o, int cap, int* nout) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     int n = 0;
     int rc = get_ncam(b, &n);
     if (rc) return rc;
@@ -985,10 +1385,10 @@ struct Batch : BatchBase {
   // the single-filter API knows its window size on the host: no count read first, and the IMU state rides along into the host
   // copy (nothing changes it between an update and the next propagate), so that the getImuState() that follows costs no wait
   int get_cams_known(int b, double* o, int n) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     if (chk(b) || n < 0 || n > n_cap) return fail(-EINVAL, "index out of range");
-    DEVICE_ENTER();
-    S* tmp = h_rb; S* tim = h_rb + (size_t)n_cap * CAM_STRIDE;        // (page-locked: a pageable destination goes through the runtime's own staging copy)
+    if (int rc = enter()) return rc;
+    S* tmp = static_cast<S*>(h_rb); S* tim = tmp + (size_t)n_cap * CAM_STRIDE;        // (page-locked: a pageable destination goes through the runtime's own staging copy)
     if (n) HIPCHK(hipMemcpyAsync(tmp, d.cam + (size_t)b * n_cap * CAM_STRIDE, (size_t)n * CAM_STRIDE * sizeof(S), hipMemcpyDeviceToHost, st));
     const bool want_imu = !h_imu_ok[b];
     if (want_imu) HIPCHK(hipMemcpyAsync(tim, d.imu + (size_t)b * IMU_STRIDE, IMU_STRIDE * sizeof(S), hipMemcpyDeviceToHost, st));
@@ -999,13 +1399,13 @@ struct Batch : BatchBase {
   }
   int set_cam(int b, int slot, const double* in) override {
     if (chk(b) || slot < 0 || slot >= n_cap) return fail(-EINVAL, "index out of range");
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     S tmp[CAM_STRIDE] = {0};
     for (int k = 0; k < 7; ++k) tmp[k] = (S)in[k];
     return write_dev(d.cam + ((size_t)b * n_cap + slot) * CAM_STRIDE, tmp, sizeof(tmp));
   }
   int get_cov(int b, double* P, int ldo) override {
-    POISON_GUARD();
+    if (int rc = guard()) return rc;
     int n = 0;
     int rc = get_ncam(b, &n);
     if (rc) return rc;
@@ -1019,7 +1419,7 @@ struct Batch : BatchBase {
   int set_cov(int b, const double* P, int D) override {
     if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
     if (D < 15 || (D - 15) % 6 || (D - 15) / 6 > n_cap) return fail(-EINVAL, "bad covariance dimension");
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     std::vector<S> tmp((size_t)d.ld * d.ld, S(0));
     for (int j = 0; j < D; ++j) for (int i = 0; i < D; ++i) tmp[(size_t)j * d.ld + i] = (S)P[(size_t)j * D + i];
     const int n = (D - 15) / 6;
@@ -1029,41 +1429,18 @@ struct Batch : BatchBase {
     h_ncam[b] = n;
     return 0;
   }
-  int get_nres(int b, long long* n) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    return read_back(n, d.n_resid + b, sizeof(long long));
-  }
-  int set_nres(int b, long long n) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    return write_dev(d.n_resid + b, &n, sizeof(long long));
-  }
-  int stats(int b, int* out) override {
-    POISON_GUARD();
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    int tmp[STAT_STRIDE];
-    if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
-    for (int i = 0; i < 7; ++i) out[i] = tmp[i];
-    if (tmp[STAT_ERR] & STAT_ERR_NCAP) return fail(-EOVERFLOW, "camera-state capacity n_cap exceeded in augmentState");
-    if (tmp[STAT_ERR] & STAT_ERR_PIVOT)
-      return fail(-EDOM, "non-positive pivot in the factorization of S = T_H P T_H^T + R_n: the covariance lost positive definiteness "
-                         "(msckf_hip_set_covariance_update(h, 1) selects the reference's Joseph form)");
-    return 0;
-  }
   // value semantics of the reference object (MSCKF<_S> is copyable, msckf.h:31-67): the filter state of every trajectory
   // -- IMU / camera states, parameters, covariance, window size, counters, flags -- and the host-side track bookkeeping;
   // work buffers and a resident scenario are not state and are not copied
-  int copy_from(BatchBase* src) override {
-    POISON_GUARD();
+  int copy_from(BatchCore* src) override {
+    if (int rc = guard()) return rc;
     Batch<S>* o = dynamic_cast<Batch<S>*>(src);
     if (!o || o->B != B || o->n_cap != n_cap || o->f_cap != f_cap || o->m_cap != m_cap || o->h16 != h16)
       return fail(-EINVAL, "copy_state: handles differ in shape or dtype");
     if (o->poisoned) return fail(-EIO, "copy_state: the source handle is unusable after a failed run_frames call (its filter states are undefined)");
     { const int rcf = o->flush_pending(); if (rcf) return rcf; }
     for (int b = 0; b < o->B; ++b) { const int rcm = resolve_map(o, b); if (rcm) return rcm; }   // (work buffers are not copied: points still on the device first)
-    DEVICE_ENTER();
+    if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(o->st));
     const size_t Bz = B, pl = (size_t)d.ld * d.ld;
     auto cp = [&](void* dst, const void* sp, size_t bytes) { return hipMemcpyAsync(dst, sp, bytes, hipMemcpyDeviceToDevice, st); };
@@ -1073,20 +1450,13 @@ struct Batch : BatchBase {
     HIPCHK(cp(d.ncam, o->d.ncam, Bz * sizeof(int))); HIPCHK(cp(d.n_resid, o->d.n_resid, Bz * sizeof(long long)));
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
-    compress_route = o->compress_route; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; nstreams = o->nstreams;
-    overlap_feature = o->overlap_feature; d.gain_fused_s = o->d.gain_fused_s; fuse_prune = o->fuse_prune;
+    knobs = o->knobs; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; d.gain_fused_s = o->d.gain_fused_s;
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
     return set_aniso(o->aniso_mode, o->lit_tol);   // re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed
   }
-  int error_flags(int b, int* flags) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
-    return read_back(flags, d.stats + (size_t)b * STAT_STRIDE + STAT_ERR, sizeof(int));
-  }
   int track_info(int b, double* out, int cap) override {
-    if (chk(b)) return fail(-EINVAL, "trajectory index out of range");
-    DEVICE_ENTER();
+    if (int rc = enter_traj(b)) return rc;
     int tmp[STAT_STRIDE];
     if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
     const int F = tmp[STAT_NTRACKS];
@@ -1118,44 +1488,6 @@ struct Batch : BatchBase {
     for (int i = 0; i < D; ++i) out[i] = (double)tmp[i];
     return D;
   }
-  // ---- scenario
-  void free_scenario_device() {
-    for (void* q : sc_allocs) {                                  // a previous scenario is replaced, not leaked
-      hipFree(q);
-      allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end());
-    }
-    sc_allocs.clear();
-    sc_rd = nullptr; sc_n = sc_M = sc_off = sc_drop = sc_slots = nullptr; sc_obs = nullptr; sc_total = 0;
-  }
-  template <class T> int sc_dalloc(T** p, size_t count) {
-    const size_t mark = allocs.size();
-    const int rc = dalloc(p, count);
-    sc_allocs.insert(sc_allocs.end(), allocs.begin() + mark, allocs.end());
-    return rc;
-  }
-  int scen_alloc(int n_frames, int K) override {
-    if (n_frames <= 0 || K <= 0) return fail(-EINVAL, "bad scenario size");
-    DEVICE_ENTER();
-    HIPCHK(hipStreamSynchronize(st));
-    free_scenario_device();
-    sc_frames = 0; committed = false;
-    unpin_host();
-    const size_t Bz = B, FB = (size_t)n_frames * Bz;
-    h_rd.assign(FB * K * RD_STRIDE, S(0)); h_n.assign(FB, 0); h_M.assign(FB * f_cap, 0); h_off.assign(FB * f_cap, 0);
-    h_drop.assign(FB, 0); h_maxslot.assign(FB, -1);
-    c_slots.assign(FB, std::vector<int>()); c_obs.assign(FB, std::vector<S>());
-    fr_base.assign((size_t)n_frames + 1, 0);
-    pinf.assign((size_t)n_frames, PinFrame());
-    int rc = 0;
-    rc |= sc_dalloc(&sc_rd, h_rd.size()); rc |= sc_dalloc(&sc_n, h_n.size()); rc |= sc_dalloc(&sc_M, h_M.size());
-    rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size());
-    if (rc) return rc;
-    // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
-    pk_rd = 0; pk_n = al256(pk_rd + Bz * K * RD_STRIDE * sizeof(S)); pk_drop = al256(pk_n + Bz * sizeof(int));
-    pk_M = al256(pk_drop + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
-    sc_frames = n_frames; sc_K = K;
-    return 0;
-  }
   int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) override {
     if (f < 0 || f >= sc_frames || chk(b)) return fail(-EINVAL, "scenario cell out of range");
     { const int rc = check_worklist(F, M, slots); if (rc) return rc; }   // before the staged cell is touched
@@ -1163,167 +1495,27 @@ struct Batch : BatchBase {
     const size_t cell = (size_t)f * B + b;
     size_t tot = 0;
     for (int t = 0; t < F; ++t) tot += M[t];
-    for (int k = 0; k < sc_K; ++k) for (int c = 0; c < RD_STRIDE; ++c) h_rd[(cell * sc_K + k) * RD_STRIDE + c] = (S)rd[k * RD_STRIDE + c];
+    S* hr = reinterpret_cast<S*>(h_rd.data()) + cell * sc_K * RD_STRIDE;   // (the core stores the cell's scalars as bytes)
+    for (int k = 0; k < sc_K; ++k) for (int c = 0; c < RD_STRIDE; ++c) hr[k * RD_STRIDE + c] = (S)rd[k * RD_STRIDE + c];
     h_n[cell] = F; h_drop[cell] = n_drop;
     for (int t = 0; t < f_cap; ++t) h_M[cell * f_cap + t] = t < F ? M[t] : 0;
     c_slots[cell].assign(slots, slots + tot);
-    c_obs[cell].resize(2 * tot);
+    c_obs[cell].resize(2 * tot * sizeof(S));
+    S* co = reinterpret_cast<S*>(c_obs[cell].data());
     int mx = -1;
-    for (size_t e = 0; e < tot; ++e) { mx = std::max(mx, slots[e]); c_obs[cell][2 * e] = (S)obs[2 * e]; c_obs[cell][2 * e + 1] = (S)obs[2 * e + 1]; }
+    for (size_t e = 0; e < tot; ++e) { mx = std::max(mx, slots[e]); co[2 * e] = (S)obs[2 * e]; co[2 * e + 1] = (S)obs[2 * e + 1]; }
     h_maxslot[cell] = mx;
     committed = false;               // offsets move: the resident copy and the frame's page-locked block are stale until the next commit
     unpin_frame(f);                  // (its chunk is released with the last of its frames: patch -> commit -> stream cycles do not grow)
     return 0;
-  }
-  // the compact cells of frame f, trajectory after trajectory, as one contiguous block: slots to hs, coordinates to ho
-  void gather_frame(int f, int* hs, S* ho) const {
-    size_t o = 0;
-    for (int b = 0; b < B; ++b) {
-      const size_t cell = (size_t)f * B + b, n = c_slots[cell].size();
-      if (n) { std::memcpy(hs + o, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * o, c_obs[cell].data(), 2 * n * sizeof(S)); }
-      o += n;
-    }
-  }
-  // H2D of everything staged.  The host copy is kept, so cells may be patched with scenario_set and committed again.
-  int scen_commit() override {
-    if (sc_frames <= 0) return fail(-EINVAL, "no scenario allocated");
-    DEVICE_ENTER();
-    HIPCHK(hipStreamSynchronize(st));
-    const size_t Bz = B;
-    size_t total = 0;
-    for (int f = 0; f < sc_frames; ++f) {
-      fr_base[f] = total;
-      size_t in_frame = 0;
-      for (size_t b = 0; b < Bz; ++b) {
-        const size_t cell = (size_t)f * Bz + b;
-        size_t o = in_frame;
-        for (int t = 0; t < f_cap; ++t) { h_off[cell * f_cap + t] = (int)o; o += h_M[cell * f_cap + t]; }
-        in_frame += c_slots[cell].size();
-      }
-      if (in_frame > 0x7fffffffu) return fail(-E2BIG, "a frame's work-lists exceed 2^31 observations");
-      total += in_frame;
-    }
-    fr_base[sc_frames] = total;
-    if (total != sc_total || !sc_slots) {          // patched cells may have changed the compact size
-      for (void* q : {(void*)sc_slots, (void*)sc_obs})
-        if (q) { hipFree(q); allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end()); sc_allocs.erase(std::remove(sc_allocs.begin(), sc_allocs.end(), q), sc_allocs.end()); }
-      sc_slots = nullptr; sc_obs = nullptr;
-      int rc = sc_dalloc(&sc_slots, total); rc |= sc_dalloc(&sc_obs, 2 * total);
-      if (rc) return rc;
-      sc_total = total;
-    }
-    HIPCHK(hipMemcpyAsync(sc_rd, h_rd.data(), h_rd.size() * sizeof(S), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_n, h_n.data(), h_n.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_M, h_M.data(), h_M.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_off, h_off.data(), h_off.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_drop, h_drop.data(), h_drop.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    {   // size the pinned staging ring once, for the largest frame
-      size_t mx = 0;
-      for (int f = 0; f < sc_frames; ++f) mx = std::max(mx, fr_base[f + 1] - fr_base[f]);
-      const int rc = stage_reserve(mx * (sizeof(int) + 2 * sizeof(S)));
-      if (rc) return rc;
-    }
-    for (int f = 0; f < sc_frames; ++f) {            // one frame at a time through the pinned staging area (bounded host memory)
-      const size_t nf = fr_base[f + 1] - fr_base[f];
-      if (!nf) continue;
-      unsigned char* raw = nullptr;
-      int rc = stage_acquire(nf * (sizeof(int) + 2 * sizeof(S)), &raw);
-      if (rc) return rc;
-      int* hs = reinterpret_cast<int*>(raw); S* ho = reinterpret_cast<S*>(raw + nf * sizeof(int));
-      gather_frame(f, hs, ho);
-      HIPCHK(hipMemcpyAsync(sc_slots + fr_base[f], hs, nf * sizeof(int), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(sc_obs + 2 * fr_base[f], ho, 2 * nf * sizeof(S), hipMemcpyHostToDevice, st));
-      rc = stage_release();
-      if (rc) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    committed = true;
-    return 0;
-  }
-  // page-locked per-frame blocks for run_frames_streamed, frames [f0, f1) that do not have one yet; also sizes the device
-  // staging ring.  Called by run_frames_streamed itself; call it beforehand to keep the pinning out of a timed region.
-  int scen_pin(int f0, int f1) override {
-    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
-    if (!committed) return fail(-EINVAL, "scenario not committed");
-    DEVICE_ENTER();
-    const size_t Bz = B;
-    size_t need = 0, maxb = sg_bytes;
-    std::vector<int> todo;
-    for (int f = f0; f < f1; ++f) {
-      const size_t nf = fr_base[f + 1] - fr_base[f];
-      const size_t off_obs = al256(pk_slots + nf * sizeof(int)), bytes = al256(off_obs + 2 * nf * sizeof(S));
-      maxb = std::max(maxb, bytes);
-      if (pinf[f].p) continue;
-      pinf[f].bytes = bytes; pinf[f].off_obs = off_obs;
-      need += bytes; todo.push_back(f);
-    }
-    if (!todo.empty()) {
-      unsigned char* chunk = nullptr;
-      if (hipHostMalloc((void**)&chunk, need, hipHostMallocDefault) != hipSuccess) {
-        for (int f : todo) pinf[f] = PinFrame();
-        return fail(-ENOMEM, "could not page-lock the frames to stream (run_frames on the resident scenario is unaffected)");
-      }
-      int ci = -1;
-      for (size_t q = 0; q < pin_chunks.size(); ++q) if (!pin_chunks[q].p) { ci = (int)q; break; }
-      if (ci < 0) { pin_chunks.push_back(PinChunk()); ci = (int)pin_chunks.size() - 1; }
-      pin_chunks[ci].p = chunk; pin_chunks[ci].live = (int)todo.size();
-      size_t o = 0;
-      for (int f : todo) {
-        unsigned char* blk = chunk + o;
-        const size_t c0 = (size_t)f * Bz;
-        std::memcpy(blk + pk_rd, h_rd.data() + c0 * sc_K * RD_STRIDE, Bz * sc_K * RD_STRIDE * sizeof(S));
-        std::memcpy(blk + pk_n, h_n.data() + c0, Bz * sizeof(int));
-        std::memcpy(blk + pk_drop, h_drop.data() + c0, Bz * sizeof(int));
-        std::memcpy(blk + pk_M, h_M.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
-        std::memcpy(blk + pk_off, h_off.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
-        gather_frame(f, reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs));
-        pinf[f].p = blk; pinf[f].chunk = ci;
-        o += pinf[f].bytes;
-      }
-    }
-    if (maxb > sg_bytes || !sg_blk[0]) {
-      HIPCHK(hipStreamSynchronize(st));
-      if (stc) HIPCHK(hipStreamSynchronize(stc));
-      for (int k = 0; k < RING_MAX; ++k) { if (sg_blk[k]) hipFree(sg_blk[k]); sg_blk[k] = nullptr; }
-      for (int k = 0; k < RING_MAX; ++k) HIPCHK(hipMalloc((void**)&sg_blk[k], maxb));
-      sg_bytes = maxb;
-    }
-    return 0;
-  }
-  int run_frames(int f0, int f1) override;
-  int run_frames_streamed(int f0, int f1) override;
-  void unpin_host() {
-    for (auto& q : pin_chunks) if (q.p) hipHostFree(q.p);
-    pin_chunks.clear();
-    for (auto& pf : pinf) pf = PinFrame();
-  }
-  int set_upload_ring(int depth, int mode) override {
-    if (depth < 2 || depth > RING_MAX || mode < 0 || mode > 1) return fail(-EINVAL, "ring depth 2..8; mode 0 host hand-over, 1 device-side event waits");
-    ring = depth; up_mode = mode;
-    return 0;
-  }
-  // ---- the frame loop of a scenario (run_frames, run_frames_streamed)
-  // Trajectories are independent, so the batch may be cut into slices that run the same kernel sequence on separate streams:
-  // the latency-bound stages of one slice (gain solve, Cholesky, propagate: one workgroup per trajectory) overlap with the
-  // chip-filling stages of the others.  One host thread per slice enqueues that slice's kernels for all frames of the call
-  // (~13 launches per frame and slice would otherwise serialise on one thread and make more than two slices launch-bound).
-  // Stage profiling forces a single stream.
-  int n_slices() const { return prof ? 1 : std::max(1, std::min(nstreams, B)); }
-  // slice hh of nh on its enqueue thread: trajectories [b0, b0 + nb) on stream q.  A frame whose prune rides on the downdate
-  // leaves the covariance in the other buffer (curP / spare) and the new window size for the next k_propagate to commit (pending)
-  struct Slice { int hh, b0, nb; hipStream_t q; S* curP; S* spare; bool pending; };
-  Slice begin_slice(int hh, int nh) {
-    (void)hipSetDevice(device);
-    (void)hipGetLastError();
-    const int b0 = (int)((long)B * hh / nh);
-    return Slice{hh, b0, (int)((long)B * (hh + 1) / nh) - b0, stx[hh], d.P, P_spare, false};
   }
   // where a frame's inputs are on the device, for a slice that starts at trajectory b0: per-trajectory arrays already offset
   // to b0, slots / obs the frame's compact entries (tracks find theirs through off)
   struct FrameIn { const S* rd; const int* n; const int* M; const int* off; const int* slots; const S* obs; const int* drop; };
   FrameIn resident_frame(int f, int b0) const {
     const size_t c = (size_t)f * B + b0;
-    return FrameIn{sc_rd + c * sc_K * RD_STRIDE, sc_n + c, sc_M + c * f_cap, sc_off + c * f_cap, sc_slots + fr_base[f], sc_obs + 2 * fr_base[f], sc_drop + c};
+    return FrameIn{reinterpret_cast<const S*>(sc_rd) + c * sc_K * RD_STRIDE, sc_n + c, sc_M + c * f_cap, sc_off + c * f_cap, sc_slots + fr_base[f],
+                   reinterpret_cast<const S*>(sc_obs) + 2 * fr_base[f], sc_drop + c};
   }
   FrameIn staged_frame(int f, int k, int b0) const {   // frame f as uploaded into staging set k
     unsigned char* blk = sg_blk[k];
@@ -1331,22 +1523,25 @@ struct Batch : BatchBase {
                    reinterpret_cast<int*>(blk + pk_M) + (size_t)b0 * f_cap, reinterpret_cast<int*>(blk + pk_off) + (size_t)b0 * f_cap,
                    reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs), reinterpret_cast<int*>(blk + pk_drop) + b0};
   }
-  // THE frame step: frame f of a call over [f0, f1) for slice s, inputs at `in` -- propagate + augmentState, the update, the
-  // prune (on the downdate or with its own launch, fuse_frame), the host mirror of the window size.
+  // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged` or (staged < 0) resident --
+  // propagate + augmentState, the update, the prune (on the downdate or with its own launch, fuse_frame), the host mirror of
+  // the window size.
   // may_overlap (resident inputs only): k_feature reads only what the previous frame's prune left behind -- camera states and
   // P blocks of slots below the newest one, the constant gravity vector -- unless a track observes the camera this frame's
   // augmentState adds.  When none does (host mirror of the window sizes, slots known since scenario_set) and the handle asks
   // for it (set_feature_overlap) it runs on a side stream concurrently with the latency-bound propagate + augment.
-  void enqueue_frame(Slice& s, int f, int f0, int f1, const FrameIn& in, bool may_overlap) {
+  void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) override {
     const int b0 = s.b0, nb = s.nb, hh = s.hh;
+    const FrameIn in = staged < 0 ? resident_frame(f, b0) : staged_frame(f, staged, b0);
+    const bool may_overlap = staged < 0;
     hipStream_t q = s.q;
     const size_t cell0 = (size_t)f * B;
     Dev<S> v = d;
-    v.P = s.curP; v.ncam_defer = s.pending ? 1 : 0;
+    v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
     v.trk_n = in.n; v.trk_M = in.M; v.trk_off = in.off; v.trk_slots = in.slots; v.trk_obs = in.obs;
     v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
-    bool early = may_overlap && overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
+    bool early = may_overlap && knobs.overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
     for (int b = b0; b < b0 + nb && early; ++b) {
       const int n_after = std::min(h_ncam[b] + 1, n_cap);
       early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2;
@@ -1367,9 +1562,9 @@ struct Batch : BatchBase {
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
     v.ncam_defer = 0;
-    if (fuse) { v.Pout = s.spare; v.fuse_drop = in.drop; }
+    if (fuse) { v.Pout = s.flipped ? d.P : P_spare; v.fuse_drop = in.drop; }
     { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1); }
-    if (fuse) std::swap(s.curP, s.spare);
+    if (fuse) s.flipped = !s.flipped;
     else {
       StageRange r("msckf_prune_empty_states");
       stage_begin(6, q);
@@ -1382,210 +1577,19 @@ struct Batch : BatchBase {
       h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
     }
   }
-  // fork: the slices' streams (and the copy stream of a streamed run) start after what is queued on st
-  int fork_slices(int nh, hipStream_t extra = nullptr) {
-    if (nh <= 1 && !extra) return 0;
-    HIPCHK(hipEventRecord(ev_fork, st));
-    for (int i = 1; i < nh; ++i) HIPCHK(hipStreamWaitEvent(stx[i], ev_fork, 0));
-    if (extra) HIPCHK(hipStreamWaitEvent(extra, ev_fork, 0));
-    return 0;
-  }
-  // the end of a call whose frames are enqueued: st waits for the slices (and the copy stream); a launch error of any slice
-  // (slice_rc: hipGetLastError is per host thread, a failed launch must not vanish with its thread) makes the handle
-  // unusable; otherwise the covariance buffer that is current now becomes the handle's
-  int finish_slices(int nh, const int* slice_rc, int f0, int f1, hipStream_t extra = nullptr) {
-    for (int i = 1; i < nh; ++i)
-      if (hipEventRecord(ev_join[i], stx[i]) != hipSuccess || hipStreamWaitEvent(st, ev_join[i], 0) != hipSuccess) return poison(-EIO, "joining the slices' streams failed");
-    if (extra && (hipEventRecord(ev_join[1], extra) != hipSuccess || hipStreamWaitEvent(st, ev_join[1], 0) != hipSuccess)) return poison(-EIO, "joining the copy stream failed");
-    for (int i = 0; i < nh; ++i)
-      if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
-    commit_buffer_parity(f0, f1);
-    return 0;
-  }
-  int sync() override {
-    DEVICE_ENTER();
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
-  }
-  int prof_enable(int on) override {
-    prof = on != 0;
-    for (int s = 0; s < NSTAGE; ++s) { ev_used[s] = 0; prof_ms[s] = 0; prof_cnt[s] = 0; }
-    return 0;
-  }
   int set_gate_early(int on) override { d.gate_early = on ? 1 : 0; return 0; }
-  int set_feature_overlap(int on) override { overlap_feature = on ? 1 : 0; return 0; }
   int set_cov_update(int form) override {
     if (form < 0 || form > 2) return fail(-EINVAL, "form: 0 square-root gain (P - W W^T), 1 Joseph, 2 square-root gain with the register-resident solve");
     d.joseph = form;
     return 0;
   }
-  int set_compression(int route) override {
-    if (route < -1 || route > 3) return fail(-EINVAL, "route: -1 default, 0 Householder TSQR, 1..3 information form (blocked matrix-core Cholesky; 1 and 2 named retired factorizations)");
-    if (route >= 1 && !d.trk_B) return fail(-ENOTSUP, "information form not available for this window size (6 n_cap + 1 > 384 or f_cap > 1024)");
-    compress_route = route;
-    return 0;
-  }
-  int set_host_affinity(const int* cpus, int n) override {
-    std::lock_guard<std::mutex> lk(workers.m);
-    workers.cpus.assign(cpus, cpus + std::max(n, 0));
-    return 0;
-  }
-  int set_streams(int n) override {
-    if (n < 1 || n > MAXS) return fail(-EINVAL, "1 to 8 streams");
-    nstreams = n;
-    return 0;
-  }
-  // what an event pair with NOTHING between its records measures on this stream (the marker packets themselves): the stage
-  // timers of prof_read hold one such pair per launch, so a single-kernel stage reads kernel time + this
-  int prof_event_overhead(double* ms) override {
-    DEVICE_ENTER();
-    hipEvent_t a, b2;
-    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b2));
-    HIPCHK(hipStreamSynchronize(st));
-    double tot = 0; const int reps = 64;
-    for (int i = 0; i < reps; ++i) {
-      HIPCHK(hipEventRecord(a, st)); HIPCHK(hipEventRecord(b2, st));
-      HIPCHK(hipEventSynchronize(b2));
-      float t = 0; HIPCHK(hipEventElapsedTime(&t, a, b2));
-      tot += t;
-    }
-    hipEventDestroy(a); hipEventDestroy(b2);
-    *ms = tot / reps;
-    return 0;
-  }
-  int prof_read(double* ms, int* cnt, int cap) override {
-    DEVICE_ENTER();
-    HIPCHK(hipStreamSynchronize(st));
-    for (int s = 0; s < NSTAGE; ++s) {
-      for (size_t i = 0; i < ev_used[s]; ++i) {
-        float t = 0;
-        HIPCHK(hipEventElapsedTime(&t, ev_pool[s][i].first, ev_pool[s][i].second));
-        prof_ms[s] += t; prof_cnt[s]++;
-      }
-      ev_used[s] = 0;
-      if (s < cap) { ms[s] = prof_ms[s]; cnt[s] = prof_cnt[s]; }
-    }
-    return 0;
-  }
 };
-
-template <class S>
-int Batch<S>::drop_oldest(int b0, int nb, int n) {
-  POISON_GUARD();
-  if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
-  DEVICE_ENTER();
-  launch_prune<S>(d, b0, nb, st, nullptr, std::max(n, 0));
-  for (int b = b0; b < b0 + nb; ++b) h_ncam[b] -= std::max(0, std::min(n, h_ncam[b]));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <class S>
-int Batch<S>::run_frames(int f0, int f1) {
-  POISON_GUARD();
-  if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
-  if (!committed) return fail(-EINVAL, "scenario not committed");
-  DEVICE_ENTER();
-  const int nh = n_slices();
-  const int rc = fork_slices(nh);
-  if (rc) return rc;
-  int slice_rc[MAXS] = {0};
-  auto enqueue = [&](int hh) {
-    Slice s = begin_slice(hh, nh);
-    for (int f = f0; f < f1; ++f) enqueue_frame(s, f, f0, f1, resident_frame(f, s.b0), true);
-    slice_rc[hh] = (int)hipGetLastError();
-  };
-  if (nh == 1) enqueue(0);
-  else {
-    workers.start(nh - 1, [&](int idx) { enqueue(idx + 1); });
-    enqueue(0);
-    workers.wait();
-  }
-  return finish_slices(nh, slice_rc, f0, f1);
-}
-
-// run_frames with the inputs handed over per frame, as the reference's callers do (asl_msckf.cpp:227-284: IMU samples and
-// the image's tracks arrive with the image): frame f's block -- IMU samples + compact work-list, what the frame really
-// holds, not a padded maximum -- goes from page-locked host memory into staging set f % ring on a copy stream, up to
-// ring - 1 frames ahead of the kernels that consume it.  Hand-over (up_mode 0): the uploading thread waits for its copy on
-// the HOST and publishes the frame number; a slice's enqueue thread launches frame f only after that, and the uploader
-// reuses a set only after every slice's "consumed" event of frame f - ring has completed -- no stream ever waits for
-// another stream's event on the device (those waits cost 0.15-0.25 ms per frame with two staging sets).  up_mode 1 keeps
-// the device-side hipStreamWaitEvent protocol, for comparison.
-template <class S>
-int Batch<S>::run_frames_streamed(int f0, int f1) {
-  POISON_GUARD();
-  if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
-  if (!committed) return fail(-EINVAL, "scenario not committed");
-  DEVICE_ENTER();
-  {
-    bool all = sg_blk[0] != nullptr;
-    for (int f = f0; f < f1 && all; ++f) all = pinf[f].p != nullptr;
-    if (!all) { int rc = scen_pin(f0, f1); if (rc) return rc; }
-  }
-  if (!stc) {
-    HIPCHK(hipStreamCreateWithFlags(&stc, hipStreamNonBlocking));
-    for (int k = 0; k < RING_MAX; ++k) {
-      HIPCHK(hipEventCreateWithFlags(&ev_up[k], hipEventDisableTiming));
-      for (int i = 0; i < MAXS; ++i) HIPCHK(hipEventCreateWithFlags(&ev_use[k][i], hipEventDisableTiming));
-    }
-  }
-  const int nh = n_slices();
-  const int R = ring, mode = up_mode;
-  const int rc = fork_slices(nh, stc);
-  if (rc) return rc;
-  // up_rdy = frames whose block may be read (mode 0: the copy has completed; mode 1: copy + event record are enqueued --
-  // an event must be recorded before a wait on it is enqueued); use_enq[s] = frames whose "consumed" record is enqueued.
-  std::atomic<int> up_rdy{f0};
-  std::atomic<int> use_enq[MAXS];
-  for (int i = 0; i < MAXS; ++i) use_enq[i].store(f0);
-  std::atomic<int> failed{0};
-  int slice_rc[MAXS] = {0};
-  auto slice = [&](int hh) {
-    Slice s = begin_slice(hh, nh);
-    for (int f = f0; f < f1; ++f) {
-      while (up_rdy.load(std::memory_order_acquire) <= f && !failed.load()) std::this_thread::yield();
-      if (failed.load()) break;
-      const int k = (f - f0) % R;
-      if (mode == 1) (void)hipStreamWaitEvent(s.q, ev_up[k], 0);
-      enqueue_frame(s, f, f0, f1, staged_frame(f, k, s.b0), false);
-      (void)hipEventRecord(ev_use[k][hh], s.q);
-      use_enq[hh].store(f + 1, std::memory_order_release);
-    }
-    slice_rc[hh] = (int)hipGetLastError();
-  };
-  // the uploading (calling) thread on its own core for the duration of the call, when a list of cores was given
-  cpu_set_t old_mask; bool repin = false;
-  if (!workers.cpus.empty() && workers.cpus[0] >= 0 && pthread_getaffinity_np(pthread_self(), sizeof(old_mask), &old_mask) == 0) {
-    cpu_set_t one; CPU_ZERO(&one); CPU_SET(workers.cpus[0], &one);
-    (void)pthread_setaffinity_np(pthread_self(), sizeof(one), &one); repin = true;
-  }
-  workers.start(nh, slice);
-  int rc_up = 0;
-  for (int f = f0; f < f1 && !rc_up; ++f) {
-    const int k = (f - f0) % R;
-    if (f - f0 >= R)
-      for (int i = 0; i < nh && !rc_up; ++i) {   // the set is free again once every slice has consumed frame f - R
-        while (use_enq[i].load(std::memory_order_acquire) <= f - R) std::this_thread::yield();
-        const hipError_t e = mode == 0 ? hipEventSynchronize(ev_use[k][i]) : hipStreamWaitEvent(stc, ev_use[k][i], 0);
-        if (e != hipSuccess) rc_up = -EIO;
-      }
-    if (!rc_up && (f == test_fail_upload || hipMemcpyAsync(sg_blk[k], pinf[f].p, pinf[f].bytes, hipMemcpyHostToDevice, stc) != hipSuccess)) rc_up = -EIO;
-    if (!rc_up && (mode == 0 ? hipStreamSynchronize(stc) : hipEventRecord(ev_up[k], stc)) != hipSuccess) rc_up = -EIO;
-    if (rc_up) failed.store(1);
-    up_rdy.store(f + 1, std::memory_order_release);
-  }
-  workers.wait();
-  if (repin) (void)pthread_setaffinity_np(pthread_self(), sizeof(old_mask), &old_mask);
-  if (rc_up) return poison(rc_up, "input upload failed");
-  return finish_slices(nh, slice_rc, f0, f1, stc);
-}
 
 // -------------------------------------------------------------------------------------------------
 // host bookkeeping shared by both dtypes (restates msckf.h:215-332, 685-717, 765-807, 1469-1485): the list work is
 // host_lists.h, free of device calls; here are the drivers that put the device calls between its steps
 // -------------------------------------------------------------------------------------------------
-int host_update(BatchBase* B, int b, const double* meas, const uint64_t* ids, int n) {
+int host_update(BatchCore* B, int b, const double* meas, const uint64_t* ids, int n) {
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
   if (t.cams.empty()) return fail(-EINVAL, "update() before augmentState() (msckf.h:238 dereferences cam_states_.end()-1)");
@@ -1593,7 +1597,7 @@ int host_update(BatchBase* B, int b, const double* meas, const uint64_t* ids, in
   return 0;
 }
 
-int host_add_features(BatchBase* B, int b, const double* meas, const uint64_t* ids, int n) {
+int host_add_features(BatchCore* B, int b, const double* meas, const uint64_t* ids, int n) {
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
   if (t.cams.empty()) return fail(-EINVAL, "addFeatures() before augmentState() (msckf.h:320)");
@@ -1601,9 +1605,9 @@ int host_add_features(BatchBase* B, int b, const double* meas, const uint64_t* i
   return 0;
 }
 
-int set_tracks(BatchBase* B, int b, const WorkList& wl) { return B->set_tracks(b, (int)wl.M.size(), wl.M.data(), wl.slots.data(), wl.obs.data()); }
+int set_tracks(BatchCore* B, int b, const WorkList& wl) { return B->set_tracks(b, (int)wl.M.size(), wl.M.data(), wl.slots.data(), wl.obs.data()); }
 
-int host_marginalize(BatchBase* B, int b) {
+int host_marginalize(BatchCore* B, int b) {
   HostTraj& t = B->traj[b];
   t.map.clear(); t.map_pending = 0;
   WorkList wl;
@@ -1618,7 +1622,7 @@ int host_marginalize(BatchBase* B, int b) {
 }
 
 // the triangulated points of the last marginalize() (msckf.h:371: map_.push_back(p_f_G)), fetched on demand
-int resolve_map(BatchBase* B, int b) {
+int resolve_map(BatchCore* B, int b) {
   HostTraj& t = B->traj[b];
   const int F = t.map_pending;
   if (F <= 0) return 0;
@@ -1637,7 +1641,7 @@ int resolve_map(BatchBase* B, int b) {
 }
 
 // retire what every trajectory of the range planned: one prune launch for the range, then the host lists
-static int prune_retired_range(BatchBase* B, int b0, const std::vector<Retirement>& ret) {
+static int prune_retired_range(BatchCore* B, int b0, const std::vector<Retirement>& ret) {
   const int nb = (int)ret.size();
   std::vector<std::vector<int>> keep(nb);
   for (int i = 0; i < nb; ++i) keep[i] = ret[i].keep;
@@ -1647,7 +1651,7 @@ static int prune_retired_range(BatchBase* B, int b0, const std::vector<Retiremen
   return 0;
 }
 
-int host_prune_empty(BatchBase* B, int b) {
+int host_prune_empty(BatchCore* B, int b) {
   HostTraj& t = B->traj[b];
   const int last_to_remove = plan_prune_empty(t);
   if (last_to_remove < 0) return 0;
@@ -1663,7 +1667,7 @@ int host_prune_empty(BatchBase* B, int b) {
 
 // MSCKF::pruneRedundantStates, msckf.h:453-682: keyframe selection and observation surgery on the host (host_lists.h),
 // the triangulation of not-yet-initialized features and the second measurement update on the device.
-int host_prune_redundant(BatchBase* B, int b) {
+int host_prune_redundant(BatchCore* B, int b) {
   HostTraj& t = B->traj[b];
   if (!t.initialized) return fail(-EINVAL, "trajectory not initialized");
   if (t.cams.size() < 20) return 0;                                           // :455
@@ -1706,7 +1710,7 @@ int host_prune_redundant(BatchBase* B, int b) {
   return prune_retired_range(B, b, ret);
 }
 
-int host_finish(BatchBase* B, int b) {
+int host_finish(BatchCore* B, int b) {
   HostTraj& t = B->traj[b];
   // D6: the reference appends to the stale feature_tracks_to_residualize_ of the previous update() (cleared only
   // at msckf.h:218), whose positional indices and pose copies are invalid once states were corrected/pruned;
@@ -1723,7 +1727,6 @@ int host_finish(BatchBase* B, int b) {
   return host_marginalize(B, b);
 }
 
-
 // -------------------------------------------------------------------------------------------------
 // One image of the ASL runner's loop (asl_msckf.cpp:269-294) for trajectories b0 .. b0 + nb - 1 of a batch IN LOCKSTEP:
 //   augmentState -> update -> addFeatures -> marginalize -> [pruneRedundantStates] -> [pruneEmptyStates]
@@ -1737,7 +1740,8 @@ int host_finish(BatchBase* B, int b) {
 // Same arithmetic per trajectory as the per-filter calls (tests/test_gpu_parity.py: bit for bit).
 // -------------------------------------------------------------------------------------------------
 // the bookkeeping of the trajectories of a range is independent: spread over host threads (created per call: tens of microseconds
-// against milliseconds of list surgery at the benchmark's 200 tracks per image); fn(i) returns 0 or an error code
+// against milliseconds of list surgery at the benchmark's 200 tracks per image); fn(i) returns 0 or an error code.  fail() leaves
+// its text with the thread it ran on: the first failure's code AND text come back to the caller's thread
 template <class Fn> static int parallel_for(int n, Fn fn) {
   unsigned hw = std::thread::hardware_concurrency();
   int nt = (int)std::min<unsigned>(hw ? hw : 1u, 32u);
@@ -1745,11 +1749,21 @@ template <class Fn> static int parallel_for(int n, Fn fn) {
   nt = std::min(nt, n);
   if (nt <= 1) { for (int i = 0; i < n; ++i) { const int rc = fn(i); if (rc) return rc; } return 0; }
   std::atomic<int> next(0), err(0);
-  auto work = [&]() { for (;;) { const int i = next.fetch_add(1); if (i >= n || err.load()) return; const int rc = fn(i); if (rc) err.store(rc); } };
+  std::string msg;   // written by the one thread that sets err, read after the join
+  auto work = [&]() {
+    for (;;) {
+      const int i = next.fetch_add(1);
+      if (i >= n || err.load()) return;
+      const int rc = fn(i);
+      int none = 0;
+      if (rc && err.compare_exchange_strong(none, rc)) msg = g_err;
+    }
+  };
   std::vector<std::thread> th;
   for (int k = 1; k < nt; ++k) th.emplace_back(work);
   work();
   for (auto& x : th) x.join();
+  if (err.load()) g_err = msg;
   return err.load();
 }
 template <class Fn> static int for_runs(const std::vector<char>& on, int b0, Fn fn) {
@@ -1766,7 +1780,7 @@ template <class Fn> static int for_runs(const std::vector<char>& on, int b0, Fn 
 }
 static bool any_of(const std::vector<char>& on) { for (char c : on) if (c) return true; return false; }
 
-int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const double* times,
+int host_image_cycle(BatchCore* B, int b0, int nb, const int* state_ids, const double* times,
                      const double* upd_meas, const uint64_t* upd_ids, const int* upd_n,
                      const double* new_meas, const uint64_t* new_ids, const int* new_n, int flags) {
   if (b0 < 0 || nb <= 0 || b0 + nb > B->B) return fail(-EINVAL, "trajectory range out of bounds");
@@ -1900,7 +1914,7 @@ int host_image_cycle(BatchBase* B, int b0, int nb, const int* state_ids, const d
   return 0;
 }
 
-BatchBase* H(msckf_hip_handle h) { return reinterpret_cast<BatchBase*>(h); }
+BatchCore* H(msckf_hip_handle h) { return reinterpret_cast<BatchCore*>(h); }
 }  // namespace
 
 #ifdef MSCKF_ABLATE
@@ -1936,13 +1950,11 @@ int msckf_hip_create(int B, int n_cap, int f_cap, int m_cap, int dtype, int devi
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(-ENODEV, "no HIP device available (this library has no CPU fallback)");
   if (device < 0 || device >= ndev) return fail(-ENODEV, "HIP device index out of range");
-  BatchBase* b = nullptr;
-  if (dtype == MSCKF_HIP_F32 || dtype == MSCKF_HIP_F16H_F32P) b = new Batch<float>();
-  else if (dtype == MSCKF_HIP_F64) b = new Batch<double>();
-  else return fail(-EINVAL, "dtype must be MSCKF_HIP_F32, MSCKF_HIP_F64 or MSCKF_HIP_F16H_F32P");
+  if (dtype != MSCKF_HIP_F32 && dtype != MSCKF_HIP_F64 && dtype != MSCKF_HIP_F16H_F32P) return fail(-EINVAL, "dtype must be MSCKF_HIP_F32, MSCKF_HIP_F64 or MSCKF_HIP_F16H_F32P");
+  BatchCore* b = dtype == MSCKF_HIP_F64 ? static_cast<BatchCore*>(new Batch<double>()) : new Batch<float>();
   b->B = B; b->n_cap = n_cap; b->f_cap = f_cap; b->m_cap = m_cap; b->dtype = dtype; b->device = device;
-  b->h16 = dtype == MSCKF_HIP_F16H_F32P;
-  int rc = dtype != MSCKF_HIP_F64 ? static_cast<Batch<float>*>(b)->create() : static_cast<Batch<double>*>(b)->create();
+  b->h16 = dtype == MSCKF_HIP_F16H_F32P; b->esz = dtype == MSCKF_HIP_F64 ? sizeof(double) : sizeof(float);
+  const int rc = b->create();
   if (rc) { delete b; return rc; }
   *out = reinterpret_cast<msckf_hip_handle>(b);
   return 0;
@@ -1950,7 +1962,7 @@ int msckf_hip_create(int B, int n_cap, int f_cap, int m_cap, int dtype, int devi
 int msckf_hip_destroy(msckf_hip_handle h) { delete H(h); return 0; }
 
 int msckf_hip_initialize(msckf_hip_handle h, int b, const double* cam12, const double* noise29, const double* params8, const double* imu29) {
-  return H(h)->init(b, cam12, noise29, params8, imu29);
+  return H(h)->init_core(b, cam12, noise29, nullptr, nullptr, params8, imu29);
 }
 int msckf_hip_initialize_full(msckf_hip_handle h, int b, const double* cam12, const double* uv2, const double* Q144, const double* P0_225,
                               const double* params8, const double* imu29) {
@@ -1959,7 +1971,7 @@ int msckf_hip_initialize_full(msckf_hip_handle h, int b, const double* cam12, co
 }
 int msckf_hip_propagate(msckf_hip_handle h, int b, const double* readings7, int K) { StageRange r("imu_prop"); return H(h)->propagate(b, 1, readings7, K, true); }
 int msckf_hip_augment_state(msckf_hip_handle h, int b, int state_id, double time) {
-  BatchBase* B = H(h);
+  BatchCore* B = H(h);
   if (b < 0 || b >= B->B) return fail(-EINVAL, "trajectory index out of range");
   if ((int)B->traj[b].cams.size() >= B->n_cap) return fail(-EOVERFLOW, "camera-state capacity n_cap exceeded");
   StageRange r("msckf_augment_state");
@@ -2006,9 +2018,7 @@ int msckf_hip_finish(msckf_hip_handle h, int b) {
   return host_finish(H(h), b);
 }
 int msckf_hip_get_num_cam_states(msckf_hip_handle h, int b) {   // cam_states_.size(): the host keeps the count (augment, prune, drop and run_frames all update it)
-  const int n = H(h)->ncam_host(b);
-  if (n == -EIO) return fail(-EIO, "handle unusable after a failed run_frames call (destroy it)");
-  return n < 0 ? fail(-EINVAL, "trajectory index out of range") : n;
+  return H(h)->ncam_host(b);
 }
 int msckf_hip_get_imu_state(msckf_hip_handle h, int b, double* imu29) { return H(h)->get_imu(b, imu29); }
 int msckf_hip_get_cam_states(msckf_hip_handle h, int b, double* cam7, int* state_ids, int cap) {

@@ -307,6 +307,41 @@ def test_prune_redundant_over_f_cap_is_the_same_error_on_both_paths(capi):
     one.close(); big.close()
 
 
+def test_batched_image_cycle_error_text_reaches_the_calling_thread(capi, monkeypatch):
+    """msckf_hip_image_cycle_range in which the second of eight trajectories is handed, as a new feature, an id it
+    already tracks: -EEXIST with addFeatures' own text.  The update / addFeatures bookkeeping of a range runs on worker
+    threads of the library when MSCKF_HIP_HOST_THREADS is unset and the range has two or more trajectories (the workers are
+    started before the calling thread joins in, so an early trajectory of a range of eight is theirs), and
+    msckf_hip_last_error() is per thread: the text written on a worker must be carried back to the thread that made the
+    call, or the caller reads whatever its own last failure left (the code alone was always right)."""
+    monkeypatch.delenv("MSCKF_HIP_HOST_THREADS", raising=False)
+    N, F, nf, B = 8, 10, 8, 8
+    trs = [sc.Trajectory(2, 80 + b, N, F, nf) for b in range(B)]
+    sts = [tr.stream() for tr in trs]
+    bt = capi.Batch(B, 16, 32, 16, capi.F64)
+    for b, tr in enumerate(trs):
+        bt.initialize(b, tr.cfg, tr.imu0)
+    with pytest.raises(capi.HipError, match="out of bounds"):     # the calling thread's own last error: not the one below
+        bt.propagate_range(0, B + 1, np.zeros((B + 1, 1, 7)))
+    raised = False
+    for k in range(nf):
+        cur = [sts[b][k]["cur"] for b in range(B)]
+        new = [sts[b][k]["new"] for b in range(B)]
+        dup = k >= 2 and len(cur[1][1]) > 0
+        if dup:     # an id that this image's update() keeps tracked comes again as new
+            new[1] = (list(new[1][0]) + [cur[1][0][0]], list(new[1][1]) + [cur[1][1][0]])
+        bt.propagate_range(0, B, np.stack([tr.imu_for_frame(k) for tr in trs]))
+        if not dup:
+            bt.image_cycle_range(0, B, [k] * B, [tr.frame_times[k] for tr in trs], cur, new)
+            continue
+        with pytest.raises(capi.HipError, match=r"\(-17\): .*already being tracked"):     # -EEXIST
+            bt.image_cycle_range(0, B, [k] * B, [tr.frame_times[k] for tr in trs], cur, new)
+        raised = True
+        break
+    assert raised
+    bt.close()
+
+
 def test_batched_range_equals_single(capi):
     """B trajectories in one launch give bit-identical results to B separate single-trajectory batches of
     the same geometry (same kernels, same chunking)."""
