@@ -27,6 +27,13 @@
  *                                                                                       types.h:69-76
  *   reading7 omega(3) a(3) dT                                                           types.h:78-84
  *   cam7     q_CG(4) p_C_G(3)                                                           types.h:57-67
+ *   frame log record, 48 scalars per frame and trajectory, all as the frame's update and prune leave them:
+ *            0-15  q_IG(4) b_g(3) v_I_G(3) b_a(3) p_I_G(3): the first 16 entries of imu29
+ *            16-30 diagonal of P_II (error-state order th b_g v b_a p)
+ *            31-36 upper triangle of the position block P[12..14][12..14]: xx xy xz yy yz zz
+ *            37    window size (camera states)
+ *            38-40 n_tracks, passed, sticky error flags of the update (out7[0], out7[4] of last_stats; get_error_flags)
+ *            41-47 cam7 of camera slot 0: the oldest surviving camera, the fixed-lag estimate; zeros for an empty window
  *
  * Pixel noise: with u_var_prime == v_var_prime (the configuration the throughput metric is quoted on) the update is
  * independent of the null-space basis and of the compression order and matches the reference to rounding.  With
@@ -189,6 +196,26 @@ int msckf_hip_scenario_pin(msckf_hip_handle h, int f0, int f1);
  * mode 1 uses hipStreamWaitEvent hand-overs.  Same results. */
 int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode);
 int msckf_hip_sync(msckf_hip_handle h);
+/* ---- per-frame device log of msckf_hip_run_frames / _streamed (off by default) ------------------------ */
+/* Storage for capacity_frames records ("frame log record" above) of every trajectory, in the handle's dtype; 0 frees the
+ * log and disables it.  Any call drops the records written so far.  -ENOMEM when the allocation fails: the log is then off and
+ * the handle as usable as before.  While the log is on, every frame of a run_frames / run_frames_streamed call ends with one
+ * small extra launch per stream that copies the record out of the filter state -- it reads the state and writes only the log,
+ * so the filter computes the same bits with and without it -- and a call over [f0, f1) writes the records
+ * count .. count + (f1 - f0) - 1.  A call whose frames do not fit behind the records written returns -ENOSPC and runs nothing.
+ * The log launch is outside the stage timers.  msckf_hip_copy_state does not copy the log. */
+int msckf_hip_frame_log_enable(msckf_hip_handle h, int capacity_frames);
+int msckf_hip_frame_log_reset(msckf_hip_handle h);   /* records written <- 0 (the storage stays) */
+int msckf_hip_frame_log_count(msckf_hip_handle h);   /* records written; advances when a run_frames call has succeeded */
+/* Records [r0, r0 + n) of trajectories [b0, b0 + nb) as doubles, out[n][nb][48]; waits for the handle's stream like the other
+ * getters.  -EINVAL for a range beyond the records written, -EIO on a handle that a failed run_frames call left unusable. */
+int msckf_hip_frame_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out);
+/* The records [r0, r1) against ground-truth positions gt_p[r1 - r0][B][3], reduced on the device: out[B][6] = per trajectory
+ * the number of records, sum |e|^2, max |e|, |e| at record r1 - 1, sum e^T P_pp^-1 e (P_pp the logged position block, 3 x 3
+ * Cholesky), and the number of records with an error flag set; e = p_I_G - gt_p, unaligned (the filters start from ground
+ * truth).  Accumulated in double in a fixed order: the same log gives the same bits.  Sums and counts, so that ranks and
+ * sequences combine by addition (ATE = sqrt(sum |e|^2 / n), mean NEES = sum / n). */
+int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double* gt_p, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

@@ -35,7 +35,19 @@ SYMBOLS = [
     "msckf_hip_set_compression", "msckf_hip_set_covariance_update", "msckf_hip_set_feature_overlap", "msckf_hip_get_pruned_states", "msckf_hip_get_cam_meta", "msckf_hip_get_tracked_feature_ids",
     "msckf_hip_set_anisotropic_noise", "msckf_hip_literal_info", "msckf_hip_get_error_flags", "msckf_hip_copy_state", "msckf_hip_set_host_affinity",
     "msckf_hip_image_cycle_range",
+    "msckf_hip_frame_log_enable", "msckf_hip_frame_log_reset", "msckf_hip_frame_log_count", "msckf_hip_frame_log_read", "msckf_hip_frame_log_metrics",
 ]
+
+# fields of a frame-log record (include/msckf_hip.h, "frame log record"): name -> slice of its 48 scalars
+FRAME_LOG_STRIDE = 48
+FRAME_LOG_FIELDS = {
+    "q": slice(0, 4), "b_g": slice(4, 7), "v": slice(7, 10), "b_a": slice(10, 13), "p": slice(13, 16),
+    "P_II_diag": slice(16, 31), "P_pp": slice(31, 37),          # P_pp: xx xy xz yy yz zz
+    "n_cam": slice(37, 38), "n_tracks": slice(38, 39), "n_passed": slice(39, 40), "error_flags": slice(40, 41),
+    "cam0": slice(41, 48),                                        # q_CG p_C_G of camera slot 0
+}
+# columns of frame_log_metrics' result
+FRAME_LOG_METRICS = ("n", "sum_sq_err", "max_err", "final_err", "sum_nees", "n_flagged")
 
 
 def build():
@@ -352,6 +364,36 @@ class Batch:
         o = np.zeros(8, dtype=np.int32)
         _chk(self.L.msckf_hip_literal_info(self.h, int(b), o.ctypes.data_as(_ip)))
         return dict(zip(["m_rows", "kept_rows", "reflected", "skipped_by_tolerance", "route", "leading_rows_handed_through", "kept_handed_through_rows", "spare"], o.tolist()))
+
+    # ---- per-frame device log of run_frames / run_frames_streamed
+    def frame_log_enable(self, capacity_frames):
+        """storage for capacity_frames records per trajectory (0: free the log and switch it off); drops the records written"""
+        _chk(self.L.msckf_hip_frame_log_enable(self.h, int(capacity_frames)))
+
+    def frame_log_reset(self):
+        _chk(self.L.msckf_hip_frame_log_reset(self.h))
+
+    def frame_log_count(self):
+        return _chk(self.L.msckf_hip_frame_log_count(self.h))
+
+    def frame_log_read(self, r0=0, n=None, b0=0, nb=None):
+        """records [r0, r0 + n) (default: all written) of trajectories [b0, b0 + nb) (default: all): the array [n][nb][48] and
+        a dict of views into it by field name (FRAME_LOG_FIELDS)"""
+        n = self.frame_log_count() - r0 if n is None else int(n)
+        nb = self.B - b0 if nb is None else int(nb)
+        o = np.zeros((max(n, 0), max(nb, 0), FRAME_LOG_STRIDE))
+        _chk(self.L.msckf_hip_frame_log_read(self.h, int(r0), n, int(b0), nb, o.ctypes.data_as(_dp)))
+        return o, {k: o[:, :, s] for k, s in FRAME_LOG_FIELDS.items()}
+
+    def frame_log_metrics(self, r0, r1, gt_p):
+        """records [r0, r1) against ground-truth positions gt_p [r1 - r0][B][3], reduced on the device: [B][6], columns
+        FRAME_LOG_METRICS (sums and counts: shard.ate_from_log_metrics turns them into ate_allreduce's accumulator)"""
+        g = np.ascontiguousarray(gt_p, dtype=np.float64)
+        if g.shape != (int(r1) - int(r0), self.B, 3):
+            raise ValueError("gt_p must be [r1 - r0][B][3]")
+        o = np.zeros((self.B, 6))
+        _chk(self.L.msckf_hip_frame_log_metrics(self.h, int(r0), int(r1), g.ctypes.data_as(_dp), o.ctypes.data_as(_dp)))
+        return o
 
     def profile_enable(self, on=True):
         _chk(self.L.msckf_hip_profile_enable(self.h, 1 if on else 0))

@@ -53,6 +53,11 @@ enum { STAT_NTRACKS = 0, STAT_MOTION_REJ, STAT_TRI_REJ, STAT_GATE_REJ, STAT_PASS
 // in the factorization of S = T_H P T_H^T + R_n (the covariance lost positive definiteness: the square-root gain form
 // P <- P - W W^T has no PSD guarantee under rounding; the pivot is clamped so that the run continues, but it is reported)
 enum { STAT_ERR_NCAP = 1, STAT_ERR_PIVOT = 2 };
+// frame log (kernels_log.hip; msckf_hip_frame_log_*): one record of LOG_STRIDE scalars per frame and trajectory, written after
+// the frame's update and prune.  imu[0..15] (q_IG b_g v b_a p) first, then the diagonal of P_II, the upper triangle of the
+// position block P[12..14][12..14] (xx xy xz yy yz zz), the window size, STAT_NTRACKS / STAT_PASSED / STAT_ERR (integers below
+// 2^24: exact in a float), the pose of camera slot 0 (q_CG p_C_G: the oldest surviving camera; zeros when the window is empty)
+enum { LOG_IMU = 0, LOG_PII = 16, LOG_PPP = 31, LOG_NCAM = 37, LOG_STATS = 38, LOG_CAM0 = 41, LOG_STRIDE = 48 };
 
 // work space of the literal anisotropic compression (kernels_literal.hip / literal_core.h), per trajectory; null when no
 // trajectory of the batch uses it
@@ -427,6 +432,11 @@ template <class S> void launch_literal(const Dev<S>& d, int b0, int nb, hipStrea
 template <class S> bool launch_chol_gram(const Dev<S>& d, int b0, int nb, hipStream_t st);
 bool launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st);
 template <class S> bool launch_chol_gain_large(const Dev<S>& d, int b0, int nb, hipStream_t st);
+// kernels_log.hip: record `rec` ([B][LOG_STRIDE], indexed by trajectory) of the frame log from the state after a frame -- P the
+// covariance buffer that is current, pending: the window size still waits in ncam_upd -- and the reduction of the records
+// [r0, r1) of a log against ground-truth positions gt[r1 - r0][B][3] into out[B][6] (both device pointers)
+template <class S> void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec);
+template <class S> void launch_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out, hipStream_t st);
 size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged = false);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();

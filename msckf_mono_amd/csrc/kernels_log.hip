@@ -1,0 +1,100 @@
+// kernels_log.hip -- the per-frame device log of run_frames / run_frames_streamed and its reduction against ground truth.
+//
+// k_frame_log copies what a caller would read with the getters after a frame -- the first 16 scalars of the IMU state, the
+// diagonal of P_II, the position block of P, the window size, three statistics and the pose of camera slot 0 -- into one
+// record of LOG_STRIDE scalars per trajectory.  It runs on the slice's stream after the frame's update and prune, only
+// reads the filter's arrays and only writes the log: the filter cannot see whether it ran.
+// k_log_metrics reduces a range of records against ground-truth positions: the sums behind ATE and NEES, per trajectory.
+#include "dev_common.h"
+
+namespace msckf {
+
+// four scalars with the alignment of one 16-byte (float) / two 16-byte (double) vector accesses
+template <class S> struct alignas(4 * sizeof(S)) Vec4 { S x[4]; };
+
+// One wavefront per trajectory, four per workgroup.  Record index (include/msckf_hip.h, "frame log record"):
+//   0..15 imu[0..15] | 16..30 diag P_II | 31..36 P_pp xx xy xz yy yz zz | 37 window size | 38..40 STAT_NTRACKS, _PASSED, _ERR |
+//   41..47 cam slot 0 (zeros when the window is empty)
+// Lanes 0..3 move the IMU part as aligned 4-vectors; lanes 16..47 load one scalar each (value = record index of the lane),
+// lanes 4..11 collect four of them over the LDS crossbar; the twelve lanes 0..11 store the record as 4-vectors.
+// P: the covariance buffer that is current after the frame; pending: the frame's prune rode on the downdate, the window
+// size waits in ncam_upd (as size + 1) and ncam is still the size before the prune.
+template <class S>
+__global__ __launch_bounds__(256) void k_frame_log(Dev<S> d, int b0, int nb, const S* P, int pending, S* rec) {
+  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (i >= nb) return;   // (whole wavefronts)
+  const int b = b0 + i;
+  const int n = pending ? d.ncam_upd[b] - 1 : d.ncam[b];
+  const S* Pb = P + (long)b * d.ld * d.ld;
+  S v = S(0);
+  if (lane >= LOG_PII && lane < LOG_PPP) { const int k = lane - LOG_PII; v = Pb[(long)k * d.ld + k]; }
+  else if (lane >= LOG_PPP && lane < LOG_NCAM) {
+    const int k = lane - LOG_PPP;                                    // xx xy xz yy yz zz: element (r, c), r <= c
+    const int r = k < 3 ? 0 : (k < 5 ? 1 : 2), c = k < 3 ? k : (k < 5 ? k - 2 : 2);
+    v = Pb[(long)(12 + c) * d.ld + 12 + r];
+  }
+  else if (lane == LOG_NCAM) v = (S)n;
+  else if (lane > LOG_NCAM && lane < LOG_CAM0) {
+    const int k = lane - LOG_STATS;
+    v = (S)d.stats[(long)b * STAT_STRIDE + (k == 0 ? STAT_NTRACKS : (k == 1 ? STAT_PASSED : STAT_ERR))];
+  }
+  else if (lane >= LOG_CAM0 && lane < LOG_STRIDE && n > 0) v = d.cam[(long)b * d.n_cap * CAM_STRIDE + (lane - LOG_CAM0)];
+  Vec4<S> o = {};
+  if (lane < 4) o = *reinterpret_cast<const Vec4<S>*>(d.imu + (long)b * IMU_STRIDE + 4 * lane);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {   // (every lane takes part in the exchange)
+    const S g = lane_gather(v, ((4 * lane + k) & 63) << 2);
+    if (lane >= 4) o.x[k] = g;
+  }
+  if (lane < LOG_STRIDE / 4) *reinterpret_cast<Vec4<S>*>(rec + (long)b * LOG_STRIDE + 4 * lane) = o;
+}
+
+// One workgroup (one wavefront) per trajectory over the records [r0, r1) of the log ([.][B][LOG_STRIDE]), ground truth
+// gt[r1 - r0][B][3].  out[b][6] = n, sum |e|^2, max |e|, |e| at r1 - 1, sum e^T P_pp^-1 e, records with STAT_ERR != 0;
+// e = p - p_gt, no alignment.  All in f64; lane l takes the records r0 + l, r0 + l + 64, ... in ascending order and the
+// lanes are combined by wave_sum's fixed tree, so the same log gives the same bits on every call.  P_pp = L L^T by
+// Cholesky, e^T P_pp^-1 e = |L^-1 e|^2 (a P_pp that is not positive definite gives NaN there).
+template <class S>
+__global__ __launch_bounds__(64) void k_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double s2 = 0, mx = 0, last = 0, nees = 0, nerr = 0, cnt = 0;
+  for (int r = r0 + lane; r < r1; r += 64) {
+    const S* q = log + ((long)r * B + b) * LOG_STRIDE;
+    const double* g = gt + ((long)(r - r0) * B + b) * 3;
+    const double e0 = (double)q[IP] - g[0], e1 = (double)q[IP + 1] - g[1], e2 = (double)q[IP + 2] - g[2];
+    const double d2 = e0 * e0 + e1 * e1 + e2 * e2, dist = sqrt(d2);
+    const double pxx = (double)q[LOG_PPP], pxy = (double)q[LOG_PPP + 1], pxz = (double)q[LOG_PPP + 2];
+    const double pyy = (double)q[LOG_PPP + 3], pyz = (double)q[LOG_PPP + 4], pzz = (double)q[LOG_PPP + 5];
+    const double l00 = sqrt(pxx), l10 = pxy / l00, l20 = pxz / l00;
+    const double l11 = sqrt(pyy - l10 * l10), l21 = (pyz - l20 * l10) / l11;
+    const double l22 = sqrt(pzz - l20 * l20 - l21 * l21);
+    const double y0 = e0 / l00, y1 = (e1 - l10 * y0) / l11, y2 = (e2 - l20 * y0 - l21 * y1) / l22;
+    s2 += d2; nees += y0 * y0 + y1 * y1 + y2 * y2; cnt += 1.0;
+    mx = dist > mx ? dist : mx;
+    if (r == r1 - 1) last = dist;
+    if (q[LOG_STATS + 2] != S(0)) nerr += 1.0;
+  }
+  cnt = wave_sum(cnt); s2 = wave_sum(s2); mx = wave_max(mx); last = wave_sum(last); nees = wave_sum(nees); nerr = wave_sum(nerr);
+  if (lane == 0) {
+    double* o = out + (long)b * 6;
+    o[0] = cnt; o[1] = s2; o[2] = mx; o[3] = last; o[4] = nees; o[5] = nerr;
+  }
+}
+
+template <class S>
+void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(k_frame_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, P, pending ? 1 : 0, rec);
+}
+template <class S>
+void launch_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_log_metrics<S>, dim3(B), dim3(64), 0, st, log, B, r0, r1, gt, out);
+}
+
+template void launch_frame_log<float>(const Dev<float>&, int, int, hipStream_t, const float*, bool, float*);
+template void launch_frame_log<double>(const Dev<double>&, int, int, hipStream_t, const double*, bool, double*);
+template void launch_log_metrics<float>(const float*, int, int, int, const double*, double*, hipStream_t);
+template void launch_log_metrics<double>(const double*, int, int, int, const double*, double*, hipStream_t);
+
+}  // namespace msckf

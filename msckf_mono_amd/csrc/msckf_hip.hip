@@ -229,6 +229,10 @@ struct BatchCore {
   }
   size_t pk_rd = 0, pk_n = 0, pk_drop = 0, pk_M = 0, pk_off = 0, pk_slots = 0;   // section offsets (256-byte aligned); obs follows the frame's slots
   Workers workers;   // enqueue threads of the slices
+  // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
+  // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
+  // (log_base = log_n at its start, read by the slices' enqueue threads) and advances log_n when it has succeeded
+  void* log_buf = nullptr; int log_cap = 0, log_n = 0, log_base = 0;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[NSTAGE];
@@ -271,6 +275,7 @@ struct BatchCore {
     hipSetDevice(device);
     if (st) hipStreamSynchronize(st);
     for (void* p : allocs) hipFree(p);
+    if (log_buf) hipFree(log_buf);
     if (h_rb) hipHostFree(h_rb);
     for (int s = 0; s < NSTAGE; ++s) for (auto& e : ev_pool[s]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int i = 1; i < MAXS; ++i) { if (stx[i]) hipStreamDestroy(stx[i]); if (ev_join[i]) hipEventDestroy(ev_join[i]); }
@@ -649,12 +654,42 @@ struct BatchCore {
     for (int i = 0; i < nh; ++i)
       if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
     commit_buffer_parity(f0, f1);
+    if (log_buf) log_n += f1 - f0;
+    return 0;
+  }
+  // ---- frame log
+  // capacity_frames records for every trajectory, or (0) none: frees a log that exists either way.  An allocation that fails
+  // leaves the log off and the handle as it was
+  int frame_log_enable(int capacity_frames) {
+    if (int rc = guard()) return rc;
+    if (capacity_frames < 0) return fail(-EINVAL, "negative capacity");
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if (log_buf) (void)hipFree(log_buf);
+    log_buf = nullptr; log_cap = 0; log_n = 0;
+    if (!capacity_frames) return 0;
+    void* q = nullptr;
+    if (hipMalloc(&q, (size_t)capacity_frames * B * LOG_STRIDE * esz) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(-ENOMEM, "could not allocate the frame log (it stays disabled; the handle is unaffected)");
+    }
+    log_buf = q; log_cap = capacity_frames;
+    return 0;
+  }
+  int frame_log_reset() { log_n = 0; return 0; }
+  int frame_log_count() const { return log_n; }
+  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's records fit, and start at log_n
+  int frame_log_reserve(int f0, int f1) {
+    if (!log_buf) return 0;
+    if ((long)log_n + (f1 - f0) > log_cap) return fail(-ENOSPC, "frame log full: the call's frames do not fit behind the records written (msckf_hip_frame_log_reset, or a larger msckf_hip_frame_log_enable); nothing was run");
+    log_base = log_n;
     return 0;
   }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
+    if (int rc = frame_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     const int nh = n_slices();
     const int rc = fork_slices(nh);
@@ -685,6 +720,7 @@ struct BatchCore {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
+    if (int rc = frame_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     {
       bool all = sg_blk[0] != nullptr;
@@ -844,6 +880,8 @@ struct BatchCore {
   virtual int set_aniso(int mode, double tol) = 0;
   virtual int copy_from(BatchCore* src) = 0;
   virtual int lit_info(int b, int* out8) = 0;
+  virtual int frame_log_read(int r0, int n, int b0, int nb, double* out) = 0;                  // [n][nb][LOG_STRIDE]
+  virtual int frame_log_metrics(int r0, int r1, const double* gt_p, double* out) = 0;          // gt_p [r1 - r0][B][3], out [B][6]
 };
 
 int resolve_map(BatchCore* B, int b);   // (defined with the host-side bookkeeping below)
@@ -1572,10 +1610,45 @@ struct Batch : BatchCore {
       stage_end(6, q);
     }
     s.pending = fuse;
+    // frame log: the state the frame leaves -- the covariance buffer that is current after the flip, the window size where the
+    // prune left it (ncam_upd while it is pending) -- as record log_base + (f - f0); outside the stage timers
+    if (log_buf) launch_frame_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, s.pending, static_cast<S*>(log_buf) + (size_t)(log_base + (f - f0)) * B * LOG_STRIDE);
     for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment, then drop n_drop (clamped as k_make_keep does)
       if (h_ncam[b] < n_cap) h_ncam[b]++;
       h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
     }
+  }
+  // records [r0, r0 + n) of trajectories [b0, b0 + nb) as doubles: one strided copy, one wait
+  int frame_log_read(int r0, int n, int b0, int nb, double* out) override {
+    if (int rc = guard()) return rc;
+    if (r0 < 0 || n < 0 || (long)r0 + n > log_n) return fail(-EINVAL, "record range beyond the records written (msckf_hip_frame_log_count)");
+    if (int rc = enter_range(b0, nb)) return rc;
+    const size_t row = (size_t)nb * LOG_STRIDE;
+    std::vector<S> tmp(std::max<size_t>(row * n, 1));
+    if (n && nb)
+      HIPCHK(hipMemcpy2DAsync(tmp.data(), row * sizeof(S), static_cast<const S*>(log_buf) + ((size_t)r0 * B + b0) * LOG_STRIDE, (size_t)B * LOG_STRIDE * sizeof(S),
+                              row * sizeof(S), (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < row * n; ++i) out[i] = (double)tmp[i];
+    return 0;
+  }
+  // the records [r0, r1) against ground-truth positions, reduced on the device (k_log_metrics): per trajectory n, sum |e|^2,
+  // max |e|, |e| at r1 - 1, sum e^T P_pp^-1 e, records with STAT_ERR != 0
+  int frame_log_metrics(int r0, int r1, const double* gt_p, double* out) override {
+    if (int rc = guard()) return rc;
+    if (r0 < 0 || r1 < r0 || r1 > log_n) return fail(-EINVAL, "record range beyond the records written (msckf_hip_frame_log_count)");
+    if (int rc = enter()) return rc;
+    const size_t ng = (size_t)(r1 - r0) * B * 3, no = (size_t)B * 6;
+    double* dg = nullptr;                                      // [ground truth | out], freed on every way out
+    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
+    double* dout = dg + std::max<size_t>(ng, 1);
+    hipError_t e = ng ? hipMemcpyAsync(dg, gt_p, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess) { launch_log_metrics<S>(static_cast<const S*>(log_buf), B, r0, r1, dg, dout, st); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dg);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("frame_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
   }
   int set_gate_early(int on) override { d.gate_early = on ? 1 : 0; return 0; }
   int set_cov_update(int form) override {
@@ -2124,6 +2197,11 @@ int msckf_hip_set_gate_early_accept(msckf_hip_handle h, int on) { if (!h) return
 int msckf_hip_set_anisotropic_noise(msckf_hip_handle h, int mode, double tail_tol) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_aniso(mode, tail_tol); }
 int msckf_hip_copy_state(msckf_hip_handle dst, msckf_hip_handle src) { if (!dst || !src) return fail(-EINVAL, "null handle"); return H(dst)->copy_from(H(src)); }
 int msckf_hip_get_error_flags(msckf_hip_handle h, int b, int* flags) { if (!h || !flags) return fail(-EINVAL, "null argument"); return H(h)->error_flags(b, flags); }
+int msckf_hip_frame_log_enable(msckf_hip_handle h, int capacity_frames) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->frame_log_enable(capacity_frames); }
+int msckf_hip_frame_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->frame_log_reset(); }
+int msckf_hip_frame_log_count(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->frame_log_count(); }
+int msckf_hip_frame_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_read(r0, n, b0, nb, out); }
+int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double* gt_p, double* out) { if (!h || !gt_p || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_metrics(r0, r1, gt_p, out); }
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"

@@ -29,6 +29,16 @@ def ate_local(p_est, p_gt, seq_ids, n_seq):
     return acc
 
 
+def ate_from_log_metrics(metrics, seq_ids, n_seq):
+    """The same accumulator from capi.Batch.frame_log_metrics' rows [B][6] (n, sum |e|^2, ...): every logged frame of every
+    trajectory counts, not only the last one."""
+    acc = np.zeros((n_seq, 2), dtype=np.float64)
+    for row, s in zip(np.asarray(metrics, dtype=np.float64), seq_ids):
+        acc[s, 0] += row[1]
+        acc[s, 1] += row[0]
+    return acc
+
+
 def ate_allreduce(acc, device=None):
     """All-reduce the partial sums over the default process group (if initialised) and return the
     per-sequence ATE (RMSE of position, no alignment: the runner initialises from ground truth,
