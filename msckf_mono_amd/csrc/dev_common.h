@@ -145,8 +145,20 @@ struct Dev {
   // prune
   int* keep; int* nkeep;
   LitBufs lit;
-  S* qf;   // [B][QF_STRIDE] full process noise and its flag (last: the offsets of every other member stay as they were)
+  S* qf;   // [B][QF_STRIDE] full process noise and its flag
+  // float blocked gain solve at 9 to 12 column blocks: workgroups per trajectory.  0: by the batch size (two from 96 trajectories
+  // on, else four); 2 | 4: that many (MSCKF_HIP_GAIN_PARTS, read when the handle is created)
+  int gain_parts;
+  // A range whose windows lie on both sides of the one-launch update's limit launches k_update_small AND the chain; each
+  // trajectory then belongs to one of them by its OWN window size: 6 ncam <= small_split to k_update_small, the others to the
+  // chain, and each kernel leaves the other's trajectories alone (other_route).  0: the launch owns every trajectory of its range
+  int small_split;
 };
+
+// mixed range (Dev::small_split): is trajectory b, with ncam camera states, the other launch sequence's?
+template <class S> __device__ __forceinline__ bool other_route(const Dev<S>& d, int ncam, bool small_kernel) {
+  return d.small_split != 0 && (6 * ncam <= d.small_split) != small_kernel;
+}
 
 // first observation of track t of the launch's i-th trajectory in trk_slots / trk_obs
 template <class S> __device__ __forceinline__ long wl_first(const Dev<S>& d, int i, int t) {
@@ -426,6 +438,7 @@ template <class S> void launch_kalman(const Dev<S>& d, int b0, int nb, hipStream
 // launch, one workgroup per trajectory; false when the window does not fit its LDS (the caller then takes the usual chain)
 template <class S> bool launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, int n_max);
 size_t update_small_lds_bytes(int n_max, int f_cap, size_t scalar);
+bool update_small_fits(int n_max, int f_cap, size_t scalar);
 template <class S> void launch_literal(const Dev<S>& d, int b0, int nb, hipStream_t st, int part = 0);   // kernels_literal.hip: Lam^ of the literal anisotropic compression (part: 0 all, 1 k_lit_pre, 2 k_lit_gamma, 3 k_literal)
 // blocked matrix-core Cholesky (kernels_chol.hip): [T | r_n] = chol(Lam^) for the information form; S = L L^T with
 // [PHt ; r_n^T] appended (W, dx) for the float Kalman stage.  Return false when the window does not fit the kernel.

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
   if (w == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(1);
   int* st = d.stats + (long)b * STAT_STRIDE;
   const int mrows_ = st[STAT_MROWS], ncam_ = d.ncam[b];   // independent scalar loads, one wait
-  if (mrows_ == 0) return;
+  if (mrows_ == 0 || other_route(d, ncam_, false)) return;
   constexpr bool GRAMLIKE = MODE == CH_GRAM || MODE == CH_GRAM_A || MODE == CH_GRAM_B;
   constexpr bool SLIKE = MODE == CH_S_A || MODE == CH_S_B;
   constexpr bool LEVEL_A = MODE == CH_GRAM_A || MODE == CH_S_A, LEVEL_B = MODE == CH_GRAM_B || MODE == CH_S_B;
@@ -651,7 +651,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
   if (!xcd_item(nb, nwg, bi_, wg_)) return;
   const int b = b0 + bi_, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int* st = d.stats + (long)b * STAT_STRIDE;
-  if (st[STAT_MROWS] == 0) return;
+  if (st[STAT_MROWS] == 0 || other_route(d, d.ncam[b], false)) return;
   const int i = 4 * wg_ + w;                             // 16-row block
   const int nfull = 6 * d.ncam[b], D = 15 + nfull;
   const int ncols = TMODE == TR_W ? nfull : min(nfull, CH_SPLIT);      // columns of L that exist
@@ -753,7 +753,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 template <class SO>
 __global__ __launch_bounds__(256) void k_dx_wz(Dev<SO> d, int b0) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x;
-  if (d.stats[(long)b * STAT_STRIDE + STAT_MROWS] == 0) return;
+  if (d.stats[(long)b * STAT_STRIDE + STAT_MROWS] == 0 || other_route(d, d.ncam[b], false)) return;
   const int n = 6 * d.ncam[b], D = 15 + n;
   __shared__ SO sz[384];
   for (int j = tid; j < n; j += 256) sz[j] = d.Linv[(long)b * d.n6cap * d.n6cap + j];
@@ -824,9 +824,9 @@ bool launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st) {
   if (nbn <= 12) {                                                             // D <= 207 <= 4 * 63 = 2 * 111 - ...
     // four parts per trajectory fill the chip at 64 trajectories; from a batch of 96 on, two parts (each redoes the factorization: half the
     // workgroups, one round of them instead of two).  Rows are independent and S's blocks are formed by the same instruction
-    // sequence whichever part owns them: same bits either way.  MSCKF_HIP_GAIN_PARTS=2|4 forces one (A/B runs).
-    static const int force = [] { const char* e = getenv("MSCKF_HIP_GAIN_PARTS"); return e ? atoi(e) : 0; }();
-    const bool two = force ? force == 2 : d.B >= 96;   // (the whole batch: its slices run these launches side by side)
+    // sequence whichever part owns them: same bits either way.  MSCKF_HIP_GAIN_PARTS=2|4 at handle creation forces one
+    // (Dev::gain_parts; A/B runs and tests).
+    const bool two = d.gain_parts ? d.gain_parts == 2 : d.B >= 96;   // (the whole batch: its slices run these launches side by side)
     if (two && 15 + 6 * d.n_cap <= 2 * 111) gain_launch<12, 7, 2>(d, b0, nb, st); else gain_launch<12, 4, 4>(d, b0, nb, st);
     return true;
   }

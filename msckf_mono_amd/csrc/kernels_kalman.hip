@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_gemm_mfma(Dev<float> d, int b0, int nb,
   const KView<S> v = make_view(d, b);
   // downdate with the frame's prune riding on it (Dev::Pout): a trajectory without an update still has its covariance moved
   const bool fused_prune = OP == OP_DOWN && d.Pout != nullptr;
-  if (mrows_ == 0 && !fused_prune) return;
+  if ((mrows_ == 0 && !fused_prune) || other_route(d, v.n / 6, false)) return;
   int nd_ = 0;
   if (fused_prune) { nd_ = d.fuse_drop[bi_]; nd_ = nd_ < 0 ? 0 : (nd_ > v.n / 6 ? v.n / 6 : nd_); }
   if (OP == OP_DOWN && bx == 0 && by == 0) {
@@ -411,7 +411,7 @@ __global__ __launch_bounds__(256) void k_gemm_mfma64(Dev<double> d, int b0) {
   const int mrows_ = d.stats[(long)b * STAT_STRIDE + STAT_MROWS];   // loaded together with the window size (independent scalar loads, one wait)
   const KView<S> v = make_view(d, b);
   const bool fused_prune = OP == OP_DOWN && d.Pout != nullptr;   // see the float kernel
-  if (mrows_ == 0 && !fused_prune) return;
+  if ((mrows_ == 0 && !fused_prune) || other_route(d, v.n / 6, false)) return;
   int nd_ = 0;
   if (fused_prune) { nd_ = d.fuse_drop[blockIdx.z]; nd_ = nd_ < 0 ? 0 : (nd_ > v.n / 6 ? v.n / 6 : nd_); }
   if (OP == OP_DOWN && blockIdx.x == 0 && blockIdx.y == 0) {
@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256) void k_chol_inv(Dev<S> d, int b0) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x;
   const int mrows_ = d.stats[(long)b * STAT_STRIDE + STAT_MROWS];   // loaded together with the window size (independent scalar loads, one wait)
   const KView<S> v = make_view(d, b);
-  if (mrows_ == 0) return;
+  if (mrows_ == 0 || other_route(d, v.n / 6, false)) return;
   const int n = v.n;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   S* L; int ldl;
@@ -714,7 +714,7 @@ __global__ __launch_bounds__(256) void k_gain_w(Dev<S> d, int b0) {
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
   const int mrows_ = d.stats[(long)b * STAT_STRIDE + STAT_MROWS];   // loaded together with the window size (independent scalar loads, one wait)
   const KView<S> v = make_view(d, b);
-  if (mrows_ == 0) return;
+  if (mrows_ == 0 || other_route(d, v.n / 6, false)) return;
   const int n = v.n, D = v.D;
   __shared__ S sCol[2][G * NBN];
   __shared__ S sW[2][G * NBW];
@@ -832,7 +832,7 @@ __global__ __launch_bounds__(256) void k_dx_w(Dev<S> d, int b0) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x;
   const int mrows_ = d.stats[(long)b * STAT_STRIDE + STAT_MROWS];   // loaded together with the window size (independent scalar loads, one wait)
   const KView<S> v = make_view(d, b);
-  if (mrows_ == 0) return;
+  if (mrows_ == 0 || other_route(d, v.n / 6, false)) return;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   S* srn = reinterpret_cast<S*>(smem_raw);
   S* sz = srn + v.ldn;
@@ -1083,7 +1083,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
   // pruned position in the other buffer; a trajectory without an update still has its covariance moved there
   const bool fused_prune = d.Pout != nullptr;
   const bool upd = mrows_ != 0;
-  if (!upd && !fused_prune) return;
+  if ((!upd && !fused_prune) || other_route(d, N, true)) return;
   int nd_ = 0;
   if (fused_prune) { nd_ = d.fuse_drop[blockIdx.x]; nd_ = nd_ < 0 ? 0 : (nd_ > N ? N : nd_); }
   const int n = 6 * N, n1 = n + 1, D = 15 + n, ld = d.ld, ldR = d.ldR, f_cap = d.f_cap;
@@ -1308,15 +1308,21 @@ size_t update_small_lds_bytes(int n_max, int f_cap, size_t scalar) {
   const size_t n1 = (size_t)n_max + 1, LL = n1 | 1, Dm = 15 + (size_t)n_max, cstride = 2 * (size_t)n_max + 20;
   return (n1 * LL + n1 + 1 + 2 * cstride) * sizeof(double) + (update_small_pt_elems(n_max, f_cap, scalar) + update_small_ph_elems(n_max, scalar) + n_max + 2 + Dm + 1) * scalar + 64;
 }
-template <class S>
-bool launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, int n_max) {
-  if (nb <= 0) return true;
-  const size_t lds = update_small_lds_bytes(n_max, d.f_cap, sizeof(S));
+// does a window of n_max camera columns fit k_update_small (its LDS, the tasks of its factorizations)?  Monotone in n_max.
+bool update_small_fits(int n_max, int f_cap, size_t scalar) {
+  const size_t lds = update_small_lds_bytes(n_max, f_cap, scalar);
   // tasks of the factorizations: ceil(n / 12) x ceil((2 n + 16) / 64) and ceil(n / 4) x ceil((n + 1) / 64) <= 32; tiles of Lam^: <= 15 of the 16 wavefronts
   const int ncs = (n_max + US_SEG_E - 1) / US_SEG_E, nrc = (2 * n_max + 16 + 63) / 64, nt1 = (n_max + 1 + 15) / 16;
   const int nrcb = (n_max + 1 + 63) / 64;
   const bool b4 = ((n_max + 3) / 4) * nrcb <= 16 * US_UMAX, b8 = ((n_max + 7) / 8) * nrcb <= 16 * US_UMAX;
-  if (!update_small_ok || lds > 156 * 1024 || ncs * nrc > 16 * US_UMAX || !(b4 || b8) || nt1 * (nt1 + 1) / 2 > 16 || (15 + n_max) * n_max > 1024 * 7) return false;
+  return update_small_ok && lds <= 156 * 1024 && ncs * nrc <= 16 * US_UMAX && (b4 || b8) && nt1 * (nt1 + 1) / 2 <= 16 && (15 + n_max) * n_max <= 1024 * 7;
+}
+template <class S>
+bool launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, int n_max) {
+  if (nb <= 0) return true;
+  if (!update_small_fits(n_max, d.f_cap, sizeof(S))) return false;
+  const size_t lds = update_small_lds_bytes(n_max, d.f_cap, sizeof(S));
+  const bool b4 = ((n_max + 3) / 4) * ((n_max + 1 + 63) / 64) <= 16 * US_UMAX;
   if (b4) hipLaunchKernelGGL((k_update_small<S, 4>), dim3(nb), dim3(1024), lds, st, d, b0, n_max);
   else hipLaunchKernelGGL((k_update_small<S, 8>), dim3(nb), dim3(1024), lds, st, d, b0, n_max);
   return true;

@@ -165,6 +165,8 @@ struct BatchCore {
     int compress_route = -1;   // -1 default, 0 Householder TSQR, != 0 information form + blocked matrix-core Cholesky
   } knobs;
   int small_update = 84;     // windows of at most this many camera columns (6 x cameras) take the one-launch update k_update_small; MSCKF_HIP_SMALL_UPDATE=0 switches it off
+  int gain_parts = 0;        // MSCKF_HIP_GAIN_PARTS: workgroups per trajectory of the float blocked gain solve (2 | 4), 0: by the batch size (Dev::gain_parts)
+  int small_limit = 0;       // ... as far as they fit the kernel at this handle's dtype and f_cap (the typed half's alloc): the per-trajectory limit launch_update routes by
   int test_fail_upload = -1;  // test hook (MSCKF_HIP_TEST_FAIL_UPLOAD): run_frames_streamed pretends that this frame's copy failed
   // anisotropic pixel noise (u_var' != v_var'): 0 = the reference's construction R_o_j = A_j^T R_j A_j, R_n = Q_1^T R_o Q_1 on
   // the device (kernels_literal.hip; default), 1 = rows pre-whitened by 1/sigma (generalized least squares, unit noise)
@@ -250,6 +252,10 @@ struct BatchCore {
   }
   // the device's tables, streams and events, host mirrors, the knobs the environment sets; then the typed half's buffers
   int create() {
+    if (const char* e = getenv("MSCKF_HIP_GAIN_PARTS")) {
+      gain_parts = atoi(e);
+      if (gain_parts != 0 && gain_parts != 2 && gain_parts != 4) return fail(-EINVAL, "MSCKF_HIP_GAIN_PARTS must be 0, 2 or 4");
+    }
     HIPCHK(hipSetDevice(device));
     feature_device_setup(); qr_device_setup(); kalman_device_setup(); gram_device_setup(); literal_device_setup();   // per device: constant tables, dynamic-LDS limits
     HIPCHK(hipGetLastError());
@@ -946,6 +952,9 @@ struct Batch : BatchCore {
     rc |= dalloc(&d_pfin, TF * 4); d.trk_pfin = d_pfin; d.mode = 0; d.joseph = 0; d.ncam_bias = 0;
     { const char* e = getenv("MSCKF_HIP_FUSED_S"); d.gain_fused_s = e ? atoi(e) : 2; }
     { const char* e = getenv("MSCKF_HIP_FEATURE_PAIR"); d.feat_pair = e ? atoi(e) : 1; }
+    d.gain_parts = gain_parts;
+    d.small_split = 0;
+    for (int n = small_update / 6 * 6; n >= 6 && !small_limit; n -= 6) if (update_small_fits(n, f_cap, sizeof(S))) small_limit = n;
     rc |= dalloc(&d.gain_bar, Bz * 32);   // 0: the S GEMM as a launch of its own (A/B runs)
     rd_cap = 64;
     rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE);
@@ -1270,8 +1279,14 @@ struct Batch : BatchCore {
     return cmp;
   }
   // ncam_ahead: run_frames advances its host mirror of the window sizes after the frame's launches (the frame's augmentState is
-  // not in h_ncam yet when its update is enqueued).  Which route a frame takes depends on the window sizes only -- never on how a
-  // frame range is cut into calls or on the API used (bit-identical results either way)
+  // not in h_ncam yet when its update is enqueued).  Which route a TRAJECTORY takes depends on its own window size only -- never
+  // on its neighbours in the range, on how a batch is cut into slices or a frame range into calls, or on the API used
+  // (bit-identical results either way).  A range whose windows all lie on one side of small_limit launches that side's sequence
+  // alone; a range with windows on both sides launches both, and every kernel of either leaves the other's trajectories alone
+  // (Dev::small_split, other_route).  Inside k_update_small the launch is still sized by the largest short window of the range
+  // (LDS strides, and the column-segment width of chol(Lam^): 4 up to 63 columns, 8 beyond); neither changes the order of the
+  // operations on any matrix element -- every element takes its rank-1 updates pivot by pivot whichever task holds it -- so the
+  // bits are the trajectory's own (tests/test_gpu_ragged.py holds it: 5 .. 14 cameras alone and beside each other).
   void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
@@ -1280,14 +1295,18 @@ struct Batch : BatchCore {
     // information form: k_select and the block-diagonal reduction share a launch (both only read k_feature's outputs)
     stage_begin(7, q); if (v.compress) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q);
     // short windows (single filters, BASELINE configs[1]): everything after the selection in ONE launch (k_update_small)
-    if (small_update && v.compress && n_lit == 0 && d.joseph == 0) {
-      int nmax = 0;
-      for (int b = b0; b < b0 + nb; ++b) nmax = std::max(nmax, 6 * std::min(h_ncam[b] + ncam_ahead, n_cap));
-      if (nmax > 0 && nmax <= small_update) {
+    if (small_limit && v.compress && n_lit == 0 && d.joseph == 0) {
+      int nmax = 0, nsmall = 0;                    // largest window of the range, largest one within the limit
+      for (int b = b0; b < b0 + nb; ++b) { const int n = 6 * std::min(h_ncam[b] + ncam_ahead, n_cap); nmax = std::max(nmax, n); if (n > 0 && n <= small_limit) nsmall = std::max(nsmall, n); }
+      // (an empty window has no update: it makes no range mixed, and in a mixed one it is k_update_small's, 6 x 0 <= small_split)
+      const bool mixed = nsmall > 0 && nmax > small_limit;
+      if ((nmax > 0 && nmax <= small_limit) || mixed) {
+        if (mixed) v.small_split = small_limit;
         stage_begin(5, q);
-        const bool ok = launch_update_small<S>(v, b0, nb, q, nmax);
+        const bool ok = launch_update_small<S>(v, b0, nb, q, nsmall);
         stage_end(5, q);
-        if (ok) return;
+        if (ok && !mixed) return;
+        if (!ok) v.small_split = 0;                // (not reached: small_limit fits) the chain takes everybody
       }
     }
     if (v.compress) {
@@ -1488,7 +1507,7 @@ struct Batch : BatchCore {
     HIPCHK(cp(d.ncam, o->d.ncam, Bz * sizeof(int))); HIPCHK(cp(d.n_resid, o->d.n_resid, Bz * sizeof(long long)));
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
-    knobs = o->knobs; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; d.gain_fused_s = o->d.gain_fused_s;
+    knobs = o->knobs; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; d.gain_fused_s = o->d.gain_fused_s; gain_parts = o->gain_parts; d.gain_parts = gain_parts;
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
     return set_aniso(o->aniso_mode, o->lit_tol);   // re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed

@@ -119,3 +119,137 @@ def copy_device_to_oracle(batch, b, o):
         o.setCamPose(i, c)
     o.setCovariance(batch.covariance(b))
     o.setNumResidualized(batch.num_residualized(b))
+
+
+# ----------------------------------------------------------------------------------- ragged batches (tests/test_gpu_ragged.py)
+STAT_KEYS = ("n_tracks", "n_motion_rejected", "n_tri_rejected", "n_gate_rejected", "n_passed", "m_rows")
+
+# (window N_b, tracks per frame F_b, kind) per trajectory of the two ragged handles: the window sizes straddle the one-launch
+# update's limit (14 | 15 cameras) and, on the second handle, the single-level factorizations' (31 | 33).  Kinds:
+#   "dense"  every track spans the window, and on full-window frames track 0 also sees the newest camera: length N_b = m_cap
+#   "idle"   F = 0 on every frame: never updates          "gaps"  handed an empty track list on every third frame
+#   "gated"  on GATED_FRAME its observations carry 20 px of noise (test_all_tracks_gated_out_leaves_state_untouched's scenario)
+RAGGED = {
+    1: dict(n_cap=32, specs=[(5, 7, ""), (9, 24, ""), (14, 40, ""), (15, 33, ""), (21, 52, ""), (27, 60, ""), (32, 6, "dense"),
+                             (10, 0, "idle"), (12, 20, "gaps"), (8, 24, "gated")]),
+    2: dict(n_cap=40, specs=[(6, 9, ""), (14, 36, ""), (15, 28, ""), (31, 60, ""), (33, 44, ""), (40, 5, "dense"),
+                             (11, 0, "idle"), (13, 22, "gaps"), (7, 30, "gated")]),
+}
+GATED_FRAME = 12
+
+
+class RaggedSet:
+    """The trajectories of one ragged handle: trajs[b] (scenario.Trajectory built for its own window N[b]), frames[b][k] the
+    work-list trajectory b is handed on frame k, and the handle's capacities (n_cap = max N_b, f_cap = max F_b, m_cap = n_cap)."""
+
+    def __init__(self, handle, seed0=500, nf=None, specs=None, n_cap=None):
+        from msckf_mono_amd import scenario as sc
+        r = RAGGED[handle] if handle else dict(n_cap=n_cap, specs=specs)
+        self.specs = list(r["specs"])
+        self.B = len(self.specs)
+        self.N = [s[0] for s in self.specs]
+        self.n_cap = r["n_cap"]
+        self.m_cap = self.n_cap
+        self.f_cap = max(max(s[1] for s in self.specs), 1)
+        self.nf = nf if nf is not None else self.n_cap + 4
+        assert max(self.N) <= self.n_cap
+        self.trajs, self.frames = [], []
+        for b, (N, F, kind) in enumerate(self.specs):
+            tr = sc.Trajectory(2, seed0 + b, N, F, self.nf, dense_tracks=(kind == "dense"))
+            fl = [dict(f) for f in tr.frames]
+            if kind == "gaps":
+                for k in range(1, self.nf, 3):
+                    fl[k] = dict(Nw=fl[k]["Nw"], M=np.zeros(0, np.int32), slots=np.zeros(0, np.int32), obs=np.zeros((0, 2)))
+            elif kind == "gated":
+                noisy = sc.Trajectory(2, seed0 + b, N, F, self.nf, obs_noise_px=20.0)      # same seed: same motion and landmarks
+                fl[GATED_FRAME] = dict(noisy.frames[GATED_FRAME])
+            elif kind == "dense":
+                for k in range(self.nf):
+                    fl[k] = self._with_newest_camera(tr, k, fl[k], N)
+            self.trajs.append(tr)
+            self.frames.append(fl)
+
+    @staticmethod
+    def _with_newest_camera(tr, k, fr, N):
+        """track 0 of a full-window frame, when it spans slots 0 .. N - 2, extended by its (noise-free) observation in the
+        camera this frame's augmentState adds: a track of N observations"""
+        if fr["Nw"] != N or not len(fr["M"]) or fr["M"][0] != N - 1:
+            return fr
+        pc = tr.C_CG[k] @ (tr.landmarks[k][0] - tr.p_C[k])
+        if pc[2] <= 0.5:
+            return fr
+        M = fr["M"].copy()
+        slots = np.insert(fr["slots"], M[0], N - 1).astype(np.int32)
+        obs = np.insert(fr["obs"], M[0], pc[:2] / pc[2], axis=0)
+        M[0] += 1
+        return dict(Nw=fr["Nw"], M=M, slots=slots, obs=obs)
+
+    def updating(self, b):
+        return self.specs[b][1] > 0
+
+    def full(self, b, k):
+        return self.frames[b][k]["Nw"] == self.N[b]
+
+    def imu(self, k):
+        return np.stack([tr.imu_for_frame(k) for tr in self.trajs])
+
+    def batch(self, capi, dtype):
+        bt = capi.Batch(self.B, self.n_cap, self.f_cap, self.m_cap, dtype)
+        for b, tr in enumerate(self.trajs):
+            bt.initialize(b, tr.cfg, tr.imu0)
+        return bt
+
+    def oracle(self, po, dtype, b):
+        o = po.Oracle(dtype, po.LEAN)
+        o.initialize(self.trajs[b].cfg, self.trajs[b].imu0)
+        return o
+
+    def oracle_frame(self, o, b, k):
+        """frame k of trajectory b on its oracle: propagate, augmentState, the update when it is handed tracks, the drop when
+        its own window is full"""
+        tr, fr = self.trajs[b], self.frames[b][k]
+        o.propagate(tr.imu_for_frame(k))
+        o.augmentState(k, tr.frame_times[k])
+        if len(fr["M"]):
+            o.setTracks(fr["M"], fr["slots"], fr["obs"])
+            o.marginalize()
+        if self.full(b, k):
+            o.dropOldest(1)
+
+    def device_frame(self, bt, k, only=None):
+        """frame k through the per-call API, every device stage ONE launch sequence over the whole range: propagate_range and
+        marginalize_range over (0, B); set_tracks per trajectory; the drop per trajectory, when its own window is full.
+        only = b: trajectory b alone is active -- its neighbours are propagated, but get no camera state and no tracks."""
+        act = range(self.B) if only is None else [only]
+        bt.propagate_range(0, self.B, self.imu(k))
+        if only is None:
+            bt.augment_range(0, self.B)
+        else:
+            bt.augment_range(only, 1)
+        for b in act:
+            fr = self.frames[b][k]
+            bt.set_tracks(b, fr["M"], fr["slots"], fr["obs"])
+        bt.marginalize_range(0, self.B)
+        for b in act:
+            if self.full(b, k):
+                bt.drop_oldest_range(b, 1, 1)
+
+    def stage_scenario(self, bt):
+        """the same frames as a resident scenario, the drop flag per trajectory from its own window"""
+        from msckf_mono_amd import scenario as sc
+        bt.scenario_alloc(self.nf, sc.IMU_PER_FRAME)
+        for k in range(self.nf):
+            for b, tr in enumerate(self.trajs):
+                fr = self.frames[b][k]
+                bt.scenario_set(k, b, tr.imu_for_frame(k), fr["M"], fr["slots"], fr["obs"], 1 if self.full(b, k) else 0)
+        bt.scenario_commit()
+
+
+def snapshot(bt, b, strict=True):
+    """everything a test compares bit for bit: IMU state, camera states, covariance, window size, statistics"""
+    st = bt.last_stats(b, strict=strict)
+    return bt.imu_state(b), bt.cam_states(b)[0], bt.covariance(b), bt.num_cam_states(b), {k: st[k] for k in STAT_KEYS + ("r_rows",)}
+
+
+def same_bits(x, y):
+    return all(np.array_equal(p, q) for p, q in zip(x[:3], y[:3])) and x[3] == y[3] and x[4] == y[4]
