@@ -10,6 +10,8 @@ for p in (ROOT, os.path.join(ROOT, "oracle")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import np_oracle  # noqa: E402  (oracle/ is on the path now)
+
 
 def quat_angle(q, qref):
     """rotation angle of q (x) qref^-1 for (w,x,y,z) quaternions (atan2 form: accurate near zero)"""
@@ -253,3 +255,166 @@ def snapshot(bt, b, strict=True):
 
 def same_bits(x, y):
     return all(np.array_equal(p, q) for p, q in zip(x[:3], y[:3])) and x[3] == y[3] and x[4] == y[4]
+
+
+# ------------------------------------------------------ state kernels (tests/test_state_inputs.py, tests/test_gpu_state_kernels.py)
+def cov_scaled_err(P, P_ref):
+    """max_ij |P_ij - Pref_ij| / sqrt(Pref_ii Pref_jj): every entry against the scale of ITS row and column, so that an error in a
+    small block (a camera's six columns, one sample's process noise) is not hidden under the norm of the whole matrix"""
+    P, P_ref = np.asarray(P, dtype=np.float64), np.asarray(P_ref, dtype=np.float64)
+    s = np.sqrt(np.diag(P_ref))
+    return float(np.max(np.abs(P - P_ref) / np.outer(s, s)))
+
+
+def imu_state_err(x, ref):
+    """worst of the attitude angle and the relative error of v and p (the fields a propagate moves) of two IMU-29 states, and
+    of their null-space anchors"""
+    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    return max(quat_angle(x[0:4], ref[0:4]), rel(x[7:10], ref[7:10]), rel(x[13:16], ref[13:16]),
+               quat_angle(x[19:23], ref[19:23]), rel(x[23:26], ref[23:26]), rel(x[26:29], ref[26:29]))
+
+
+# Process noise and covariance scale of the state-kernel inputs.  With scenario.filter_config's Q_imu_diag one sample adds
+# Q dT ~ 1e-4 * 0.005 to a P_II diagonal of 1e-5 .. 1e-2: a lost sample is 1e-8 of ||P||.  Here every diagonal entry of P_II that
+# takes process noise (theta, b_g, v, b_a) starts at STATE_P_OVER_Q = 0.1 s times its Q_imu entry, so that one sample adds
+# dT / 0.1 s of it: 2.5e-2 at the shortest dT of the families (0.0025 s), never below the 1e-3 the tests need (checked on the
+# CPU in tests/test_state_inputs.py; the dT = 0 samples of `jitter` add nothing by definition).
+STATE_Q_DIAG = [4e-3] * 3 + [4e-4] * 3 + [4e-2] * 3 + [4e-3] * 3
+STATE_P_OVER_Q = 0.1
+STATE_P_IMU_DIAG = [STATE_P_OVER_Q * q for q in STATE_Q_DIAG] + [1e-2] * 3
+STATE_P_CAM_DIAG = [1e-3] * 3 + [1e-2] * 3
+STATE_FAMILIES = ("nominal", "still", "fast", "jitter", "mixed")
+STATE_JITTER_DT = (0.0025, 0.005, 0.01, 0.02)
+STATE_JITTER_ZERO_AT = (5, 20)     # samples of `jitter` with dT = 0 exactly (finite in both references: test_state_inputs.py)
+STATE_FAST_ANGLE = 0.5             # |omega - b_g| dT of the `fast` samples [rad]
+
+
+def _state_sample(kind, rng, bg, k, fast_angle):
+    """one reading of family `kind`: omega(3) a(3) dT"""
+    u = rng.normal(3)
+    u /= np.linalg.norm(u)
+    acc = 3.0 * rng.normal(3) + np.array([0.0, 0.0, 9.81])
+    jit = STATE_JITTER_DT[int(rng.integers(1, len(STATE_JITTER_DT))[0])]
+    dT = 0.005
+    if kind == "still":
+        om = bg.copy()                                  # omega - b_g = 0 exactly (in float too: both round the same way)
+    elif kind == "fast":
+        om = bg + u * (fast_angle / dT)
+    elif kind == "jitter":
+        dT = 0.0 if k in STATE_JITTER_ZERO_AT else jit
+        om = bg + 0.4 * u
+    else:
+        om = bg + 0.4 * u + 0.01 * rng.normal(3)
+    return np.concatenate([om, acc, [dT]])
+
+
+def state_inputs(case, seed, K=40, fast_angle=STATE_FAST_ANGLE):
+    """(imu29, cfg, readings [K][7]) of reading family `case` (STATE_FAMILIES), from scenario.SplitMix64(seed) alone.  `mixed`
+    cycles through the four other families and has a `still` and a `fast` sample on each side of index 16 (14, 15 | 17, 18);
+    sample 16 itself is a nominal one of 0.01 s."""
+    from msckf_mono_amd import scenario as sc
+    assert case in STATE_FAMILIES
+    rng = sc.SplitMix64(0x57A7E000 + 7919 * int(seed) + STATE_FAMILIES.index(case))
+    q = rng.normal(4)
+    q = q / np.linalg.norm(q) * (1.0 if q[0] >= 0 else -1.0)
+    bg, v, ba, p = 0.01 * rng.normal(3), rng.normal(3), 0.05 * rng.normal(3), 2.0 * rng.normal(3)
+    imu = np.concatenate([q, bg, v, ba, p, sc.GRAVITY, q, v, p])
+    cfg = sc.filter_config(64)
+    cfg["Q_imu_diag"] = list(STATE_Q_DIAG)
+    cfg["P0_diag"] = list(STATE_P_IMU_DIAG)
+    cfg["max_cam_states"] = 63
+    fixed = {14: "still", 15: "fast", 16: "nominal", 17: "fast", 18: "still"}
+    rd = np.zeros((K, 7))
+    for k in range(K):
+        kind = case if case != "mixed" else fixed.get(k, STATE_FAMILIES[k % 4])
+        rd[k] = _state_sample(kind, rng, bg, k, fast_angle)
+        if case == "mixed" and k == 16:
+            rd[k, 6] = 0.01
+    return imu, cfg, rd
+
+
+def state_spd(ncam, seed):
+    """random symmetric positive definite covariance of a window of ncam camera states: a random correlation matrix (Wishart,
+    2 D degrees of freedom) scaled to the diagonals STATE_P_IMU_DIAG / STATE_P_CAM_DIAG"""
+    from msckf_mono_amd import scenario as sc
+    D = 15 + 6 * ncam
+    rng = sc.SplitMix64(0xC0FA0000 + 104729 * int(seed) + ncam)
+    A = rng.normal(2 * D * D).reshape(D, 2 * D)
+    C = A @ A.T
+    d = np.sqrt(np.diag(C))
+    s = np.sqrt(np.array(STATE_P_IMU_DIAG + STATE_P_CAM_DIAG * ncam))
+    P = C / np.outer(d, d) * np.outer(s, s)
+    return (P + P.T) / 2
+
+
+def state_cam_poses(ncam, seed):
+    """ncam distinct camera poses q_CG(4, unit) p_C_G(3)"""
+    from msckf_mono_amd import scenario as sc
+    rng = sc.SplitMix64(0xCA3E0000 + int(seed))
+    q = rng.normal(4 * ncam).reshape(ncam, 4)
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    q *= np.where(q[:, :1] >= 0, 1.0, -1.0)
+    return np.concatenate([q, 3.0 * rng.normal(3 * ncam).reshape(ncam, 3)], 1)
+
+
+def oracle_window(o, cfg, imu, P, poses):
+    """oracle `o` holding the IMU state, the len(poses) camera states and the covariance given"""
+    o.initialize(cfg, imu)
+    for i in range(len(poses)):
+        o.augmentState(i, 0.0)
+    o.setImuState(imu)
+    for i, c in enumerate(poses):
+        o.setCamPose(i, c)
+    o.setCovariance(P)
+    return o
+
+
+def device_window(bt, b, cfg, imu, P, poses):
+    """the same on trajectory b of a device batch (set_covariance, set_imu_state, set_cam_pose)"""
+    bt.initialize(b, cfg, imu)
+    bt.set_covariance(b, P)                 # (sets the window size with it)
+    bt.set_imu_state(b, imu)
+    for i, c in enumerate(poses):
+        bt.set_cam_pose(b, i, c)
+
+
+class TwinMutant(np_oracle.NpMSCKF):
+    """oracle/np_oracle.NpMSCKF (the numpy/scipy twin) with a block propagate and, optionally, ONE deliberate mistake -- applied
+    to this reference only, never to the code under test -- to show that inputs and metric can see it:
+      "a"  no G Q G^T dT for sample 16 of a call        "b"  sample 16's null-space patch anchored at the state before sample 0
+      "c"  the last camera's six P_IC columns are left unmultiplied        "d"  p advanced with the NEW velocity
+    P / ncam: start from this covariance with ncam camera states; a config's whole "Q_imu" is used when it has one."""
+
+    def __init__(self, cfg, imu, mutation=None, P=None, ncam=0):
+        super().__init__(cfg, imu)
+        assert mutation in (None, "a", "b", "c", "d")
+        self.mutation = mutation
+        if "Q_imu" in cfg:
+            self.Q = np.array(cfg["Q_imu"], dtype=np.float64)
+        if "P0" in cfg:
+            self.P = np.array(cfg["P0"], dtype=np.float64)
+        for i in range(ncam):
+            self.augment(i)
+        if P is not None:
+            self.P = np.array(P, dtype=np.float64)
+
+    def propagate_block(self, rds):
+        rds = np.asarray(rds, dtype=np.float64).reshape(-1, 7)
+        start = (self.q.copy(), self.v.copy(), self.p.copy())
+        for k, rd in enumerate(rds):
+            Q, keep = self.Q, None
+            if self.mutation == "a" and k == 16:
+                self.Q = np.zeros_like(Q)
+            if self.mutation == "b" and k == 16:
+                self.q_null, self.v_null, self.p_null = (x.copy() for x in start)
+            if self.mutation == "c" and self.P.shape[0] > 15:
+                keep = self.P[:15, -6:].copy()
+            p_old = self.p.copy()
+            self.propagate(rd)
+            self.Q = Q
+            if keep is not None:
+                self.P[:15, -6:] = keep
+                self.P[-6:, :15] = keep.T
+            if self.mutation == "d":
+                self.p = p_old + self.v * float(rd[6])
+                self.p_null = self.p.copy()
