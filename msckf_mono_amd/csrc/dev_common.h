@@ -346,27 +346,101 @@ template <int CTRL, int ROWMASK> __device__ __forceinline__ double dppm_x(double
 }
 constexpr int DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
 
-template <class S> __device__ __forceinline__ S wave_sum(S v) {
+// the four in-row steps: afterwards every lane of a row of 16 holds the row's result.  The order of the steps is the
+// summation tree, part of the bit-level contract of every reduction below
+template <class S> __device__ __forceinline__ S row16_sum(S v) {
   v += dpp_x<DPP_QUAD_X1>(v); v += dpp_x<DPP_QUAD_X2>(v); v += dpp_x<DPP_HALF_MIRROR>(v); v += dpp_x<DPP_ROW_MIRROR>(v);
+  return v;
+}
+template <class S> __device__ __forceinline__ S row16_max(S v) {
+  S t;
+  t = dpp_x<DPP_QUAD_X1>(v); v = t > v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t > v ? t : v;
+  t = dpp_x<DPP_HALF_MIRROR>(v); v = t > v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t > v ? t : v;
+  return v;
+}
+__device__ __forceinline__ int row16_min(int v) {
+  int t;
+  t = dpp_x<DPP_QUAD_X1>(v); v = t < v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t < v ? t : v;
+  t = dpp_x<DPP_HALF_MIRROR>(v); v = t < v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t < v ? t : v;
+  return v;
+}
+
+template <class S> __device__ __forceinline__ S wave_sum(S v) {
+  v = row16_sum(v);
   // every lane holds its row's sum: fold row 0 into 1 and 2 into 3, then rows {0,1} into 3; lane 63 has the total
   v += dppm_x<DPP_ROW_BCAST15, 0xA>(v);
   v += dppm_x<DPP_ROW_BCAST31, 0xC>(v);
   return wave_bcast(v, 63);
 }
 template <class S> __device__ __forceinline__ S wave_max(S v) {
-  S t;
-  t = dpp_x<DPP_QUAD_X1>(v); v = t > v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t > v ? t : v;
-  t = dpp_x<DPP_HALF_MIRROR>(v); v = t > v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t > v ? t : v;
+  v = row16_max(v);
   const S a = wave_bcast(v, 0), b = wave_bcast(v, 16), c = wave_bcast(v, 32), e = wave_bcast(v, 48);
   const S ab = a > b ? a : b, ce = c > e ? c : e;
   return ab > ce ? ab : ce;
 }
 __device__ __forceinline__ int wave_min_i(int v) {
-  int t;
-  t = dpp_x<DPP_QUAD_X1>(v); v = t < v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t < v ? t : v;
-  t = dpp_x<DPP_HALF_MIRROR>(v); v = t < v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t < v ? t : v;
+  v = row16_min(v);
   return min(min(wave_bcast(v, 0), wave_bcast(v, 16)), min(wave_bcast(v, 32), wave_bcast(v, 48)));
 }
+
+// The same over the lane's HALF of the wavefront (rows {0, 1} or {2, 3}: two tracks per wavefront in k_feature_pair): the two
+// rows of a half meet through v_permlane16_swap; every lane of the half gets the same bits
+__device__ __forceinline__ float x16_sum(float v) {   // v[lane] + v[lane ^ 16]
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ double x16_sum(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)(b & 0xffffffffull), hi = (unsigned)(b >> 32);
+  const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  const double a = __longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0]));
+  const double c = __longlong_as_double((long long)(((unsigned long long)rh[1] << 32) | rl[1]));
+  return a + c;
+}
+template <class T> __device__ __forceinline__ T half_sum(T v) { return x16_sum(row16_sum(v)); }
+__device__ __forceinline__ float half_max(float v) {
+  v = row16_max(v);
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  const float a = __uint_as_float(r[0]), c = __uint_as_float(r[1]);
+  return a > c ? a : c;
+}
+__device__ __forceinline__ int half_min_i(int v) {
+  v = row16_min(v);
+  const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+  return min((int)r[0], (int)r[1]);
+}
+
+// LDS hand-over between the lanes of ONE wavefront: what a lane wrote to LDS before it, every lane of the wavefront may read
+// after it.  No workgroup barrier is needed -- a wavefront's LDS operations complete in order -- but the two fences are: they
+// are what keeps the COMPILER from moving a read above the write it depends on (wave_barrier alone orders no memory
+// operation).  Without them the f64 instance of k_trsm_rows (kernels_chol.hip: written in one lane layout, read in another, so
+// the per-thread addresses differ) was miscompiled: its reads ran before the writes (docs/HISTORY.md, round 2).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The 16 x 16 x 4 matrix-core tile of the scalar type.  A operand: lane (g = lane >> 4, m = lane & 15) holds A[m][k0 + g];
+// B operand: B[k0 + g][m].  C/D, four values per lane, register r:
+//   f64 (v_mfma_f64_16x16x4_f64): row = (lane >> 4) + 4 r, col = lane & 15
+//   f32 (v_mfma_f32_16x16x4_f32): row = 4 (lane >> 4) + r, col = lane & 15
+// row(lane, r) is that row; row_of_group(g, r) the same for a caller that holds g = lane >> 4 already (k_propagate: written
+// out here and not as row(16 g, r), which the compiler turns into other instructions there)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+template <class T> struct Mfma16;
+template <> struct Mfma16<double> {
+  typedef f64x4 V;
+  static __device__ __forceinline__ V mma(double a, double b, V c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
+  static __device__ __forceinline__ int row_of_group(int g, int r) { return g + 4 * r; }
+};
+template <> struct Mfma16<float> {
+  typedef f32x4 V;
+  static __device__ __forceinline__ V mma(float a, float b, V c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
+  static __device__ __forceinline__ int row_of_group(int g, int r) { return 4 * g + r; }
+};
 
 // 1/sqrt(x) for the pivots of the register-resident factorizations: hardware rsq seed + Newton steps instead of the
 // IEEE sqrt and division sequences (the pivot sits on the critical path of every elimination step)
@@ -384,6 +458,7 @@ template <> __device__ __forceinline__ double fast_rsqrt<double>(double x) {
 
 // 1/x from the hardware seed + Newton steps (full precision of the type to ~1 ulp): the IEEE division sequence is ~10 (f32)
 // / ~25 (f64) instructions
+// (not lm_rcp of kernels_feature.hip nor qr_rcp of kernels_qr.hip: other Newton forms and counts, other bits -- the names stay apart)
 template <class S> __device__ __forceinline__ S fast_rcp(S x);
 template <> __device__ __forceinline__ float fast_rcp<float>(float x) {
   const float r = __builtin_amdgcn_rcpf(x);

@@ -32,21 +32,6 @@ namespace msckf {
 __device__ __forceinline__ float clamp_min(float x, float lo) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(lo)); return r; }
 __device__ __forceinline__ double clamp_min(double x, double lo) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "v"(lo)); return r; }
 
-typedef double cd4 __attribute__((ext_vector_type(4)));
-typedef float cf4 __attribute__((ext_vector_type(4)));
-
-template <class T> struct Mf;
-template <> struct Mf<double> {   // v_mfma_f64_16x16x4_f64: C/D row = (lane >> 4) + 4 r, col = lane & 15
-  typedef cd4 V;
-  static __device__ __forceinline__ V mma(double a, double b, V c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-};
-template <> struct Mf<float> {    // v_mfma_f32_16x16x4_f32: C/D row = 4 (lane >> 4) + r, col = lane & 15
-  typedef cf4 V;
-  static __device__ __forceinline__ V mma(float a, float b, V c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
-};
-
 template <class F, int... Ps>
 __device__ __forceinline__ void cstatic_for_impl(F&& f, std::integer_sequence<int, Ps...>) { (f(std::integral_constant<int, Ps>{}), ...); }
 template <int N, class F>
@@ -79,7 +64,7 @@ __device__ int g_chol_dbg = 0;   // ablation: 1 the other wavefronts skip output
 // NB: 16-column blocks of the factored matrix; NA: appended 16-row blocks held by ONE workgroup (GAIN), 0 for GRAM
 template <class T, class SO, int NB, int NA, int MODE, int NPART>
 __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
-  typedef typename Mf<T>::V V;
+  typedef typename Mfma16<T>::V V;
   constexpr int NR = NB + NA, HR = (NR + 3) / 4, HC = (NB + 3) / 4, LP = 17;   // sixteen wavefronts: block (i, j) belongs to wavefront 4 (i & 3) + (j & 3)
   // GAIN: the NPART workgroups of a trajectory read the same T and P T_H^T: on one XCD (xcd_item), whose L2 then serves three of the four
   int bi_ = (int)blockIdx.x, part = 0;
@@ -182,13 +167,13 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
             // T_H is upper triangular: the part of row 16 i + rr left of its diagonal is masked here rather than trusted to be an
             // exact zero in whatever route produced Rbuf (the k-blocks start at kb = i, so only the diagonal block has such entries)
             const bool ok = k0 + s4 < n, upper = k0 + s4 >= 16 * i + rr;   // (the A operand's row is 16 i + rr; B's lane index is a column)
-            sacc = Mf<T>::mma(ok && upper ? a4[u][s4] : T(0), ok ? bv[u][s4] : T(0), sacc);
+            sacc = Mfma16<T>::mma(ok && upper ? a4[u][s4] : T(0), ok ? bv[u][s4] : T(0), sacc);
           }
         }
       }
       const T sg2 = (T)d.prm[(long)b * PRM_STRIDE + PRM_SIG2];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) out[r] = sacc[r] + ((i == j && Mf<T>::row(lane, r) == (lane & 15)) ? sg2 : T(0));
+      for (int r = 0; r < 4; ++r) out[r] = sacc[r] + ((i == j && Mfma16<T>::row(lane, r) == (lane & 15)) ? sg2 : T(0));
     }
     return out;
   };
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
       if (MODE == CH_GAIN && d.gain_fused_s >= 2 && i < NB && s_owner(ii, jj) != part) continue;   // a sibling part forms this block
       if (MODE == CH_GAIN && d.gain_fused_s && i < NB) { acc[ii][jj] = s_block(i, j); continue; }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[ii][jj][r] = *el_ptr(16 * i + Mf<T>::row(lane, r), 16 * j + (lane & 15));
+      for (int r = 0; r < 4; ++r) acc[ii][jj][r] = *el_ptr(16 * i + Mfma16<T>::row(lane, r), 16 * j + (lane & 15));
       // split-K SYRK (kernels_gram.hip): the tiles of block column j / 4 came in min(j / 4 + P - 2, P) partial sums (P =
       // d.gram_parts), lam_part apart; added here in a fixed order (the loads are as unconditional as the ones above: more
       // round trips, no waits between)
@@ -215,7 +200,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
         for (int c = 1; c < 4; ++c)
           if (c < ncopy) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[ii][jj][r] += *(el_ptr(16 * i + Mf<T>::row(lane, r), 16 * j + (lane & 15)) + c * d.lam_part);
+            for (int r = 0; r < 4; ++r) acc[ii][jj][r] += *(el_ptr(16 * i + Mfma16<T>::row(lane, r), 16 * j + (lane & 15)) + c * d.lam_part);
           }
       }
     }
@@ -240,7 +225,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
           if (i >= NB || j > i || 16 * j >= n || 16 * i >= main_rows || s_owner(ii, jj) != part) continue;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int row = 16 * i + Mf<T>::row(lane, r), col = 16 * j + (lane & 15);
+            const int row = 16 * i + Mfma16<T>::row(lane, r), col = 16 * j + (lane & 15);
             if (row < d.n6cap && col < d.n6cap) __hip_atomic_store(Sg + (long)row * d.n6cap + col, acc[ii][jj][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
@@ -281,7 +266,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
           if (!all_here) { acc[ii][jj] = s_block(i, j); continue; }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int row = min(16 * i + Mf<T>::row(lane, r), d.n6cap - 1), col = min(16 * j + (lane & 15), d.n6cap - 1);
+            const int row = min(16 * i + Mfma16<T>::row(lane, r), d.n6cap - 1), col = min(16 * j + (lane & 15), d.n6cap - 1);
             acc[ii][jj][r] = __hip_atomic_load(Sg + (long)row * d.n6cap + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
@@ -300,7 +285,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
       if (i >= NR || j >= NB || (i < NB && j > i) || 16 * j >= n) continue;
       if (i < NB && 16 * i >= main_rows) continue;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) if (!el_ok(16 * i + Mf<T>::row(lane, r), 16 * j + (lane & 15))) acc[ii][jj][r] = T(0);
+      for (int r = 0; r < 4; ++r) if (!el_ok(16 * i + Mfma16<T>::row(lane, r), 16 * j + (lane & 15))) acc[ii][jj][r] = T(0);
     }
   if (GRAMLIKE)
     for (int t = tid; t < 16 * NB; t += 1024) {
@@ -347,7 +332,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {
             const T a = -sP[16 * i + (lane & 15)][4 * s4 + (lane >> 4)];
-            acc[ii][jj] = Mf<T>::mma(a, bq[s4], acc[ii][jj]);
+            acc[ii][jj] = Mfma16<T>::mma(a, bq[s4], acc[ii][jj]);
           }
         }
       }
@@ -372,7 +357,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
         if (WHICH == 1 && i != p) continue;
         if (WHICH == 2 && i == p) continue;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sP[16 * i + Mf<T>::row(lane, r)][lane & 15] = acc[ii][p >> 2][r];
+        for (int r = 0; r < 4; ++r) sP[16 * i + Mfma16<T>::row(lane, r)][lane & 15] = acc[ii][p >> 2][r];
       }
     }
   };
@@ -493,9 +478,9 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
       for (int s4 = 0; s4 < 4; ++s4) a[s4] = sP[16 * i + (lane & 15)][(lane >> 4) + 4 * s4];
       V y = V{0, 0, 0, 0};
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) y = Mf<T>::mma(a[s4], bq[s4], y);
+      for (int s4 = 0; s4 < 4; ++s4) y = Mfma16<T>::mma(a[s4], bq[s4], y);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sP[16 * i + Mf<T>::row(lane, r)][lane & 15] = y[r];
+      for (int r = 0; r < 4; ++r) sP[16 * i + Mfma16<T>::row(lane, r)][lane & 15] = y[r];
     }
   };
   // (4) results of panel p, written by wavefronts 1..15 (960 threads) while wavefront 0 factors the next diagonal block
@@ -572,7 +557,7 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
           const T a = -sP[16 * i + (lane & 15)][4 * s4 + (lane >> 4)];
-          acc[ii][jj] = Mf<T>::mma(a, bq[s4], acc[ii][jj]);
+          acc[ii][jj] = Mfma16<T>::mma(a, bq[s4], acc[ii][jj]);
         }
       }
     }
@@ -639,12 +624,9 @@ __global__ __launch_bounds__(1024) void k_chol_mfma(Dev<SO> d, int b0, int nb) {
 //   TR_W     X = [P T_H^T ; r_n^T] (D + 1 rows, all n columns): W = P T_H^T L^-T (msckf.h:1370 without the inverse) and
 //            z = L^-1 r_n, left in W and Linv[0..n)
 enum { TR_GRAM = 0, TR_S21 = 1, TR_W = 2 };
-// LDS hand-over between the lanes of ONE wavefront (write in one layout, read in another): no s_barrier needed, but the
-// compiler must not move the reads above the writes -- per-thread addresses differ, so only the fences order them
-#define WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); } while (0)
 template <class T, class SO, int NP, int TMODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) void k_trsm_rows(Dev<SO> d, int b0, int nb, int nwg) {
-  typedef typename Mf<T>::V V;
+  typedef typename Mfma16<T>::V V;
   constexpr int LP = 17;
   // the row blocks of a trajectory all read its factor L: on one XCD (xcd_item), whose private L2 then fetches it once
   int bi_, wg_;
@@ -687,7 +669,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 #pragma unroll
   for (int q = 0; q < NP; ++q)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) acc[q][r] = active ? xin(R0 + Mf<T>::row(lane, r), 16 * q + (lane & 15)) : T(0);
+    for (int r = 0; r < 4; ++r) acc[q][r] = active ? xin(R0 + Mfma16<T>::row(lane, r), 16 * q + (lane & 15)) : T(0);
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
     if (16 * p >= ncols) continue;
@@ -704,25 +686,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     if (!active) continue;
     // Y = X_p M_p
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sT[w][Mf<T>::row(lane, r)][lane & 15] = acc[p][r];
-    WAVE_LDS_SYNC();
+    for (int r = 0; r < 4; ++r) sT[w][Mfma16<T>::row(lane, r)][lane & 15] = acc[p][r];
+    wave_lds_sync();
     V y = V{0, 0, 0, 0};
 #pragma unroll
     for (int s4 = 0; s4 < 4; ++s4) {
       const T a = sT[w][lane & 15][(lane >> 4) + 4 * s4];
       const int mi = ((lane >> 4) + 4 * s4) * 16 + (lane & 15);
       const T bq = TMODE == TR_GRAM ? (T)d.Mp[((long)b * (CH_SPLIT / 16) + p) * 256 + mi] : (T)d.Mp2[((long)b * 24 + p) * 256 + mi];
-      y = Mf<T>::mma(a, bq, y);
+      y = Mfma16<T>::mma(a, bq, y);
     }
-    WAVE_LDS_SYNC();
+    wave_lds_sync();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = Mf<T>::row(lane, r), col = lane & 15;
+      const int row = Mfma16<T>::row(lane, r), col = lane & 15;
       sT[w][row][col] = y[r];
       if (TMODE == TR_GRAM) { if (R0 + row <= nfull) Lam[(long)(R0 + row) * d.ldR + 16 * p + col] = (double)y[r]; }
       if (TMODE == TR_S21) { if (R0 + row < nfull && 16 * p + col < ncols) Sm[(long)(R0 + row) * d.n6cap + 16 * p + col] = (SO)y[r]; }
     }
-    WAVE_LDS_SYNC();
+    wave_lds_sync();
     // transposed outputs, lanes along the rows of the block
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -742,9 +724,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     for (int q = p + 1; q < NP; ++q) {
       if (16 * q >= ncols) continue;
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) acc[q] = Mf<T>::mma(a[s4], sLc[(q - p - 1) * 16 + (lane & 15)][4 * s4 + (lane >> 4)], acc[q]);
+      for (int s4 = 0; s4 < 4; ++s4) acc[q] = Mfma16<T>::mma(a[s4], sLc[(q - p - 1) * 16 + (lane & 15)][4 * s4 + (lane >> 4)], acc[q]);
     }
-    WAVE_LDS_SYNC();
+    wave_lds_sync();
     __builtin_amdgcn_sched_barrier(0);   // keep the next panels' loads of L out of this one (the scheduler otherwise hoists them all: spills)
   }
 }

@@ -34,6 +34,7 @@ template <class S> struct Pose { M3<S> R; V3<S> t; };
 // follows the reference's iterates).  float: hardware rcp + one Newton step (<= 1 ulp) instead of the ~10-instruction IEEE
 // division sequence -- the iteration is 28 % of the kernel's VALU instructions, half of them divisions; the float filter's
 // tolerances (tests/helpers.py:check_tracks) are four orders of magnitude above the difference.
+// (not fast_rcp / fast_rsqrt of dev_common.h: r (2 - x r) here, r + r (1 - x r) there, IEEE in double -- other bits, other names)
 template <class S> __device__ __forceinline__ S lm_rcp(S x);
 template <> __device__ __forceinline__ double lm_rcp<double>(double x) { return 1.0 / x; }
 template <> __device__ __forceinline__ float lm_rcp<float>(float x) { const float r = __builtin_amdgcn_rcpf(x); return r * __builtin_fmaf(-x, r, 2.0f); }
@@ -1025,9 +1026,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LONG ? 1 : (
 // the two Cholesky factorizations run one after the other on the full 8 x 8 lane grid (gate_chol, as in k_feature).
 // Same arithmetic per track as k_feature<float> (sums over a half instead of the wavefront: identical terms, the zeros
 // of the idle lanes fall elsewhere in the tree); decisions and gamma agree to rounding (tests/test_gpu_parity.py A/B).
-constexpr int GS = 32;   // lanes per track
-// LDS hand-over inside ONE wavefront (its LDS operations complete in order; the fences stop the compiler from moving reads above writes)
-__device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+constexpr int GS = 32;   // lanes per track: the sums over a track are dev_common.h's half_sum / half_max / half_min_i
 #ifdef MSCKF_ABLATE
 // phase timers of the -DMSCKF_ABLATE build (scripts/feat_phases.py): shader-clock cycles per phase summed over ALL wavefronts
 // [0 pairing, 1 loads + checkMotion + first cost, 2 Levenberg-Marquardt, 3 Jacobian + B^ + publish, 4 G assembly, 5 factorizations, 6 tail, 7 wavefronts]
@@ -1039,40 +1038,6 @@ __device__ unsigned long long g_featp_cycles[8];
 #else
 #define FP_TICK(slot) do { } while (0)
 #endif
-
-__device__ __forceinline__ float x16_sum(float v) {   // v[lane] + v[lane ^ 16]
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ double x16_sum(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)(b & 0xffffffffull), hi = (unsigned)(b >> 32);
-  const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-  const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-  const double a = __longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0]));
-  const double c = __longlong_as_double((long long)(((unsigned long long)rh[1] << 32) | rl[1]));
-  return a + c;
-}
-// sum over the lane's half of the wavefront; every lane of the half gets the same bits
-template <class T> __device__ __forceinline__ T half_sum(T v) {
-  v += dpp_x<DPP_QUAD_X1>(v); v += dpp_x<DPP_QUAD_X2>(v); v += dpp_x<DPP_HALF_MIRROR>(v); v += dpp_x<DPP_ROW_MIRROR>(v);
-  return x16_sum(v);
-}
-__device__ __forceinline__ float half_max(float v) {
-  float t;
-  t = dpp_x<DPP_QUAD_X1>(v); v = t > v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t > v ? t : v;
-  t = dpp_x<DPP_HALF_MIRROR>(v); v = t > v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t > v ? t : v;
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  const float a = __uint_as_float(r[0]), c = __uint_as_float(r[1]);
-  return a > c ? a : c;
-}
-__device__ __forceinline__ int half_min_i(int v) {
-  int t;
-  t = dpp_x<DPP_QUAD_X1>(v); v = t < v ? t : v; t = dpp_x<DPP_QUAD_X2>(v); v = t < v ? t : v;
-  t = dpp_x<DPP_HALF_MIRROR>(v); v = t < v ? t : v; t = dpp_x<DPP_ROW_MIRROR>(v); v = t < v ? t : v;
-  const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-  return min((int)r[0], (int)r[1]);
-}
 
 // Register budget: three wavefronts per SIMD (168 registers, 5 values per lane in scratch).  At four (128 registers) 34 live values
 // per lane sit in scratch: 56 MB of the launch's 96 MB of writes at 64 trajectories (166 MB of traffic per launch instead of 64),

@@ -35,7 +35,6 @@ __device__ unsigned long long g_gram_cycles[8][5];
 #define GR_TICK(slot) do {} while (0)
 #endif
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int GK = 24;   // rows of B per staged chunk = 8 tracks
 constexpr int GT_MAX = 1; // 64 x 64 tiles of one block row held by one workgroup (1: every tile its own workgroup -- the MFMA work of a
                           // trajectory spreads over 6 CUs instead of 3 at a 30-camera window; measured against 3)
@@ -170,13 +169,13 @@ __global__ __launch_bounds__(512) void k_gram(Dev<S> d, int b0, int nb, int npai
         if (tj0 + u > ti && tj0 + u < nt) sB[u][lr + 4 * it][lc] = (ok && ((r.ok >> (8 * (u + 1) + it)) & 1u)) ? r.b[u][it] : 0.0;
     }
   };
-  v4d acc[GT_MAX][2][2];
+  f64x4 acc[GT_MAX][2][2];
 #pragma unroll
   for (int u = 0; u < GT_MAX; ++u)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc[u][i][j] = v4d{0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j < 2; ++j) acc[u][i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
   auto compute = [&]() {
 #pragma unroll
     for (int k4 = 0; k4 < GK; k4 += 4) {

@@ -401,7 +401,6 @@ __global__ __launch_bounds__(256) void k_gemm_mfma(Dev<float> d, int b0, int nb,
 // f64 tile GEMM on the matrix cores: v_mfma_f64_16x16x4_f64, 64 x 64 output tile per workgroup, each wavefront a
 // 32 x 32 sub-tile as 2 x 2 accumulators.  As in the f32 kernel the product is formed transposed (MFMA "A" operand =
 // B-tile) so that the accumulator's lane index runs along the output row index i and the stores are coalesced.
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 template <int OP>
 __global__ __launch_bounds__(256) void k_gemm_mfma64(Dev<double> d, int b0) {
   using S = double;
@@ -973,21 +972,10 @@ void us_cycles_read(unsigned long long* out16, int reset) {
 #else
 #define US_TICK(slot) do {} while (0)
 #endif
-typedef double us_d4 __attribute__((ext_vector_type(4)));
-typedef float us_f4 __attribute__((ext_vector_type(4)));
-template <class T> struct UsM;
-template <> struct UsM<double> {
-  typedef us_d4 V;
-  static __device__ __forceinline__ V mma(double a, double b, V c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int lane, int r) { return (lane >> 4) + 4 * r; }
-  static __device__ __forceinline__ double clamp() { return 1e-300; }    // a non-positive pivot (reported): its rsqrt squared stays finite
-};
-template <> struct UsM<float> {
-  typedef us_f4 V;
-  static __device__ __forceinline__ V mma(float a, float b, V c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int row(int lane, int r) { return 4 * (lane >> 4) + r; }
-  static __device__ __forceinline__ float clamp() { return 1e-30f; }
-};
+// a non-positive pivot of chol(S) (reported) is raised to this: its rsqrt squared stays finite
+template <class T> __device__ __forceinline__ T us_clamp();
+template <> __device__ __forceinline__ double us_clamp<double>() { return 1e-300; }
+template <> __device__ __forceinline__ float us_clamp<float>() { return 1e-30f; }
 constexpr int US_UMAX = 2;     // tasks per wavefront of the factorizations
 constexpr int US_SEG_E = 12;   // columns per task of chol(S) with its D + 1 riding rows (10 cameras: 3 row chunks x 5 segments = 15 tasks); chol(Lam^): SEGB = 4 (61 rows: one chunk, 15 tasks) or 8
 // scalars of the PHt / W block [15 + n_max][n_max | 1]: it also stages 24 rows of B^ (doubles, 16 ceil((n_max + 1) / 16) + 1 columns) in
@@ -1004,10 +992,10 @@ __host__ __device__ inline size_t update_small_pt_elems(int n_max, int f_cap, si
 }
 // one 16 x 16 tile of sum_k a(16 ti + m, k) b(k, 16 tj + c), k in [k0, k1) in steps of 4 (the functors return zero out of range)
 template <class T, class FA, class FB>
-__device__ __forceinline__ typename UsM<T>::V us_tile(int ti, int tj, int k0, int k1, int lane, FA&& fa, FB&& fb) {
-  typename UsM<T>::V acc = {0, 0, 0, 0};
+__device__ __forceinline__ typename Mfma16<T>::V us_tile(int ti, int tj, int k0, int k1, int lane, FA&& fa, FB&& fb) {
+  typename Mfma16<T>::V acc = {0, 0, 0, 0};
   const int m = lane & 15, g = lane >> 4;
-  for (int k = k0; k < k1; k += 4) acc = UsM<T>::mma(fa(16 * ti + m, k + g), fb(k + g, 16 * tj + m), acc);
+  for (int k = k0; k < k1; k += 4) acc = Mfma16<T>::mma(fa(16 * ti + m, k + g), fb(k + g, 16 * tj + m), acc);
   return acc;
 }
 // Right-looking Cholesky of the leading n x n block of a tall matrix (R rows) held in registers, rows n .. R-1 riding along.
@@ -1034,7 +1022,7 @@ __device__ __forceinline__ void us_chol_tall(T (&x)[US_UMAX][SEG], const int n, 
     if (i_u[u] == j1) {
       T piv = v; bool skip = false;
       if (SEMIDEF) { skip = !(piv > told[u]); if (skip) atomicAdd(&sFlag[0], 1); }
-      else { if (!(piv > T(0))) sFlag[1] = 1; piv = piv > UsM<T>::clamp() ? piv : UsM<T>::clamp(); }
+      else { if (!(piv > T(0))) sFlag[1] = 1; piv = piv > us_clamp<T>() ? piv : us_clamp<T>(); }
       col[R] = skip ? T(0) : fast_rsqrt(piv);
     }
   };
@@ -1073,8 +1061,8 @@ __device__ __forceinline__ void us_chol_tall(T (&x)[US_UMAX][SEG], const int n, 
 
 template <class S, int US_SEG_B>
 __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_max) {
-  typedef typename UsM<S>::V VS;
-  typedef typename UsM<double>::V VD;
+  typedef typename Mfma16<S>::V VS;
+  typedef typename Mfma16<double>::V VD;
   const int b = b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   int* st = d.stats + (long)b * STAT_STRIDE;
@@ -1124,7 +1112,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
     double dgt[4];                                                    // the tile's block-diagonal terms: loads issued now, used at the end of the phase
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = 16 * ati + UsM<double>::row(lane, r), j = 16 * atj + (lane & 15);
+      const int i = 16 * ati + Mfma16<double>::row(lane, r), j = 16 * atj + (lane & 15);
       dgt[r] = (atile && i <= n && j <= i && !(i == n && j == n)) ? lam_diag_term(Dg, n, d.n_cap, i, j) : 0.0;
     }
     {
@@ -1156,7 +1144,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
         if (atile) {
           const int m = lane & 15, g = lane >> 4;
 #pragma unroll
-          for (int k = 0; k < 24; k += 4) lacc = UsM<double>::mma(sB[(k + g) * nb1 + 16 * ati + m], sB[(k + g) * nb1 + 16 * atj + m], lacc);
+          for (int k = 0; k < 24; k += 4) lacc = Mfma16<double>::mma(sB[(k + g) * nb1 + 16 * ati + m], sB[(k + g) * nb1 + 16 * atj + m], lacc);
         }
       }
     }
@@ -1164,7 +1152,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
     if (atile) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int i = 16 * ati + UsM<double>::row(lane, r), j = 16 * atj + (lane & 15);
+        const int i = 16 * ati + Mfma16<double>::row(lane, r), j = 16 * atj + (lane & 15);
         if (i <= n && j <= i) {
           const double v = dgt[r] - lacc[r];
           sL[i * LL + j] = v;
@@ -1205,7 +1193,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
                                   [&](int r, int c) -> S { return (r < D && c < n) ? sPT[c * Dp + r] : S(0); },
                                   [&](int c, int k) -> S { return (c < n && k < n) ? (S)sL[c * LL + k] : S(0); });
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int i = 16 * ti + UsM<S>::row(lane, r), k = 16 * tj + (lane & 15); if (i < D && k < n) sPH[i * LS + k] = acc[r]; }
+        for (int r = 0; r < 4; ++r) { const int i = 16 * ti + Mfma16<S>::row(lane, r), k = 16 * tj + (lane & 15); if (i < D && k < n) sPH[i * LS + k] = acc[r]; }
       }
     }
     __syncthreads();
@@ -1224,7 +1212,7 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
                                     [&](int c, int j) -> S { return (c < n && j < n) ? sPH[(15 + c) * LS + j] : S(0); });
           // (sS aliases the P staging block, which phase C has finished reading; this phase reads sL and sPH only)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) { const int i = 16 * ti + UsM<S>::row(lane, r), j = 16 * tj + (lane & 15); if (i < n && j <= i) sS[i * LS + j] = acc[r] + (i == j ? sig2 : S(0)); }
+          for (int r = 0; r < 4; ++r) { const int i = 16 * ti + Mfma16<S>::row(lane, r), j = 16 * tj + (lane & 15); if (i < n && j <= i) sS[i * LS + j] = acc[r] + (i == j ? sig2 : S(0)); }
         }
     }
     __syncthreads();
@@ -1277,13 +1265,13 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
         if ((t & 15) != w) continue;
         S pv[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { const int i = min(16 * ti + UsM<S>::row(lane, r), D - 1), j = min(16 * tj + (lane & 15), D - 1); pv[r] = Pr[(long)j * ld + i]; }
+        for (int r = 0; r < 4; ++r) { const int i = min(16 * ti + Mfma16<S>::row(lane, r), D - 1), j = min(16 * tj + (lane & 15), D - 1); pv[r] = Pr[(long)j * ld + i]; }
         const VS acc = us_tile<S>(ti, tj, 0, kend, lane,
                                   [&](int i, int k) -> S { return (i < D && k < n) ? sPH[i * LS + k] : S(0); },
                                   [&](int k, int j) -> S { return (j < D && k < n) ? sPH[j * LS + k] : S(0); });
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int i = 16 * ti + UsM<S>::row(lane, r), j = 16 * tj + (lane & 15);
+          const int i = 16 * ti + Mfma16<S>::row(lane, r), j = 16 * tj + (lane & 15);
           const bool keep = (i < 15 || i >= cut) && (j < 15 || j >= cut);
           if (i < D && j <= i && keep) {
             const int di = i < 15 ? i : i - 6 * nd_, dj = j < 15 ? j : j - 6 * nd_;

@@ -293,7 +293,6 @@ __global__ __launch_bounds__(64) void k_lit_pre(Dev<S> d, int b0, int nb, int it
 // k_lit_gamma: Gam = Du - sum_j (B_j^T D_j + D_j^T B_j) (lower triangle), one wavefront per 32 x 32 tile.  With the rows of a
 // track ordered [B ; D] on the left and [D ; B] on the right the sum is one product with six contraction rows per track;
 // two tracks fill three k = 4 steps of v_mfma_f64_16x16x4_f64.
-typedef double lg_v4d __attribute__((ext_vector_type(4)));
 template <class S>
 __global__ __launch_bounds__(64) void k_lit_gamma(Dev<S> d, int b0, int nb, int ntile) {
   int bi, tile;
@@ -313,11 +312,11 @@ __global__ __launch_bounds__(64) void k_lit_gamma(Dev<S> d, int b0, int nb, int 
   const int* order = d.trk_order + (long)b * f_cap;
   const int lr = lane & 15, lk = lane >> 4;
   const int ci0 = 32 * ti + lr, ci1 = ci0 + 16, cj0 = 32 * tj + lr, cj1 = cj0 + 16;
-  lg_v4d acc[2][2];
+  f64x4 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = lg_v4d{0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < 2; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
   const double* dummy = L.Du;                                // an always-valid word for the lanes whose column a track does not have
   // the sorted track list and the tracks' slot ranges, 64 per register (four registers: up to 256 stacked tracks are served by
   // v_readlane; a pair's operands then depend on nothing but registers -- two levels of dependent loads per pair otherwise).

@@ -32,6 +32,7 @@ __device__ int g_qr_dbg[4] = {0, 0, 0, 0};   // ablation knobs of the -DMSCKF_AB
 // Reflector scalars: beta = sqrt(s), g = 1/(beta*u).  Double: IEEE sqrt / divide.  Float: hardware rsq / rcp
 // (~1 ulp) refined by one Newton step each -- within 1 ulp of the correctly rounded values at a third of the
 // instructions of the IEEE expansions, which sit on the per-step critical path of the elimination.
+// (not fast_rcp / fast_rsqrt of dev_common.h: another Newton form in float, IEEE in double -- other bits, other names)
 template <class S> __device__ __forceinline__ S qr_rcp(S x) { return S(1) / x; }
 template <> __device__ __forceinline__ float qr_rcp<float>(float x) {
   const float g0 = __builtin_amdgcn_rcpf(x);

@@ -36,7 +36,6 @@ __device__ __forceinline__ void mm15_abt(S* C, const S* A, const S* B, int lane)
     C[e] = s;
   }
 }
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
 
 constexpr int PG = 16;      // IMU samples per group
 constexpr int SST = 20;     // LDS stride of one IMU state: q(4) b_g(3) v(3) b_a(3) p(3) dT(1) pad
@@ -158,21 +157,6 @@ __global__ __launch_bounds__(256) void k_augment(Dev<S> d, int b0) {
   augment_body<S>(d, b, tid, reinterpret_cast<S*>(smem_raw));
 }
 
-// 16x16x4 MFMA of the scalar type, with the row a lane group's accumulator register r belongs to
-typedef double pd4 __attribute__((ext_vector_type(4)));
-typedef float pf4 __attribute__((ext_vector_type(4)));
-template <class T> struct Mfs;
-template <> struct Mfs<double> {   // v_mfma_f64_16x16x4_f64: C/D row = g + 4 r
-  typedef pd4 V;
-  static __device__ __forceinline__ V mma(double a, double b, V c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int crow(int g, int r) { return g + 4 * r; }
-};
-template <> struct Mfs<float> {    // v_mfma_f32_16x16x4_f32: C/D row = 4 g + r
-  typedef pf4 V;
-  static __device__ __forceinline__ V mma(float a, float b, V c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-  static __device__ __forceinline__ int crow(int g, int r) { return 4 * g + r; }
-};
-
 template <class S, bool AUGMENT, int QM>
 __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
     for (int t = 0; t < PIC_T; ++t) {
       const int col = (w + 4 * t) * 16 + c;
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) { const int k = Mfs<S>::crow(g, kk); pic[t][kk] = P[(long)(15 + min(col, d.n6cap - 1)) * ld + min(k, 14)]; }   // unconditional (masked where used): no wait for the window size in front of the kernel's first loads
+      for (int kk = 0; kk < 4; ++kk) { const int k = Mfma16<S>::row_of_group(g, kk); pic[t][kk] = P[(long)(15 + min(col, d.n6cap - 1)) * ld + min(k, 14)]; }   // unconditional (masked where used): no wait for the window size in front of the kernel's first loads
     }
   }
   if (tid < 16) sState[tid] = imu[tid];                 // q b_g v b_a p
@@ -235,12 +219,12 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
   for (int e = tid; e < min(PG, K) * RD_STRIDE; e += 256) sRd[e] = rd[e];   // the first group's IMU samples ride on the same round trip
   __syncthreads();
   // chain matrices in MFMA accumulator layout (phase C): wave 0 P_II, wave 1 Phi_total
-  typename Mfs<S>::V Mreg = {0, 0, 0, 0};
+  typename Mfma16<S>::V Mreg = {0, 0, 0, 0};
   {
     const int g = lane >> 4, c = lane & 15;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int i = Mfs<S>::crow(g, r);
+      const int i = Mfma16<S>::row_of_group(g, r);
       if (i < 15 && c < 15) Mreg[r] = w == 0 ? sPii[i * 15 + c] : (i == c ? S(1) : S(0));
     }
   }
@@ -443,23 +427,23 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
     PR_TICK(2);
     // ---- C: sequential chains over the group on the matrix cores, in registers.  Wave 0 carries P_II <- sym(Phi (P_II +
     // G Q G^T dT) Phi^T) (:134,143), wave 1 carries Phi_total <- Phi Phi_total; both hold their 16 x 16 (zero-padded) matrix
-    // in the accumulator layout of the 16x16x4 MFMA, lane (g, c) register r = M[crow(g, r)][c].  Taking the k-slot of MFMA kk,
-    // lane group g, to mean k = crow(g, kk), that same register file IS the B operand of M (B[k][c]) and the A operand of M^T
-    // (A[c][k]), and one set of four values per lane, aPhi[kk] = Phi[c][crow(g, kk)], is both the A operand of Phi and the B
+    // in the accumulator layout of the 16x16x4 MFMA, lane (g, c) register r = M[row_of_group(g, r)][c].  Taking the k-slot of MFMA kk,
+    // lane group g, to mean k = row_of_group(g, kk), that same register file IS the B operand of M (B[k][c]) and the A operand of M^T
+    // (A[c][k]), and one set of four values per lane, aPhi[kk] = Phi[c][row_of_group(g, kk)], is both the A operand of Phi and the B
     // operand of Phi^T.  So with P symmetric:  Y = P Phi^T = mma(A = P regs, B = aPhi),  Phi Y = mma(A = aPhi, B = Y regs),
     // (Phi Y)^T = Y^T Phi^T = mma(A = Y regs, B = aPhi) -- the transpose comes out of the matrix core with the same products
     // summed in the same order, so the symmetrisation of :143 is a register add and both halves get the same bits.  No
     // barrier and no LDS traffic inside the chain besides the four reads of Phi and the process-noise term (table sQt,
     // filled by waves 1-3 during phase B; QT entries per sample).
     {
-      typedef Mfs<S> MF;
+      typedef Mfma16<S> MF;
       const int g = lane >> 4, c = lane & 15;
       if (w < 2) {
         const S* qt = sQt;
         int qidx[4];   // where this lane's four elements find their process-noise term in a sample's table
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int i = MF::crow(g, r), bi = i / 3;
+          const int i = MF::row_of_group(g, r), bi = i / 3;
           if (FULLQ) qidx[r] = (i < 12 && c < 12) ? i * 12 + c : 144;
           else qidx[r] = (bi != c / 3 || bi >= 4) ? 31 : (bi == 2 ? 15 + (i - 6) * 3 + (c - 6) : (i == c ? i : 31));
         }
@@ -471,7 +455,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
           const S* Ph = sPhi + s * 225;
           S aPhi[4];
 #pragma unroll
-          for (int kk = 0; kk < 4; ++kk) { const int k = MF::crow(g, kk); aPhi[kk] = (k < 15 && c < 15) ? Ph[c * 15 + k] : S(0); }
+          for (int kk = 0; kk < 4; ++kk) { const int k = MF::row_of_group(g, kk); aPhi[kk] = (k < 15 && c < 15) ? Ph[c * 15 + k] : S(0); }
           typename MF::V zero = {0, 0, 0, 0};
           if (w == 0) {
             typename MF::V Y = zero, Pn = zero, Pt = zero;
@@ -501,7 +485,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
     const int g = lane >> 4, c = lane & 15;
     S* dst = w == 0 ? sPii : sTot;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int i = Mfs<S>::crow(g, r); if (i < 15 && c < 15) dst[i * 15 + c] = Mreg[r]; }
+    for (int r = 0; r < 4; ++r) { const int i = Mfma16<S>::row_of_group(g, r); if (i < 15 && c < 15) dst[i * 15 + c] = Mreg[r]; }
   }
   __syncthreads();
   // ---- write back: state, nulls (re-anchored to the final state), P_II, P_IC
@@ -515,18 +499,18 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
     const int g = lane >> 4, c = lane & 15;
     S aT[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) { const int k = Mfs<S>::crow(g, kk); aT[kk] = (k < 15 && c < 15) ? sTot[c * 15 + k] : S(0); }
+    for (int kk = 0; kk < 4; ++kk) { const int k = Mfma16<S>::row_of_group(g, kk); aT[kk] = (k < 15 && c < 15) ? sTot[c * 15 + k] : S(0); }
 #pragma unroll
     for (int t = 0; t < PIC_T; ++t) {
       const int col = (w + 4 * t) * 16 + c;
       if ((w + 4 * t) * 16 >= n) break;
-      typename Mfs<S>::V o = {0, 0, 0, 0};
+      typename Mfma16<S>::V o = {0, 0, 0, 0};
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) o = Mfs<S>::mma(aT[kk], (col < n && Mfs<S>::crow(g, kk) < 15) ? pic[t][kk] : S(0), o);
+      for (int kk = 0; kk < 4; ++kk) o = Mfma16<S>::mma(aT[kk], (col < n && Mfma16<S>::row_of_group(g, kk) < 15) ? pic[t][kk] : S(0), o);
       if (col < n) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int i = Mfs<S>::crow(g, r);
+          const int i = Mfma16<S>::row_of_group(g, r);
           if (i < 15) { P[(long)(15 + col) * ld + i] = o[r]; P[(long)i * ld + 15 + col] = o[r]; }
         }
       }

@@ -149,9 +149,7 @@ template <class F> LIT_FN void rowlane_for(const Ctx& c, long lo, long hi, F f) 
 template <class F> LIT_FN double row_sum_range(const Ctx& c, long lo, long hi, F f) {
   double s = 0;
   for (long i = lo + (c.lane & 15); i < hi; i += 16) s += f(i);
-  // the four DPP steps inside a row of 16 lanes: every lane of the row ends up with the row's sum (dev_common.h: wave_sum's first half)
-  s += dpp_x<DPP_QUAD_X1>(s); s += dpp_x<DPP_QUAD_X2>(s); s += dpp_x<DPP_HALF_MIRROR>(s); s += dpp_x<DPP_ROW_MIRROR>(s);
-  return s;
+  return row16_sum(s);   // every lane of the row gets the row's sum
 }
 LIT_FN bool first_rowlane(const Ctx& c) { return (c.lane & 15) == 0; }
 template <class FU, class FS> LIT_FN void rowlane_update(const Ctx& c, long lo, long hi, FU upd, FS st) {
@@ -212,20 +210,19 @@ template <int TS, class ST> LIT_FN void syrk_lower_ts(const Ctx& c, const double
 // rows is staged [row][column] (zero beyond the matrix, row stride 208: rows k and k + 1 half the banks apart) and every MFMA
 // takes its two operands straight from there.  The tile version is bound by its LDS reads (ten 8-byte reads per 25 FMAs and
 // thread: 2.3 ms for the 3 200 x 180 H_u of a 30-camera window); an MFMA reads two operands per 1 024 FMAs.
-typedef double lit_v4d __attribute__((ext_vector_type(4)));
 template <class ST> LIT_FN void syrk_lower_mfma(const Ctx& c, const double* G, long ldg, int nr, int mobs, ST st) {
   constexpr int LDL = 208, MAXB = 5;
   const int nbk = (nr + 15) / 16, nblk = nbk * (nbk + 1) / 2;
   const int rows = (c.lds_doubles / LDL) & ~3;                 // rows of G per chunk (a multiple of the MFMA's k = 4)
   int bi[MAXB], bj[MAXB];
-  lit_v4d acc[MAXB];
+  f64x4 acc[MAXB];
 #pragma unroll
   for (int q = 0; q < MAXB; ++q) {
     const int e = c.wave + c.nw * q;
     int ti = 0, tj = 0;
     if (e < nblk) { ti = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5); while (ti * (ti + 1) / 2 > e) --ti; while ((ti + 1) * (ti + 2) / 2 <= e) ++ti; tj = e - ti * (ti + 1) / 2; }
     bi[q] = ti; bj[q] = tj;
-    acc[q] = lit_v4d{0.0, 0.0, 0.0, 0.0};
+    acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
   }
   const int lr = c.lane & 15, lk = c.lane >> 4;
   for (int o0 = 0; o0 < mobs; o0 += rows) {
@@ -283,8 +280,7 @@ template <class FV, class FS> LIT_FN void par_map4(const Ctx& c, int n, FV val, 
   for (int i = c.tid; i < n; i += c.nt) st(i, val(i));
 }
 LIT_FN bool first_wave(const Ctx& c) { return c.wave == 0; }
-// LDS hand-over between the lanes of one wavefront: the fences keep the compiler from moving reads above writes
-LIT_FN void wave_sync(const Ctx&) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+LIT_FN void wave_sync(const Ctx&) { wave_lds_sync(); }   // dev_common.h
 // GLOBAL-memory hand-over between the lanes of one wavefront (a lane reads what another lane of its wavefront stored): the
 // stores are released to the device's coherence point and the loads that follow do not come out of a stale first-level line
 LIT_FN void wave_mem_sync(const Ctx&) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
@@ -608,7 +604,7 @@ LIT_FN void information_from_rn(const Ctx& c, const Args<HT>& a, int n, int nr, 
           double old[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) { const int jj = 16 * bj + lk + 4 * r; old[r] = (ii < mt && jj <= ii) ? Z[(j0 + ii) + ldz * (j0 + jj)] : 0.0; }
-          lit_v4d acc = lit_v4d{0.0, 0.0, 0.0, 0.0};
+          f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) {
             const int q = 4 * kk + lk;
@@ -1498,7 +1494,7 @@ LIT_FN SweepOut sweep_gram_blocked(const Ctx& c, const Args<HT>& a, int e, int n
           const double* pa = isE ? sEP + 16 * bj + lr : sGP + 16 * bj + lr;           // A: the result's column index (the step's s / R entries)
           const double* pb_ = isE ? sEC + pb + ii : sGP + ii;                       // B: the result's row index
           const long sa = n1, sb = isE ? lde : (long)n1;
-          lit_v4d acc = lit_v4d{0.0, 0.0, 0.0, 0.0};
+          f64x4 acc = f64x4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) { const int q = 4 * kk + lk; acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[sa * q], pb_[sb * q], acc, 0, 0, 0); }
 #pragma unroll

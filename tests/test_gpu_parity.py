@@ -453,6 +453,56 @@ def test_square_root_gain_form_equals_joseph_form(capi, prec, N, F):
     assert H.worst(e2) < (tol64 if prec == "f64" else 1e-3), e2
 
 
+@pytest.mark.parametrize("N", [5, 11])
+def test_register_resident_gain_kernels_with_a_partial_last_block(capi, po, N):
+    """k_gain (set_covariance_update(1), the Joseph sequence) and k_gain_w (2, the register-resident square-root solve) keep S in
+    registers as 16 x 16 blocks.  n = 6 N = 30 is two column blocks, the second partial (k_gain<., 4>, k_gain_w<., 4, 8>); n = 66
+    is five, the last with two columns (the NBN = 8 instantiations); the window grows by six columns a frame, so on the way
+    there every block boundary up to 64 is crossed with a partial block behind it.  Two trajectories in one launch, 12 tracks, 12 frames, against the oracle of the same scalar
+    type after every step: double free-running at 1e-6, float teacher-forced at 1e-3 (the tolerances of the stage-wise tests
+    above); the state carries dx, the covariance the downdate.  The sticky error flags stay clear."""
+    F, nf, B = 12, 12, 2
+    trs = [sc.Trajectory(2, 40 + b, N, F, nf) for b in range(B)]
+    for prec in ("f64", "f32"):
+        cd, od = _dt(capi, po, prec)
+        for form in (1, 2):
+            bt = capi.Batch(B, N, F, max(N, 4), cd)
+            bt.set_covariance_update(form)
+            orc = []
+            for b, tr in enumerate(trs):
+                orc.append(po.Oracle(od, po.LEAN)); orc[b].initialize(tr.cfg, tr.imu0)
+                bt.initialize(b, tr.cfg, tr.imu0)
+            rows = 0
+            for k in range(nf):
+                for b, tr in enumerate(trs):
+                    if prec == "f32" and k:
+                        H.copy_oracle_to_device(orc[b], bt, b)
+                    bt.propagate_range(b, 1, tr.imu_for_frame(k))
+                bt.augment_range(0, B)
+                for b, tr in enumerate(trs):
+                    fr = tr.frames[k]
+                    bt.set_tracks(b, fr["M"], fr["slots"], fr["obs"])
+                if any(len(tr.frames[k]["M"]) for tr in trs):
+                    bt.marginalize_range(0, B)
+                for b, (tr, o) in enumerate(zip(trs, orc)):
+                    fr = tr.frames[k]
+                    o.propagate(tr.imu_for_frame(k)); o.augmentState(k, 0.0)
+                    if len(fr["M"]):
+                        o.setTracks(fr["M"], fr["slots"], fr["obs"]); o.marginalize()
+                        so, sd = o.lastStats(), bt.last_stats(b)        # (raises when a sticky flag is up)
+                        assert so["m_rows"] == sd["m_rows"] and so["n_passed"] == sd["n_passed"], (prec, form, k, b, so, sd)
+                        rows += sd["m_rows"]
+                    e = _errs(bt, b, o)
+                    assert H.worst(e) < TOL[prec], (prec, form, k, b, e)
+                    assert bt.error_flags(b) == 0, (prec, form, k, b)
+                if orc[0].getNumCamStates() == N:
+                    for o in orc:
+                        o.dropOldest(1)
+                    bt.drop_oldest_range(0, B, 1)
+            assert rows > 0 and bt.num_cam_states(0) == N - 1, (prec, form, rows)
+            bt.close()
+
+
 def test_resident_scenario_equals_per_call(capi):
     N, F, nf, B = 8, 16, 13, 3
     trs = [sc.Trajectory(2, 60 + b, N, F, nf) for b in range(B)]
