@@ -72,8 +72,12 @@ enum { MSCKF_HIP_F32 = 0, MSCKF_HIP_F64 = 1, MSCKF_HIP_F16H_F32P = 2 };
 int msckf_hip_create(int B, int n_cap, int f_cap, int m_cap, int dtype, int device, msckf_hip_handle* out);
 int msckf_hip_destroy(msckf_hip_handle h);
 /* Value semantics of the reference object (MSCKF<_S> is copyable, msckf.h:31-67): dst <- the filter state of every trajectory
- * of src (states, parameters, covariance, counters, flags, host-side track bookkeeping, mode switches).  Both handles must
- * have been created with the same B, capacities and dtype; work buffers and a resident scenario are not copied. */
+ * of src (states, parameters, covariance, counters, flags, host-side track bookkeeping) and every setting of src that decides
+ * numerics or which kernels run, whether a setter or the environment at src's creation chose it ("Settings":
+ * the column "copy"): dst continues bit for bit as src would.  The staging ring, host affinity and test hooks stay dst's own.
+ * Both handles must have been created with the same B, capacities and dtype (-EINVAL otherwise; also when src runs the
+ * anisotropic sweep over the dense stack, MSCKF_HIP_LITERAL_ROUTE=1, and dst's literal work space was allocated without that
+ * stack); work buffers and a resident scenario are not copied. */
 int msckf_hip_copy_state(msckf_hip_handle dst, msckf_hip_handle src);
 const char* msckf_hip_last_error(void);
 

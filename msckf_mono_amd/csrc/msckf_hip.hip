@@ -34,10 +34,12 @@
 #include "../../include/msckf_hip.h"
 #include "dev_common.h"
 #include "host_lists.h"
+#include "settings.h"
 
 namespace {
 using namespace msckf;
 using namespace msckf_lists;
+using msckf_settings::Settings;
 static_assert(TRK_MOTION_OK == ST_MOTION_OK && TRK_TRI_VALID == ST_TRI_VALID && TRK_MOTION_SKIPPED == ST_MOTION_SKIPPED, "host_lists.h reads the feature kernel's status bits");
 
 // rocTX ranges under the reference's stage names (asl_msckf.cpp:229-296: imu_prop, msckf_augment_state, msckf_update,
@@ -155,24 +157,10 @@ struct BatchCore {
   // slot its work-list touches: run_frames overlaps k_feature with propagate + augment when no track sees the newest camera
   std::vector<int> h_ncam, h_maxslot;
   hipStream_t sty[MAXS] = {nullptr}; hipEvent_t ev_fa[MAXS] = {nullptr}, ev_fb[MAXS] = {nullptr};
-  // the settings a copy of the handle takes over (copy_from assigns the group; the knobs inside Dev<S> and the anisotropic-noise
-  // mode travel with the typed half).  What follows the group stays with its own handle.
-  struct Knobs {
-    int nstreams = 1;
-    int fuse_prune = 1;        // run_frames: prune rides on the downdate (MSCKF_HIP_FUSE_PRUNE=0: separate k_prune_inplace launch)
-    int overlap_feature = 0;   // measured on MI355X at cfg3: 100 k -> 82 k updates/s with the overlap on (k_feature floods the CUs the
-                               // latency-bound propagate/augment workgroups need); kept selectable, off by default
-    int compress_route = -1;   // -1 default, 0 Householder TSQR, != 0 information form + blocked matrix-core Cholesky
-  } knobs;
-  int small_update = 84;     // windows of at most this many camera columns (6 x cameras) take the one-launch update k_update_small; MSCKF_HIP_SMALL_UPDATE=0 switches it off
-  int gain_parts = 0;        // MSCKF_HIP_GAIN_PARTS: workgroups per trajectory of the float blocked gain solve (2 | 4), 0: by the batch size (Dev::gain_parts)
-  int small_limit = 0;       // ... as far as they fit the kernel at this handle's dtype and f_cap (the typed half's alloc): the per-trajectory limit launch_update routes by
-  int test_fail_upload = -1;  // test hook (MSCKF_HIP_TEST_FAIL_UPLOAD): run_frames_streamed pretends that this frame's copy failed
-  // anisotropic pixel noise (u_var' != v_var'): 0 = the reference's construction R_o_j = A_j^T R_j A_j, R_n = Q_1^T R_o Q_1 on
-  // the device (kernels_literal.hip; default), 1 = rows pre-whitened by 1/sigma (generalized least squares, unit noise)
-  int aniso_mode = 0;
-  int lit_route = 0;         // 0 the compact route; 1 the sweep over the dense stack (tests, A/B)
-  double lit_tol = -1;       // zero-tail tolerance of the literal route; < 0: 1e-10 (double) / 8e-4 (float: H_x is float-rounded)
+  // every tunable of the handle (settings.h: defaults, environment variables, what a copy takes over); the typed half's
+  // apply_settings() carries them into the kernel argument
+  Settings settings;
+  int small_limit = 0;       // settings.small_update as far as it fits k_update_small at this handle's dtype and f_cap (apply_settings): the per-trajectory limit launch_update routes by
   bool info_form = false;    // the information form's buffers exist (Dev::trk_B; set by the typed half's create)
   std::vector<double> h_uv;  // [B][2] u_var', v_var' as initialize() got them
   std::vector<char> h_imu_ok;   // [B] the typed half's host copy of the IMU state is current (see Batch<S>::h_imu)
@@ -209,7 +197,6 @@ struct BatchCore {
   // Page-locked blocks are built on demand (scen_pin, or the first streamed run over a frame), only for frames that are
   // streamed: a run_frames-only user never pays for them.
   static constexpr int RING_MAX = 8;
-  int ring = 6, up_mode = 0;   // up_mode 0: the host threads hand frames over (no device-side cross-stream wait); 1: hipStreamWaitEvent
   hipStream_t stc = nullptr; hipEvent_t ev_up[RING_MAX] = {nullptr}; hipEvent_t ev_use[RING_MAX][MAXS] = {{nullptr}};
   unsigned char* sg_blk[RING_MAX] = {nullptr}; size_t sg_bytes = 0;
   struct PinFrame { unsigned char* p = nullptr; size_t bytes = 0, off_obs = 0; int chunk = -1; };
@@ -250,12 +237,9 @@ struct BatchCore {
     *p = (T*)q;
     return 0;
   }
-  // the device's tables, streams and events, host mirrors, the knobs the environment sets; then the typed half's buffers
+  // the settings the environment gives, the device's tables, streams and events, host mirrors; then the typed half's buffers
   int create() {
-    if (const char* e = getenv("MSCKF_HIP_GAIN_PARTS")) {
-      gain_parts = atoi(e);
-      if (gain_parts != 0 && gain_parts != 2 && gain_parts != 4) return fail(-EINVAL, "MSCKF_HIP_GAIN_PARTS must be 0, 2 or 4");
-    }
+    { std::string err; if (!msckf_settings::settings_from_env(settings, err)) return fail(-EINVAL, err); }
     HIPCHK(hipSetDevice(device));
     feature_device_setup(); qr_device_setup(); kalman_device_setup(); gram_device_setup(); literal_device_setup();   // per device: constant tables, dynamic-LDS limits
     HIPCHK(hipGetLastError());
@@ -271,10 +255,6 @@ struct BatchCore {
     }
     h_ncam.assign(B, 0); h_uv.assign((size_t)2 * B, 0.0); h_lit.assign(B, 0); h_qfull.assign(B, 0); h_imu_ok.assign(B, 0);
     traj.assign(B, HostTraj());
-    if (const char* e = getenv("MSCKF_HIP_FUSE_PRUNE")) knobs.fuse_prune = atoi(e) != 0;
-    if (const char* e = getenv("MSCKF_HIP_TEST_FAIL_UPLOAD")) test_fail_upload = atoi(e);   // test hook: the upload of this frame fails
-    if (const char* e = getenv("MSCKF_HIP_LITERAL_ROUTE")) lit_route = atoi(e);   // A/B runs and tests: 1 = the sweep over the dense stack
-    if (const char* e = getenv("MSCKF_HIP_SMALL_UPDATE")) small_update = atoi(e);
     return alloc();
   }
   virtual ~BatchCore() {
@@ -622,8 +602,8 @@ struct BatchCore {
   }
   int set_upload_ring(int depth, int mode) {
     if (depth < 2 || depth > RING_MAX || mode < 0 || mode > 1) return fail(-EINVAL, "ring depth 2..8; mode 0 host hand-over, 1 device-side event waits");
-    ring = depth; up_mode = mode;
-    return 0;
+    settings.ring = depth;
+    return store(&Settings::up_mode, mode);
   }
   // ---- the frame loop of a scenario (run_frames, run_frames_streamed)
   // Trajectories are independent, so the batch may be cut into slices that run the same kernel sequence on separate streams:
@@ -631,7 +611,7 @@ struct BatchCore {
   // chip-filling stages of the others.  One host thread per slice enqueues that slice's kernels for all frames of the call
   // (~13 launches per frame and slice would otherwise serialise on one thread and make more than two slices launch-bound).
   // Stage profiling forces a single stream.
-  int n_slices() const { return prof ? 1 : std::max(1, std::min(knobs.nstreams, B)); }
+  int n_slices() const { return prof ? 1 : std::max(1, std::min(settings.nstreams, B)); }
   // slice hh of nh on its enqueue thread: trajectories [b0, b0 + nb) on stream q.  A frame whose prune rides on the downdate
   // leaves the covariance in the other buffer (flipped: the slice's current one is the handle's spare) and the new window size
   // for the next k_propagate to commit (pending)
@@ -741,7 +721,7 @@ struct BatchCore {
       }
     }
     const int nh = n_slices();
-    const int R = ring, mode = up_mode;
+    const int R = settings.ring, mode = settings.up_mode;
     const int rc = fork_slices(nh, stc);
     if (rc) return rc;
     // up_rdy = frames whose block may be read (mode 0: the copy has completed; mode 1: copy + event record are enqueued --
@@ -780,7 +760,7 @@ struct BatchCore {
           const hipError_t e = mode == 0 ? hipEventSynchronize(ev_use[k][i]) : hipStreamWaitEvent(stc, ev_use[k][i], 0);
           if (e != hipSuccess) rc_up = -EIO;
         }
-      if (!rc_up && (f == test_fail_upload || hipMemcpyAsync(sg_blk[k], pinf[f].p, pinf[f].bytes, hipMemcpyHostToDevice, stc) != hipSuccess)) rc_up = -EIO;
+      if (!rc_up && (f == settings.test_fail_upload || hipMemcpyAsync(sg_blk[k], pinf[f].p, pinf[f].bytes, hipMemcpyHostToDevice, stc) != hipSuccess)) rc_up = -EIO;
       if (!rc_up && (mode == 0 ? hipStreamSynchronize(stc) : hipEventRecord(ev_up[k], stc)) != hipSuccess) rc_up = -EIO;
       if (rc_up) failed.store(1);
       up_rdy.store(f + 1, std::memory_order_release);
@@ -795,12 +775,18 @@ struct BatchCore {
     HIPCHK(hipStreamSynchronize(st));
     return 0;
   }
-  int set_feature_overlap(int on) { knobs.overlap_feature = on ? 1 : 0; return 0; }
+  // the setters of the C interface: validate, store, apply
+  int store(int Settings::* field, int v) { settings.*field = v; apply_settings(); return 0; }
+  int set_feature_overlap(int on) { return store(&Settings::overlap_feature, on ? 1 : 0); }
   int set_compression(int route) {
     if (route < -1 || route > 3) return fail(-EINVAL, "route: -1 default, 0 Householder TSQR, 1..3 information form (blocked matrix-core Cholesky; 1 and 2 named retired factorizations)");
     if (route >= 1 && !info_form) return fail(-ENOTSUP, "information form not available for this window size (6 n_cap + 1 > 384 or f_cap > 1024)");
-    knobs.compress_route = route;
-    return 0;
+    return store(&Settings::compress_route, route);
+  }
+  int set_gate_early(int on) { return store(&Settings::gate_early, on ? 1 : 0); }
+  int set_cov_update(int form) {
+    if (form < 0 || form > 2) return fail(-EINVAL, "form: 0 square-root gain (P - W W^T), 1 Joseph, 2 square-root gain with the register-resident solve");
+    return store(&Settings::cov_update, form);
   }
   int set_host_affinity(const int* cpus, int n) {
     std::lock_guard<std::mutex> lk(workers.m);
@@ -809,8 +795,7 @@ struct BatchCore {
   }
   int set_streams(int n) {
     if (n < 1 || n > MAXS) return fail(-EINVAL, "1 to 8 streams");
-    knobs.nstreams = n;
-    return 0;
+    return store(&Settings::nstreams, n);
   }
   int prof_enable(int on) {
     prof = on != 0;
@@ -881,8 +866,7 @@ struct BatchCore {
   // `staged` of the upload ring, or (staged < 0) resident
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
   virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
-  virtual int set_gate_early(int on) = 0;
-  virtual int set_cov_update(int form) = 0;
+  virtual void apply_settings() = 0;   // the one place where `settings` reaches the kernel argument
   virtual int set_aniso(int mode, double tol) = 0;
   virtual int copy_from(BatchCore* src) = 0;
   virtual int lit_info(int b, int* out8) = 0;
@@ -949,13 +933,10 @@ struct Batch : BatchCore {
     rc |= dalloc(&d.PHt, Bz * dn); rc |= dalloc(&d.Smat, Bz * nl); rc |= dalloc(&d.Linv, Bz * nl); rc |= dalloc(&d.W, Bz * dn);
     rc |= dalloc(&d.K, Bz * dn); rc |= dalloc(&d.A, Bz * pl); rc |= dalloc(&d.AP, Bz * pl); rc |= dalloc(&d.X, Bz * pl); rc |= dalloc(&d.dx, Bz * d.ld);
     rc |= dalloc(&d.keep, Bz * n_cap); rc |= dalloc(&d.nkeep, Bz); rc |= dalloc(&d.ncam_upd, Bz); rc |= dalloc(&d.nres_upd, Bz);
-    rc |= dalloc(&d_pfin, TF * 4); d.trk_pfin = d_pfin; d.mode = 0; d.joseph = 0; d.ncam_bias = 0;
-    { const char* e = getenv("MSCKF_HIP_FUSED_S"); d.gain_fused_s = e ? atoi(e) : 2; }
-    { const char* e = getenv("MSCKF_HIP_FEATURE_PAIR"); d.feat_pair = e ? atoi(e) : 1; }
-    d.gain_parts = gain_parts;
+    rc |= dalloc(&d_pfin, TF * 4); d.trk_pfin = d_pfin; d.mode = 0; d.ncam_bias = 0;
     d.small_split = 0;
-    for (int n = small_update / 6 * 6; n >= 6 && !small_limit; n -= 6) if (update_small_fits(n, f_cap, sizeof(S))) small_limit = n;
-    rc |= dalloc(&d.gain_bar, Bz * 32);   // 0: the S GEMM as a launch of its own (A/B runs)
+    apply_settings();
+    rc |= dalloc(&d.gain_bar, Bz * 32);
     rd_cap = 64;
     rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE);
     HIPCHK(hipHostMalloc(&h_rb, ((size_t)n_cap * CAM_STRIDE + IMU_STRIDE) * sizeof(S), hipHostMallocDefault));
@@ -967,6 +948,14 @@ struct Batch : BatchCore {
     if (feature_lds_bytes(m_cap, sizeof(S)) > 160 * 1024) return fail(-EINVAL, "m_cap too large for the feature kernel's LDS budget");
     HIPCHK(hipStreamSynchronize(st));
     return 0;
+  }
+  void apply_settings() override {
+    const Settings& s = settings;
+    d.joseph = s.cov_update; d.gate_early = s.gate_early; d.gain_fused_s = s.fused_s; d.feat_pair = s.feat_pair; d.gain_parts = s.gain_parts;
+    d.lit.serial = s.lit_serial; d.lit.route = s.lit_route;
+    d.lit.tol = s.lit_tol >= 0 ? s.lit_tol : (sizeof(S) == 4 ? 8e-4 : 1e-10);
+    small_limit = 0;
+    for (int n = s.small_update / 6 * 6; n >= 6 && !small_limit; n -= 6) if (update_small_fits(n, f_cap, sizeof(S))) small_limit = n;
   }
   void use_single_worklists() {
     d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
@@ -1004,7 +993,7 @@ struct Batch : BatchCore {
     const bool was = h_lit[b] != 0;
     bool lit = false;
     if (u == v) { out5[0] = 1; out5[1] = 1; out5[2] = (S)u; out5[3] = (S)u; out5[4] = 0; }
-    else if (aniso_mode == 0 && !h16 && d.trk_B) { out5[0] = 1; out5[1] = 1; out5[2] = 1; out5[3] = (S)u; out5[4] = 1; lit = true; }
+    else if (settings.aniso_mode == 0 && !h16 && d.trk_B) { out5[0] = 1; out5[1] = 1; out5[2] = 1; out5[3] = (S)u; out5[4] = 1; lit = true; }
     else { out5[0] = (S)(1.0 / std::sqrt(u)); out5[1] = (S)(1.0 / std::sqrt(v)); out5[2] = 1; out5[3] = 1; out5[4] = 0; }
     if (lit && !d.lit.W2) { const int rc = lit_alloc(); if (rc) return rc; }
     if (lit != was) { n_lit += lit ? 1 : -1; h_lit[b] = lit ? 1 : 0; }
@@ -1018,8 +1007,6 @@ struct Batch : BatchCore {
     const size_t Bz = B, n1 = (size_t)d.n6cap + 1;
     L.ldx = ((f_cap * std::max(2 * m_cap - 3, 1) + 7) / 8) * 8;
     L.r_cap = d.n6cap + 15; L.ldg = f_cap * m_cap + 8; L.ldz = L.r_cap + (int)n1; L.kept_stride = 6 * (d.n6cap + 16) + 64;
-    L.tol = lit_tol >= 0 ? lit_tol : (sizeof(S) == 4 ? 8e-4 : 1e-10);
-    L.route = lit_route;
     int rc = 0;
     rc |= dalloc(&L.tau, Bz * (2 * n1 + 2));
     rc |= dalloc(&L.Vf, Bz * f_cap * 2 * m_cap * 3); rc |= dalloc(&L.Tf, Bz * f_cap * 9);
@@ -1028,20 +1015,18 @@ struct Batch : BatchCore {
     L.w2_stride = lit_ws_doubles(d.n6cap, m_cap, L.r_cap);
     rc |= dalloc(&L.W2, Bz * (size_t)L.w2_stride);
     // the sweep over the dense stack (MSCKF_HIP_LITERAL_ROUTE=1: tests, A/B runs) needs the stack itself and the u-rows of A Q_1
-    if (lit_route == 1) { rc |= dalloc(&L.X, Bz * L.ldx * n1); rc |= dalloc(&L.G, Bz * (size_t)L.ldg * L.r_cap); }
+    if (settings.lit_route == 1) { rc |= dalloc(&L.X, Bz * L.ldx * n1); rc |= dalloc(&L.G, Bz * (size_t)L.ldg * L.r_cap); }
     rc |= dalloc(&L.info, Bz * 8);
     rc |= dalloc(&L.BD, Bz * f_cap * 6 * (size_t)d.ldR); rc |= dalloc(&L.Gam, Bz * (size_t)d.ldR * d.ldR); rc |= dalloc(&L.Du, Bz * n_cap * 24);
-    if (const char* e = getenv("MSCKF_HIP_LITERAL_SERIAL")) L.serial = atoi(e);
-    if (const char* e = getenv("MSCKF_HIP_LITERAL_TIMERS")) if (atoi(e)) rc |= dalloc(&L.tim, Bz * LIT_TIM_SLOTS);
+    if (settings.lit_timers) rc |= dalloc(&L.tim, Bz * LIT_TIM_SLOTS);
     if (rc) { L.W2 = nullptr; return fail(-ENOMEM, "work space of the literal anisotropic route (msckf_hip_set_anisotropic_noise(h, 1, 0) selects pre-whitening)"); }
     return 0;
   }
   int set_aniso(int mode, double tol) override {
     if (mode < 0 || mode > 1) return fail(-EINVAL, "mode: 0 the reference's R_n = Q_1^T R_o Q_1 on the device, 1 pre-whitened rows");
     if (int rc = enter()) return rc;
-    aniso_mode = mode; lit_tol = tol;
-    d.lit.tol = tol >= 0 ? tol : (sizeof(S) == 4 ? 8e-4 : 1e-10);
-    d.lit.route = lit_route;
+    settings.aniso_mode = mode; settings.lit_tol = tol;
+    apply_settings();
     for (int b = 0; b < B; ++b) {
       if (!traj[b].initialized) continue;
       S out5[5];
@@ -1261,7 +1246,7 @@ struct Batch : BatchCore {
   // Frame f of a call over [.., f1): does its prune ride on the downdate (the covariance lands, pruned, in the other buffer and
   // the next frame's k_propagate commits the window size)?  Never the call's last frame: it prunes with its own launch, so that
   // ncam is final when the call returns.  The frame step and commit_buffer_parity both ask here.
-  bool fuse_frame(int f, int f1) const { return knobs.fuse_prune && !prof && !knobs.overlap_feature && d.joseph == 0 && f + 1 < f1; }
+  bool fuse_frame(int f, int f1) const { return settings.fuse_prune && !prof && !settings.overlap_feature && d.joseph == 0 && f + 1 < f1; }
   // every slice ran the same frames; each fused one flipped the buffers
   void commit_buffer_parity(int f0, int f1) override {
     int flips = 0;
@@ -1274,7 +1259,7 @@ struct Batch : BatchCore {
   // asks here.
   int update_compress(int base) const {
     int cmp = base;
-    if (knobs.compress_route >= 0) cmp = (knobs.compress_route && d.trk_B) ? 3 : 0;
+    if (settings.compress_route >= 0) cmp = (settings.compress_route && d.trk_B) ? 3 : 0;
     if (n_lit > 0 && !cmp) cmp = d.compress;
     return cmp;
   }
@@ -1492,7 +1477,8 @@ struct Batch : BatchCore {
   int copy_from(BatchCore* src) override {
     if (int rc = guard()) return rc;
     Batch<S>* o = dynamic_cast<Batch<S>*>(src);
-    if (!o || o->B != B || o->n_cap != n_cap || o->f_cap != f_cap || o->m_cap != m_cap || o->h16 != h16)
+    // (a literal work space allocated without the dense stack cannot take over the sweep over it: lit_alloc sizes by lit_route)
+    if (!o || o->B != B || o->n_cap != n_cap || o->f_cap != f_cap || o->m_cap != m_cap || o->h16 != h16 || (d.lit.W2 && !d.lit.X && o->settings.lit_route == 1))
       return fail(-EINVAL, "copy_state: handles differ in shape or dtype");
     if (o->poisoned) return fail(-EIO, "copy_state: the source handle is unusable after a failed run_frames call (its filter states are undefined)");
     { const int rcf = o->flush_pending(); if (rcf) return rcf; }
@@ -1507,10 +1493,10 @@ struct Batch : BatchCore {
     HIPCHK(cp(d.ncam, o->d.ncam, Bz * sizeof(int))); HIPCHK(cp(d.n_resid, o->d.n_resid, Bz * sizeof(long long)));
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
-    knobs = o->knobs; d.joseph = o->d.joseph; d.gate_early = o->d.gate_early; d.gain_fused_s = o->d.gain_fused_s; gain_parts = o->gain_parts; d.gain_parts = gain_parts;
+    settings.take_over(o->settings);
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
-    return set_aniso(o->aniso_mode, o->lit_tol);   // re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed
+    return set_aniso(settings.aniso_mode, settings.lit_tol);   // applies the settings, re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed
   }
   int track_info(int b, double* out, int cap) override {
     if (int rc = enter_traj(b)) return rc;
@@ -1598,7 +1584,7 @@ struct Batch : BatchCore {
     const bool fuse = fuse_frame(f, f1);
     v.trk_n = in.n; v.trk_M = in.M; v.trk_off = in.off; v.trk_slots = in.slots; v.trk_obs = in.obs;
     v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
-    bool early = may_overlap && knobs.overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
+    bool early = may_overlap && settings.overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
     for (int b = b0; b < b0 + nb && early; ++b) {
       const int n_after = std::min(h_ncam[b] + 1, n_cap);
       early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2;
@@ -1667,12 +1653,6 @@ struct Batch : BatchCore {
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dg);
     if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("frame_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
-    return 0;
-  }
-  int set_gate_early(int on) override { d.gate_early = on ? 1 : 0; return 0; }
-  int set_cov_update(int form) override {
-    if (form < 0 || form > 2) return fail(-EINVAL, "form: 0 square-root gain (P - W W^T), 1 Joseph, 2 square-root gain with the register-resident solve");
-    d.joseph = form;
     return 0;
   }
 };

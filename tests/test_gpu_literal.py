@@ -92,6 +92,39 @@ def test_literal_general_route_alone_on_the_device(capi, po, monkeypatch):
     bt.close()
 
 
+def test_a_copy_takes_the_literal_route_over_or_refuses(capi, monkeypatch):
+    """msckf_hip_copy_state hands the source's literal route (MSCKF_HIP_LITERAL_ROUTE at ITS creation) to the copy.  A destination
+    without literal work space allocates it for that route and continues bit for bit (literal_info: route 2 = the sweep over the
+    dense stack, 3 = the compact route).  The dense stack is only allocated for route 1, and a copy does not reallocate: a
+    destination whose work space exists without it refuses a source on route 1 (-EINVAL) and stays as it was; the other way
+    round it adopts the compact route."""
+    N, F, nf = 8, 24, 8
+    tr = _aniso(N, F, nf, 5)
+    make = lambda: capi.Batch(1, N, F, N, capi.F64)
+    monkeypatch.setenv("MSCKF_HIP_LITERAL_ROUTE", "1")
+    a = make(); a.initialize(0, tr.cfg, tr.imu0)
+    monkeypatch.delenv("MSCKF_HIP_LITERAL_ROUTE")
+    fresh = make()                                            # never initialised: no literal work space yet
+    used = make(); used.initialize(0, tr.cfg, tr.imu0)        # anisotropic noise: work space of the compact route
+    for k in range(5):
+        H.device_frame(a, 0, tr, k, N)
+    assert a.literal_info(0)["route"] == 2 and a.literal_info(0)["m_rows"] > 0
+    fresh.copy_state_from(a)
+    with pytest.raises(capi.HipError, match=r"\(-22\): copy_state: handles differ in shape or dtype"):
+        used.copy_state_from(a)
+    for k in range(5, nf):
+        H.device_frame(a, 0, tr, k, N); H.device_frame(fresh, 0, tr, k, N)
+    assert fresh.literal_info(0)["route"] == 2 and fresh.literal_info(0)["m_rows"] > 0
+    assert H.same_bits(H.snapshot(fresh, 0), H.snapshot(a, 0))
+    a.copy_state_from(used)                                   # the refused destination is untouched: still at its initial state
+    for k in range(5):
+        H.device_frame(a, 0, tr, k, N); H.device_frame(used, 0, tr, k, N)
+    assert a.literal_info(0)["route"] == 3 and used.literal_info(0)["route"] == 3 and a.literal_info(0)["m_rows"] > 0
+    assert H.same_bits(H.snapshot(a, 0), H.snapshot(used, 0))
+    for bt in (a, fresh, used):
+        bt.close()
+
+
 def test_literal_route_float_vs_restatement(capi, po):
     N, F, nf = 10, 50, 16
     tr = _aniso(N, F, nf, 7)

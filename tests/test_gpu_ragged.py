@@ -419,3 +419,38 @@ def test_ragged_batch_of_96_vs_oracle(capi, po):
         P = bt.covariance(b)
         assert np.all(np.isfinite(P)) and np.array_equal(P, P.T), b
     bt.close()
+
+
+# ------------------------------------------------------------------------------------------------ E: a copy keeps its source's routes
+@pytest.mark.parametrize("env", [{"MSCKF_HIP_SMALL_UPDATE": "0", "MSCKF_HIP_FEATURE_PAIR": "0"}, {}], ids=["source created under other routes", "ordinary twin"])
+def test_a_copy_continues_on_its_source_s_routes_bit_for_bit(capi, ragged_sets, monkeypatch, env):
+    """msckf_hip_copy_state hands over every setting that decides which kernels run, whoever chose it: handle A is created with
+    MSCKF_HIP_SMALL_UPDATE=0 and MSCKF_HIP_FEATURE_PAIR=0 in the environment (the chain of kernels instead of k_update_small,
+    k_feature instead of k_feature_pair), handle B without them; A runs two frames, B takes A's state over, both run three more
+    (two updates at 4 and 5 cameras, the 5-camera window's first drop): IMU state, camera states, the whole covariance, window
+    size and statistics of both trajectories are the same bits.  (The two routes agree to 1e-4 in float, not to the bit:
+    tests/test_gpu_parity.py.)  Without the variables: the ordinary twin.  Float, the first handle's capacities, its 5- and
+    14-camera trajectories."""
+    rs = H.RaggedSet(0, seed0=500, n_cap=ragged_sets[1].n_cap, specs=[(5, 7, ""), (14, 40, "")], nf=5)
+    rs.f_cap = ragged_sets[1].f_cap
+    for name in ("MSCKF_HIP_SMALL_UPDATE", "MSCKF_HIP_FEATURE_PAIR"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    a = rs.batch(capi, capi.F32)
+    for name in env:
+        monkeypatch.delenv(name)
+    b = capi.Batch(rs.B, rs.n_cap, rs.f_cap, rs.m_cap, capi.F32)
+    for k in range(2):
+        rs.device_frame(a, k)
+    b.copy_state_from(a)
+    passed = [0] * rs.B
+    for k in range(2, 5):
+        rs.device_frame(a, k); rs.device_frame(b, k)
+        for t in range(rs.B):
+            passed[t] += a.last_stats(t)["n_passed"] if len(rs.frames[t][k]["M"]) else 0
+    sa, sb = _snap_all(a, rs.B), _snap_all(b, rs.B)
+    a.close(); b.close()
+    assert min(passed) > 0, passed                       # both trajectories updated after the copy
+    assert sa[0][3] == 4 and sa[1][3] == 5, (sa[0][3], sa[1][3])      # the 5-camera window has dropped its oldest camera
+    assert _differing(sa, sb, rs.B) == [], [float(np.abs(x[2] - y[2]).max()) for x, y in zip(sa, sb)]
