@@ -156,6 +156,10 @@ int msckf_hip_last_deltax(msckf_hip_handle h, int b, double* dx, int cap);
 int msckf_hip_set_tracks(msckf_hip_handle h, int b, int F, const int* M, const int* slots, const double* obs2);
 /* propagate / augment / marginalize / prune for the trajectory range [b0, b0+nb) in single launches */
 int msckf_hip_propagate_range(msckf_hip_handle h, int b0, int nb, const double* readings7, int K); /* [nb][K][7] */
+/* The same with a sample count per trajectory: readings7 holds the trajectories' samples one after the other, K[i] >= 0 rows for
+ * trajectory b0 + i.  Bit for bit msckf_hip_propagate_range(h, b0 + i, 1, rows_i, K[i]) called trajectory by trajectory; a
+ * trajectory with K[i] == 0 is not touched.  -EINVAL for a negative K[i] (nothing is propagated). */
+int msckf_hip_propagate_range_counts(msckf_hip_handle h, int b0, int nb, const double* readings7, const int* K);
 int msckf_hip_augment_range(msckf_hip_handle h, int b0, int nb);
 int msckf_hip_marginalize_range(msckf_hip_handle h, int b0, int nb);
 int msckf_hip_drop_oldest_range(msckf_hip_handle h, int b0, int nb, int n_drop);
@@ -178,6 +182,18 @@ int msckf_hip_scenario_alloc(msckf_hip_handle h, int n_frames, int K);
 /* stage one (frame, trajectory) cell on the host side of the handle */
 int msckf_hip_scenario_set(msckf_hip_handle h, int frame, int b, const double* readings7 /*[K][7]*/, int F,
                            const int* M, const int* slots, const double* obs2, int n_drop);
+/* The same cell with its OWN number of IMU samples and, for batches whose sequences differ in length, a skip mark.
+ *   k      0 <= k <= K of msckf_hip_scenario_alloc: only k rows of readings7 are read (null allowed when k == 0), by the host
+ *          and by the device.  k == 0: the frame propagates nothing -- state and covariance are not rewritten -- and
+ *          augments: bit for bit msckf_hip_augment_range alone.
+ *   flags  bit 0 (MSCKF_HIP_CELL_SKIP): this trajectory's sequence has no image on this frame.  Nothing of the trajectory
+ *          changes: no propagate, no camera state, no update, no prune; its frame-log record repeats the unchanged state.
+ *          A skipped cell has k == 0, F == 0 and n_drop == 0.
+ * -EINVAL for k out of range, a skipped cell that carries samples, tracks or a drop, or an unknown flag bit; the cell staged
+ * before stays.  msckf_hip_scenario_set is this entry with k = K and flags = 0.  Like it, the call un-commits the scenario. */
+enum { MSCKF_HIP_CELL_SKIP = 1 };
+int msckf_hip_scenario_set_cell(msckf_hip_handle h, int frame, int b, const double* readings7 /*[k][7]*/, int k, int F,
+                                const int* M, const int* slots, const double* obs2, int n_drop, int flags);
 int msckf_hip_scenario_commit(msckf_hip_handle h);   /* H2D of everything staged */
 /* one filter update per trajectory per frame: K x propagate + augmentState + marginalize + prune, for
  * frames [f0, f1), asynchronously on the handle's stream.  Results do not depend on how a range is cut into calls.
@@ -220,6 +236,10 @@ int msckf_hip_frame_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, 
  * truth).  Accumulated in double in a fixed order: the same log gives the same bits.  Sums and counts, so that ranks and
  * sequences combine by addition (ATE = sqrt(sum |e|^2 / n), mean NEES = sum / n). */
 int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double* gt_p, double* out);
+/* The same with a record range per trajectory, [r0[b], r1[b]) (r0[B], r1[B]): sequences of unequal length set r1[b] to their
+ * own frame count, so that the records of their skipped tail stay out.  gt_p[max(r1) - min(r0)][B][3] is indexed from
+ * min(r0); "|e| at record r1 - 1" is at r1[b] - 1.  With every range equal: the bits of msckf_hip_frame_log_metrics. */
+int msckf_hip_frame_log_metrics_ranges(msckf_hip_handle h, const int* r0, const int* r1, const double* gt_p, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

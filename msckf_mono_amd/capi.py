@@ -36,7 +36,9 @@ SYMBOLS = [
     "msckf_hip_set_anisotropic_noise", "msckf_hip_literal_info", "msckf_hip_get_error_flags", "msckf_hip_copy_state", "msckf_hip_set_host_affinity",
     "msckf_hip_image_cycle_range",
     "msckf_hip_frame_log_enable", "msckf_hip_frame_log_reset", "msckf_hip_frame_log_count", "msckf_hip_frame_log_read", "msckf_hip_frame_log_metrics",
+    "msckf_hip_scenario_set_cell", "msckf_hip_propagate_range_counts", "msckf_hip_frame_log_metrics_ranges",
 ]
+CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
 # fields of a frame-log record (include/msckf_hip.h, "frame log record"): name -> slice of its 48 scalars
 FRAME_LOG_STRIDE = 48
@@ -268,6 +270,16 @@ class Batch:
         r, p = _d(np.asarray(readings).reshape(nb, -1, 7))
         _chk(self.L.msckf_hip_propagate_range(self.h, b0, nb, p, r.shape[1]))
 
+    def propagate_range_counts(self, b0, nb, readings):
+        """propagate_range with a sample count per trajectory: readings[i] is the [K_i][7] array of trajectory b0 + i (K_i = 0:
+        the trajectory is not touched)"""
+        rs = [np.asarray(r, dtype=np.float64).reshape(-1, 7) for r in readings]
+        if len(rs) != nb:
+            raise ValueError("one array of readings per trajectory of the range")
+        K, pK = _i([len(r) for r in rs])
+        r, p = _d(np.concatenate(rs) if nb else np.zeros((0, 7)))
+        _chk(self.L.msckf_hip_propagate_range_counts(self.h, b0, nb, p, pK))
+
     def augment_range(self, b0, nb):
         _chk(self.L.msckf_hip_augment_range(self.h, b0, nb))
 
@@ -302,9 +314,11 @@ class Batch:
     def scenario_alloc(self, n_frames, K):
         _chk(self.L.msckf_hip_scenario_alloc(self.h, n_frames, K))
 
-    def scenario_set(self, frame, b, readings, M, slots, obs, n_drop):
-        r, pr = _d(np.asarray(readings).reshape(-1, 7)); Ma, pM = _i(M); s, ps = _i(slots); o, po = _d(obs)
-        _chk(self.L.msckf_hip_scenario_set(self.h, frame, b, pr, len(Ma), pM, ps, po, int(n_drop)))
+    def scenario_set(self, frame, b, readings, M, slots, obs, n_drop, skip=False):
+        """one (frame, trajectory) cell: its own len(readings) IMU samples (0 .. K of scenario_alloc), its work-list, its drop.
+        skip: the trajectory's sequence has no image on this frame (no readings, tracks or drop) -- nothing of it changes"""
+        r, pr = _d(np.asarray(readings, dtype=np.float64).reshape(-1, 7)); Ma, pM = _i(M); s, ps = _i(slots); o, po = _d(obs)
+        _chk(self.L.msckf_hip_scenario_set_cell(self.h, frame, b, pr, r.shape[0], len(Ma), pM, ps, po, int(n_drop), CELL_SKIP if skip else 0))
 
     def scenario_commit(self):
         _chk(self.L.msckf_hip_scenario_commit(self.h))
@@ -393,6 +407,19 @@ class Batch:
             raise ValueError("gt_p must be [r1 - r0][B][3]")
         o = np.zeros((self.B, 6))
         _chk(self.L.msckf_hip_frame_log_metrics(self.h, int(r0), int(r1), g.ctypes.data_as(_dp), o.ctypes.data_as(_dp)))
+        return o
+
+    def frame_log_metrics_ranges(self, r0, r1, gt_p):
+        """frame_log_metrics with a record range [r0[b], r1[b]) per trajectory (sequences of unequal length: r1[b] = the
+        sequence's frame count); gt_p [max(r1) - min(r0)][B][3], indexed from min(r0)"""
+        a0, p0 = _i(r0); a1, p1 = _i(r1)
+        if a0.shape != (self.B,) or a1.shape != (self.B,):
+            raise ValueError("r0 and r1 must hold one record index per trajectory")
+        g = np.ascontiguousarray(gt_p, dtype=np.float64)
+        if g.shape != (int(a1.max()) - int(a0.min()), self.B, 3):
+            raise ValueError("gt_p must be [max(r1) - min(r0)][B][3]")
+        o = np.zeros((self.B, 6))
+        _chk(self.L.msckf_hip_frame_log_metrics_ranges(self.h, p0, p1, g.ctypes.data_as(_dp), o.ctypes.data_as(_dp)))
         return o
 
     def profile_enable(self, on=True):

@@ -498,8 +498,10 @@ __device__ __forceinline__ double lam_hat(const double* Lam, const double* /*Dg*
 // ---------------------------------------------------------------- launch entry points (one per .hip file)
 // qroute: 0 no trajectory of [b0, b0 + nb) carries a full Q_imu (the diagonal kernel alone, over the range), 1 some do (both
 // instantiations over the range, each skips the other's trajectories), 2 all do (the full-Q instantiation alone)
-template <class S> void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute);
-template <class S> void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st);
+// cnt (null: K samples for every trajectory, none skipped): per trajectory of the launch its own sample count <= K, or IMU_SKIP
+constexpr int IMU_SKIP = -1;
+template <class S> void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute, const int* cnt = nullptr);
+template <class S> void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* cnt = nullptr);
 template <class S> void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop = nullptr, int drop_const = -1);
 template <class S> void launch_feature(const Dev<S>& d, int b0, int nb, hipStream_t st);
 template <class S> void launch_select(const Dev<S>& d, int b0, int nb, hipStream_t st);
@@ -524,7 +526,7 @@ template <class S> bool launch_chol_gain_large(const Dev<S>& d, int b0, int nb, 
 // covariance buffer that is current, pending: the window size still waits in ncam_upd -- and the reduction of the records
 // [r0, r1) of a log against ground-truth positions gt[r1 - r0][B][3] into out[B][6] (both device pointers)
 template <class S> void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec);
-template <class S> void launch_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out, hipStream_t st);
+template <class S> void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, double* out, hipStream_t st);
 size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged = false);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();

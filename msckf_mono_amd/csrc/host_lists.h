@@ -45,6 +45,17 @@ struct WorkList {
 // the per-track status bits of the feature kernel that the bookkeeping reads (dev_common.h: ST_*; msckf_hip.hip asserts the match)
 enum { TRK_MOTION_OK = 1, TRK_TRI_VALID = 2, TRK_MOTION_SKIPPED = 16 };
 
+// The rule for one scenario cell's IMU sample count k (0 .. K of the scenario) and its flags (CELL_SKIP: the trajectory's
+// sequence has no image on this frame, so the cell carries nothing): null when the cell is acceptable, else why it is not
+enum { CELL_SKIP = 1 };
+inline const char* cell_refusal(int k, int K, int F, int n_drop, int flags) {
+  if (flags & ~CELL_SKIP) return "unknown cell flag bit";
+  if (k < 0) return "negative IMU sample count k";
+  if (k > K) return "IMU sample count k exceeds the scenario's K (msckf_hip_scenario_alloc)";
+  if ((flags & CELL_SKIP) && (k != 0 || F != 0 || n_drop != 0)) return "a skipped cell carries no IMU samples, no tracks and no drop";
+  return nullptr;
+}
+
 inline void remove_tracked_feature(HostTraj& t, uint64_t fid, std::vector<int>& slots) {
   slots.clear();
   for (size_t c = 0; c < t.cams.size(); ++c) {

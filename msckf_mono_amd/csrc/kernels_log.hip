@@ -54,13 +54,17 @@ __global__ __launch_bounds__(256) void k_frame_log(Dev<S> d, int b0, int nb, con
 // e = p - p_gt, no alignment.  All in f64; lane l takes the records r0 + l, r0 + l + 64, ... in ascending order and the
 // lanes are combined by wave_sum's fixed tree, so the same log gives the same bits on every call.  P_pp = L L^T by
 // Cholesky, e^T P_pp^-1 e = |L^-1 e|^2 (a P_pp that is not positive definite gives NaN there).
+// r0b / r1b (both or neither): the trajectory's own range [r0b[b], r1b[b]) inside [r0, r1) -- sequences of unequal length
+// leave their skipped tail out; the ground truth is still indexed from r0.  Null: [r0, r1) for every trajectory.
 template <class S>
-__global__ __launch_bounds__(64) void k_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out) {
+__global__ __launch_bounds__(64) void k_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, double* out) {
   const int b = blockIdx.x, lane = threadIdx.x;
+  const int rg = r0;                       // the ground truth's first record
+  if (r0b) { r0 = r0b[b]; r1 = r1b[b]; }
   double s2 = 0, mx = 0, last = 0, nees = 0, nerr = 0, cnt = 0;
   for (int r = r0 + lane; r < r1; r += 64) {
     const S* q = log + ((long)r * B + b) * LOG_STRIDE;
-    const double* g = gt + ((long)(r - r0) * B + b) * 3;
+    const double* g = gt + ((long)(r - rg) * B + b) * 3;
     const double e0 = (double)q[IP] - g[0], e1 = (double)q[IP + 1] - g[1], e2 = (double)q[IP + 2] - g[2];
     const double d2 = e0 * e0 + e1 * e1 + e2 * e2, dist = sqrt(d2);
     const double pxx = (double)q[LOG_PPP], pxy = (double)q[LOG_PPP + 1], pxz = (double)q[LOG_PPP + 2];
@@ -87,14 +91,14 @@ void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* 
   hipLaunchKernelGGL(k_frame_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, P, pending ? 1 : 0, rec);
 }
 template <class S>
-void launch_log_metrics(const S* log, int B, int r0, int r1, const double* gt, double* out, hipStream_t st) {
+void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, double* out, hipStream_t st) {
   if (B <= 0) return;
-  hipLaunchKernelGGL(k_log_metrics<S>, dim3(B), dim3(64), 0, st, log, B, r0, r1, gt, out);
+  hipLaunchKernelGGL(k_log_metrics<S>, dim3(B), dim3(64), 0, st, log, B, r0, r1, r0b, r1b, gt, out);
 }
 
 template void launch_frame_log<float>(const Dev<float>&, int, int, hipStream_t, const float*, bool, float*);
 template void launch_frame_log<double>(const Dev<double>&, int, int, hipStream_t, const double*, bool, double*);
-template void launch_log_metrics<float>(const float*, int, int, int, const double*, double*, hipStream_t);
-template void launch_log_metrics<double>(const double*, int, int, int, const double*, double*, hipStream_t);
+template void launch_log_metrics<float>(const float*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
+template void launch_log_metrics<double>(const double*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
 
 }  // namespace msckf

@@ -149,17 +149,24 @@ __device__ __forceinline__ void augment_body(const Dev<S>& d, int b, int tid, S*
   if (tid == 0) d.ncam[b] = n + 1;
 }
 
+// cnt: see k_propagate (the profiled frame loop launches the two apart); only its skip mark matters here
 template <class S>
-__global__ __launch_bounds__(256) void k_augment(Dev<S> d, int b0) {
+__global__ __launch_bounds__(256) void k_augment(Dev<S> d, int b0, const int* cnt) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x;
+  if (cnt && cnt[blockIdx.x] < 0) return;   // skipped cell: no image, no camera state
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   augment_body<S>(d, b, tid, reinterpret_cast<S*>(smem_raw));
 }
 
+// cnt (null: every trajectory of the launch has K samples): the trajectory's own number of samples, cnt[i] <= K for the
+// launch's i-th trajectory -- uniform over its workgroup; only that many rows of its readings are read.  0: nothing is propagated
+// (state and covariance are not rewritten), the fused augment still runs: bit for bit k_augment alone.  IMU_SKIP (< 0): the
+// trajectory has no image on this frame -- a deferred window size is committed (the frame's later kernels read ncam), nothing else.
 template <class S, bool AUGMENT, int QM>
-__global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K) {
+__global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K, const int* cnt) {
   const int b = b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (cnt) K = cnt[blockIdx.x];
   constexpr bool FULLQ = QM == 2;
   if (QM != 0 && (d.qf[(long)b * QF_STRIDE + QF_FLAG] != S(0)) != FULLQ) return;   // the other instantiation's trajectory
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
@@ -203,6 +210,14 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) { const int k = Mfma16<S>::row_of_group(g, kk); pic[t][kk] = P[(long)(15 + min(col, d.n6cap - 1)) * ld + min(k, 14)]; }   // unconditional (masked where used): no wait for the window size in front of the kernel's first loads
     }
+  }
+  if (K <= 0) {   // (after the loads above were issued: the count is not waited for in front of them)
+    if (AUGMENT && K == 0) {
+      __syncthreads();   // ncam as committed above, for all threads
+      extern __shared__ __attribute__((aligned(16))) unsigned char smem_aug0[];
+      augment_body<S>(d, b, tid, reinterpret_cast<S*>(smem_aug0));
+    }
+    return;
   }
   if (tid < 16) sState[tid] = imu[tid];                 // q b_g v b_a p
   if (tid < 3) sG[tid] = imu[IG + tid];
@@ -583,22 +598,22 @@ __global__ __launch_bounds__(1024) void k_prune_inplace(Dev<S> d, int b0, const 
 }
 
 template <class S, int QM>
-static void launch_propagate_q(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment) {
-  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true, QM>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K);
-  else hipLaunchKernelGGL((k_propagate<S, false, QM>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K);
+static void launch_propagate_q(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, const int* cnt) {
+  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true, QM>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K, cnt);
+  else hipLaunchKernelGGL((k_propagate<S, false, QM>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K, cnt);
 }
 template <class S>
-void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute) {
+void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute, const int* cnt) {
   if (nb <= 0) return;
-  if (K <= 0) { if (then_augment) launch_augment<S>(d, b0, nb, st); return; }
-  if (qroute == 0) { launch_propagate_q<S, 0>(d, b0, nb, readings, rd_stride, K, st, then_augment); return; }
-  if (qroute == 1) launch_propagate_q<S, 1>(d, b0, nb, readings, rd_stride, K, st, then_augment);   // disjoint trajectories: same stream, either order
-  launch_propagate_q<S, 2>(d, b0, nb, readings, rd_stride, K, st, then_augment);
+  if (K <= 0 && !cnt) { if (then_augment) launch_augment<S>(d, b0, nb, st); return; }
+  if (qroute == 0) { launch_propagate_q<S, 0>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt); return; }
+  if (qroute == 1) launch_propagate_q<S, 1>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt);   // disjoint trajectories: same stream, either order
+  launch_propagate_q<S, 2>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt);
 }
 template <class S>
-void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st) {
+void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* cnt) {
   if (nb <= 0) return;
-  hipLaunchKernelGGL(k_augment<S>, dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0);
+  hipLaunchKernelGGL(k_augment<S>, dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, cnt);
 }
 // drop == nullptr && drop_const < 0: the host's keep list (d.keep, d.nkeep); otherwise drop the oldest drop[i] (i = trajectory
 // index relative to b0) or drop_const camera states
@@ -612,10 +627,10 @@ void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* dr
   else hipLaunchKernelGGL((k_prune_inplace<S, 2, 12>), grid, dim3(1024), 0, st, d, b0, drop, drop_const, use_keep);
 }
 
-template void launch_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, bool, int);
-template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool, int);
-template void launch_augment<float>(const Dev<float>&, int, int, hipStream_t);
-template void launch_augment<double>(const Dev<double>&, int, int, hipStream_t);
+template void launch_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, bool, int, const int*);
+template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool, int, const int*);
+template void launch_augment<float>(const Dev<float>&, int, int, hipStream_t, const int*);
+template void launch_augment<double>(const Dev<double>&, int, int, hipStream_t, const int*);
 template void launch_prune<float>(const Dev<float>&, int, int, hipStream_t, const int*, int);
 template void launch_prune<double>(const Dev<double>&, int, int, hipStream_t, const int*, int);
 

@@ -184,15 +184,17 @@ struct BatchCore {
   // cell starts at off[cell][t] counted from the frame's first entry (Dev::trk_off) -- not [f_cap][m_cap] padded rows (1.9x
   // the payload at cfg3's track lengths, on the host, in HBM and in every per-frame upload).
   // h_rd / sc_rd ([frames][B][K][RD_STRIDE]) and c_obs / sc_obs (coordinate pairs) hold scalars of esz bytes.
+  // h_k / sc_k: per cell its own number of IMU samples (0 .. sc_K; the rows beyond it are padding that nothing reads), or
+  // IMU_SKIP: the trajectory has no image on that frame (k_propagate's cnt)
   int sc_frames = 0, sc_K = 0;
   bool committed = false;
-  unsigned char* sc_rd = nullptr; int* sc_n = nullptr; int* sc_M = nullptr; int* sc_off = nullptr; int* sc_drop = nullptr;
+  unsigned char* sc_rd = nullptr; int* sc_n = nullptr; int* sc_M = nullptr; int* sc_off = nullptr; int* sc_drop = nullptr; int* sc_k = nullptr;
   int* sc_slots = nullptr; unsigned char* sc_obs = nullptr; size_t sc_total = 0;      // sum over all cells
-  std::vector<unsigned char> h_rd; std::vector<int> h_n, h_M, h_off, h_drop;
+  std::vector<unsigned char> h_rd; std::vector<int> h_n, h_M, h_off, h_drop, h_k;
   std::vector<std::vector<int>> c_slots; std::vector<std::vector<unsigned char>> c_obs;   // per cell
   std::vector<size_t> fr_base;                                             // [frames + 1] first entry of a frame in sc_slots / sc_obs
   std::vector<void*> sc_allocs;
-  // streamed inputs (run_frames_streamed): frame f's block [rd | n | drop | M | off | slots | obs] is copied from page-locked
+  // streamed inputs (run_frames_streamed): frame f's block [rd | n | drop | k | M | off | slots | obs] is copied from page-locked
   // host memory into one of `ring` device staging sets on a copy stream, `ring` - 1 frames ahead of the kernels that read it.
   // Page-locked blocks are built on demand (scen_pin, or the first streamed run over a frame), only for frames that are
   // streamed: a run_frames-only user never pays for them.
@@ -216,7 +218,7 @@ struct BatchCore {
     pin_chunks.clear();
     for (auto& pf : pinf) pf = PinFrame();
   }
-  size_t pk_rd = 0, pk_n = 0, pk_drop = 0, pk_M = 0, pk_off = 0, pk_slots = 0;   // section offsets (256-byte aligned); obs follows the frame's slots
+  size_t pk_rd = 0, pk_n = 0, pk_drop = 0, pk_k = 0, pk_M = 0, pk_off = 0, pk_slots = 0;   // section offsets (256-byte aligned); obs follows the frame's slots
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
   // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
@@ -400,6 +402,15 @@ struct BatchCore {
     if (int rc = enter()) return rc;
     return propagate_device(b0, nb, rd, K);
   }
+  // propagate() with a sample count per trajectory: rd holds K[0] rows, then K[1] rows, ...
+  int propagate_counts(int b0, int nb, const double* rd, const int* K) {
+    if (int rc = guard()) return rc;
+    if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
+    for (int i = 0; i < nb; ++i) if (K[i] < 0) return fail(-EINVAL, "negative sample count K[" + std::to_string(i) + "]");
+    for (int i = 0; i < nb; ++i) if (K[i] > 0) invalidate_imu(b0 + i, 1);
+    if (int rc = enter()) return rc;
+    return propagate_device_counts(b0, nb, rd, K);
+  }
   // ---- the device's integer arrays
   // last_stats of a marginalize() that had nothing to residualize (the reference returns early, msckf.h:337)
   int clear_stats(int b) {
@@ -454,7 +465,7 @@ struct BatchCore {
       allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end());
     }
     sc_allocs.clear();
-    sc_rd = nullptr; sc_n = sc_M = sc_off = sc_drop = sc_slots = nullptr; sc_obs = nullptr; sc_total = 0;
+    sc_rd = nullptr; sc_n = sc_M = sc_off = sc_drop = sc_k = sc_slots = nullptr; sc_obs = nullptr; sc_total = 0;
   }
   template <class T> int sc_dalloc(T** p, size_t count, size_t elem = sizeof(T)) {
     const size_t mark = allocs.size();
@@ -471,17 +482,17 @@ struct BatchCore {
     unpin_host();
     const size_t Bz = B, FB = (size_t)n_frames * Bz;
     h_rd.assign(FB * K * RD_STRIDE * esz, 0); h_n.assign(FB, 0); h_M.assign(FB * f_cap, 0); h_off.assign(FB * f_cap, 0);
-    h_drop.assign(FB, 0); h_maxslot.assign(FB, -1);
+    h_drop.assign(FB, 0); h_k.assign(FB, K); h_maxslot.assign(FB, -1);
     c_slots.assign(FB, std::vector<int>()); c_obs.assign(FB, std::vector<unsigned char>());
     fr_base.assign((size_t)n_frames + 1, 0);
     pinf.assign((size_t)n_frames, PinFrame());
     int rc = 0;
     rc |= sc_dalloc(&sc_rd, FB * K * RD_STRIDE, esz); rc |= sc_dalloc(&sc_n, h_n.size()); rc |= sc_dalloc(&sc_M, h_M.size());
-    rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size());
+    rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size()); rc |= sc_dalloc(&sc_k, h_k.size());
     if (rc) return rc;
     // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
     pk_rd = 0; pk_n = al256(pk_rd + Bz * K * RD_STRIDE * esz); pk_drop = al256(pk_n + Bz * sizeof(int));
-    pk_M = al256(pk_drop + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
+    pk_k = al256(pk_drop + Bz * sizeof(int)); pk_M = al256(pk_k + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
     sc_frames = n_frames; sc_K = K;
     return 0;
   }
@@ -527,6 +538,7 @@ struct BatchCore {
     HIPCHK(hipMemcpyAsync(sc_M, h_M.data(), h_M.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(sc_off, h_off.data(), h_off.size() * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(sc_drop, h_drop.data(), h_drop.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(sc_k, h_k.data(), h_k.size() * sizeof(int), hipMemcpyHostToDevice, st));
     {   // size the pinned staging ring once, for the largest frame
       size_t mx = 0;
       for (int f = 0; f < sc_frames; ++f) mx = std::max(mx, fr_base[f + 1] - fr_base[f]);
@@ -584,6 +596,7 @@ struct BatchCore {
         std::memcpy(blk + pk_rd, h_rd.data() + c0 * sc_K * RD_STRIDE * esz, Bz * sc_K * RD_STRIDE * esz);
         std::memcpy(blk + pk_n, h_n.data() + c0, Bz * sizeof(int));
         std::memcpy(blk + pk_drop, h_drop.data() + c0, Bz * sizeof(int));
+        std::memcpy(blk + pk_k, h_k.data() + c0, Bz * sizeof(int));
         std::memcpy(blk + pk_M, h_M.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
         std::memcpy(blk + pk_off, h_off.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
         gather_frame(f, reinterpret_cast<int*>(blk + pk_slots), blk + pinf[f].off_obs);
@@ -841,6 +854,7 @@ struct BatchCore {
   virtual int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) = 0;
   virtual void mirror_advance(int b, const double* rd, int K) = 0;   // propagate()'s K samples on the host copy of the IMU state
   virtual int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment = false) = 0;
+  virtual int propagate_device_counts(int b0, int nb, const double* rd, const int* K) = 0;
   virtual int augment(int b0, int nb) = 0;
   virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
   virtual int marginalize(int b0, int nb, int mode = 0) = 0;   // mode 1: the second update of pruneRedundantStates (stored p_f_G per track, set_given_range)
@@ -861,7 +875,7 @@ struct BatchCore {
   virtual int set_cov(int b, const double* P, int D) = 0;
   virtual int track_info(int b, double* out, int cap) = 0;
   virtual int deltax(int b, double* out, int cap) = 0;
-  virtual int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) = 0;
+  virtual int scen_set(int f, int b, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) = 0;
   // THE frame step of run_frames / run_frames_streamed: frame f of a call over [f0, f1) for slice s, inputs in staging set
   // `staged` of the upload ring, or (staged < 0) resident
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
@@ -871,7 +885,17 @@ struct BatchCore {
   virtual int copy_from(BatchCore* src) = 0;
   virtual int lit_info(int b, int* out8) = 0;
   virtual int frame_log_read(int r0, int n, int b0, int nb, double* out) = 0;                  // [n][nb][LOG_STRIDE]
-  virtual int frame_log_metrics(int r0, int r1, const double* gt_p, double* out) = 0;          // gt_p [r1 - r0][B][3], out [B][6]
+  // gt_p [r1 - r0][B][3], out [B][6]; r0b / r1b (both or neither): a record range per trajectory inside [r0, r1)
+  virtual int frame_log_metrics(int r0, int r1, const double* gt_p, double* out, const int* r0b = nullptr, const int* r1b = nullptr) = 0;
+  int frame_log_metrics_ranges(const int* r0b, const int* r1b, const double* gt_p, double* out) {
+    int lo = INT32_MAX, hi = 0;
+    for (int b = 0; b < B; ++b) {
+      if (r0b[b] < 0 || r1b[b] < r0b[b] || r1b[b] > log_n)
+        return fail(-EINVAL, "record range of trajectory " + std::to_string(b) + " beyond the records written (msckf_hip_frame_log_count)");
+      lo = std::min(lo, r0b[b]); hi = std::max(hi, r1b[b]);
+    }
+    return frame_log_metrics(lo, hi, gt_p, out, r0b, r1b);
+  }
 };
 
 int resolve_map(BatchCore* B, int b);   // (defined with the host-side bookkeeping below)
@@ -889,6 +913,7 @@ struct Batch : BatchCore {
   std::vector<S> h_imu;
   // single-call staging on device
   S* d_rd = nullptr;                                // [B][rd_cap][7]
+  int* d_cnt = nullptr;                             // [B] sample counts of a propagate_range_counts chunk
   S* d_pfin = nullptr;                              // [B][f_cap][4] stored feature positions (mode 1)
   S* wl_obs = nullptr;         // the observations of the single-call work-lists: [B][2 wl_ib], beside the core's wl_i
 
@@ -938,7 +963,7 @@ struct Batch : BatchCore {
     apply_settings();
     rc |= dalloc(&d.gain_bar, Bz * 32);
     rd_cap = 64;
-    rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE);
+    rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE); rc |= dalloc(&d_cnt, Bz);
     HIPCHK(hipHostMalloc(&h_rb, ((size_t)n_cap * CAM_STRIDE + IMU_STRIDE) * sizeof(S), hipHostMallocDefault));
     wl_f4 = (f_cap + 3) & ~3; wl_ib = (4 + wl_f4 + (long)f_cap * m_cap + 3) & ~3L;
     rc |= dalloc(&wl_i, Bz * wl_ib); rc |= dalloc(&wl_obs, Bz * wl_ib * 2);
@@ -1184,6 +1209,34 @@ struct Batch : BatchCore {
     }
     return 0;
   }
+  // The rd_cap-sample staging chunks are cut per trajectory: in chunk c trajectory i has clamp(K[i] - rd_cap c, 0, rd_cap) samples --
+  // the chunks of its own propagate_device(b0 + i, 1, ., K[i]), so the same launches see the same samples -- and none once it
+  // has run out (k_propagate leaves a trajectory with no samples alone).  Rows padded to the chunk's longest trajectory.
+  int propagate_device_counts(int b0, int nb, const double* rd, const int* K) override {
+    int kmax = 0;
+    std::vector<size_t> row0(nb);                     // trajectory i's first row in rd
+    { size_t o = 0; for (int i = 0; i < nb; ++i) { row0[i] = o; o += K[i]; kmax = std::max(kmax, K[i]); } }
+    for (int k0 = 0; k0 < kmax; k0 += rd_cap) {
+      const int kk = std::min(rd_cap, kmax - k0);
+      const size_t cnt = (size_t)nb * kk * RD_STRIDE, off_c = (cnt * sizeof(S) + 15) / 16 * 16;
+      unsigned char* raw = nullptr;
+      int rc = stage_acquire(off_c + nb * sizeof(int), &raw);
+      if (rc) return rc;
+      S* tmp = reinterpret_cast<S*>(raw); int* hc = reinterpret_cast<int*>(raw + off_c);
+      for (int i = 0; i < nb; ++i) {
+        hc[i] = std::max(0, std::min(K[i] - k0, rd_cap));
+        for (int k = 0; k < kk; ++k)
+          for (int c = 0; c < RD_STRIDE; ++c) tmp[((size_t)i * kk + k) * RD_STRIDE + c] = k < hc[i] ? (S)rd[(row0[i] + k0 + k) * RD_STRIDE + c] : S(0);
+      }
+      HIPCHK(hipMemcpyAsync(d_rd, tmp, cnt * sizeof(S), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(d_cnt, hc, nb * sizeof(int), hipMemcpyHostToDevice, st));
+      rc = stage_release();
+      if (rc) return rc;
+      launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, false, qroute(b0, nb), d_cnt);
+      HIPCHK(hipGetLastError());
+    }
+    return 0;
+  }
   int augment(int b0, int nb) override {
     if (int rc = guard()) return rc;
     if (chk_range(b0, nb)) return fail(-EINVAL, "trajectory range out of bounds");
@@ -1272,7 +1325,8 @@ struct Batch : BatchCore {
   // (LDS strides, and the column-segment width of chol(Lam^): 4 up to 63 columns, 8 beyond); neither changes the order of the
   // operations on any matrix element -- every element takes its rank-1 updates pivot by pivot whichever task holds it -- so the
   // bits are the trajectory's own (tests/test_gpu_ragged.py holds it: 5 .. 14 cameras alone and beside each other).
-  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0) {
+  // cell_k (run_frames: the frame's h_k from b0 on): a skipped cell has no augmentState ahead.
+  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
     v.compress = update_compress(v.compress);
@@ -1282,7 +1336,7 @@ struct Batch : BatchCore {
     // short windows (single filters, BASELINE configs[1]): everything after the selection in ONE launch (k_update_small)
     if (small_limit && v.compress && n_lit == 0 && d.joseph == 0) {
       int nmax = 0, nsmall = 0;                    // largest window of the range, largest one within the limit
-      for (int b = b0; b < b0 + nb; ++b) { const int n = 6 * std::min(h_ncam[b] + ncam_ahead, n_cap); nmax = std::max(nmax, n); if (n > 0 && n <= small_limit) nsmall = std::max(nsmall, n); }
+      for (int b = b0; b < b0 + nb; ++b) { const int n = 6 * std::min(h_ncam[b] + (cell_k && cell_k[b - b0] == IMU_SKIP ? 0 : ncam_ahead), n_cap); nmax = std::max(nmax, n); if (n > 0 && n <= small_limit) nsmall = std::max(nsmall, n); }
       // (an empty window has no update: it makes no range mixed, and in a mixed one it is k_update_small's, 6 x 0 <= small_split)
       const bool mixed = nsmall > 0 && nmax > small_limit;
       if ((nmax > 0 && nmax <= small_limit) || mixed) {
@@ -1531,16 +1585,19 @@ struct Batch : BatchCore {
     for (int i = 0; i < D; ++i) out[i] = (double)tmp[i];
     return D;
   }
-  int scen_set(int f, int b, const double* rd, int F, const int* M, const int* slots, const double* obs, int n_drop) override {
+  int scen_set(int f, int b, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) override {
     if (f < 0 || f >= sc_frames || chk(b)) return fail(-EINVAL, "scenario cell out of range");
     { const int rc = check_worklist(F, M, slots); if (rc) return rc; }   // before the staged cell is touched
     if (n_drop < 0) return fail(-EINVAL, "negative n_drop");
+    if (const char* why = cell_refusal(k, sc_K, F, n_drop, flags)) return fail(-EINVAL, why);
+    if (k > 0 && !rd) return fail(-EINVAL, "null readings for a cell with samples");
+    const bool skip = (flags & CELL_SKIP) != 0;
     const size_t cell = (size_t)f * B + b;
     size_t tot = 0;
     for (int t = 0; t < F; ++t) tot += M[t];
     S* hr = reinterpret_cast<S*>(h_rd.data()) + cell * sc_K * RD_STRIDE;   // (the core stores the cell's scalars as bytes)
-    for (int k = 0; k < sc_K; ++k) for (int c = 0; c < RD_STRIDE; ++c) hr[k * RD_STRIDE + c] = (S)rd[k * RD_STRIDE + c];
-    h_n[cell] = F; h_drop[cell] = n_drop;
+    for (int s = 0; s < sc_K; ++s) for (int c = 0; c < RD_STRIDE; ++c) hr[s * RD_STRIDE + c] = s < k ? (S)rd[s * RD_STRIDE + c] : S(0);   // (padding beyond k: never read again)
+    h_n[cell] = F; h_drop[cell] = n_drop; h_k[cell] = skip ? IMU_SKIP : k;
     for (int t = 0; t < f_cap; ++t) h_M[cell * f_cap + t] = t < F ? M[t] : 0;
     c_slots[cell].assign(slots, slots + tot);
     c_obs[cell].resize(2 * tot * sizeof(S));
@@ -1554,17 +1611,18 @@ struct Batch : BatchCore {
   }
   // where a frame's inputs are on the device, for a slice that starts at trajectory b0: per-trajectory arrays already offset
   // to b0, slots / obs the frame's compact entries (tracks find theirs through off)
-  struct FrameIn { const S* rd; const int* n; const int* M; const int* off; const int* slots; const S* obs; const int* drop; };
+  struct FrameIn { const S* rd; const int* n; const int* M; const int* off; const int* slots; const S* obs; const int* drop; const int* k; };
   FrameIn resident_frame(int f, int b0) const {
     const size_t c = (size_t)f * B + b0;
     return FrameIn{reinterpret_cast<const S*>(sc_rd) + c * sc_K * RD_STRIDE, sc_n + c, sc_M + c * f_cap, sc_off + c * f_cap, sc_slots + fr_base[f],
-                   reinterpret_cast<const S*>(sc_obs) + 2 * fr_base[f], sc_drop + c};
+                   reinterpret_cast<const S*>(sc_obs) + 2 * fr_base[f], sc_drop + c, sc_k + c};
   }
   FrameIn staged_frame(int f, int k, int b0) const {   // frame f as uploaded into staging set k
     unsigned char* blk = sg_blk[k];
     return FrameIn{reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, reinterpret_cast<int*>(blk + pk_n) + b0,
                    reinterpret_cast<int*>(blk + pk_M) + (size_t)b0 * f_cap, reinterpret_cast<int*>(blk + pk_off) + (size_t)b0 * f_cap,
-                   reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs), reinterpret_cast<int*>(blk + pk_drop) + b0};
+                   reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs), reinterpret_cast<int*>(blk + pk_drop) + b0,
+                   reinterpret_cast<int*>(blk + pk_k) + b0};
   }
   // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged` or (staged < 0) resident --
   // propagate + augmentState, the update, the prune (on the downdate or with its own launch, fuse_frame), the host mirror of
@@ -1587,7 +1645,8 @@ struct Batch : BatchCore {
     bool early = may_overlap && settings.overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
     for (int b = b0; b < b0 + nb && early; ++b) {
       const int n_after = std::min(h_ncam[b] + 1, n_cap);
-      early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2;
+      // (a skipped cell gets no camera state: the early k_feature's window size, ncam_upd = "after the next augment", would be one too many)
+      early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2 && h_k[cell0 + b] != IMU_SKIP;
     }
     if (early) {
       (void)hipEventRecord(ev_fa[hh], q);
@@ -1600,13 +1659,13 @@ struct Batch : BatchCore {
     // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
     {
       StageRange r("imu_prop+msckf_augment_state");
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb)); stage_end(0, q);
-      if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q); stage_end(1, q); }
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
+      if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q, in.k); stage_end(1, q); }
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
     v.ncam_defer = 0;
     if (fuse) { v.Pout = s.flipped ? d.P : P_spare; v.fuse_drop = in.drop; }
-    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1); }
+    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1, h_k.data() + cell0 + b0); }
     if (fuse) s.flipped = !s.flipped;
     else {
       StageRange r("msckf_prune_empty_states");
@@ -1618,8 +1677,8 @@ struct Batch : BatchCore {
     // frame log: the state the frame leaves -- the covariance buffer that is current after the flip, the window size where the
     // prune left it (ncam_upd while it is pending) -- as record log_base + (f - f0); outside the stage timers
     if (log_buf) launch_frame_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, s.pending, static_cast<S*>(log_buf) + (size_t)(log_base + (f - f0)) * B * LOG_STRIDE);
-    for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment, then drop n_drop (clamped as k_make_keep does)
-      if (h_ncam[b] < n_cap) h_ncam[b]++;
+    for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment (not for a skipped cell), then drop n_drop (clamped as k_make_keep does)
+      if (h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP) h_ncam[b]++;
       h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
     }
   }
@@ -1639,16 +1698,19 @@ struct Batch : BatchCore {
   }
   // the records [r0, r1) against ground-truth positions, reduced on the device (k_log_metrics): per trajectory n, sum |e|^2,
   // max |e|, |e| at r1 - 1, sum e^T P_pp^-1 e, records with STAT_ERR != 0
-  int frame_log_metrics(int r0, int r1, const double* gt_p, double* out) override {
+  int frame_log_metrics(int r0, int r1, const double* gt_p, double* out, const int* r0b, const int* r1b) override {
     if (int rc = guard()) return rc;
     if (r0 < 0 || r1 < r0 || r1 > log_n) return fail(-EINVAL, "record range beyond the records written (msckf_hip_frame_log_count)");
     if (int rc = enter()) return rc;
     const size_t ng = (size_t)(r1 - r0) * B * 3, no = (size_t)B * 6;
-    double* dg = nullptr;                                      // [ground truth | out], freed on every way out
-    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
+    double* dg = nullptr;                                      // [ground truth | out | r0b r1b], freed on every way out
+    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + 2 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
     double* dout = dg + std::max<size_t>(ng, 1);
+    int* dr = reinterpret_cast<int*>(dout + no);
     hipError_t e = ng ? hipMemcpyAsync(dg, gt_p, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-    if (e == hipSuccess) { launch_log_metrics<S>(static_cast<const S*>(log_buf), B, r0, r1, dg, dout, st); e = hipGetLastError(); }
+    if (e == hipSuccess && r0b) e = hipMemcpyAsync(dr, r0b, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && r0b) e = hipMemcpyAsync(dr + B, r1b, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { launch_log_metrics<S>(static_cast<const S*>(log_buf), B, r0, r1, r0b ? dr : nullptr, r0b ? dr + B : nullptr, dg, dout, st); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dg);
@@ -2169,13 +2231,23 @@ int msckf_hip_last_deltax(msckf_hip_handle h, int b, double* dx, int cap) { retu
 
 int msckf_hip_set_tracks(msckf_hip_handle h, int b, int F, const int* M, const int* slots, const double* obs2) { return H(h)->set_tracks(b, F, M, slots, obs2); }
 int msckf_hip_propagate_range(msckf_hip_handle h, int b0, int nb, const double* readings7, int K) { return H(h)->propagate(b0, nb, readings7, K); }
+int msckf_hip_propagate_range_counts(msckf_hip_handle h, int b0, int nb, const double* readings7, const int* K) {
+  if (!h || (nb > 0 && !K)) return fail(-EINVAL, "null argument");
+  return H(h)->propagate_counts(b0, nb, readings7, K);
+}
 int msckf_hip_augment_range(msckf_hip_handle h, int b0, int nb) { return H(h)->augment(b0, nb); }
 int msckf_hip_marginalize_range(msckf_hip_handle h, int b0, int nb) { return H(h)->marginalize(b0, nb, 0); }
 int msckf_hip_drop_oldest_range(msckf_hip_handle h, int b0, int nb, int n_drop) { return H(h)->drop_oldest(b0, nb, n_drop); }
 
 int msckf_hip_scenario_alloc(msckf_hip_handle h, int n_frames, int K) { return H(h)->scen_alloc(n_frames, K); }
 int msckf_hip_scenario_set(msckf_hip_handle h, int frame, int b, const double* readings7, int F, const int* M, const int* slots, const double* obs2, int n_drop) {
-  return H(h)->scen_set(frame, b, readings7, F, M, slots, obs2, n_drop);
+  if (!h) return fail(-EINVAL, "null handle");
+  return H(h)->scen_set(frame, b, readings7, H(h)->sc_K, F, M, slots, obs2, n_drop, 0);
+}
+static_assert(MSCKF_HIP_CELL_SKIP == CELL_SKIP, "host_lists.h states the cell rule with the header's flag bit");
+int msckf_hip_scenario_set_cell(msckf_hip_handle h, int frame, int b, const double* readings7, int k, int F, const int* M, const int* slots, const double* obs2, int n_drop, int flags) {
+  if (!h) return fail(-EINVAL, "null handle");
+  return H(h)->scen_set(frame, b, readings7, k, F, M, slots, obs2, n_drop, flags);
 }
 int msckf_hip_scenario_commit(msckf_hip_handle h) { return H(h)->scen_commit(); }
 int msckf_hip_run_frames(msckf_hip_handle h, int f0, int f1) { return H(h)->run_frames(f0, f1); }
@@ -2201,6 +2273,7 @@ int msckf_hip_frame_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL,
 int msckf_hip_frame_log_count(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->frame_log_count(); }
 int msckf_hip_frame_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_read(r0, n, b0, nb, out); }
 int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double* gt_p, double* out) { if (!h || !gt_p || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_metrics(r0, r1, gt_p, out); }
+int msckf_hip_frame_log_metrics_ranges(msckf_hip_handle h, const int* r0, const int* r1, const double* gt_p, double* out) { if (!h || !r0 || !r1 || !gt_p || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_metrics_ranges(r0, r1, gt_p, out); }
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"
