@@ -34,6 +34,16 @@
  *            37    window size (camera states)
  *            38-40 n_tracks, passed, sticky error flags of the update (out7[0], out7[4] of last_stats; get_error_flags)
  *            41-47 cam7 of camera slot 0: the oldest surviving camera, the fixed-lag estimate; zeros for an empty window
+ *   map log record, 8 scalars per logged track (a track the reference's map_ would hold, msckf.h:371: motion check passed
+ *            or skipped, triangulation valid), as the frame's update leaves them:
+ *            0-2   p_f_G, the triangulated landmark
+ *            3     gamma, the track's gate statistic (chi-square with 2 M - 3 degrees of freedom for a passed track)
+ *            4     frame ordinal: frames run since msckf_hip_map_log_enable / _reset
+ *            5     track index in the frame's work-list
+ *            6     flags: 1 gate passed, 2 included in the update, 4 gamma is the early-accept bound
+ *                  (msckf_hip_set_gate_early_accept), not the statistic
+ *            7     M, the track's observation count
+ *            (4-7 are integers below 2^24: exact in a float)
  *
  * Pixel noise: with u_var_prime == v_var_prime (the configuration the throughput metric is quoted on) the update is
  * independent of the null-space basis and of the compression order and matches the reference to rounding.  With
@@ -240,6 +250,34 @@ int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double
  * own frame count, so that the records of their skipped tail stay out.  gt_p[max(r1) - min(r0)][B][3] is indexed from
  * min(r0); "|e| at record r1 - 1" is at r1[b] - 1.  With every range equal: the bits of msckf_hip_frame_log_metrics. */
 int msckf_hip_frame_log_metrics_ranges(msckf_hip_handle h, const int* r0, const int* r1, const double* gt_p, double* out);
+/* ---- per-track device log of msckf_hip_run_frames / _streamed: the landmark map (off by default) ------- */
+/* Storage for capacity_per_trajectory records ("map log record" above) of every trajectory, in the handle's dtype, and a
+ * cursor per trajectory; 0 frees the log and disables it.  Any call drops the records held so far.  -ENOMEM when the allocation
+ * fails: the log is then off and the handle as usable as before.  While the log is on, every frame of a run_frames /
+ * run_frames_streamed call ends with one small extra launch per stream that appends the frame's logged tracks, in track order,
+ * behind the trajectory's records -- it reads the filter's arrays and writes only the log, so the filter computes the same
+ * bits with and without it.  A trajectory that finds more than its capacity keeps the first capacity_per_trajectory records
+ * in (frame, track) order and goes on counting (msckf_hip_map_log_counts).  A skipped cell and a cell without tracks log
+ * nothing; the frame ordinal advances all the same.  Only run_frames / run_frames_streamed write the log (the per-filter
+ * entries and msckf_hip_image_cycle_range return their map through msckf_hip_get_map); msckf_hip_copy_state does not copy it. */
+int msckf_hip_map_log_enable(msckf_hip_handle h, int capacity_per_trajectory);
+int msckf_hip_map_log_reset(msckf_hip_handle h);    /* cursors and frame ordinal <- 0 (the storage stays) */
+int msckf_hip_map_log_frames(msckf_hip_handle h);   /* frame ordinals handed out; advances when a run_frames call has succeeded */
+/* Trajectories [b0, b0 + nb): found[i] records found, stored[i] = min(found[i], capacity) of them held; found > stored: the log
+ * overflowed.  Waits for the handle's stream.  -EINVAL while the log is off. */
+int msckf_hip_map_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found);
+/* Stored records [r0, r0 + n) of trajectory b as doubles, out[n][8].  -EINVAL for a range beyond stored (and while the log is
+ * off), -EIO on a handle that a failed run_frames call left unusable. */
+int msckf_hip_map_log_read(msckf_hip_handle h, int b, int r0, int n, double* out);
+/* The stored records with frame ordinal in [q0, q1) (0 <= q0 <= q1 <= msckf_hip_map_log_frames) reduced on the device.
+ * Ground truth: gt_off[(q1 - q0) * B + 1] is CSR over the cells (frame - q0) * B + b, non-decreasing (else -EINVAL); the
+ * landmark of a record is gt_xyz[gt_off[cell] + track][3].  gt_xyz and gt_off both null: no ground truth.
+ * out[B][8] = per trajectory: 0 records in range, 1 records matched to ground truth, 2 sum |e|^2 and 3 max |e| over those
+ * (e = p_f_G - landmark), 4 gate-passed records that do not carry flag 4, 5 sum of gamma and 6 sum of 2 M - 3 over those,
+ * 7 records whose track index is >= their cell's CSR length (unmatched, left out of the error sums).  Accumulated in double
+ * in a fixed order: the same log gives the same bits.  Sums and counts, so that ranks combine by addition; mean normalised
+ * gate statistic = column 5 / column 6 (1 for a consistent filter). */
+int msckf_hip_map_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_xyz, const int* gt_off, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

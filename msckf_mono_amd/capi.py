@@ -37,6 +37,7 @@ SYMBOLS = [
     "msckf_hip_image_cycle_range",
     "msckf_hip_frame_log_enable", "msckf_hip_frame_log_reset", "msckf_hip_frame_log_count", "msckf_hip_frame_log_read", "msckf_hip_frame_log_metrics",
     "msckf_hip_scenario_set_cell", "msckf_hip_propagate_range_counts", "msckf_hip_frame_log_metrics_ranges",
+    "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -50,6 +51,12 @@ FRAME_LOG_FIELDS = {
 }
 # columns of frame_log_metrics' result
 FRAME_LOG_METRICS = ("n", "sum_sq_err", "max_err", "final_err", "sum_nees", "n_flagged")
+# fields of a map-log record (include/msckf_hip.h, "map log record"): name -> slice of its 8 scalars
+MAP_LOG_STRIDE = 8
+MAP_LOG_FIELDS = {"p": slice(0, 3), "gamma": slice(3, 4), "frame": slice(4, 5), "track": slice(5, 6), "flags": slice(6, 7), "M": slice(7, 8)}
+MAP_FLAG_PASS, MAP_FLAG_INCLUDED, MAP_FLAG_BOUND = 1, 2, 4   # bits of "flags": gate passed, included in the update, gamma is the early-accept bound
+# columns of map_log_metrics' result
+MAP_LOG_METRICS = ("n", "n_matched", "sum_sq_err", "max_err", "n_gated", "sum_gamma", "sum_dof", "n_unmatched")
 
 
 def build():
@@ -420,6 +427,46 @@ class Batch:
             raise ValueError("gt_p must be [max(r1) - min(r0)][B][3]")
         o = np.zeros((self.B, 6))
         _chk(self.L.msckf_hip_frame_log_metrics_ranges(self.h, p0, p1, g.ctypes.data_as(_dp), o.ctypes.data_as(_dp)))
+        return o
+
+    # ---- per-track device log of run_frames / run_frames_streamed: the landmark map
+    def map_log_enable(self, capacity_per_trajectory):
+        """storage for capacity_per_trajectory records per trajectory (0: free the log and switch it off); drops the records held"""
+        _chk(self.L.msckf_hip_map_log_enable(self.h, int(capacity_per_trajectory)))
+
+    def map_log_reset(self):
+        _chk(self.L.msckf_hip_map_log_reset(self.h))
+
+    def map_log_frames(self):
+        return _chk(self.L.msckf_hip_map_log_frames(self.h))
+
+    def map_log_counts(self, b0=0, nb=None):
+        """(stored, found) of trajectories [b0, b0 + nb) (default: all); found > stored: the trajectory's log overflowed"""
+        nb = self.B - b0 if nb is None else int(nb)
+        s = np.zeros(max(nb, 0), dtype=np.int32); f = np.zeros(max(nb, 0), dtype=np.int32)
+        _chk(self.L.msckf_hip_map_log_counts(self.h, int(b0), nb, s.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
+        return s, f
+
+    def map_log_read(self, b, r0=0, n=None):
+        """stored records [r0, r0 + n) (default: all behind r0) of trajectory b: the array [n][8] and a dict of views into it by
+        field name (MAP_LOG_FIELDS)"""
+        n = int(self.map_log_counts(b, 1)[0][0]) - r0 if n is None else int(n)
+        o = np.zeros((max(n, 0), MAP_LOG_STRIDE))
+        _chk(self.L.msckf_hip_map_log_read(self.h, int(b), int(r0), n, o.ctypes.data_as(_dp)))
+        return o, {k: o[:, s] for k, s in MAP_LOG_FIELDS.items()}
+
+    def map_log_metrics(self, q0, q1, gt=None):
+        """the stored records with frame ordinal in [q0, q1), reduced on the device: [B][8], columns MAP_LOG_METRICS (sums and
+        counts).  gt: (gt_xyz [.][3], gt_off [(q1 - q0) * B + 1]) as scenario.landmark_csr builds them, or None"""
+        o = np.zeros((self.B, 8))
+        if gt is None:
+            _chk(self.L.msckf_hip_map_log_metrics(self.h, int(q0), int(q1), None, None, o.ctypes.data_as(_dp)))
+            return o
+        g = np.ascontiguousarray(gt[0], dtype=np.float64).reshape(-1, 3)
+        off, po = _i(gt[1])
+        if off.shape != ((int(q1) - int(q0)) * self.B + 1,) or (off.size and int(off[-1]) > len(g)):
+            raise ValueError("gt_off must hold (q1 - q0) * B + 1 offsets into gt_xyz")
+        _chk(self.L.msckf_hip_map_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), po, o.ctypes.data_as(_dp)))
         return o
 
     def profile_enable(self, on=True):

@@ -58,6 +58,10 @@ enum { STAT_ERR_NCAP = 1, STAT_ERR_PIVOT = 2 };
 // position block P[12..14][12..14] (xx xy xz yy yz zz), the window size, STAT_NTRACKS / STAT_PASSED / STAT_ERR (integers below
 // 2^24: exact in a float), the pose of camera slot 0 (q_CG p_C_G: the oldest surviving camera; zeros when the window is empty)
 enum { LOG_IMU = 0, LOG_PII = 16, LOG_PPP = 31, LOG_NCAM = 37, LOG_STATS = 38, LOG_CAM0 = 41, LOG_STRIDE = 48 };
+// map log (kernels_log.hip; msckf_hip_map_log_*): one record of MAP_STRIDE scalars per track of a frame whose triangulation
+// the reference would put into map_ (msckf.h:371): p_f_G, gamma, frame ordinal, track index, flags, observation count
+enum { MAP_PF = 0, MAP_GAMMA = 3, MAP_FRAME = 4, MAP_TRACK = 5, MAP_FLAGS = 6, MAP_M = 7, MAP_STRIDE = 8 };
+enum { MAP_FLAG_PASS = 1, MAP_FLAG_INCLUDED = 2, MAP_FLAG_BOUND = 4 };
 
 // work space of the literal anisotropic compression (kernels_literal.hip / literal_core.h), per trajectory; null when no
 // trajectory of the batch uses it
@@ -527,6 +531,8 @@ template <class S> bool launch_chol_gain_large(const Dev<S>& d, int b0, int nb, 
 // [r0, r1) of a log against ground-truth positions gt[r1 - r0][B][3] into out[B][6] (both device pointers)
 template <class S> void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec);
 template <class S> void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, double* out, hipStream_t st);
+template <class S> void launch_map_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* n, const int* M, int ordinal, int cap, S* rec, int* found);
+template <class S> void launch_map_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const double* gt, const int* off, double* out, hipStream_t st);
 size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged = false);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();

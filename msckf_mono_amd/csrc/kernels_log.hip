@@ -5,6 +5,8 @@
 // record of LOG_STRIDE scalars per trajectory.  It runs on the slice's stream after the frame's update and prune, only
 // reads the filter's arrays and only writes the log: the filter cannot see whether it ran.
 // k_log_metrics reduces a range of records against ground-truth positions: the sums behind ATE and NEES, per trajectory.
+// k_map_log is the per-track counterpart: the frame's triangulated landmarks with their gate statistics, compacted inside
+// the wavefront behind a per-trajectory cursor; k_map_metrics reduces them against ground-truth landmarks.
 #include "dev_common.h"
 
 namespace msckf {
@@ -85,6 +87,99 @@ __global__ __launch_bounds__(64) void k_log_metrics(const S* log, int B, int r0,
   }
 }
 
+// The map log: the frame's triangulated landmarks and gate statistics, one record of MAP_STRIDE scalars per track that
+// append_map (host_lists.h) would take -- motion check passed or skipped, triangulation valid -- compacted in track order
+// behind the trajectory's cursor found[b].  One wavefront per trajectory, four per workgroup, launched for the slice
+// [b0, b0 + nb) after the frame's update; n / M: the work-list counts the update read (already offset to b0).  A skipped cell
+// has n == 0, so nothing of the stale per-track arrays is logged.  Record index (include/msckf_hip.h, "map log record"):
+//   0..2 p_f_G | 3 gamma | 4 frame ordinal | 5 track index | 6 flags (1 gate passed, 2 included, 4 gamma is the early-accept
+//   bound) | 7 M
+// The wavefront walks the tracks in chunks of 64: ballot of the keep flag, rank = kept lanes below, destination = cursor +
+// kept of the earlier chunks + rank.  A destination >= cap is counted but not stored, so the records stored are the first
+// cap in (frame, track) order.  The trajectory belongs to one slice and its frames are ordered on that slice's stream: lane 0
+// reads the cursor and stores it back, no atomics.
+template <class S>
+__global__ __launch_bounds__(256) void k_map_log(Dev<S> d, int b0, int nb, const int* n, const int* M, int ordinal, int cap, S* rec, int* found) {
+  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (i >= nb) return;   // (whole wavefronts)
+  const int b = b0 + i;
+  const int F = min(max(n[i], 0), d.f_cap);
+  if (F == 0) return;
+  int cur = 0;
+  if (lane == 0) cur = found[b];
+  long base = wave_bcast(cur, 0);
+  const long first = (long)b * cap;
+  for (int t0 = 0; t0 < F; t0 += 64) {
+    const int t = t0 + lane;
+    const long tb = (long)b * d.f_cap + t;
+    const int st = t < F ? d.trk_status[tb] : 0;
+    const bool keep = (st & (ST_MOTION_OK | ST_MOTION_SKIPPED)) && (st & ST_TRI_VALID);
+    const unsigned long long mask = __ballot(keep ? 1 : 0);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    const long dst = base + rank;
+    if (keep && dst < cap) {
+      Vec4<S> a = *reinterpret_cast<const Vec4<S>*>(d.trk_pf + tb * 4), c;
+      a.x[3] = d.trk_gamma[tb];
+      c.x[0] = (S)ordinal; c.x[1] = (S)t;
+      c.x[2] = (S)(((st & ST_GATE_PASS) ? MAP_FLAG_PASS : 0) | ((st & ST_INCLUDED) ? MAP_FLAG_INCLUDED : 0) | ((st & ST_GATE_BOUND) ? MAP_FLAG_BOUND : 0));
+      c.x[3] = (S)M[(long)i * d.f_cap + t];
+      Vec4<S>* o = reinterpret_cast<Vec4<S>*>(rec + (first + dst) * MAP_STRIDE);
+      o[0] = a; o[1] = c;
+    }
+    base += __popcll(mask);
+  }
+  if (lane == 0) found[b] = (int)min(base, (long)INT32_MAX);
+}
+
+// One workgroup (one wavefront) per trajectory over the stored records of the map log whose frame ordinal lies in [q0, q1).
+// Ground truth (gt and off both null: none): off is CSR over the cells (frame - q0) * B + b, the landmark of a record is
+// gt[off[cell] + track]; a record whose track index is >= its cell's length is unmatched.
+// out[b][8] = records in range, matched, sum |e|^2, max |e|, gate-passed records whose gamma is not the early-accept bound,
+// sum of gamma and sum of 2 M - 3 over those, unmatched.  All in f64; lane l takes the records l, l + 64, ... in ascending
+// order and the lanes are combined by wave_sum's fixed tree: the same log gives the same bits on every call.
+template <class S>
+__global__ __launch_bounds__(64) void k_map_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const double* gt, const int* off, double* out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = min(max(found[b], 0), cap);
+  double cnt = 0, nm = 0, s2 = 0, mx = 0, ng = 0, sg = 0, sd = 0, un = 0;
+  for (int r = lane; r < n; r += 64) {
+    const Vec4<S>* q = reinterpret_cast<const Vec4<S>*>(rec + ((long)b * cap + r) * MAP_STRIDE);
+    const Vec4<S> a = q[0], c = q[1];
+    const int fr = (int)c.x[0], trk = (int)c.x[1], flags = (int)c.x[2];
+    if (fr < q0 || fr >= q1) continue;
+    cnt += 1.0;
+    if (gt) {
+      const long cell = (long)(fr - q0) * B + b;
+      const int o0 = off[cell], len = off[cell + 1] - o0;
+      if (trk >= len) un += 1.0;
+      else {
+        const double* g = gt + ((long)o0 + trk) * 3;
+        const double e0 = (double)a.x[0] - g[0], e1 = (double)a.x[1] - g[1], e2 = (double)a.x[2] - g[2];
+        const double d2 = e0 * e0 + e1 * e1 + e2 * e2, dist = sqrt(d2);
+        nm += 1.0; s2 += d2;
+        mx = dist > mx ? dist : mx;
+      }
+    }
+    if ((flags & MAP_FLAG_PASS) && !(flags & MAP_FLAG_BOUND)) { ng += 1.0; sg += (double)a.x[3]; sd += 2.0 * (double)c.x[3] - 3.0; }
+  }
+  cnt = wave_sum(cnt); nm = wave_sum(nm); s2 = wave_sum(s2); mx = wave_max(mx); ng = wave_sum(ng); sg = wave_sum(sg); sd = wave_sum(sd); un = wave_sum(un);
+  if (lane == 0) {
+    double* o = out + (long)b * 8;
+    o[0] = cnt; o[1] = nm; o[2] = s2; o[3] = mx; o[4] = ng; o[5] = sg; o[6] = sd; o[7] = un;
+  }
+}
+
+template <class S>
+void launch_map_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* n, const int* M, int ordinal, int cap, S* rec, int* found) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(k_map_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, n, M, ordinal, cap, rec, found);
+}
+template <class S>
+void launch_map_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const double* gt, const int* off, double* out, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_map_metrics<S>, dim3(B), dim3(64), 0, st, rec, found, cap, B, q0, q1, gt, off, out);
+}
+
 template <class S>
 void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec) {
   if (nb <= 0) return;
@@ -100,5 +195,9 @@ template void launch_frame_log<float>(const Dev<float>&, int, int, hipStream_t, 
 template void launch_frame_log<double>(const Dev<double>&, int, int, hipStream_t, const double*, bool, double*);
 template void launch_log_metrics<float>(const float*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
 template void launch_log_metrics<double>(const double*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
+template void launch_map_log<float>(const Dev<float>&, int, int, hipStream_t, const int*, const int*, int, int, float*, int*);
+template void launch_map_log<double>(const Dev<double>&, int, int, hipStream_t, const int*, const int*, int, int, double*, int*);
+template void launch_map_metrics<float>(const float*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
+template void launch_map_metrics<double>(const double*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
 
 }  // namespace msckf

@@ -224,6 +224,11 @@ struct BatchCore {
   // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
   // (log_base = log_n at its start, read by the slices' enqueue threads) and advances log_n when it has succeeded
   void* log_buf = nullptr; int log_cap = 0, log_n = 0, log_base = 0;
+  // map log (msckf_hip_map_log_*; kernels_log.hip): [B][map_cap][MAP_STRIDE] scalars of esz bytes and the device cursors
+  // map_found[B] (records found per trajectory, stored or not), null unless enabled.  map_ord counts the frame ordinals handed
+  // out; a run_frames / run_frames_streamed call over [f0, f1) stamps its records with map_base + (f - f0) (map_base = map_ord
+  // at its start) and advances map_ord when it has succeeded
+  void* map_buf = nullptr; int* map_found = nullptr; int map_cap = 0, map_ord = 0, map_base = 0;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[NSTAGE];
@@ -264,6 +269,8 @@ struct BatchCore {
     if (st) hipStreamSynchronize(st);
     for (void* p : allocs) hipFree(p);
     if (log_buf) hipFree(log_buf);
+    if (map_buf) hipFree(map_buf);
+    if (map_found) hipFree(map_found);
     if (h_rb) hipHostFree(h_rb);
     for (int s = 0; s < NSTAGE; ++s) for (auto& e : ev_pool[s]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int i = 1; i < MAXS; ++i) { if (stx[i]) hipStreamDestroy(stx[i]); if (ev_join[i]) hipEventDestroy(ev_join[i]); }
@@ -654,6 +661,7 @@ struct BatchCore {
       if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
     commit_buffer_parity(f0, f1);
     if (log_buf) log_n += f1 - f0;
+    if (map_buf) map_ord += f1 - f0;
     return 0;
   }
   // ---- frame log
@@ -684,11 +692,81 @@ struct BatchCore {
     log_base = log_n;
     return 0;
   }
+  // ---- map log
+  // capacity_per_trajectory records for every trajectory and a cursor each, or (0) none: frees a log that exists either way
+  // and drops its records.  An allocation that fails leaves the log off and the handle as it was
+  int map_log_enable(int capacity) {
+    if (int rc = guard()) return rc;
+    if (capacity < 0) return fail(-EINVAL, "negative capacity");
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if (map_buf) (void)hipFree(map_buf);
+    if (map_found) (void)hipFree(map_found);
+    map_buf = nullptr; map_found = nullptr; map_cap = 0; map_ord = 0;
+    if (!capacity) return 0;
+    void* q = nullptr; void* c = nullptr;
+    if (hipMalloc(&q, (size_t)capacity * B * MAP_STRIDE * esz) != hipSuccess || hipMalloc(&c, (size_t)B * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (q) (void)hipFree(q);
+      return fail(-ENOMEM, "could not allocate the map log (it stays disabled; the handle is unaffected)");
+    }
+    if (hipMemsetAsync(c, 0, (size_t)B * sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(q); (void)hipFree(c);
+      return fail(-EIO, "could not clear the map log's cursors (it stays disabled)");
+    }
+    map_buf = q; map_found = static_cast<int*>(c); map_cap = capacity;
+    return 0;
+  }
+  // cursors and frame ordinal <- 0 (the storage stays); ordered on st before the next call's frames
+  int map_log_reset() {
+    if (int rc = guard()) return rc;
+    map_ord = 0;
+    if (!map_buf) return 0;
+    if (int rc = enter()) return rc;
+    HIPCHK(hipMemsetAsync(map_found, 0, (size_t)B * sizeof(int), st));
+    return 0;
+  }
+  int map_log_frames() const { return map_ord; }
+  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's ordinals start at map_ord and stay exact
+  // in a float record
+  int map_log_reserve(int f0, int f1) {
+    if (!map_buf) return 0;
+    if ((long)map_ord + (f1 - f0) > (1L << 24)) return fail(-ENOSPC, "map log: the call's frame ordinals would pass 2^24 (msckf_hip_map_log_reset); nothing was run");
+    map_base = map_ord;
+    return 0;
+  }
+  // after the handle's stream: per trajectory of [b0, b0 + nb) the records found and how many of them are stored
+  int map_log_counts(int b0, int nb, int* stored, int* found) {
+    if (int rc = guard()) return rc;
+    if (!map_buf) return fail(-EINVAL, "map log not enabled (msckf_hip_map_log_enable)");
+    if (int rc = enter_range(b0, nb)) return rc;
+    std::vector<int> tmp(std::max(nb, 1));
+    if (nb) HIPCHK(hipMemcpyAsync(tmp.data(), map_found + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < nb; ++i) {
+      if (found) found[i] = tmp[i];
+      if (stored) stored[i] = std::min(tmp[i], map_cap);
+    }
+    return 0;
+  }
+  // what map_log_metrics checks before anything reaches the device: the ordinal range, and off as CSR over its cells
+  int map_log_check_gt(int q0, int q1, const double* gt_xyz, const int* gt_off) {
+    if (!map_buf) return fail(-EINVAL, "map log not enabled (msckf_hip_map_log_enable)");
+    if (q0 < 0 || q1 < q0 || q1 > map_ord) return fail(-EINVAL, "frame ordinal range beyond the ordinals handed out (msckf_hip_map_log_frames)");
+    if ((gt_xyz == nullptr) != (gt_off == nullptr)) return fail(-EINVAL, "gt_xyz and gt_off: both or neither");
+    if (!gt_off) return 0;
+    const size_t cells = (size_t)(q1 - q0) * B;
+    if (gt_off[0] < 0) return fail(-EINVAL, "gt_off starts below 0");
+    for (size_t c = 0; c < cells; ++c)
+      if (gt_off[c + 1] < gt_off[c]) return fail(-EINVAL, "gt_off decreases at cell " + std::to_string(c) + " (CSR offsets over the cells (frame - q0) * B + b)");
+    return 0;
+  }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = frame_log_reserve(f0, f1)) return rc;
+    if (int rc = map_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     const int nh = n_slices();
     const int rc = fork_slices(nh);
@@ -720,6 +798,7 @@ struct BatchCore {
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = frame_log_reserve(f0, f1)) return rc;
+    if (int rc = map_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     {
       bool all = sg_blk[0] != nullptr;
@@ -896,6 +975,8 @@ struct BatchCore {
     }
     return frame_log_metrics(lo, hi, gt_p, out, r0b, r1b);
   }
+  virtual int map_log_read(int b, int r0, int n, double* out) = 0;                              // [n][MAP_STRIDE]
+  virtual int map_log_metrics(int q0, int q1, const double* gt_xyz, const int* gt_off, double* out) = 0;   // out [B][8]
 };
 
 int resolve_map(BatchCore* B, int b);   // (defined with the host-side bookkeeping below)
@@ -1677,6 +1758,9 @@ struct Batch : BatchCore {
     // frame log: the state the frame leaves -- the covariance buffer that is current after the flip, the window size where the
     // prune left it (ncam_upd while it is pending) -- as record log_base + (f - f0); outside the stage timers
     if (log_buf) launch_frame_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, s.pending, static_cast<S*>(log_buf) + (size_t)(log_base + (f - f0)) * B * LOG_STRIDE);
+    // map log: the tracks of the work-list the update read (in.n, in.M: resident or staged) with frame ordinal
+    // map_base + (f - f0), behind the trajectories' cursors; also outside the stage timers
+    if (map_buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map_base + (f - f0), map_cap, static_cast<S*>(map_buf), map_found);
     for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment (not for a skipped cell), then drop n_drop (clamped as k_make_keep does)
       if (h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP) h_ncam[b]++;
       h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
@@ -1715,6 +1799,39 @@ struct Batch : BatchCore {
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dg);
     if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("frame_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // stored records [r0, r0 + n) of trajectory b as doubles: the cursor first (a range beyond min(found, capacity) is refused),
+  // then one copy
+  int map_log_read(int b, int r0, int n, double* out) override {
+    int stored = 0;
+    if (int rc = map_log_counts(b, 1, &stored, nullptr)) return rc;
+    if (r0 < 0 || n < 0 || (long)r0 + n > stored) return fail(-EINVAL, "record range beyond the records stored (msckf_hip_map_log_counts)");
+    if (!n) return 0;
+    std::vector<S> tmp((size_t)n * MAP_STRIDE);
+    if (const int rc = read_back(tmp.data(), static_cast<const S*>(map_buf) + ((size_t)b * map_cap + r0) * MAP_STRIDE, tmp.size() * sizeof(S))) return rc;
+    for (size_t i = 0; i < tmp.size(); ++i) out[i] = (double)tmp[i];
+    return 0;
+  }
+  // the stored records with frame ordinal in [q0, q1) against ground-truth landmarks (CSR per cell; both null: none), reduced on
+  // the device (k_map_metrics): per trajectory records, matched, sum |e|^2, max |e|, gated records with their own gamma,
+  // sum gamma, sum 2 M - 3, unmatched
+  int map_log_metrics(int q0, int q1, const double* gt_xyz, const int* gt_off, double* out) override {
+    if (int rc = guard()) return rc;
+    if (int rc = map_log_check_gt(q0, q1, gt_xyz, gt_off)) return rc;
+    if (int rc = enter()) return rc;
+    const size_t cells = (size_t)(q1 - q0) * B, noff = gt_off ? cells + 1 : 0, ng = gt_off ? (size_t)gt_off[cells] * 3 : 0, no = (size_t)B * 8;
+    double* dg = nullptr;                                      // [ground truth | out | off], freed on every way out
+    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + std::max<size_t>(noff, 1) * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
+    double* dout = dg + std::max<size_t>(ng, 1);
+    int* doff = reinterpret_cast<int*>(dout + no);
+    hipError_t e = ng ? hipMemcpyAsync(dg, gt_xyz, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess && noff) e = hipMemcpyAsync(doff, gt_off, noff * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { launch_map_metrics<S>(static_cast<const S*>(map_buf), map_found, map_cap, B, q0, q1, gt_off ? dg : nullptr, gt_off ? doff : nullptr, dout, st); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dg);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("map_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
     return 0;
   }
 };
@@ -2274,6 +2391,12 @@ int msckf_hip_frame_log_count(msckf_hip_handle h) { if (!h) return fail(-EINVAL,
 int msckf_hip_frame_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_read(r0, n, b0, nb, out); }
 int msckf_hip_frame_log_metrics(msckf_hip_handle h, int r0, int r1, const double* gt_p, double* out) { if (!h || !gt_p || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_metrics(r0, r1, gt_p, out); }
 int msckf_hip_frame_log_metrics_ranges(msckf_hip_handle h, const int* r0, const int* r1, const double* gt_p, double* out) { if (!h || !r0 || !r1 || !gt_p || !out) return fail(-EINVAL, "null argument"); return H(h)->frame_log_metrics_ranges(r0, r1, gt_p, out); }
+int msckf_hip_map_log_enable(msckf_hip_handle h, int capacity_per_trajectory) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->map_log_enable(capacity_per_trajectory); }
+int msckf_hip_map_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->map_log_reset(); }
+int msckf_hip_map_log_frames(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->map_log_frames(); }
+int msckf_hip_map_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found) { if (!h || !stored || !found) return fail(-EINVAL, "null argument"); return H(h)->map_log_counts(b0, nb, stored, found); }
+int msckf_hip_map_log_read(msckf_hip_handle h, int b, int r0, int n, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_read(b, r0, n, out); }
+int msckf_hip_map_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_xyz, const int* gt_off, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_metrics(q0, q1, gt_xyz, gt_off, out); }
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"

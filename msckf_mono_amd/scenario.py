@@ -178,6 +178,17 @@ def imu29_from_gt(gt_at_t, b_g, b_a):
     return np.concatenate([q, b_g, v, b_a, p, GRAVITY, q, v, p])
 
 
+def landmark_csr(trajs, f0, f1):
+    """Ground-truth landmarks of the frames [f0, f1) of a batch, as Batch.map_log_metrics takes them: (gt_xyz [.][3], gt_off)
+    with gt_off CSR over the cells (frame - f0) * B + b -- track t of trajectory b on frame k observes
+    gt_xyz[gt_off[(k - f0) * B + b] + t] = trajs[b].landmarks[k][t]."""
+    cells = [np.asarray(tr.landmarks[k], dtype=np.float64).reshape(-1, 3) for k in range(f0, f1) for tr in trajs]
+    off = np.zeros(len(cells) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(c) for c in cells])
+    xyz = np.concatenate(cells) if cells else np.zeros((0, 3))
+    return np.ascontiguousarray(xyz), off
+
+
 class Trajectory:
     """One seeded trajectory: IMU stream + per-frame ending-track work-lists."""
 
