@@ -1025,7 +1025,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LONG ? 1 : (
 // The gate products G = H_x P_cc H_x^T of both tracks are enumerated together over the 64 lanes (pairs of observations),
 // the two Cholesky factorizations run one after the other on the full 8 x 8 lane grid (gate_chol, as in k_feature).
 // Same arithmetic per track as k_feature<float> (sums over a half instead of the wavefront: identical terms, the zeros
-// of the idle lanes fall elsewhere in the tree); decisions and gamma agree to rounding (tests/test_gpu_parity.py A/B).
+// of the idle lanes fall elsewhere in the tree); decisions and gamma agree to rounding (tests/test_gpu_feature_kernels.py).
 constexpr int GS = 32;   // lanes per track: the sums over a track are dev_common.h's half_sum / half_max / half_min_i
 #ifdef MSCKF_ABLATE
 // phase timers of the -DMSCKF_ABLATE build (scripts/feat_phases.py): shader-clock cycles per phase summed over ALL wavefronts
