@@ -44,6 +44,15 @@
  *                  (msckf_hip_set_gate_early_accept), not the statistic
  *            7     M, the track's observation count
  *            (4-7 are integers below 2^24: exact in a float)
+ *   pruned-state log record, 32 scalars per camera state that a frame drops, as the frame's update leaves it (before the prune):
+ *            0-6   cam7 of the dropped state: its last, fully corrected pose -- the fixed-lag smoothed estimate
+ *            7     prune frame ordinal: frames run since msckf_hip_pruned_log_enable / _reset
+ *            8-28  upper triangle of the state's 6 x 6 posterior covariance block (error-state order th_C p_C), row by row:
+ *                  (0,0) (0,1) .. (0,5) (1,1) .. (1,5) (2,2) .. (5,5)
+ *            29    window size before the prune
+ *            30    k: the state is the k-th oldest of those the frame drops (its camera slot before the prune)
+ *            31    0
+ *            (7, 29, 30 are integers below 2^24: exact in a float)
  *
  * Pixel noise: with u_var_prime == v_var_prime (the configuration the throughput metric is quoted on) the update is
  * independent of the null-space basis and of the compression order and matches the reference to rounding.  With
@@ -278,6 +287,41 @@ int msckf_hip_map_log_read(msckf_hip_handle h, int b, int r0, int n, double* out
  * in a fixed order: the same log gives the same bits.  Sums and counts, so that ranks combine by addition; mean normalised
  * gate statistic = column 5 / column 6 (1 for a consistent filter). */
 int msckf_hip_map_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_xyz, const int* gt_off, double* out);
+/* ---- pruned-state device log of msckf_hip_run_frames / _streamed: the smoothed camera poses (off by default) ------- */
+/* Storage for capacity_per_trajectory records ("pruned-state log record" above) of every trajectory, in the handle's dtype, and
+ * a cursor per trajectory; 0 frees the log and disables it.  Any call drops the records held so far.  -EINVAL for a negative
+ * capacity, -ENOMEM when the allocation fails: the log is then off and the handle as usable as before.  While the log is on,
+ * every frame of a run_frames / run_frames_streamed call prunes with its own launch (no prune rides on the covariance downdate:
+ * one more launch per frame and stream than with the log off) and one small launch before it appends every camera state the
+ * frame is about to drop (the cell's n_drop oldest), oldest first, behind the trajectory's records: what getPrunedStates()
+ * (msckf.h:631, 714) keeps, with the posterior covariance block added.  It reads the filter's arrays and writes only the log,
+ * and a prune of its own computes the bits of one that rides: the filter's results are the same with and without the log.
+ * A trajectory that drops more than its capacity keeps the first capacity_per_trajectory records and goes on counting.  A
+ * skipped cell and a cell that drops nothing log nothing; the frame ordinal advances all the same.  Only run_frames /
+ * run_frames_streamed write the log; msckf_hip_copy_state does not copy it. */
+int msckf_hip_pruned_log_enable(msckf_hip_handle h, int capacity_per_trajectory);
+int msckf_hip_pruned_log_reset(msckf_hip_handle h);    /* cursors and frame ordinal <- 0 (the storage stays) */
+int msckf_hip_pruned_log_frames(msckf_hip_handle h);   /* frame ordinals handed out; advances when a run_frames call has succeeded */
+/* Trajectories [b0, b0 + nb): found[i] states dropped, stored[i] = min(found[i], capacity) of them held.  Waits for the handle's
+ * stream.  -EINVAL while the log is off. */
+int msckf_hip_pruned_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found);
+/* Stored records [r0, r0 + n) of trajectory b as doubles, out[n][32], and aug_ord[n]: per record the ordinal of the frame whose
+ * augmentState created the state (run_frames drops oldest-first, so the host keeps the window's ordinals in a queue), or -1
+ * for a state that was in the window when the log was enabled or reset, or that another call than run_frames /
+ * run_frames_streamed put there.  -EINVAL for a range beyond stored (and while the log is off), -EIO on a handle that a failed
+ * run_frames call left unusable. */
+int msckf_hip_pruned_log_read(msckf_hip_handle h, int b, int r0, int n, double* out, int* aug_ord);
+/* The stored records with prune ordinal in [q0, q1) (0 <= q0 <= q1 <= msckf_hip_pruned_log_frames) against ground-truth camera
+ * poses gt_pose[n_ord][B][7] (cam7 of the camera of frame ordinal o, trajectory b), reduced on the device.  A record is matched
+ * through its augment ordinal; -1 or >= n_ord: unmatched.  n_ord < 0, or a null gt_pose with n_ord > 0: -EINVAL.
+ * Pose error e = [e_th ; e_p]: e_p = p_C_G - p_gt; e_th is the error-state angle of the filter's own update (buildUpdateQuat,
+ * msckf.h:851-872): q_CG = buildUpdateQuat(e_th) * q_gt, e_th = -2 vec(q_CG * q_gt^-1) with a non-negative scalar part.
+ * out[B][10] = per trajectory: 0 records in range, 1 matched, 2 sum |e_p|^2, 3 max |e_p|, 4 sum |e_th|^2, 5 max |e_th|,
+ * 6 sum e^T P6^-1 e over the matched records whose logged block has a Cholesky factor, 7 their number, 8 matched records with
+ * a non-positive pivot (left out of 6), 9 unmatched.  Accumulated in double in a fixed order: the same log gives the same bits.
+ * Sums and counts, so that ranks combine by addition: position ATE = sqrt(col 2 / col 1), mean NEES = col 6 / col 7 (6 for a
+ * consistent filter). */
+int msckf_hip_pruned_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_pose, int n_ord, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

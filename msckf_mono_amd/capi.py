@@ -38,6 +38,7 @@ SYMBOLS = [
     "msckf_hip_frame_log_enable", "msckf_hip_frame_log_reset", "msckf_hip_frame_log_count", "msckf_hip_frame_log_read", "msckf_hip_frame_log_metrics",
     "msckf_hip_scenario_set_cell", "msckf_hip_propagate_range_counts", "msckf_hip_frame_log_metrics_ranges",
     "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
+    "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -57,6 +58,12 @@ MAP_LOG_FIELDS = {"p": slice(0, 3), "gamma": slice(3, 4), "frame": slice(4, 5), 
 MAP_FLAG_PASS, MAP_FLAG_INCLUDED, MAP_FLAG_BOUND = 1, 2, 4   # bits of "flags": gate passed, included in the update, gamma is the early-accept bound
 # columns of map_log_metrics' result
 MAP_LOG_METRICS = ("n", "n_matched", "sum_sq_err", "max_err", "n_gated", "sum_gamma", "sum_dof", "n_unmatched")
+# fields of a pruned-state log record (include/msckf_hip.h, "pruned-state log record"): name -> slice of its 32 scalars
+PRUNED_LOG_STRIDE = 32
+PRUNED_LOG_FIELDS = {"q": slice(0, 4), "p": slice(4, 7), "frame": slice(7, 8), "cov": slice(8, 29),   # cov: upper triangle of the 6 x 6 block, row by row
+                     "n_cam": slice(29, 30), "k": slice(30, 31), "pad": slice(31, 32)}
+# columns of pruned_log_metrics' result
+PRUNED_LOG_METRICS = ("n", "n_matched", "sum_sq_pos_err", "max_pos_err", "sum_sq_ang_err", "max_ang_err", "sum_nees", "n_nees", "n_bad_pivot", "n_unmatched")
 
 
 def build():
@@ -467,6 +474,47 @@ class Batch:
         if off.shape != ((int(q1) - int(q0)) * self.B + 1,) or (off.size and int(off[-1]) > len(g)):
             raise ValueError("gt_off must hold (q1 - q0) * B + 1 offsets into gt_xyz")
         _chk(self.L.msckf_hip_map_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), po, o.ctypes.data_as(_dp)))
+        return o
+
+    # ---- pruned-state device log of run_frames / run_frames_streamed: the smoothed camera poses
+    def pruned_log_enable(self, capacity_per_trajectory):
+        """storage for capacity_per_trajectory records per trajectory (0: free the log, switch it off and give the prune on the
+        downdate back); drops the records held"""
+        _chk(self.L.msckf_hip_pruned_log_enable(self.h, int(capacity_per_trajectory)))
+
+    def pruned_log_reset(self):
+        _chk(self.L.msckf_hip_pruned_log_reset(self.h))
+
+    def pruned_log_frames(self):
+        return _chk(self.L.msckf_hip_pruned_log_frames(self.h))
+
+    def pruned_log_counts(self, b0=0, nb=None):
+        """(stored, found) of trajectories [b0, b0 + nb) (default: all); found > stored: the trajectory's log overflowed"""
+        nb = self.B - b0 if nb is None else int(nb)
+        s = np.zeros(max(nb, 0), dtype=np.int32); f = np.zeros(max(nb, 0), dtype=np.int32)
+        _chk(self.L.msckf_hip_pruned_log_counts(self.h, int(b0), nb, s.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
+        return s, f
+
+    def pruned_log_read(self, b, r0=0, n=None):
+        """stored records [r0, r0 + n) (default: all behind r0) of trajectory b: the array [n][32], a dict of views into it by
+        field name (PRUNED_LOG_FIELDS) and the records' augment ordinals [n] (-1: the state's image is not known)"""
+        n = int(self.pruned_log_counts(b, 1)[0][0]) - r0 if n is None else int(n)
+        o = np.zeros((max(n, 0), PRUNED_LOG_STRIDE)); a = np.full(max(n, 1), -1, dtype=np.int32)
+        _chk(self.L.msckf_hip_pruned_log_read(self.h, int(b), int(r0), n, o.ctypes.data_as(_dp), a.ctypes.data_as(_ip)))
+        return o, {k: o[:, s] for k, s in PRUNED_LOG_FIELDS.items()}, a[:max(n, 0)]
+
+    def pruned_log_metrics(self, q0, q1, gt_pose=None):
+        """the stored records with prune ordinal in [q0, q1) against ground-truth camera poses gt_pose [n_ord][B][7] (q_CG p_C_G
+        of the camera of frame ordinal o; None: none, every record unmatched), reduced on the device: [B][10], columns
+        PRUNED_LOG_METRICS (sums and counts: shard.ate_from_pruned_metrics turns them into ate_allreduce's accumulator)"""
+        o = np.zeros((self.B, 10))
+        if gt_pose is None:
+            _chk(self.L.msckf_hip_pruned_log_metrics(self.h, int(q0), int(q1), None, 0, o.ctypes.data_as(_dp)))
+            return o
+        g = np.ascontiguousarray(gt_pose, dtype=np.float64)
+        if g.ndim != 3 or g.shape[1:] != (self.B, 7):
+            raise ValueError("gt_pose must be [n_ord][B][7]")
+        _chk(self.L.msckf_hip_pruned_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), int(g.shape[0]), o.ctypes.data_as(_dp)))
         return o
 
     def profile_enable(self, on=True):

@@ -62,6 +62,11 @@ enum { LOG_IMU = 0, LOG_PII = 16, LOG_PPP = 31, LOG_NCAM = 37, LOG_STATS = 38, L
 // the reference would put into map_ (msckf.h:371): p_f_G, gamma, frame ordinal, track index, flags, observation count
 enum { MAP_PF = 0, MAP_GAMMA = 3, MAP_FRAME = 4, MAP_TRACK = 5, MAP_FLAGS = 6, MAP_M = 7, MAP_STRIDE = 8 };
 enum { MAP_FLAG_PASS = 1, MAP_FLAG_INCLUDED = 2, MAP_FLAG_BOUND = 4 };
+// pruned-state log (kernels_log.hip; msckf_hip_pruned_log_*): one record of PRN_STRIDE scalars per camera state that a frame of
+// run_frames drops, read after the frame's update and before its prune: the posterior pose q_CG p_C_G, the prune frame's ordinal,
+// the upper triangle of the state's posterior 6 x 6 covariance block row by row (tt tt tt tp tp tp | tt tt tp .. | .. | pp), the
+// window size before the prune and the index of the dropped slot in the frame (integers below 2^24: exact in a float)
+enum { PRN_Q = 0, PRN_P = 4, PRN_FRAME = 7, PRN_COV = 8, PRN_NCAM = 29, PRN_K = 30, PRN_PAD = 31, PRN_STRIDE = 32 };
 
 // work space of the literal anisotropic compression (kernels_literal.hip / literal_core.h), per trajectory; null when no
 // trajectory of the batch uses it
@@ -533,6 +538,11 @@ template <class S> void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStr
 template <class S> void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, double* out, hipStream_t st);
 template <class S> void launch_map_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* n, const int* M, int ordinal, int cap, S* rec, int* found);
 template <class S> void launch_map_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const double* gt, const int* off, double* out, hipStream_t st);
+// the camera states that the frame's prune is about to drop (drop: the cell's n_drop per trajectory of the launch, clamped as
+// k_prune_inplace clamps it), from d.cam and d.P after the update, behind the cursors found[B]; and the reduction of the stored
+// records with prune ordinal in [q0, q1) against ground-truth poses gt[n_ord][B][7], matched through aug[B][cap], into out[B][10]
+template <class S> void launch_pruned_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop, int ordinal, int cap, S* rec, int* found);
+template <class S> void launch_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out, hipStream_t st);
 size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged = false);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();

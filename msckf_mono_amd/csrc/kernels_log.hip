@@ -7,6 +7,9 @@
 // k_log_metrics reduces a range of records against ground-truth positions: the sums behind ATE and NEES, per trajectory.
 // k_map_log is the per-track counterpart: the frame's triangulated landmarks with their gate statistics, compacted inside
 // the wavefront behind a per-trajectory cursor; k_map_metrics reduces them against ground-truth landmarks.
+// k_pruned_log records the camera states a frame is about to prune, between the frame's update and its prune launch: the
+// posterior pose with its 6 x 6 covariance block, the fixed-lag smoothed trajectory; k_pruned_metrics reduces them against
+// ground-truth poses.
 #include "dev_common.h"
 
 namespace msckf {
@@ -169,6 +172,146 @@ __global__ __launch_bounds__(64) void k_map_metrics(const S* rec, const int* fou
   }
 }
 
+// The pruned-state log: the camera states that the frame's prune drops, as the frame's update left them -- one record of
+// PRN_STRIDE scalars per dropped state, in (frame, slot) order behind the trajectory's cursor found[b].  One wavefront per
+// trajectory, four per workgroup, launched for the slice [b0, b0 + nb) between the frame's update and its k_prune_inplace
+// launch: d.P is the posterior covariance in place, d.cam the corrected camera states, d.ncam the window size before the prune.
+// drop (already offset to b0): the cell's n_drop, clamped to 0 .. window size as k_prune_inplace / k_make_keep clamp it; the
+// dropped states are the slots 0 .. nd - 1.  A skipped cell has n_drop == 0 (cell_refusal): it and a cell that drops nothing
+// write nothing, not even the cursor.  Record index (include/msckf_hip.h, "pruned-state log record"):
+//   0..3 q_CG | 4..6 p_C_G | 7 prune frame ordinal | 8..28 upper triangle of P[15 + 6 k .. 15 + 6 k + 5]^2 row by row |
+//   29 window size before the prune | 30 k, the dropped slot | 31 zero
+// Two records per step: lane = 32 * (record of the pair) + record index loads one scalar, the sixteen lanes 0..15 collect four
+// each over the LDS crossbar (lane l: scalars 4 l .. 4 l + 3 of the pair) and store them as aligned 4-vectors.  A destination
+// >= cap is counted but not stored (the map log's rule).  The trajectory belongs to one slice and its frames are ordered on
+// that slice's stream: lane 0 reads the cursor and stores it back, no atomics.
+template <class S>
+__global__ __launch_bounds__(256) void k_pruned_log(Dev<S> d, int b0, int nb, const int* drop, int ordinal, int cap, S* rec, int* found) {
+  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (i >= nb) return;   // (whole wavefronts)
+  const int b = b0 + i;
+  const int n = min(d.ncam[b], d.n_cap);
+  int nd = drop[i];
+  nd = nd < 0 ? 0 : (nd > n ? n : nd);
+  if (nd == 0) return;
+  int cur = 0;
+  if (lane == 0) cur = found[b];
+  const long base = wave_bcast(cur, 0);
+  const int half = lane >> 5, j = lane & 31;
+  const int t = j - PRN_COV;                                         // triangle entry t = (r, c), r <= c: row r starts at r (13 - r) / 2
+  const int r = t < 6 ? 0 : (t < 11 ? 1 : (t < 15 ? 2 : (t < 18 ? 3 : (t < 20 ? 4 : 5))));
+  const int c = t - r * (13 - r) / 2 + r;
+  const S* Pb = d.P + (long)b * d.ld * d.ld;
+  const S* cam = d.cam + (long)b * d.n_cap * CAM_STRIDE;
+  for (int k0 = 0; k0 < nd; k0 += 2) {
+    const int k = k0 + half;
+    S v = S(0);
+    if (k < nd) {
+      if (j < PRN_FRAME) v = cam[(long)k * CAM_STRIDE + j];
+      else if (j == PRN_FRAME) v = (S)ordinal;
+      else if (j < PRN_NCAM) { const int o = 15 + 6 * k; v = Pb[(long)(o + c) * d.ld + o + r]; }
+      else if (j == PRN_NCAM) v = (S)n;
+      else if (j == PRN_K) v = (S)k;
+    }
+    Vec4<S> o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o.x[e] = lane_gather(v, ((4 * lane + e) & 63) << 2);   // (every lane takes part in the exchange)
+    const int ks = k0 + (lane >> 3);                                 // lanes 0..15: the record whose vector lane & 7 this lane stores
+    const long dst = base + ks;
+    if (lane < 16 && ks < nd && dst < cap) *reinterpret_cast<Vec4<S>*>(rec + ((long)b * cap + dst) * PRN_STRIDE + 4 * (lane & 7)) = o;
+  }
+  if (lane == 0) found[b] = (int)min(base + nd, (long)INT32_MAX);
+}
+
+// One workgroup (one wavefront) per trajectory over the stored records of the pruned-state log whose prune ordinal lies in
+// [q0, q1).  aug[B][cap]: per stored record the ordinal of the frame that augmented its camera state, or -1; a record with
+// 0 <= ordinal < n_ord is matched to the ground-truth pose gt[ordinal][B][7] (q_CG p_C_G), any other is unmatched.
+// Pose error e = [e_th ; e_p]: e_p = p - p_gt, e_th the small angle with which the filter's own injection (k_inject:
+// q <- update_quat(dtheta) * q) turns the ground truth into the estimate, q = update_quat(e_th) * q_gt: update_quat(x) is the
+// unit quaternion (sqrt(1 - |x / 2|^2), -x / 2), so e_th = -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign of q that makes the
+// scalar part >= 0.
+// out[b][10] = records in range, matched, sum |e_p|^2, max |e_p|, sum |e_th|^2, max |e_th|, sum e^T P6^-1 e over the matched
+// records whose logged block factors (6 x 6 Cholesky in registers, P6 = L L^T, |L^-1 e|^2), their number, the matched records
+// with a non-positive pivot (left out of that sum), unmatched.  All in f64; lane l takes the records l, l + 64, ... in
+// ascending order and the lanes are combined by wave_sum's fixed tree: the same log gives the same bits on every call.
+template <class S>
+__global__ __launch_bounds__(64) void k_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = min(max(found[b], 0), cap);
+  double cnt = 0, nm = 0, sp = 0, mp = 0, sth = 0, mth = 0, nees = 0, nn = 0, bad = 0, un = 0;
+  for (int rr = lane; rr < n; rr += 64) {
+    const Vec4<S>* q = reinterpret_cast<const Vec4<S>*>(rec + ((long)b * cap + rr) * PRN_STRIDE);
+    double x[PRN_STRIDE];
+#pragma unroll
+    for (int v = 0; v < PRN_STRIDE / 4; ++v) {
+      const Vec4<S> a = q[v];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) x[4 * v + e] = (double)a.x[e];
+    }
+    const int fr = (int)x[PRN_FRAME];
+    if (fr < q0 || fr >= q1) continue;
+    cnt += 1.0;
+    const int ord = aug[(long)b * cap + rr];
+    if (ord < 0 || ord >= n_ord) { un += 1.0; continue; }
+    const double* g = gt + ((long)ord * B + b) * 7;
+    // q * q_gt^-1 = s (1 + dq * q_gt^-1) with dq = s q - q_gt, s the sign of q . q_gt: the products are of the small
+    // difference, so that e_th keeps its relative precision where a plain q * q_gt^-1 cancels down to it
+    const Q4<double> qh = ldq(x + PRN_Q), qg = ldq(g);
+    const double sg = qh.w * qg.w + qh.x * qg.x + qh.y * qg.y + qh.z * qg.z < 0 ? -1.0 : 1.0;
+    Q4<double> dq; dq.w = sg * qh.w - qg.w; dq.x = sg * qh.x - qg.x; dq.y = sg * qh.y - qg.y; dq.z = sg * qh.z - qg.z;
+    Q4<double> u = qmul(dq, qinverse(qg));
+    u.w += 1.0;
+    const double sc = -2.0 / sqrt(u.w * u.w + u.x * u.x + u.y * u.y + u.z * u.z);
+    double e[6] = {sc * u.x, sc * u.y, sc * u.z, x[PRN_P] - g[4], x[PRN_P + 1] - g[5], x[PRN_P + 2] - g[6]};
+    const double t2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2], p2 = e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
+    const double dt = sqrt(t2), dp = sqrt(p2);
+    nm += 1.0; sp += p2; sth += t2;
+    mp = dp > mp ? dp : mp; mth = dt > mth ? dt : mth;
+    double L[6][6];
+    bool ok = true;
+    double y2 = 0;
+#pragma unroll
+    for (int jc = 0; jc < 6; ++jc) {                                   // column jc of L, then row jc of the forward solve
+      double s = x[PRN_COV + jc * (13 - jc) / 2];
+#pragma unroll
+      for (int k = 0; k < jc; ++k) s -= L[jc][k] * L[jc][k];
+      ok = ok && (s > 0);
+      const double piv = sqrt(s);
+      L[jc][jc] = piv;
+#pragma unroll
+      for (int ir = jc + 1; ir < 6; ++ir) {
+        double a = x[PRN_COV + jc * (13 - jc) / 2 + (ir - jc)];
+#pragma unroll
+        for (int k = 0; k < jc; ++k) a -= L[ir][k] * L[jc][k];
+        L[ir][jc] = a / piv;
+      }
+      double y = e[jc];
+#pragma unroll
+      for (int k = 0; k < jc; ++k) y -= L[jc][k] * e[k];
+      e[jc] = y / piv;                                                 // (e is overwritten by L^-1 e from the top)
+      y2 += e[jc] * e[jc];
+    }
+    if (ok) { nees += y2; nn += 1.0; } else bad += 1.0;
+  }
+  cnt = wave_sum(cnt); nm = wave_sum(nm); sp = wave_sum(sp); mp = wave_max(mp); sth = wave_sum(sth); mth = wave_max(mth);
+  nees = wave_sum(nees); nn = wave_sum(nn); bad = wave_sum(bad); un = wave_sum(un);
+  if (lane == 0) {
+    double* o = out + (long)b * 10;
+    o[0] = cnt; o[1] = nm; o[2] = sp; o[3] = mp; o[4] = sth; o[5] = mth; o[6] = nees; o[7] = nn; o[8] = bad; o[9] = un;
+  }
+}
+
+template <class S>
+void launch_pruned_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop, int ordinal, int cap, S* rec, int* found) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(k_pruned_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, drop, ordinal, cap, rec, found);
+}
+template <class S>
+void launch_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_pruned_metrics<S>, dim3(B), dim3(64), 0, st, rec, found, cap, B, q0, q1, aug, gt, n_ord, out);
+}
+
 template <class S>
 void launch_map_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* n, const int* M, int ordinal, int cap, S* rec, int* found) {
   if (nb <= 0) return;
@@ -199,5 +342,9 @@ template void launch_map_log<float>(const Dev<float>&, int, int, hipStream_t, co
 template void launch_map_log<double>(const Dev<double>&, int, int, hipStream_t, const int*, const int*, int, int, double*, int*);
 template void launch_map_metrics<float>(const float*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
 template void launch_map_metrics<double>(const double*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
+template void launch_pruned_log<float>(const Dev<float>&, int, int, hipStream_t, const int*, int, int, float*, int*);
+template void launch_pruned_log<double>(const Dev<double>&, int, int, hipStream_t, const int*, int, int, double*, int*);
+template void launch_pruned_metrics<float>(const float*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
+template void launch_pruned_metrics<double>(const double*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
 
 }  // namespace msckf

@@ -229,6 +229,15 @@ struct BatchCore {
   // out; a run_frames / run_frames_streamed call over [f0, f1) stamps its records with map_base + (f - f0) (map_base = map_ord
   // at its start) and advances map_ord when it has succeeded
   void* map_buf = nullptr; int* map_found = nullptr; int map_cap = 0, map_ord = 0, map_base = 0;
+  // pruned-state log (msckf_hip_pruned_log_*; kernels_log.hip): [B][prn_cap][PRN_STRIDE] scalars of esz bytes and the device
+  // cursors prn_found[B], null unless enabled; prn_ord / prn_base hand out the frame ordinals as map_ord / map_base do.  While
+  // it is on no frame's prune rides on the downdate (fuse_frame): the record is read between the update and the prune launch.
+  // Which image's camera a record is: run_frames drops oldest-first, so per trajectory prn_fifo holds the augment ordinals of
+  // the states in the window, oldest first (-1: a state that was there at enable / reset time or came in through another
+  // call), and prn_aug the popped ordinal of every stored record.  Both are written by the enqueue thread of the
+  // trajectory's slice only (the loop at the end of enqueue_frame that mirrors augment and drop into h_ncam).
+  void* prn_buf = nullptr; int* prn_found = nullptr; int prn_cap = 0, prn_ord = 0, prn_base = 0;
+  std::vector<std::vector<int>> prn_fifo, prn_aug;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[NSTAGE];
@@ -271,6 +280,8 @@ struct BatchCore {
     if (log_buf) hipFree(log_buf);
     if (map_buf) hipFree(map_buf);
     if (map_found) hipFree(map_found);
+    if (prn_buf) hipFree(prn_buf);
+    if (prn_found) hipFree(prn_found);
     if (h_rb) hipHostFree(h_rb);
     for (int s = 0; s < NSTAGE; ++s) for (auto& e : ev_pool[s]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int i = 1; i < MAXS; ++i) { if (stx[i]) hipStreamDestroy(stx[i]); if (ev_join[i]) hipEventDestroy(ev_join[i]); }
@@ -662,6 +673,7 @@ struct BatchCore {
     commit_buffer_parity(f0, f1);
     if (log_buf) log_n += f1 - f0;
     if (map_buf) map_ord += f1 - f0;
+    if (prn_buf) prn_ord += f1 - f0;
     return 0;
   }
   // ---- frame log
@@ -761,12 +773,86 @@ struct BatchCore {
       if (gt_off[c + 1] < gt_off[c]) return fail(-EINVAL, "gt_off decreases at cell " + std::to_string(c) + " (CSR offsets over the cells (frame - q0) * B + b)");
     return 0;
   }
+  // ---- pruned-state log
+  // every state in the window becomes one whose image is unknown (ordinal -1)
+  void pruned_log_forget() { for (int b = 0; b < (int)prn_fifo.size(); ++b) prn_fifo[b].assign(h_ncam[b], -1); }
+  // capacity_per_trajectory records for every trajectory and a cursor each, or (0) none: frees a log that exists either way,
+  // drops its records and gives the fused prune back.  An allocation that fails leaves the log off and the handle as it was
+  int pruned_log_enable(int capacity) {
+    if (int rc = guard()) return rc;
+    if (capacity < 0) return fail(-EINVAL, "negative capacity");
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if (prn_buf) (void)hipFree(prn_buf);
+    if (prn_found) (void)hipFree(prn_found);
+    prn_buf = nullptr; prn_found = nullptr; prn_cap = 0; prn_ord = 0;
+    prn_fifo.clear(); prn_aug.clear();
+    if (!capacity) return 0;
+    void* q = nullptr; void* c = nullptr;
+    if (hipMalloc(&q, (size_t)capacity * B * PRN_STRIDE * esz) != hipSuccess || hipMalloc(&c, (size_t)B * sizeof(int)) != hipSuccess) {
+      (void)hipGetLastError();
+      if (q) (void)hipFree(q);
+      return fail(-ENOMEM, "could not allocate the pruned-state log (it stays disabled; the handle is unaffected)");
+    }
+    if (hipMemsetAsync(c, 0, (size_t)B * sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(q); (void)hipFree(c);
+      return fail(-EIO, "could not clear the pruned-state log's cursors (it stays disabled)");
+    }
+    prn_buf = q; prn_found = static_cast<int*>(c); prn_cap = capacity;
+    prn_fifo.assign(B, std::vector<int>()); prn_aug.assign(B, std::vector<int>());
+    pruned_log_forget();
+    return 0;
+  }
+  // cursors and frame ordinal <- 0 (the storage stays); ordered on st before the next call's frames
+  int pruned_log_reset() {
+    if (int rc = guard()) return rc;
+    prn_ord = 0;
+    if (!prn_buf) return 0;
+    if (int rc = enter()) return rc;
+    HIPCHK(hipMemsetAsync(prn_found, 0, (size_t)B * sizeof(int), st));
+    for (auto& a : prn_aug) a.clear();
+    pruned_log_forget();
+    return 0;
+  }
+  int pruned_log_frames() const { return prn_ord; }
+  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's ordinals start at prn_ord and stay exact
+  // in a float record; a trajectory whose window changed size behind the log's back (any other call) holds unknown states
+  int pruned_log_reserve(int f0, int f1) {
+    if (!prn_buf) return 0;
+    if ((long)prn_ord + (f1 - f0) > (1L << 24)) return fail(-ENOSPC, "pruned-state log: the call's frame ordinals would pass 2^24 (msckf_hip_pruned_log_reset); nothing was run");
+    prn_base = prn_ord;
+    for (int b = 0; b < B; ++b) if ((int)prn_fifo[b].size() != h_ncam[b]) prn_fifo[b].assign(h_ncam[b], -1);
+    return 0;
+  }
+  // enqueue_frame's host mirror of one cell, called where h_ncam takes the same steps: the augment pushes the frame's ordinal,
+  // the drop pops the nd oldest into the ordinals of the records that the frame's k_pruned_log launch stores
+  void pruned_log_mirror(int b, bool augmented, int nd, int ordinal) {
+    std::vector<int>& q = prn_fifo[b];
+    if (augmented) q.push_back(ordinal);
+    for (int k = 0; k < nd; ++k) if ((int)prn_aug[b].size() < prn_cap) prn_aug[b].push_back(q[k]);
+    q.erase(q.begin(), q.begin() + nd);
+  }
+  // after the handle's stream: per trajectory of [b0, b0 + nb) the records found and how many of them are stored
+  int pruned_log_counts(int b0, int nb, int* stored, int* found) {
+    if (int rc = guard()) return rc;
+    if (!prn_buf) return fail(-EINVAL, "pruned-state log not enabled (msckf_hip_pruned_log_enable)");
+    if (int rc = enter_range(b0, nb)) return rc;
+    std::vector<int> tmp(std::max(nb, 1));
+    if (nb) HIPCHK(hipMemcpyAsync(tmp.data(), prn_found + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int i = 0; i < nb; ++i) {
+      if (found) found[i] = tmp[i];
+      if (stored) stored[i] = std::min(tmp[i], prn_cap);
+    }
+    return 0;
+  }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = frame_log_reserve(f0, f1)) return rc;
     if (int rc = map_log_reserve(f0, f1)) return rc;
+    if (int rc = pruned_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     const int nh = n_slices();
     const int rc = fork_slices(nh);
@@ -799,6 +885,7 @@ struct BatchCore {
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = frame_log_reserve(f0, f1)) return rc;
     if (int rc = map_log_reserve(f0, f1)) return rc;
+    if (int rc = pruned_log_reserve(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     {
       bool all = sg_blk[0] != nullptr;
@@ -977,6 +1064,8 @@ struct BatchCore {
   }
   virtual int map_log_read(int b, int r0, int n, double* out) = 0;                              // [n][MAP_STRIDE]
   virtual int map_log_metrics(int q0, int q1, const double* gt_xyz, const int* gt_off, double* out) = 0;   // out [B][8]
+  virtual int pruned_log_read(int b, int r0, int n, double* out, int* aug_ord) = 0;             // [n][PRN_STRIDE], [n]
+  virtual int pruned_log_metrics(int q0, int q1, const double* gt_pose, int n_ord, double* out) = 0;       // gt_pose [n_ord][B][7], out [B][10]
 };
 
 int resolve_map(BatchCore* B, int b);   // (defined with the host-side bookkeeping below)
@@ -1379,8 +1468,9 @@ struct Batch : BatchCore {
   }
   // Frame f of a call over [.., f1): does its prune ride on the downdate (the covariance lands, pruned, in the other buffer and
   // the next frame's k_propagate commits the window size)?  Never the call's last frame: it prunes with its own launch, so that
-  // ncam is final when the call returns.  The frame step and commit_buffer_parity both ask here.
-  bool fuse_frame(int f, int f1) const { return settings.fuse_prune && !prof && !settings.overlap_feature && d.joseph == 0 && f + 1 < f1; }
+  // ncam is final when the call returns; and no frame while the pruned-state log is on: its record is the state between the update
+  // and the prune, which only the prune's own launch leaves in reach.  The frame step and commit_buffer_parity both ask here.
+  bool fuse_frame(int f, int f1) const { return settings.fuse_prune && !prof && !settings.overlap_feature && d.joseph == 0 && f + 1 < f1 && !prn_buf; }
   // every slice ran the same frames; each fused one flipped the buffers
   void commit_buffer_parity(int f0, int f1) override {
     int flips = 0;
@@ -1629,6 +1719,7 @@ struct Batch : BatchCore {
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
     settings.take_over(o->settings);
+    pruned_log_forget();   // (the log stays with its handle; the states taken over are none of its images)
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
     return set_aniso(settings.aniso_mode, settings.lit_tol);   // applies the settings, re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed
@@ -1749,6 +1840,9 @@ struct Batch : BatchCore {
     { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1, h_k.data() + cell0 + b0); }
     if (fuse) s.flipped = !s.flipped;
     else {
+      // pruned-state log: the states this frame drops, as the update left them (v.P: in place), with frame ordinal
+      // prn_base + (f - f0), behind the trajectories' cursors; outside the stage timers
+      if (prn_buf) launch_pruned_log<S>(v, b0, nb, q, in.drop, prn_base + (f - f0), prn_cap, static_cast<S*>(prn_buf), prn_found);
       StageRange r("msckf_prune_empty_states");
       stage_begin(6, q);
       launch_prune<S>(v, b0, nb, q, in.drop, 0);
@@ -1762,8 +1856,11 @@ struct Batch : BatchCore {
     // map_base + (f - f0), behind the trajectories' cursors; also outside the stage timers
     if (map_buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map_base + (f - f0), map_cap, static_cast<S*>(map_buf), map_found);
     for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment (not for a skipped cell), then drop n_drop (clamped as k_make_keep does)
-      if (h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP) h_ncam[b]++;
-      h_ncam[b] -= std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
+      const bool augmented = h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP;
+      if (augmented) h_ncam[b]++;
+      const int nd = std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
+      h_ncam[b] -= nd;
+      if (prn_buf) pruned_log_mirror(b, augmented, nd, prn_base + (f - f0));
     }
   }
   // records [r0, r0 + n) of trajectories [b0, b0 + nb) as doubles: one strided copy, one wait
@@ -1832,6 +1929,44 @@ struct Batch : BatchCore {
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dg);
     if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("map_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // stored records [r0, r0 + n) of trajectory b as doubles and the augment ordinal of each: the cursor first (a range beyond
+  // min(found, capacity) is refused), then one copy
+  int pruned_log_read(int b, int r0, int n, double* out, int* aug_ord) override {
+    int stored = 0;
+    if (int rc = pruned_log_counts(b, 1, &stored, nullptr)) return rc;
+    if (r0 < 0 || n < 0 || (long)r0 + n > stored) return fail(-EINVAL, "record range beyond the records stored (msckf_hip_pruned_log_counts)");
+    if (!n) return 0;
+    if ((int)prn_aug[b].size() < r0 + n) return fail(-EIO, "pruned-state log: fewer augment ordinals on the host than records on the device");
+    std::vector<S> tmp((size_t)n * PRN_STRIDE);
+    if (const int rc = read_back(tmp.data(), static_cast<const S*>(prn_buf) + ((size_t)b * prn_cap + r0) * PRN_STRIDE, tmp.size() * sizeof(S))) return rc;
+    for (size_t i = 0; i < tmp.size(); ++i) out[i] = (double)tmp[i];
+    if (aug_ord) std::copy(prn_aug[b].begin() + r0, prn_aug[b].begin() + r0 + n, aug_ord);
+    return 0;
+  }
+  // the stored records with prune ordinal in [q0, q1) against ground-truth poses gt_pose[n_ord][B][7], matched through their
+  // augment ordinals (uploaded here, off the frame path), reduced on the device (k_pruned_metrics): out [B][10]
+  int pruned_log_metrics(int q0, int q1, const double* gt_pose, int n_ord, double* out) override {
+    if (int rc = guard()) return rc;
+    if (!prn_buf) return fail(-EINVAL, "pruned-state log not enabled (msckf_hip_pruned_log_enable)");
+    if (q0 < 0 || q1 < q0 || q1 > prn_ord) return fail(-EINVAL, "frame ordinal range beyond the ordinals handed out (msckf_hip_pruned_log_frames)");
+    if (n_ord < 0 || (n_ord > 0 && !gt_pose)) return fail(-EINVAL, "gt_pose: n_ord poses per trajectory, n_ord >= 0, null only with n_ord == 0");
+    if (int rc = enter()) return rc;
+    const size_t ng = (size_t)n_ord * B * 7, no = (size_t)B * 10, na = (size_t)B * prn_cap;
+    std::vector<int> aug(na, -1);
+    for (int b = 0; b < B; ++b) std::copy(prn_aug[b].begin(), prn_aug[b].end(), aug.begin() + (size_t)b * prn_cap);
+    double* dg = nullptr;                                      // [ground truth | out | aug], freed on every way out
+    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + na * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
+    double* dout = dg + std::max<size_t>(ng, 1);
+    int* daug = reinterpret_cast<int*>(dout + no);
+    hipError_t e = ng ? hipMemcpyAsync(dg, gt_pose, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpyAsync(daug, aug.data(), na * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { launch_pruned_metrics<S>(static_cast<const S*>(prn_buf), prn_found, prn_cap, B, q0, q1, daug, dg, n_ord, dout, st); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dg);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("pruned_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
     return 0;
   }
 };
@@ -2397,6 +2532,12 @@ int msckf_hip_map_log_frames(msckf_hip_handle h) { if (!h) return fail(-EINVAL, 
 int msckf_hip_map_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found) { if (!h || !stored || !found) return fail(-EINVAL, "null argument"); return H(h)->map_log_counts(b0, nb, stored, found); }
 int msckf_hip_map_log_read(msckf_hip_handle h, int b, int r0, int n, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_read(b, r0, n, out); }
 int msckf_hip_map_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_xyz, const int* gt_off, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_metrics(q0, q1, gt_xyz, gt_off, out); }
+int msckf_hip_pruned_log_enable(msckf_hip_handle h, int capacity_per_trajectory) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->pruned_log_enable(capacity_per_trajectory); }
+int msckf_hip_pruned_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->pruned_log_reset(); }
+int msckf_hip_pruned_log_frames(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->pruned_log_frames(); }
+int msckf_hip_pruned_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found) { if (!h || !stored || !found) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_counts(b0, nb, stored, found); }
+int msckf_hip_pruned_log_read(msckf_hip_handle h, int b, int r0, int n, double* out, int* aug_ord) { if (!h || !out || !aug_ord) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_read(b, r0, n, out, aug_ord); }
+int msckf_hip_pruned_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_pose, int n_ord, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_metrics(q0, q1, gt_pose, n_ord, out); }
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"

@@ -189,6 +189,16 @@ def landmark_csr(trajs, f0, f1):
     return np.ascontiguousarray(xyz), off
 
 
+def camera_pose_gt(trajs, f0, f1):
+    """Ground-truth camera poses of the frames [f0, f1) of a batch, as Batch.pruned_log_metrics takes them: [f1 - f0][B][7],
+    q_CG (w, x, y, z) p_C_G of the camera that frame k's augmentState adds (trajs[b].C_CG[k], .p_C[k])."""
+    out = np.zeros((max(f1 - f0, 0), len(trajs), 7))
+    for k in range(f0, f1):
+        for b, tr in enumerate(trajs):
+            out[k - f0, b, 0:4], out[k - f0, b, 4:7] = rot_to_quat(tr.C_CG[k]), tr.p_C[k]
+    return out
+
+
 class Trajectory:
     """One seeded trajectory: IMU stream + per-frame ending-track work-lists."""
 

@@ -39,6 +39,17 @@ def ate_from_log_metrics(metrics, seq_ids, n_seq):
     return acc
 
 
+def ate_from_pruned_metrics(metrics, seq_ids, n_seq, angle=False):
+    """The same accumulator from capi.Batch.pruned_log_metrics' rows [B][10] (n, matched, sum |e_p|^2, max |e_p|, sum |e_th|^2,
+    ...): the smoothed camera poses, every matched record counts; angle: the attitude error's sums instead of the position's
+    (ate_allreduce then returns the RMS angle in radians)."""
+    acc = np.zeros((n_seq, 2), dtype=np.float64)
+    for row, s in zip(np.asarray(metrics, dtype=np.float64), seq_ids):
+        acc[s, 0] += row[4] if angle else row[2]
+        acc[s, 1] += row[1]
+    return acc
+
+
 def ate_allreduce(acc, device=None):
     """All-reduce the partial sums over the default process group (if initialised) and return the
     per-sequence ATE (RMSE of position, no alignment: the runner initialises from ground truth,
