@@ -436,6 +436,20 @@ class Batch:
         _chk(self.L.msckf_hip_frame_log_metrics_ranges(self.h, p0, p1, g.ctypes.data_as(_dp), o.ctypes.data_as(_dp)))
         return o
 
+    # ---- the cursor logs' counts and read, stated once: prefix "map" or "pruned", the record's stride
+    def _cursor_log_counts(self, prefix, b0, nb):
+        nb = self.B - b0 if nb is None else int(nb)
+        s = np.zeros(max(nb, 0), dtype=np.int32); f = np.zeros(max(nb, 0), dtype=np.int32)
+        _chk(getattr(self.L, "msckf_hip_%s_log_counts" % prefix)(self.h, int(b0), nb, s.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
+        return s, f
+
+    def _cursor_log_read(self, prefix, stride, b, r0, n, aug=False):
+        """([n][stride], augment ordinals [n] or None) of the stored records [r0, r0 + n) (default: all behind r0) of trajectory b"""
+        n = int(self._cursor_log_counts(prefix, b, 1)[0][0]) - r0 if n is None else int(n)
+        o = np.zeros((max(n, 0), stride)); a = np.full(max(n, 1), -1, dtype=np.int32) if aug else None
+        _chk(getattr(self.L, "msckf_hip_%s_log_read" % prefix)(self.h, int(b), int(r0), n, o.ctypes.data_as(_dp), *([a.ctypes.data_as(_ip)] if aug else [])))
+        return o, a
+
     # ---- per-track device log of run_frames / run_frames_streamed: the landmark map
     def map_log_enable(self, capacity_per_trajectory):
         """storage for capacity_per_trajectory records per trajectory (0: free the log and switch it off); drops the records held"""
@@ -449,17 +463,12 @@ class Batch:
 
     def map_log_counts(self, b0=0, nb=None):
         """(stored, found) of trajectories [b0, b0 + nb) (default: all); found > stored: the trajectory's log overflowed"""
-        nb = self.B - b0 if nb is None else int(nb)
-        s = np.zeros(max(nb, 0), dtype=np.int32); f = np.zeros(max(nb, 0), dtype=np.int32)
-        _chk(self.L.msckf_hip_map_log_counts(self.h, int(b0), nb, s.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
-        return s, f
+        return self._cursor_log_counts("map", b0, nb)
 
     def map_log_read(self, b, r0=0, n=None):
         """stored records [r0, r0 + n) (default: all behind r0) of trajectory b: the array [n][8] and a dict of views into it by
         field name (MAP_LOG_FIELDS)"""
-        n = int(self.map_log_counts(b, 1)[0][0]) - r0 if n is None else int(n)
-        o = np.zeros((max(n, 0), MAP_LOG_STRIDE))
-        _chk(self.L.msckf_hip_map_log_read(self.h, int(b), int(r0), n, o.ctypes.data_as(_dp)))
+        o = self._cursor_log_read("map", MAP_LOG_STRIDE, b, r0, n)[0]
         return o, {k: o[:, s] for k, s in MAP_LOG_FIELDS.items()}
 
     def map_log_metrics(self, q0, q1, gt=None):
@@ -490,18 +499,13 @@ class Batch:
 
     def pruned_log_counts(self, b0=0, nb=None):
         """(stored, found) of trajectories [b0, b0 + nb) (default: all); found > stored: the trajectory's log overflowed"""
-        nb = self.B - b0 if nb is None else int(nb)
-        s = np.zeros(max(nb, 0), dtype=np.int32); f = np.zeros(max(nb, 0), dtype=np.int32)
-        _chk(self.L.msckf_hip_pruned_log_counts(self.h, int(b0), nb, s.ctypes.data_as(_ip), f.ctypes.data_as(_ip)))
-        return s, f
+        return self._cursor_log_counts("pruned", b0, nb)
 
     def pruned_log_read(self, b, r0=0, n=None):
         """stored records [r0, r0 + n) (default: all behind r0) of trajectory b: the array [n][32], a dict of views into it by
         field name (PRUNED_LOG_FIELDS) and the records' augment ordinals [n] (-1: the state's image is not known)"""
-        n = int(self.pruned_log_counts(b, 1)[0][0]) - r0 if n is None else int(n)
-        o = np.zeros((max(n, 0), PRUNED_LOG_STRIDE)); a = np.full(max(n, 1), -1, dtype=np.int32)
-        _chk(self.L.msckf_hip_pruned_log_read(self.h, int(b), int(r0), n, o.ctypes.data_as(_dp), a.ctypes.data_as(_ip)))
-        return o, {k: o[:, s] for k, s in PRUNED_LOG_FIELDS.items()}, a[:max(n, 0)]
+        o, a = self._cursor_log_read("pruned", PRUNED_LOG_STRIDE, b, r0, n, aug=True)
+        return o, {k: o[:, s] for k, s in PRUNED_LOG_FIELDS.items()}, a[:o.shape[0]]
 
     def pruned_log_metrics(self, q0, q1, gt_pose=None):
         """the stored records with prune ordinal in [q0, q1) against ground-truth camera poses gt_pose [n_ord][B][7] (q_CG p_C_G

@@ -56,6 +56,29 @@ inline const char* cell_refusal(int k, int K, int F, int n_drop, int flags) {
   return nullptr;
 }
 
+// The pruned-state log's host mirror: which image's camera a record is.  The frame loop drops oldest-first, so per trajectory
+// fifo holds the augment ordinals of the states in the window, oldest first (-1: a state that was there at enable / reset
+// time or came in through another call), and aug the popped ordinal of every stored record.  ncam: the host mirror of the
+// window sizes.  An empty mirror (the log is off) takes every step as a no-op.
+struct PrunedFifo {
+  std::vector<std::vector<int>> fifo, aug;
+  void clear() { fifo.clear(); aug.clear(); }
+  // no records, and a window of unknown states: the log was enabled or reset
+  void start(const std::vector<int>& ncam) { fifo.assign(ncam.size(), std::vector<int>()); aug.assign(ncam.size(), std::vector<int>()); forget(ncam); }
+  // every state in the window becomes one whose image is unknown (ordinal -1)
+  void forget(const std::vector<int>& ncam) { for (size_t b = 0; b < fifo.size(); ++b) fifo[b].assign(ncam[b], -1); }
+  // a trajectory whose window changed size behind the log's back (any call but the frame loop) holds unknown states
+  void resync(const std::vector<int>& ncam) { for (size_t b = 0; b < fifo.size(); ++b) if ((int)fifo[b].size() != ncam[b]) fifo[b].assign(ncam[b], -1); }
+  // one cell of the frame loop, where the window size takes the same steps: the augment pushes the frame's ordinal, the drop
+  // pops the nd oldest into the ordinals of the records the frame stores -- as long as the log's capacity lasts
+  void mirror(int b, bool augmented, int nd, int ordinal, int cap) {
+    std::vector<int>& q = fifo[b];
+    if (augmented) q.push_back(ordinal);
+    for (int k = 0; k < nd; ++k) if ((int)aug[b].size() < cap) aug[b].push_back(q[k]);
+    q.erase(q.begin(), q.begin() + nd);
+  }
+};
+
 inline void remove_tracked_feature(HostTraj& t, uint64_t fid, std::vector<int>& slots) {
   slots.clear();
   for (size_t c = 0; c < t.cams.size(); ++c) {

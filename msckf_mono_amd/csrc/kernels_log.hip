@@ -17,6 +17,25 @@ namespace msckf {
 // four scalars with the alignment of one 16-byte (float) / two 16-byte (double) vector accesses
 template <class S> struct alignas(4 * sizeof(S)) Vec4 { S x[4]; };
 
+// The log kernels of the frame path run one wavefront per trajectory, four per workgroup: the lane, and the trajectory's index
+// i within the slice's nb.  False: the wavefront has no trajectory and leaves as a whole.
+__device__ __forceinline__ bool log_wave(int nb, int& lane, int& i) {
+  lane = threadIdx.x & 63; i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  return i < nb;
+}
+// The cursor of a cursor log, found[b]: records found so far, stored or not.  The trajectory belongs to one slice and its
+// frames are ordered on that slice's stream: lane 0 reads the cursor (every lane gets it) and stores it back, no atomics.  A
+// record whose destination is >= cap is counted but not stored, so the stored ones are the first cap in order.
+__device__ __forceinline__ long cursor_read(const int* found, int b, int lane) {
+  int cur = 0;
+  if (lane == 0) cur = found[b];
+  return wave_bcast(cur, 0);
+}
+__device__ __forceinline__ void cursor_store(int* found, int b, int lane, long end) { if (lane == 0) found[b] = (int)min(end, (long)INT32_MAX); }
+// What the metrics kernels of a cursor log walk: the records stored, and of those the ones stamped with an ordinal in [q0, q1)
+__device__ __forceinline__ int cursor_stored(const int* found, int b, int cap) { return min(max(found[b], 0), cap); }
+__device__ __forceinline__ bool ordinal_in(int fr, int q0, int q1) { return fr >= q0 && fr < q1; }
+
 // One wavefront per trajectory, four per workgroup.  Record index (include/msckf_hip.h, "frame log record"):
 //   0..15 imu[0..15] | 16..30 diag P_II | 31..36 P_pp xx xy xz yy yz zz | 37 window size | 38..40 STAT_NTRACKS, _PASSED, _ERR |
 //   41..47 cam slot 0 (zeros when the window is empty)
@@ -26,8 +45,8 @@ template <class S> struct alignas(4 * sizeof(S)) Vec4 { S x[4]; };
 // size waits in ncam_upd (as size + 1) and ncam is still the size before the prune.
 template <class S>
 __global__ __launch_bounds__(256) void k_frame_log(Dev<S> d, int b0, int nb, const S* P, int pending, S* rec) {
-  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-  if (i >= nb) return;   // (whole wavefronts)
+  int lane, i;
+  if (!log_wave(nb, lane, i)) return;
   const int b = b0 + i;
   const int n = pending ? d.ncam_upd[b] - 1 : d.ncam[b];
   const S* Pb = P + (long)b * d.ld * d.ld;
@@ -98,19 +117,15 @@ __global__ __launch_bounds__(64) void k_log_metrics(const S* log, int B, int r0,
 //   0..2 p_f_G | 3 gamma | 4 frame ordinal | 5 track index | 6 flags (1 gate passed, 2 included, 4 gamma is the early-accept
 //   bound) | 7 M
 // The wavefront walks the tracks in chunks of 64: ballot of the keep flag, rank = kept lanes below, destination = cursor +
-// kept of the earlier chunks + rank.  A destination >= cap is counted but not stored, so the records stored are the first
-// cap in (frame, track) order.  The trajectory belongs to one slice and its frames are ordered on that slice's stream: lane 0
-// reads the cursor and stores it back, no atomics.
+// kept of the earlier chunks + rank (cursor_read: the records stored are the first cap in (frame, track) order).
 template <class S>
 __global__ __launch_bounds__(256) void k_map_log(Dev<S> d, int b0, int nb, const int* n, const int* M, int ordinal, int cap, S* rec, int* found) {
-  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-  if (i >= nb) return;   // (whole wavefronts)
+  int lane, i;
+  if (!log_wave(nb, lane, i)) return;
   const int b = b0 + i;
   const int F = min(max(n[i], 0), d.f_cap);
   if (F == 0) return;
-  int cur = 0;
-  if (lane == 0) cur = found[b];
-  long base = wave_bcast(cur, 0);
+  long base = cursor_read(found, b, lane);
   const long first = (long)b * cap;
   for (int t0 = 0; t0 < F; t0 += 64) {
     const int t = t0 + lane;
@@ -131,7 +146,7 @@ __global__ __launch_bounds__(256) void k_map_log(Dev<S> d, int b0, int nb, const
     }
     base += __popcll(mask);
   }
-  if (lane == 0) found[b] = (int)min(base, (long)INT32_MAX);
+  cursor_store(found, b, lane, base);
 }
 
 // One workgroup (one wavefront) per trajectory over the stored records of the map log whose frame ordinal lies in [q0, q1).
@@ -143,13 +158,13 @@ __global__ __launch_bounds__(256) void k_map_log(Dev<S> d, int b0, int nb, const
 template <class S>
 __global__ __launch_bounds__(64) void k_map_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const double* gt, const int* off, double* out) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = min(max(found[b], 0), cap);
+  const int n = cursor_stored(found, b, cap);
   double cnt = 0, nm = 0, s2 = 0, mx = 0, ng = 0, sg = 0, sd = 0, un = 0;
   for (int r = lane; r < n; r += 64) {
     const Vec4<S>* q = reinterpret_cast<const Vec4<S>*>(rec + ((long)b * cap + r) * MAP_STRIDE);
     const Vec4<S> a = q[0], c = q[1];
     const int fr = (int)c.x[0], trk = (int)c.x[1], flags = (int)c.x[2];
-    if (fr < q0 || fr >= q1) continue;
+    if (!ordinal_in(fr, q0, q1)) continue;
     cnt += 1.0;
     if (gt) {
       const long cell = (long)(fr - q0) * B + b;
@@ -182,21 +197,18 @@ __global__ __launch_bounds__(64) void k_map_metrics(const S* rec, const int* fou
 //   0..3 q_CG | 4..6 p_C_G | 7 prune frame ordinal | 8..28 upper triangle of P[15 + 6 k .. 15 + 6 k + 5]^2 row by row |
 //   29 window size before the prune | 30 k, the dropped slot | 31 zero
 // Two records per step: lane = 32 * (record of the pair) + record index loads one scalar, the sixteen lanes 0..15 collect four
-// each over the LDS crossbar (lane l: scalars 4 l .. 4 l + 3 of the pair) and store them as aligned 4-vectors.  A destination
-// >= cap is counted but not stored (the map log's rule).  The trajectory belongs to one slice and its frames are ordered on
-// that slice's stream: lane 0 reads the cursor and stores it back, no atomics.
+// each over the LDS crossbar (lane l: scalars 4 l .. 4 l + 3 of the pair) and store them as aligned 4-vectors, behind the
+// cursor (cursor_read).
 template <class S>
 __global__ __launch_bounds__(256) void k_pruned_log(Dev<S> d, int b0, int nb, const int* drop, int ordinal, int cap, S* rec, int* found) {
-  const int lane = threadIdx.x & 63, i = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
-  if (i >= nb) return;   // (whole wavefronts)
+  int lane, i;
+  if (!log_wave(nb, lane, i)) return;
   const int b = b0 + i;
   const int n = min(d.ncam[b], d.n_cap);
   int nd = drop[i];
   nd = nd < 0 ? 0 : (nd > n ? n : nd);
   if (nd == 0) return;
-  int cur = 0;
-  if (lane == 0) cur = found[b];
-  const long base = wave_bcast(cur, 0);
+  const long base = cursor_read(found, b, lane);
   const int half = lane >> 5, j = lane & 31;
   const int t = j - PRN_COV;                                         // triangle entry t = (r, c), r <= c: row r starts at r (13 - r) / 2
   const int r = t < 6 ? 0 : (t < 11 ? 1 : (t < 15 ? 2 : (t < 18 ? 3 : (t < 20 ? 4 : 5))));
@@ -220,7 +232,7 @@ __global__ __launch_bounds__(256) void k_pruned_log(Dev<S> d, int b0, int nb, co
     const long dst = base + ks;
     if (lane < 16 && ks < nd && dst < cap) *reinterpret_cast<Vec4<S>*>(rec + ((long)b * cap + dst) * PRN_STRIDE + 4 * (lane & 7)) = o;
   }
-  if (lane == 0) found[b] = (int)min(base + nd, (long)INT32_MAX);
+  cursor_store(found, b, lane, base + nd);
 }
 
 // One workgroup (one wavefront) per trajectory over the stored records of the pruned-state log whose prune ordinal lies in
@@ -237,7 +249,7 @@ __global__ __launch_bounds__(256) void k_pruned_log(Dev<S> d, int b0, int nb, co
 template <class S>
 __global__ __launch_bounds__(64) void k_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int n = min(max(found[b], 0), cap);
+  const int n = cursor_stored(found, b, cap);
   double cnt = 0, nm = 0, sp = 0, mp = 0, sth = 0, mth = 0, nees = 0, nn = 0, bad = 0, un = 0;
   for (int rr = lane; rr < n; rr += 64) {
     const Vec4<S>* q = reinterpret_cast<const Vec4<S>*>(rec + ((long)b * cap + rr) * PRN_STRIDE);
@@ -249,7 +261,7 @@ __global__ __launch_bounds__(64) void k_pruned_metrics(const S* rec, const int* 
       for (int e = 0; e < 4; ++e) x[4 * v + e] = (double)a.x[e];
     }
     const int fr = (int)x[PRN_FRAME];
-    if (fr < q0 || fr >= q1) continue;
+    if (!ordinal_in(fr, q0, q1)) continue;
     cnt += 1.0;
     const int ord = aug[(long)b * cap + rr];
     if (ord < 0 || ord >= n_ord) { un += 1.0; continue; }
@@ -334,17 +346,14 @@ void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, con
   hipLaunchKernelGGL(k_log_metrics<S>, dim3(B), dim3(64), 0, st, log, B, r0, r1, r0b, r1b, gt, out);
 }
 
-template void launch_frame_log<float>(const Dev<float>&, int, int, hipStream_t, const float*, bool, float*);
-template void launch_frame_log<double>(const Dev<double>&, int, int, hipStream_t, const double*, bool, double*);
-template void launch_log_metrics<float>(const float*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
-template void launch_log_metrics<double>(const double*, int, int, int, const int*, const int*, const double*, double*, hipStream_t);
-template void launch_map_log<float>(const Dev<float>&, int, int, hipStream_t, const int*, const int*, int, int, float*, int*);
-template void launch_map_log<double>(const Dev<double>&, int, int, hipStream_t, const int*, const int*, int, int, double*, int*);
-template void launch_map_metrics<float>(const float*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
-template void launch_map_metrics<double>(const double*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t);
-template void launch_pruned_log<float>(const Dev<float>&, int, int, hipStream_t, const int*, int, int, float*, int*);
-template void launch_pruned_log<double>(const Dev<double>&, int, int, hipStream_t, const int*, int, int, double*, int*);
-template void launch_pruned_metrics<float>(const float*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
-template void launch_pruned_metrics<double>(const double*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
+#define MSCKF_LOG_LAUNCHERS(S)                                                                                        \
+  template void launch_frame_log<S>(const Dev<S>&, int, int, hipStream_t, const S*, bool, S*);                         \
+  template void launch_log_metrics<S>(const S*, int, int, int, const int*, const int*, const double*, double*, hipStream_t); \
+  template void launch_map_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, const int*, int, int, S*, int*);   \
+  template void launch_map_metrics<S>(const S*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t); \
+  template void launch_pruned_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, int, int, S*, int*);            \
+  template void launch_pruned_metrics<S>(const S*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
+MSCKF_LOG_LAUNCHERS(float)
+MSCKF_LOG_LAUNCHERS(double)
 
 }  // namespace msckf

@@ -224,20 +224,23 @@ struct BatchCore {
   // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
   // (log_base = log_n at its start, read by the slices' enqueue threads) and advances log_n when it has succeeded
   void* log_buf = nullptr; int log_cap = 0, log_n = 0, log_base = 0;
-  // map log (msckf_hip_map_log_*; kernels_log.hip): [B][map_cap][MAP_STRIDE] scalars of esz bytes and the device cursors
-  // map_found[B] (records found per trajectory, stored or not), null unless enabled.  map_ord counts the frame ordinals handed
-  // out; a run_frames / run_frames_streamed call over [f0, f1) stamps its records with map_base + (f - f0) (map_base = map_ord
-  // at its start) and advances map_ord when it has succeeded
-  void* map_buf = nullptr; int* map_found = nullptr; int map_cap = 0, map_ord = 0, map_base = 0;
-  // pruned-state log (msckf_hip_pruned_log_*; kernels_log.hip): [B][prn_cap][PRN_STRIDE] scalars of esz bytes and the device
-  // cursors prn_found[B], null unless enabled; prn_ord / prn_base hand out the frame ordinals as map_ord / map_base do.  While
-  // it is on no frame's prune rides on the downdate (fuse_frame): the record is read between the update and the prune launch.
-  // Which image's camera a record is: run_frames drops oldest-first, so per trajectory prn_fifo holds the augment ordinals of
-  // the states in the window, oldest first (-1: a state that was there at enable / reset time or came in through another
-  // call), and prn_aug the popped ordinal of every stored record.  Both are written by the enqueue thread of the
-  // trajectory's slice only (the loop at the end of enqueue_frame that mirrors augment and drop into h_ncam).
-  void* prn_buf = nullptr; int* prn_found = nullptr; int prn_cap = 0, prn_ord = 0, prn_base = 0;
-  std::vector<std::vector<int>> prn_fifo, prn_aug;
+  // A cursor log (kernels_log.hip): buf [B][cap][stride] scalars of esz bytes and the device cursors found[B] (records found
+  // per trajectory, stored or not), null unless enabled.  ord counts the frame ordinals handed out; a run_frames /
+  // run_frames_streamed call over [f0, f1) stamps its records with ordinal(f, f0) (base = ord at its start, read by the
+  // slices' enqueue threads) and advances ord when it has succeeded.  name and api word the messages.
+  struct CursorLog {
+    int stride; const char* name; const char* api;
+    void* buf = nullptr; int* found = nullptr; int cap = 0, ord = 0, base = 0;
+    int ordinal(int f, int f0) const { return base + (f - f0); }
+  };
+  // map log (msckf_hip_map_log_*): one record per triangulated track
+  CursorLog map{MAP_STRIDE, "map log", "msckf_hip_map_log"};
+  // pruned-state log (msckf_hip_pruned_log_*): one record per dropped camera state.  While it is on no frame's prune rides on
+  // the downdate (fuse_frame): the record is read between the update and the prune launch.  prn_list (host_lists.h) knows
+  // which image's camera a record is; it is written by the enqueue thread of the trajectory's slice only (the loop at the end
+  // of enqueue_frame that mirrors augment and drop into h_ncam).
+  CursorLog prn{PRN_STRIDE, "pruned-state log", "msckf_hip_pruned_log"};
+  PrunedFifo prn_list;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[NSTAGE];
@@ -277,11 +280,7 @@ struct BatchCore {
     hipSetDevice(device);
     if (st) hipStreamSynchronize(st);
     for (void* p : allocs) hipFree(p);
-    if (log_buf) hipFree(log_buf);
-    if (map_buf) hipFree(map_buf);
-    if (map_found) hipFree(map_found);
-    if (prn_buf) hipFree(prn_buf);
-    if (prn_found) hipFree(prn_found);
+    release_logs();
     if (h_rb) hipHostFree(h_rb);
     for (int s = 0; s < NSTAGE; ++s) for (auto& e : ev_pool[s]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int i = 1; i < MAXS; ++i) { if (stx[i]) hipStreamDestroy(stx[i]); if (ev_join[i]) hipEventDestroy(ev_join[i]); }
@@ -671,100 +670,151 @@ struct BatchCore {
     for (int i = 0; i < nh; ++i)
       if (slice_rc[i]) return poison(-EIO, std::string("kernel launch failed on slice ") + std::to_string(i) + ": " + hipGetErrorString((hipError_t)slice_rc[i]));
     commit_buffer_parity(f0, f1);
-    if (log_buf) log_n += f1 - f0;
-    if (map_buf) map_ord += f1 - f0;
-    if (prn_buf) prn_ord += f1 - f0;
+    advance_logs(f1 - f0);
     return 0;
   }
-  // ---- frame log
-  // capacity_frames records for every trajectory, or (0) none: frees a log that exists either way.  An allocation that fails
-  // leaves the log off and the handle as it was
-  int frame_log_enable(int capacity_frames) {
+  // ---- the device logs of the frame loop: the frame log (dense: record = frame), the map log and the pruned-state log (cursor
+  // logs).  Enabled with a capacity, or (0) switched off: either way a log that exists is freed and its records are dropped.
+  template <class T> static void dfree(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
+  // what every *_log_enable does first; the handle's stream is idle when the old storage goes
+  int log_enable_enter(int capacity) {
     if (int rc = guard()) return rc;
-    if (capacity_frames < 0) return fail(-EINVAL, "negative capacity");
+    if (capacity < 0) return fail(-EINVAL, "negative capacity");
     if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(st));
-    if (log_buf) (void)hipFree(log_buf);
-    log_buf = nullptr; log_cap = 0; log_n = 0;
-    if (!capacity_frames) return 0;
-    void* q = nullptr;
-    if (hipMalloc(&q, (size_t)capacity_frames * B * LOG_STRIDE * esz) != hipSuccess) {
+    return 0;
+  }
+  // a log's storage of `bytes` and, for a cursor log, its B cursors at zero.  A step that fails gives back what the earlier
+  // ones got: the log stays off and the handle as it was
+  int log_alloc(const char* name, size_t bytes, void** buf, int** cursors) {
+    void* q = nullptr; void* c = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess || (cursors && hipMalloc(&c, (size_t)B * sizeof(int)) != hipSuccess)) {
       (void)hipGetLastError();
-      return fail(-ENOMEM, "could not allocate the frame log (it stays disabled; the handle is unaffected)");
+      dfree(q);
+      return fail(-ENOMEM, std::string("could not allocate the ") + name + " (it stays disabled; the handle is unaffected)");
     }
-    log_buf = q; log_cap = capacity_frames;
+    if (cursors && (hipMemsetAsync(c, 0, (size_t)B * sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+      dfree(q); dfree(c);
+      return fail(-EIO, std::string("could not clear the ") + name + "'s cursors (it stays disabled)");
+    }
+    *buf = q;
+    if (cursors) *cursors = static_cast<int*>(c);
+    return 0;
+  }
+  // head of run_frames / run_frames_streamed, before anything is enqueued, in the order frame, map, pruned: a log that refuses
+  // the call leaves the later ones untouched
+  int reserve_logs(int f0, int f1) {
+    if (int rc = frame_log_reserve(f0, f1)) return rc;
+    if (int rc = cursor_log_reserve(map, f0, f1)) return rc;
+    return pruned_log_reserve(f0, f1);
+  }
+  // finish_slices, when the call's frames have succeeded
+  void advance_logs(int frames) {
+    if (log_buf) log_n += frames;
+    for (CursorLog* g : {&map, &prn}) if (g->buf) g->ord += frames;
+  }
+  void release_logs() {
+    dfree(log_buf);
+    for (CursorLog* g : {&map, &prn}) { dfree(g->buf); dfree(g->found); }
+  }
+  // ---- frame log
+  int frame_log_enable(int capacity_frames) {
+    if (int rc = log_enable_enter(capacity_frames)) return rc;
+    dfree(log_buf); log_cap = 0; log_n = 0;
+    if (!capacity_frames) return 0;
+    if (int rc = log_alloc("frame log", (size_t)capacity_frames * B * LOG_STRIDE * esz, &log_buf, nullptr)) return rc;
+    log_cap = capacity_frames;
     return 0;
   }
   int frame_log_reset() { log_n = 0; return 0; }
   int frame_log_count() const { return log_n; }
-  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's records fit, and start at log_n
+  // the call's records fit, and start at log_n
   int frame_log_reserve(int f0, int f1) {
     if (!log_buf) return 0;
     if ((long)log_n + (f1 - f0) > log_cap) return fail(-ENOSPC, "frame log full: the call's frames do not fit behind the records written (msckf_hip_frame_log_reset, or a larger msckf_hip_frame_log_enable); nothing was run");
     log_base = log_n;
     return 0;
   }
-  // ---- map log
-  // capacity_per_trajectory records for every trajectory and a cursor each, or (0) none: frees a log that exists either way
-  // and drops its records.  An allocation that fails leaves the log off and the handle as it was
-  int map_log_enable(int capacity) {
-    if (int rc = guard()) return rc;
-    if (capacity < 0) return fail(-EINVAL, "negative capacity");
-    if (int rc = enter()) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    if (map_buf) (void)hipFree(map_buf);
-    if (map_found) (void)hipFree(map_found);
-    map_buf = nullptr; map_found = nullptr; map_cap = 0; map_ord = 0;
+  // ---- cursor logs
+  int cursor_log_enable(CursorLog& g, int capacity) {
+    if (int rc = log_enable_enter(capacity)) return rc;
+    dfree(g.buf); dfree(g.found); g.cap = 0; g.ord = 0;
     if (!capacity) return 0;
-    void* q = nullptr; void* c = nullptr;
-    if (hipMalloc(&q, (size_t)capacity * B * MAP_STRIDE * esz) != hipSuccess || hipMalloc(&c, (size_t)B * sizeof(int)) != hipSuccess) {
-      (void)hipGetLastError();
-      if (q) (void)hipFree(q);
-      return fail(-ENOMEM, "could not allocate the map log (it stays disabled; the handle is unaffected)");
-    }
-    if (hipMemsetAsync(c, 0, (size_t)B * sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(q); (void)hipFree(c);
-      return fail(-EIO, "could not clear the map log's cursors (it stays disabled)");
-    }
-    map_buf = q; map_found = static_cast<int*>(c); map_cap = capacity;
+    if (int rc = log_alloc(g.name, (size_t)capacity * B * g.stride * esz, &g.buf, &g.found)) return rc;
+    g.cap = capacity;
     return 0;
   }
   // cursors and frame ordinal <- 0 (the storage stays); ordered on st before the next call's frames
-  int map_log_reset() {
+  int cursor_log_reset(CursorLog& g) {
     if (int rc = guard()) return rc;
-    map_ord = 0;
-    if (!map_buf) return 0;
+    g.ord = 0;
+    if (!g.buf) return 0;
     if (int rc = enter()) return rc;
-    HIPCHK(hipMemsetAsync(map_found, 0, (size_t)B * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(g.found, 0, (size_t)B * sizeof(int), st));
     return 0;
   }
-  int map_log_frames() const { return map_ord; }
-  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's ordinals start at map_ord and stay exact
-  // in a float record
-  int map_log_reserve(int f0, int f1) {
-    if (!map_buf) return 0;
-    if ((long)map_ord + (f1 - f0) > (1L << 24)) return fail(-ENOSPC, "map log: the call's frame ordinals would pass 2^24 (msckf_hip_map_log_reset); nothing was run");
-    map_base = map_ord;
+  // the call's ordinals start at ord and stay exact in a float record
+  int cursor_log_reserve(CursorLog& g, int f0, int f1) {
+    if (!g.buf) return 0;
+    if ((long)g.ord + (f1 - f0) > (1L << 24)) return fail(-ENOSPC, std::string(g.name) + ": the call's frame ordinals would pass 2^24 (" + g.api + "_reset); nothing was run");
+    g.base = g.ord;
     return 0;
   }
-  // after the handle's stream: per trajectory of [b0, b0 + nb) the records found and how many of them are stored
-  int map_log_counts(int b0, int nb, int* stored, int* found) {
+  int cursor_log_enabled(const CursorLog& g) const { return g.buf ? 0 : fail(-EINVAL, std::string(g.name) + " not enabled (" + g.api + "_enable)"); }
+  // after the handle's stream: per trajectory of [b0, b0 + nb) the records found and how many of them are stored -- found
+  // counts on beyond the capacity, stored does not
+  int cursor_log_counts(CursorLog& g, int b0, int nb, int* stored, int* found) {
     if (int rc = guard()) return rc;
-    if (!map_buf) return fail(-EINVAL, "map log not enabled (msckf_hip_map_log_enable)");
+    if (int rc = cursor_log_enabled(g)) return rc;
     if (int rc = enter_range(b0, nb)) return rc;
     std::vector<int> tmp(std::max(nb, 1));
-    if (nb) HIPCHK(hipMemcpyAsync(tmp.data(), map_found + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (nb) HIPCHK(hipMemcpyAsync(tmp.data(), g.found + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (int i = 0; i < nb; ++i) {
       if (found) found[i] = tmp[i];
-      if (stored) stored[i] = std::min(tmp[i], map_cap);
+      if (stored) stored[i] = std::min(tmp[i], g.cap);
     }
     return 0;
   }
+  // what a read checks: the cursor first, then the range [r0, r0 + n) against trajectory b's stored records
+  int cursor_log_check_range(CursorLog& g, int b, int r0, int n) {
+    int stored = 0;
+    if (int rc = cursor_log_counts(g, b, 1, &stored, nullptr)) return rc;
+    if (r0 < 0 || n < 0 || (long)r0 + n > stored) return fail(-EINVAL, std::string("record range beyond the records stored (") + g.api + "_counts)");
+    return 0;
+  }
+  // what a metrics call checks first: the log is on and [q0, q1) lies within the ordinals handed out
+  int cursor_log_check_ordinals(const CursorLog& g, int q0, int q1) const {
+    if (int rc = cursor_log_enabled(g)) return rc;
+    if (q0 < 0 || q1 < q0 || q1 > g.ord) return fail(-EINVAL, std::string("frame ordinal range beyond the ordinals handed out (") + g.api + "_frames)");
+    return 0;
+  }
+  // One metrics call: the block [ground truth | out | ints] goes to the device on st, launch(gt, out, ints) enqueues the
+  // kernel there, out[no] comes back; the block is freed on every way out and the first error of the two (enqueueing,
+  // waiting) is the one reported
+  template <class Launch>
+  int log_metrics_call(const char* what, const double* gt, size_t ng, const int* ints, size_t ni, double* out, size_t no, Launch launch) {
+    double* dg = nullptr;
+    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + std::max<size_t>(ni, 1) * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
+    double* dout = dg + std::max<size_t>(ng, 1);
+    int* di = reinterpret_cast<int*>(dout + no);
+    hipError_t e = ng ? hipMemcpyAsync(dg, gt, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
+    if (e == hipSuccess && ni) e = hipMemcpyAsync(di, ints, ni * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) { launch(dg, dout, di); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dg);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string(what) + ": " + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // ---- map log
+  int map_log_enable(int capacity) { return cursor_log_enable(map, capacity); }
+  int map_log_reset() { return cursor_log_reset(map); }
+  int map_log_frames() const { return map.ord; }
+  int map_log_counts(int b0, int nb, int* stored, int* found) { return cursor_log_counts(map, b0, nb, stored, found); }
   // what map_log_metrics checks before anything reaches the device: the ordinal range, and off as CSR over its cells
   int map_log_check_gt(int q0, int q1, const double* gt_xyz, const int* gt_off) {
-    if (!map_buf) return fail(-EINVAL, "map log not enabled (msckf_hip_map_log_enable)");
-    if (q0 < 0 || q1 < q0 || q1 > map_ord) return fail(-EINVAL, "frame ordinal range beyond the ordinals handed out (msckf_hip_map_log_frames)");
+    if (int rc = cursor_log_check_ordinals(map, q0, q1)) return rc;
     if ((gt_xyz == nullptr) != (gt_off == nullptr)) return fail(-EINVAL, "gt_xyz and gt_off: both or neither");
     if (!gt_off) return 0;
     const size_t cells = (size_t)(q1 - q0) * B;
@@ -773,86 +823,31 @@ struct BatchCore {
       if (gt_off[c + 1] < gt_off[c]) return fail(-EINVAL, "gt_off decreases at cell " + std::to_string(c) + " (CSR offsets over the cells (frame - q0) * B + b)");
     return 0;
   }
-  // ---- pruned-state log
-  // every state in the window becomes one whose image is unknown (ordinal -1)
-  void pruned_log_forget() { for (int b = 0; b < (int)prn_fifo.size(); ++b) prn_fifo[b].assign(h_ncam[b], -1); }
-  // capacity_per_trajectory records for every trajectory and a cursor each, or (0) none: frees a log that exists either way,
-  // drops its records and gives the fused prune back.  An allocation that fails leaves the log off and the handle as it was
+  // ---- pruned-state log: a cursor log, and the host mirror of which image's camera a record is
+  // switching it off gives the fused prune back
   int pruned_log_enable(int capacity) {
-    if (int rc = guard()) return rc;
-    if (capacity < 0) return fail(-EINVAL, "negative capacity");
-    if (int rc = enter()) return rc;
-    HIPCHK(hipStreamSynchronize(st));
-    if (prn_buf) (void)hipFree(prn_buf);
-    if (prn_found) (void)hipFree(prn_found);
-    prn_buf = nullptr; prn_found = nullptr; prn_cap = 0; prn_ord = 0;
-    prn_fifo.clear(); prn_aug.clear();
-    if (!capacity) return 0;
-    void* q = nullptr; void* c = nullptr;
-    if (hipMalloc(&q, (size_t)capacity * B * PRN_STRIDE * esz) != hipSuccess || hipMalloc(&c, (size_t)B * sizeof(int)) != hipSuccess) {
-      (void)hipGetLastError();
-      if (q) (void)hipFree(q);
-      return fail(-ENOMEM, "could not allocate the pruned-state log (it stays disabled; the handle is unaffected)");
-    }
-    if (hipMemsetAsync(c, 0, (size_t)B * sizeof(int), st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(q); (void)hipFree(c);
-      return fail(-EIO, "could not clear the pruned-state log's cursors (it stays disabled)");
-    }
-    prn_buf = q; prn_found = static_cast<int*>(c); prn_cap = capacity;
-    prn_fifo.assign(B, std::vector<int>()); prn_aug.assign(B, std::vector<int>());
-    pruned_log_forget();
-    return 0;
+    const int rc = cursor_log_enable(prn, capacity);
+    if (!prn.buf) prn_list.clear();              // off, or the old log went and no new one came
+    else if (!rc) prn_list.start(h_ncam);
+    return rc;
   }
-  // cursors and frame ordinal <- 0 (the storage stays); ordered on st before the next call's frames
   int pruned_log_reset() {
-    if (int rc = guard()) return rc;
-    prn_ord = 0;
-    if (!prn_buf) return 0;
-    if (int rc = enter()) return rc;
-    HIPCHK(hipMemsetAsync(prn_found, 0, (size_t)B * sizeof(int), st));
-    for (auto& a : prn_aug) a.clear();
-    pruned_log_forget();
+    if (int rc = cursor_log_reset(prn)) return rc;
+    if (prn.buf) prn_list.start(h_ncam);
     return 0;
   }
-  int pruned_log_frames() const { return prn_ord; }
-  // head of run_frames / run_frames_streamed, before anything is enqueued: the call's ordinals start at prn_ord and stay exact
-  // in a float record; a trajectory whose window changed size behind the log's back (any other call) holds unknown states
+  int pruned_log_frames() const { return prn.ord; }
   int pruned_log_reserve(int f0, int f1) {
-    if (!prn_buf) return 0;
-    if ((long)prn_ord + (f1 - f0) > (1L << 24)) return fail(-ENOSPC, "pruned-state log: the call's frame ordinals would pass 2^24 (msckf_hip_pruned_log_reset); nothing was run");
-    prn_base = prn_ord;
-    for (int b = 0; b < B; ++b) if ((int)prn_fifo[b].size() != h_ncam[b]) prn_fifo[b].assign(h_ncam[b], -1);
+    if (int rc = cursor_log_reserve(prn, f0, f1)) return rc;
+    prn_list.resync(h_ncam);
     return 0;
   }
-  // enqueue_frame's host mirror of one cell, called where h_ncam takes the same steps: the augment pushes the frame's ordinal,
-  // the drop pops the nd oldest into the ordinals of the records that the frame's k_pruned_log launch stores
-  void pruned_log_mirror(int b, bool augmented, int nd, int ordinal) {
-    std::vector<int>& q = prn_fifo[b];
-    if (augmented) q.push_back(ordinal);
-    for (int k = 0; k < nd; ++k) if ((int)prn_aug[b].size() < prn_cap) prn_aug[b].push_back(q[k]);
-    q.erase(q.begin(), q.begin() + nd);
-  }
-  // after the handle's stream: per trajectory of [b0, b0 + nb) the records found and how many of them are stored
-  int pruned_log_counts(int b0, int nb, int* stored, int* found) {
-    if (int rc = guard()) return rc;
-    if (!prn_buf) return fail(-EINVAL, "pruned-state log not enabled (msckf_hip_pruned_log_enable)");
-    if (int rc = enter_range(b0, nb)) return rc;
-    std::vector<int> tmp(std::max(nb, 1));
-    if (nb) HIPCHK(hipMemcpyAsync(tmp.data(), prn_found + b0, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < nb; ++i) {
-      if (found) found[i] = tmp[i];
-      if (stored) stored[i] = std::min(tmp[i], prn_cap);
-    }
-    return 0;
-  }
+  int pruned_log_counts(int b0, int nb, int* stored, int* found) { return cursor_log_counts(prn, b0, nb, stored, found); }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
-    if (int rc = frame_log_reserve(f0, f1)) return rc;
-    if (int rc = map_log_reserve(f0, f1)) return rc;
-    if (int rc = pruned_log_reserve(f0, f1)) return rc;
+    if (int rc = reserve_logs(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     const int nh = n_slices();
     const int rc = fork_slices(nh);
@@ -883,9 +878,7 @@ struct BatchCore {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
-    if (int rc = frame_log_reserve(f0, f1)) return rc;
-    if (int rc = map_log_reserve(f0, f1)) return rc;
-    if (int rc = pruned_log_reserve(f0, f1)) return rc;
+    if (int rc = reserve_logs(f0, f1)) return rc;
     if (int rc = enter()) return rc;
     {
       bool all = sg_blk[0] != nullptr;
@@ -1470,7 +1463,7 @@ struct Batch : BatchCore {
   // the next frame's k_propagate commits the window size)?  Never the call's last frame: it prunes with its own launch, so that
   // ncam is final when the call returns; and no frame while the pruned-state log is on: its record is the state between the update
   // and the prune, which only the prune's own launch leaves in reach.  The frame step and commit_buffer_parity both ask here.
-  bool fuse_frame(int f, int f1) const { return settings.fuse_prune && !prof && !settings.overlap_feature && d.joseph == 0 && f + 1 < f1 && !prn_buf; }
+  bool fuse_frame(int f, int f1) const { return settings.fuse_prune && !prof && !settings.overlap_feature && d.joseph == 0 && f + 1 < f1 && !prn.buf; }
   // every slice ran the same frames; each fused one flipped the buffers
   void commit_buffer_parity(int f0, int f1) override {
     int flips = 0;
@@ -1719,7 +1712,7 @@ struct Batch : BatchCore {
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
     settings.take_over(o->settings);
-    pruned_log_forget();   // (the log stays with its handle; the states taken over are none of its images)
+    prn_list.forget(h_ncam);   // (the log stays with its handle; the states taken over are none of its images)
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
     return set_aniso(settings.aniso_mode, settings.lit_tol);   // applies the settings, re-derives the per-trajectory noise parameters, allocates the literal route's work space if needed
@@ -1841,8 +1834,8 @@ struct Batch : BatchCore {
     if (fuse) s.flipped = !s.flipped;
     else {
       // pruned-state log: the states this frame drops, as the update left them (v.P: in place), with frame ordinal
-      // prn_base + (f - f0), behind the trajectories' cursors; outside the stage timers
-      if (prn_buf) launch_pruned_log<S>(v, b0, nb, q, in.drop, prn_base + (f - f0), prn_cap, static_cast<S*>(prn_buf), prn_found);
+      // prn.ordinal(f, f0), behind the trajectories' cursors; outside the stage timers
+      if (prn.buf) launch_pruned_log<S>(v, b0, nb, q, in.drop, prn.ordinal(f, f0), prn.cap, static_cast<S*>(prn.buf), prn.found);
       StageRange r("msckf_prune_empty_states");
       stage_begin(6, q);
       launch_prune<S>(v, b0, nb, q, in.drop, 0);
@@ -1853,14 +1846,14 @@ struct Batch : BatchCore {
     // prune left it (ncam_upd while it is pending) -- as record log_base + (f - f0); outside the stage timers
     if (log_buf) launch_frame_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, s.pending, static_cast<S*>(log_buf) + (size_t)(log_base + (f - f0)) * B * LOG_STRIDE);
     // map log: the tracks of the work-list the update read (in.n, in.M: resident or staged) with frame ordinal
-    // map_base + (f - f0), behind the trajectories' cursors; also outside the stage timers
-    if (map_buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map_base + (f - f0), map_cap, static_cast<S*>(map_buf), map_found);
+    // map.ordinal(f, f0), behind the trajectories' cursors; also outside the stage timers
+    if (map.buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map.ordinal(f, f0), map.cap, static_cast<S*>(map.buf), map.found);
     for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment (not for a skipped cell), then drop n_drop (clamped as k_make_keep does)
       const bool augmented = h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP;
       if (augmented) h_ncam[b]++;
       const int nd = std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
       h_ncam[b] -= nd;
-      if (prn_buf) pruned_log_mirror(b, augmented, nd, prn_base + (f - f0));
+      if (prn.buf) prn_list.mirror(b, augmented, nd, prn.ordinal(f, f0), prn.cap);
     }
   }
   // records [r0, r0 + n) of trajectories [b0, b0 + nb) as doubles: one strided copy, one wait
@@ -1883,33 +1876,25 @@ struct Batch : BatchCore {
     if (int rc = guard()) return rc;
     if (r0 < 0 || r1 < r0 || r1 > log_n) return fail(-EINVAL, "record range beyond the records written (msckf_hip_frame_log_count)");
     if (int rc = enter()) return rc;
-    const size_t ng = (size_t)(r1 - r0) * B * 3, no = (size_t)B * 6;
-    double* dg = nullptr;                                      // [ground truth | out | r0b r1b], freed on every way out
-    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + 2 * (size_t)B * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
-    double* dout = dg + std::max<size_t>(ng, 1);
-    int* dr = reinterpret_cast<int*>(dout + no);
-    hipError_t e = ng ? hipMemcpyAsync(dg, gt_p, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-    if (e == hipSuccess && r0b) e = hipMemcpyAsync(dr, r0b, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && r0b) e = hipMemcpyAsync(dr + B, r1b, (size_t)B * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { launch_log_metrics<S>(static_cast<const S*>(log_buf), B, r0, r1, r0b ? dr : nullptr, r0b ? dr + B : nullptr, dg, dout, st); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    (void)hipFree(dg);
-    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("frame_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
-    return 0;
+    std::vector<int> rb;                                       // r0b | r1b
+    if (r0b) { rb.assign(r0b, r0b + B); rb.insert(rb.end(), r1b, r1b + B); }
+    return log_metrics_call("frame_log_metrics", gt_p, (size_t)(r1 - r0) * B * 3, rb.data(), rb.size(), out, (size_t)B * 6, [&](const double* dg, double* dout, const int* dr) {
+      launch_log_metrics<S>(static_cast<const S*>(log_buf), B, r0, r1, r0b ? dr : nullptr, r0b ? dr + B : nullptr, dg, dout, st);
+    });
   }
-  // stored records [r0, r0 + n) of trajectory b as doubles: the cursor first (a range beyond min(found, capacity) is refused),
-  // then one copy
-  int map_log_read(int b, int r0, int n, double* out) override {
-    int stored = 0;
-    if (int rc = map_log_counts(b, 1, &stored, nullptr)) return rc;
-    if (r0 < 0 || n < 0 || (long)r0 + n > stored) return fail(-EINVAL, "record range beyond the records stored (msckf_hip_map_log_counts)");
+  // stored records [r0, r0 + n) of trajectory b of a cursor log as doubles: one copy, after cursor_log_check_range
+  int cursor_log_copy(const CursorLog& g, int b, int r0, int n, double* out) {
     if (!n) return 0;
-    std::vector<S> tmp((size_t)n * MAP_STRIDE);
-    if (const int rc = read_back(tmp.data(), static_cast<const S*>(map_buf) + ((size_t)b * map_cap + r0) * MAP_STRIDE, tmp.size() * sizeof(S))) return rc;
+    std::vector<S> tmp((size_t)n * g.stride);
+    if (const int rc = read_back(tmp.data(), static_cast<const S*>(g.buf) + ((size_t)b * g.cap + r0) * g.stride, tmp.size() * sizeof(S))) return rc;
     for (size_t i = 0; i < tmp.size(); ++i) out[i] = (double)tmp[i];
     return 0;
   }
+  int cursor_log_read(CursorLog& g, int b, int r0, int n, double* out) {
+    if (int rc = cursor_log_check_range(g, b, r0, n)) return rc;
+    return cursor_log_copy(g, b, r0, n, out);
+  }
+  int map_log_read(int b, int r0, int n, double* out) override { return cursor_log_read(map, b, r0, n, out); }
   // the stored records with frame ordinal in [q0, q1) against ground-truth landmarks (CSR per cell; both null: none), reduced on
   // the device (k_map_metrics): per trajectory records, matched, sum |e|^2, max |e|, gated records with their own gamma,
   // sum gamma, sum 2 M - 3, unmatched
@@ -1917,57 +1902,33 @@ struct Batch : BatchCore {
     if (int rc = guard()) return rc;
     if (int rc = map_log_check_gt(q0, q1, gt_xyz, gt_off)) return rc;
     if (int rc = enter()) return rc;
-    const size_t cells = (size_t)(q1 - q0) * B, noff = gt_off ? cells + 1 : 0, ng = gt_off ? (size_t)gt_off[cells] * 3 : 0, no = (size_t)B * 8;
-    double* dg = nullptr;                                      // [ground truth | out | off], freed on every way out
-    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + std::max<size_t>(noff, 1) * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
-    double* dout = dg + std::max<size_t>(ng, 1);
-    int* doff = reinterpret_cast<int*>(dout + no);
-    hipError_t e = ng ? hipMemcpyAsync(dg, gt_xyz, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-    if (e == hipSuccess && noff) e = hipMemcpyAsync(doff, gt_off, noff * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { launch_map_metrics<S>(static_cast<const S*>(map_buf), map_found, map_cap, B, q0, q1, gt_off ? dg : nullptr, gt_off ? doff : nullptr, dout, st); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    (void)hipFree(dg);
-    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("map_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
-    return 0;
+    const size_t cells = (size_t)(q1 - q0) * B, noff = gt_off ? cells + 1 : 0, ng = gt_off ? (size_t)gt_off[cells] * 3 : 0;
+    return log_metrics_call("map_log_metrics", gt_xyz, ng, gt_off, noff, out, (size_t)B * 8, [&](const double* dg, double* dout, const int* doff) {
+      launch_map_metrics<S>(static_cast<const S*>(map.buf), map.found, map.cap, B, q0, q1, gt_off ? dg : nullptr, gt_off ? doff : nullptr, dout, st);
+    });
   }
-  // stored records [r0, r0 + n) of trajectory b as doubles and the augment ordinal of each: the cursor first (a range beyond
-  // min(found, capacity) is refused), then one copy
+  // the map log's read, and the augment ordinal of each record from the host mirror
   int pruned_log_read(int b, int r0, int n, double* out, int* aug_ord) override {
-    int stored = 0;
-    if (int rc = pruned_log_counts(b, 1, &stored, nullptr)) return rc;
-    if (r0 < 0 || n < 0 || (long)r0 + n > stored) return fail(-EINVAL, "record range beyond the records stored (msckf_hip_pruned_log_counts)");
+    if (int rc = cursor_log_check_range(prn, b, r0, n)) return rc;
     if (!n) return 0;
-    if ((int)prn_aug[b].size() < r0 + n) return fail(-EIO, "pruned-state log: fewer augment ordinals on the host than records on the device");
-    std::vector<S> tmp((size_t)n * PRN_STRIDE);
-    if (const int rc = read_back(tmp.data(), static_cast<const S*>(prn_buf) + ((size_t)b * prn_cap + r0) * PRN_STRIDE, tmp.size() * sizeof(S))) return rc;
-    for (size_t i = 0; i < tmp.size(); ++i) out[i] = (double)tmp[i];
-    if (aug_ord) std::copy(prn_aug[b].begin() + r0, prn_aug[b].begin() + r0 + n, aug_ord);
+    const std::vector<int>& aug = prn_list.aug[b];
+    if ((int)aug.size() < r0 + n) return fail(-EIO, "pruned-state log: fewer augment ordinals on the host than records on the device");
+    if (int rc = cursor_log_copy(prn, b, r0, n, out)) return rc;
+    if (aug_ord) std::copy(aug.begin() + r0, aug.begin() + r0 + n, aug_ord);
     return 0;
   }
   // the stored records with prune ordinal in [q0, q1) against ground-truth poses gt_pose[n_ord][B][7], matched through their
   // augment ordinals (uploaded here, off the frame path), reduced on the device (k_pruned_metrics): out [B][10]
   int pruned_log_metrics(int q0, int q1, const double* gt_pose, int n_ord, double* out) override {
     if (int rc = guard()) return rc;
-    if (!prn_buf) return fail(-EINVAL, "pruned-state log not enabled (msckf_hip_pruned_log_enable)");
-    if (q0 < 0 || q1 < q0 || q1 > prn_ord) return fail(-EINVAL, "frame ordinal range beyond the ordinals handed out (msckf_hip_pruned_log_frames)");
+    if (int rc = cursor_log_check_ordinals(prn, q0, q1)) return rc;
     if (n_ord < 0 || (n_ord > 0 && !gt_pose)) return fail(-EINVAL, "gt_pose: n_ord poses per trajectory, n_ord >= 0, null only with n_ord == 0");
     if (int rc = enter()) return rc;
-    const size_t ng = (size_t)n_ord * B * 7, no = (size_t)B * 10, na = (size_t)B * prn_cap;
-    std::vector<int> aug(na, -1);
-    for (int b = 0; b < B; ++b) std::copy(prn_aug[b].begin(), prn_aug[b].end(), aug.begin() + (size_t)b * prn_cap);
-    double* dg = nullptr;                                      // [ground truth | out | aug], freed on every way out
-    if (hipMalloc((void**)&dg, (std::max<size_t>(ng, 1) + no) * sizeof(double) + na * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return fail(-ENOMEM, "could not allocate the ground truth on the device"); }
-    double* dout = dg + std::max<size_t>(ng, 1);
-    int* daug = reinterpret_cast<int*>(dout + no);
-    hipError_t e = ng ? hipMemcpyAsync(dg, gt_pose, ng * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-    if (e == hipSuccess) e = hipMemcpyAsync(daug, aug.data(), na * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) { launch_pruned_metrics<S>(static_cast<const S*>(prn_buf), prn_found, prn_cap, B, q0, q1, daug, dg, n_ord, dout, st); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, no * sizeof(double), hipMemcpyDeviceToHost, st);
-    const hipError_t es = hipStreamSynchronize(st);
-    (void)hipFree(dg);
-    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("pruned_log_metrics: ") + hipGetErrorString(e != hipSuccess ? e : es));
-    return 0;
+    std::vector<int> aug((size_t)B * prn.cap, -1);
+    for (int b = 0; b < B; ++b) std::copy(prn_list.aug[b].begin(), prn_list.aug[b].end(), aug.begin() + (size_t)b * prn.cap);
+    return log_metrics_call("pruned_log_metrics", gt_pose, (size_t)n_ord * B * 7, aug.data(), aug.size(), out, (size_t)B * 10, [&](const double* dg, double* dout, const int* daug) {
+      launch_pruned_metrics<S>(static_cast<const S*>(prn.buf), prn.found, prn.cap, B, q0, q1, daug, dg, n_ord, dout, st);
+    });
   }
 };
 
