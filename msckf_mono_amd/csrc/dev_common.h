@@ -16,6 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <type_traits>
+
+#include "update_routes.h"
+
 namespace msckf {
 
 constexpr int IMU_STRIDE = 32;
@@ -186,6 +190,11 @@ __device__ __forceinline__ bool xcd_item(int nb, int items, int& i, int& item) {
   return i < nb;
 }
 inline int xcd_grid(int nb, int items) { return 8 * ((nb + 7) / 8) * items; }
+
+// Host side: a route (update_routes.h) names a template argument by its value; f(std::integral_constant<int, V>) runs for the
+// first V of Vs equal to v, so that each launch line is written once over its instantiations.  False: v is none of them.
+template <int... Vs, class F>
+inline bool dispatch_int(int v, F&& f) { return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...); }
 
 // Bookkeeping of a prune, by one workgroup of the trajectory (first 64 threads; nthreads >= 64): publishes the keep list when
 // it is "drop the nd oldest", the window size after the next augment (ncam_upd), and compacts cam[] (keep[] ascending =>
@@ -520,17 +529,16 @@ template <class S> void launch_compress(const Dev<S>& d, int b0, int nb, hipStre
 // phase: 0 = both, 1 = Gram accumulation only, 2 = Cholesky only, 3 = SYRK only (the block-diagonal part came with launch_select_diag)
 template <class S> void launch_gram(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase);
 template <class S> void launch_kalman(const Dev<S>& d, int b0, int nb, hipStream_t st);
-// kernels_kalman.hip: Gram matrix, both factorizations, gain, state injection and covariance downdate of a SMALL window (n_max = 6 x cameras) in one
-// launch, one workgroup per trajectory; false when the window does not fit its LDS (the caller then takes the usual chain)
-template <class S> bool launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, int n_max);
-size_t update_small_lds_bytes(int n_max, int f_cap, size_t scalar);
-bool update_small_fits(int n_max, int f_cap, size_t scalar);
+// kernels_kalman.hip: Gram matrix, both factorizations, gain, state injection and covariance downdate of a SMALL window in one
+// launch, one workgroup per trajectory, sized as routes::small_route says (nsmall = 6 x cameras, segb)
+template <class S> void launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::SmallRoute& r);
+bool update_small_granted();   // the device granted k_update_small its dynamic LDS (kalman_device_setup)
 template <class S> void launch_literal(const Dev<S>& d, int b0, int nb, hipStream_t st, int part = 0);   // kernels_literal.hip: Lam^ of the literal anisotropic compression (part: 0 all, 1 k_lit_pre, 2 k_lit_gamma, 3 k_literal)
 // blocked matrix-core Cholesky (kernels_chol.hip): [T | r_n] = chol(Lam^) for the information form; S = L L^T with
-// [PHt ; r_n^T] appended (W, dx) for the float Kalman stage.  Return false when the window does not fit the kernel.
-template <class S> bool launch_chol_gram(const Dev<S>& d, int b0, int nb, hipStream_t st);
-bool launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st);
-template <class S> bool launch_chol_gain_large(const Dev<S>& d, int b0, int nb, hipStream_t st);
+// [PHt ; r_n^T] appended (W, dx) for the float Kalman stage.  Each carries out the route it is handed.
+template <class S> void launch_chol_gram(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::CompressRoute& r);
+void launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st, const routes::KalmanRoute& r);
+template <class S> void launch_chol_gain_large(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::KalmanRoute& r);
 // kernels_log.hip: record `rec` ([B][LOG_STRIDE], indexed by trajectory) of the frame log from the state after a frame -- P the
 // covariance buffer that is current, pending: the window size still waits in ncam_upd -- and the reduction of the records
 // [r0, r1) of a log against ground-truth positions gt[r1 - r0][B][3] into out[B][6] (both device pointers)
@@ -543,7 +551,6 @@ template <class S> void launch_map_metrics(const S* rec, const int* found, int c
 // records with prune ordinal in [q0, q1) against ground-truth poses gt[n_ord][B][7], matched through aug[B][cap], into out[B][10]
 template <class S> void launch_pruned_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop, int ordinal, int cap, S* rec, int* found);
 template <class S> void launch_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out, hipStream_t st);
-size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged = false);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();
 void qr_device_setup();

@@ -752,67 +752,38 @@ __global__ __launch_bounds__(256) void k_dx_wz(Dev<SO> d, int b0) {
 
 // S = L L^T in two levels, W = P T_H^T L^-T, z = L^-1 r_n, dx = W z for windows with n > 192 (6 n_cap in {256, 320, 384} padded)
 template <class S>
-bool launch_chol_gain_large(const Dev<S>& d, int b0, int nb, hipStream_t st) {
-  if (nb <= 0) return true;
-  const int nblk = (d.n6cap + 15) / 16;
-  if (!d.Mp2 || nblk <= 12 || nblk > 24) return false;
+void launch_chol_gain_large(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::KalmanRoute& r) {
+  if (nb <= 0) return;
   hipLaunchKernelGGL((k_chol_mfma<S, S, 12, 0, CH_S_A, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  hipLaunchKernelGGL((k_trsm_rows<S, S, 12, TR_S21>), dim3(xcd_grid(nb, (nblk - 12 + 3) / 4)), dim3(256), 0, st, d, b0, nb, (nblk - 12 + 3) / 4);
-  if (nblk <= 16) hipLaunchKernelGGL((k_chol_mfma<S, S, 4, 0, CH_S_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  else if (nblk <= 20) hipLaunchKernelGGL((k_chol_mfma<S, S, 8, 0, CH_S_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  else hipLaunchKernelGGL((k_chol_mfma<S, S, 12, 0, CH_S_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  const int rblk = (15 + d.n6cap + 1 + 15) / 16;          // 16-row blocks of [P T_H^T ; r_n^T]
-  if (nblk <= 16) hipLaunchKernelGGL((k_trsm_rows<S, S, 16, TR_W>), dim3(xcd_grid(nb, (rblk + 3) / 4)), dim3(256), 0, st, d, b0, nb, (rblk + 3) / 4);
-  else if (nblk <= 20) hipLaunchKernelGGL((k_trsm_rows<S, S, 20, TR_W>), dim3(xcd_grid(nb, (rblk + 3) / 4)), dim3(256), 0, st, d, b0, nb, (rblk + 3) / 4);
-  else hipLaunchKernelGGL((k_trsm_rows<S, S, 24, TR_W>), dim3(xcd_grid(nb, (rblk + 3) / 4)), dim3(256), 0, st, d, b0, nb, (rblk + 3) / 4);
+  hipLaunchKernelGGL((k_trsm_rows<S, S, 12, TR_S21>), dim3(xcd_grid(nb, r.items_s21)), dim3(256), 0, st, d, b0, nb, r.items_s21);
+  dispatch_int<4, 8, 12>(r.nb_b, [&](auto NB) { hipLaunchKernelGGL((k_chol_mfma<S, S, NB(), 0, CH_S_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); });
+  dispatch_int<16, 20, 24>(r.nb_w, [&](auto NB) { hipLaunchKernelGGL((k_trsm_rows<S, S, NB(), TR_W>), dim3(xcd_grid(nb, r.items_w)), dim3(256), 0, st, d, b0, nb, r.items_w); });
   hipLaunchKernelGGL((k_dx_wz<S>), dim3(nb), dim3(256), 0, st, d, b0);
-  return true;
 }
 
 // (Measured and rejected, round 4: the factorizations padded with unused dynamic LDS so that they have their compute unit to
 // themselves -- the gain factorization leaves 128 registers per SIMD free, room for one k_feature wavefront of another slice
 // each, sharing the LDS pipe its pivot chain runs on: 200.9 k / 199.4 k -> 202.3 k updates/s in four slices, inside the noise.)
 template <class S>
-bool launch_chol_gram(const Dev<S>& d, int b0, int nb, hipStream_t st) {
-  if (nb <= 0) return true;
-  const int nblk = d.ldR / 16;
-  switch (nblk) {
-    case 4: hipLaunchKernelGGL((k_chol_mfma<double, S, 4, 0, CH_GRAM, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); return true;
-    case 8: hipLaunchKernelGGL((k_chol_mfma<double, S, 8, 0, CH_GRAM, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); return true;
-    case 12: hipLaunchKernelGGL((k_chol_mfma<double, S, 12, 0, CH_GRAM, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); return true;
-    default: break;
+void launch_chol_gram(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::CompressRoute& r) {
+  if (nb <= 0) return;
+  if (r.chol_levels == 1) {
+    dispatch_int<4, 8, 12>(r.nb_a, [&](auto NB) { hipLaunchKernelGGL((k_chol_mfma<double, S, NB(), 0, CH_GRAM, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); });
+  } else if (r.chol_levels == 2) {
+    // two levels: columns [0, 192), L21, Schur complement
+    hipLaunchKernelGGL((k_chol_mfma<double, S, 12, 0, CH_GRAM_A, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
+    hipLaunchKernelGGL((k_trsm_rows<double, S, 12, TR_GRAM>), dim3(xcd_grid(nb, r.trsm_items)), dim3(256), 0, st, d, b0, nb, r.trsm_items);
+    dispatch_int<4, 8, 12>(r.nb_b, [&](auto NB) { hipLaunchKernelGGL((k_chol_mfma<double, S, NB(), 0, CH_GRAM_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb); });
   }
-  if (!d.Mp || (nblk != 16 && nblk != 20 && nblk != 24)) return false;
-  // two levels: columns [0, 192), L21, Schur complement
-  hipLaunchKernelGGL((k_chol_mfma<double, S, 12, 0, CH_GRAM_A, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  hipLaunchKernelGGL((k_trsm_rows<double, S, 12, TR_GRAM>), dim3(xcd_grid(nb, (nblk - 12 + 3) / 4)), dim3(256), 0, st, d, b0, nb, (nblk - 12 + 3) / 4);
-  if (nblk == 16) hipLaunchKernelGGL((k_chol_mfma<double, S, 4, 0, CH_GRAM_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  else if (nblk == 20) hipLaunchKernelGGL((k_chol_mfma<double, S, 8, 0, CH_GRAM_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  else hipLaunchKernelGGL((k_chol_mfma<double, S, 12, 0, CH_GRAM_B, 1>), dim3(nb), dim3(1024), 0, st, d, b0, nb);
-  return true;
 }
 
-// GAIN: parts x NA blocks of 16 rows must cover the D + 1 appended rows (each part also carries r_n^T)
-template <int NB, int NA, int NPART>
-static void gain_launch(const Dev<float>& d, int b0, int nb, hipStream_t st) {
-  hipLaunchKernelGGL((k_chol_mfma<float, float, NB, NA, CH_GAIN, NPART>), dim3(xcd_grid(nb, NPART)), dim3(1024), 0, st, d, b0, nb);
-}
-bool launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st) {
-  if (nb <= 0) return true;
-  const int nbn = (d.n6cap + 15) / 16;
-  // rows per part = 16 NA - 1; D = 15 + 6 n_cap <= NPART (16 NA - 1)
-  if (nbn <= 4) { gain_launch<4, 2, 3>(d, b0, nb, st); return true; }          // D <= 79 <= 3 * 31
-  if (nbn <= 8) { gain_launch<8, 3, 3>(d, b0, nb, st); return true; }          // D <= 143 <= 3 * 47
-  if (nbn <= 12) {                                                             // D <= 207 <= 4 * 63 = 2 * 111 - ...
-    // four parts per trajectory fill the chip at 64 trajectories; from a batch of 96 on, two parts (each redoes the factorization: half the
-    // workgroups, one round of them instead of two).  Rows are independent and S's blocks are formed by the same instruction
-    // sequence whichever part owns them: same bits either way.  MSCKF_HIP_GAIN_PARTS=2|4 at handle creation forces one
-    // (Dev::gain_parts; A/B runs and tests).
-    const bool two = d.gain_parts ? d.gain_parts == 2 : d.B >= 96;   // (the whole batch: its slices run these launches side by side)
-    if (two && 15 + 6 * d.n_cap <= 2 * 111) gain_launch<12, 7, 2>(d, b0, nb, st); else gain_launch<12, 4, 4>(d, b0, nb, st);
-    return true;
-  }
-  return false;
+// GAIN: routes::BLOCKED_GAIN states the four forms <NB, NA, NPART> and which window takes which
+void launch_chol_gain(const Dev<float>& d, int b0, int nb, hipStream_t st, const routes::KalmanRoute& r) {
+  if (nb <= 0) return;
+  dispatch_int<0, 1, 2, 3>(r.blocked, [&](auto I) {
+    constexpr routes::BlockedGain g = routes::BLOCKED_GAIN[I()];
+    hipLaunchKernelGGL((k_chol_mfma<float, float, g.nb, g.na, CH_GAIN, g.npart>), dim3(xcd_grid(nb, g.npart)), dim3(1024), 0, st, d, b0, nb);
+  });
 }
 
 #ifdef MSCKF_ABLATE
@@ -827,9 +798,9 @@ void chol_cycles_read(unsigned long long* out16, int reset) {
 }
 #endif
 
-template bool launch_chol_gram<float>(const Dev<float>&, int, int, hipStream_t);
-template bool launch_chol_gain_large<float>(const Dev<float>&, int, int, hipStream_t);
-template bool launch_chol_gain_large<double>(const Dev<double>&, int, int, hipStream_t);
-template bool launch_chol_gram<double>(const Dev<double>&, int, int, hipStream_t);
+template void launch_chol_gram<float>(const Dev<float>&, int, int, hipStream_t, const routes::CompressRoute&);
+template void launch_chol_gain_large<float>(const Dev<float>&, int, int, hipStream_t, const routes::KalmanRoute&);
+template void launch_chol_gain_large<double>(const Dev<double>&, int, int, hipStream_t, const routes::KalmanRoute&);
+template void launch_chol_gram<double>(const Dev<double>&, int, int, hipStream_t, const routes::CompressRoute&);
 
 }  // namespace msckf

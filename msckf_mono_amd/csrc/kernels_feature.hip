@@ -1541,13 +1541,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
 #endif
 }
 
-size_t feature_pair_lds_bytes(int lm, int& s_cap) {
-  const int r2 = 2 * lm + 4;
-  s_cap = r2 * (r2 + 1) / 2 + 12 * 13 / 2;            // the longest track + a 4-observation partner
-  if (s_cap < 64) s_cap = 64;                          // the prologue's histogram lives there
-  return ((size_t)s_cap + 16) * sizeof(float) + 2 * (size_t)lm * sizeof(int) + 16;
-}
-
 // One wavefront per trajectory: resolves the order-dependent part of marginalize (:352-399) -- checkMotion is
 // skipped while fewer than 4 tracks have ever been residualized (Q4, msckf.h:354) -- and lays the gated-in
 // tracks' rows out for the compression stage: tracks are counting-sorted by their first camera slot (stable,
@@ -1813,12 +1806,6 @@ __global__ __launch_bounds__(256) void k_select_diag(Dev<S> d, int b0, int nb, i
   }
 }
 
-size_t feature_lds_bytes(int m_cap, size_t scalar, bool staged) {
-  const size_t r2 = 2 * (size_t)m_cap + 4;
-  const size_t x = std::max<size_t>((size_t)m_cap * 12, 16);
-  return ((staged ? r2 * 17 : r2 * (r2 + 1) / 2) + x) * scalar + (size_t)m_cap * sizeof(int) + 16;
-}
-
 // one-time, per-device setup (called from msckf_hip_create after hipSetDevice): chi-square table, LDS limits
 void feature_device_setup() {
   (void)hipMemcpyToSymbol(HIP_SYMBOL(c_chi2), kChi2Q05, sizeof(double) * 99);
@@ -1829,51 +1816,42 @@ void feature_device_setup() {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_feature_pair), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
+// routes::feature_route (update_routes.h) says which launches.  What was measured on the way to it:
+// * float filters on the information-form route take tracks of up to 30 observations two per wavefront (k_feature_pair).  A small
+//   launch (a filter or a few: at most 1 024 tracks) takes ONE track per wavefront -- the kernel's latency is then its slowest
+//   wavefront's, and a wavefront with a single track has half the gate work.  A slice of run_frames (16 trajectories, 3 200
+//   tracks) keeps the pairs: alone the single form is 1.5 us faster (40 -> 38.5 us), but with the other slices' kernels beside it
+//   twice the wavefronts cost more than that -- 191-194 k -> 201-202 k updates/s (medians 193-195 k -> 203-205 k), three
+//   alternating runs on one lease.
+// * (measured and rejected, round 4: the tracks of at most 12 / 16 / 20 observations in a launch of their own with the LDS sized
+//   for them -- five wavefronts per SIMD instead of four for those: 183 k -> 172 k updates/s on one stream, 201 k -> 199 k in four
+//   slices; the second launch's tail costs more than the occupancy gives.  cfg5's windows are another matter:)
+// * long windows: tracks binned by length, one launch per bin over the same grid (a workgroup whose track belongs to another
+//   bin returns at once).  Occupancy is set by the LDS of the bin's longest track, not of the window's.
+// * float filters, tracks of 31 .. 62 observations: the gate matrix goes through LDS sixteen columns at a time (gate_chol_staged) -- the
+//   launch's LDS no longer depends on the square of the longest track, and ONE launch takes every long track (the two bins by length
+//   existed for the LDS of the packed triangle: 31 KB at 60 observations)
+// * (measured and rejected: the tracks of 31 .. 46 observations in a launch of their own whose instance holds 12 x 12 blocks at most --
+//   168 registers, three wavefronts per SIMD instead of two: 4.70 -> 4.67 ms at cfg5, the second launch's tail takes what the occupancy gives)
 template <class S>
 void launch_feature(const Dev<S>& d, int b0, int nb, hipStream_t st) {
   if (nb <= 0) return;
   const dim3 grid(xcd_grid(nb, d.f_cap));
-  constexpr int ALL_LO = -0x7fffffff, ALL_HI = 0x7fffffff, M_REG = 30;   // 2 * 30 + 4 = 64: the register-resident gate factorization
-  // float filters on the information-form route: tracks of up to 30 observations two per wavefront (k_feature_pair)
-  bool pair = false;
-  if constexpr (sizeof(S) == 4) {
-    if (d.feat_pair && d.compress && d.f_cap <= 512) {
-      pair = true;
-      // a small launch (a filter or a few: at most 1 024 tracks) takes ONE track per wavefront -- the kernel's latency is then its
-      // slowest wavefront's, and a wavefront with a single track has half the gate work.  A slice of run_frames (16 trajectories, 3 200
-      // tracks) keeps the pairs: alone the single form is 1.5 us faster (40 -> 38.5 us), but with the other slices' kernels beside it
-      // twice the wavefronts cost more than that -- 191-194 k -> 201-202 k updates/s (medians 193-195 k -> 203-205 k), three
-      // alternating runs on one lease.  feat_pair 2 forces pairs, 3 forces the single form.
-      const int single = (d.feat_pair == 3 || (d.feat_pair == 1 && (long)nb * d.f_cap <= 1024)) ? 1 : 0;
-      const int lm = d.m_cap < M_REG ? d.m_cap : M_REG, items = single ? d.f_cap : (d.f_cap + 1) / 2;
-      int s_cap = 0;
-      const size_t lds = feature_pair_lds_bytes(lm, s_cap);
-      hipLaunchKernelGGL(k_feature_pair, dim3(xcd_grid(nb, items)), dim3(64), lds, st, d, b0, nb, lm, ALL_LO, d.m_cap <= M_REG ? ALL_HI : M_REG, s_cap, items, single);
-      if (d.m_cap <= M_REG) return;
+  const routes::FeatureRoute r = routes::feature_route(sizeof(S), d.f_cap, d.m_cap, nb, d.feat_pair, d.compress);
+  for (int i = 0; i < r.n; ++i) {
+    const routes::FeatureLaunch& l = r.l[i];
+    if (l.pair) {
+      if constexpr (sizeof(S) == 4) {
+        int s_cap = 0;
+        const size_t lds = routes::feature_pair_lds_bytes(l.lm, s_cap);
+        hipLaunchKernelGGL(k_feature_pair, dim3(xcd_grid(nb, l.items)), dim3(64), lds, st, d, b0, nb, l.lm, l.m_lo, l.m_hi, s_cap, l.items, l.single);
+      }
+      continue;
     }
+    const size_t lds = routes::feature_lds_bytes(l.lm, sizeof(S), l.staged != 0);
+    if (l.long_form) hipLaunchKernelGGL((k_feature<S, true>), grid, dim3(64), lds, st, d, b0, nb, l.lm, l.m_lo, l.m_hi, l.staged);
+    else hipLaunchKernelGGL((k_feature<S, false>), grid, dim3(64), lds, st, d, b0, nb, l.lm, l.m_lo, l.m_hi, l.staged);
   }
-  if (d.m_cap <= M_REG) {
-    // (measured and rejected, round 4: the tracks of at most 12 / 16 / 20 observations in a launch of their own with the LDS sized
-    // for them -- five wavefronts per SIMD instead of four for those: 183 k -> 172 k updates/s on one stream, 201 k -> 199 k in four
-    // slices; the second launch's tail costs more than the occupancy gives.  cfg5's windows are another matter, below)
-    hipLaunchKernelGGL((k_feature<S, false>), grid, dim3(64), feature_lds_bytes(d.m_cap, sizeof(S)), st, d, b0, nb, d.m_cap, ALL_LO, ALL_HI, 0);
-    return;
-  }
-  // long windows: tracks binned by length, one launch per bin over the same grid (a workgroup whose track belongs to another
-  // bin returns at once).  Occupancy is set by the LDS of the bin's longest track, not of the window's
-  if (!pair) hipLaunchKernelGGL((k_feature<S, false>), grid, dim3(64), feature_lds_bytes(M_REG, sizeof(S)), st, d, b0, nb, M_REG, ALL_LO, M_REG, 0);
-  // float filters, tracks of 31 .. 62 observations: the gate matrix goes through LDS sixteen columns at a time (gate_chol_staged) -- the
-  // launch's LDS no longer depends on the square of the longest track, and ONE launch takes every long track (the two bins by length
-  // existed for the LDS of the packed triangle: 31 KB at 60 observations)
-  const bool staged = sizeof(S) == 4 && d.m_cap <= 62 && d.feat_pair;
-  // (measured and rejected: the tracks of 31 .. 46 observations in a launch of their own whose instance holds 12 x 12 blocks at most --
-  // 168 registers, three wavefronts per SIMD instead of two: 4.70 -> 4.67 ms at cfg5, the second launch's tail takes what the occupancy gives)
-  if (staged) { hipLaunchKernelGGL((k_feature<S, true>), grid, dim3(64), feature_lds_bytes(d.m_cap, sizeof(S), true), st, d, b0, nb, d.m_cap, M_REG, ALL_HI, 1); return; }
-  const int mid = (M_REG + d.m_cap + 1) / 2;
-  if (d.m_cap - M_REG >= 16) {
-    hipLaunchKernelGGL((k_feature<S, true>), grid, dim3(64), feature_lds_bytes(mid, sizeof(S)), st, d, b0, nb, mid, M_REG, mid, 0);
-    hipLaunchKernelGGL((k_feature<S, true>), grid, dim3(64), feature_lds_bytes(d.m_cap, sizeof(S)), st, d, b0, nb, d.m_cap, mid, ALL_HI, 0);
-  } else hipLaunchKernelGGL((k_feature<S, true>), grid, dim3(64), feature_lds_bytes(d.m_cap, sizeof(S)), st, d, b0, nb, d.m_cap, M_REG, ALL_HI, 0);
 }
 #ifdef MSCKF_ABLATE
 void feat_debug_set(int val) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_feat_dbg), &val, sizeof(int)); }

@@ -304,8 +304,8 @@ template <class S>
 void launch_gram(const Dev<S>& din, int b0, int nb, hipStream_t st, int phase) {
   if (nb <= 0) return;
   Dev<S> d = din;
-  // split-K partial sums only where the consumer adds them up: the single-level blocked Cholesky (k_chol_mfma, CH_GRAM)
-  d.gram_parts = (d.compress && d.ldR <= 192 && d.lam_part > 0) ? (din.gram_parts >= 3 ? din.gram_parts : 3) : 1;
+  const routes::CompressRoute r = routes::compress_route(d.compress, d.ldR, d.Mp != nullptr, d.lam_part > 0, din.gram_parts);
+  d.gram_parts = r.gram_parts;
 #ifdef MSCKF_ABLATE
   const int g_dbg = g_gram_dbg;
 #else
@@ -316,7 +316,7 @@ void launch_gram(const Dev<S>& din, int b0, int nb, hipStream_t st, int phase) {
   if (phase != 2)   // the block-diagonal reduction already ran in k_select's launch (launch_select_diag)
     hipLaunchKernelGGL(k_gram<S>, dim3(xcd_grid(nb, npairs)), dim3(512), gram_lds_bytes(), st, d, b0, nb, npairs, g_dbg, 0);
   if (phase == 3) return;
-  (void)launch_chol_gram<S>(d, b0, nb, st);   // blocked matrix-core Cholesky, kernels_chol.hip (two levels beyond 192 columns)
+  launch_chol_gram<S>(d, b0, nb, st, r);   // blocked matrix-core Cholesky, kernels_chol.hip (two levels beyond 192 columns)
 }
 
 template void launch_gram<float>(const Dev<float>&, int, int, hipStream_t, int);

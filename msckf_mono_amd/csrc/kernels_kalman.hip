@@ -932,19 +932,12 @@ static void gemm(const Dev<S>& d, int b0, int nb, int Mmax, int Nmax, hipStream_
   gemm_launch<OP>(d, b0, nb, Mmax, Nmax, st);
 }
 
-static void gemm_pht_rowmajor(const Dev<float>& d, int b0, int nb, int Mmax, int Nmax, hipStream_t st) { gemm_launch<OP_PHTT>(d, b0, nb, Mmax, Nmax, st); }
-static void gemm_pht_rowmajor(const Dev<double>& d, int b0, int nb, int Mmax, int Nmax, hipStream_t st) { gemm_launch<OP_PHT>(d, b0, nb, Mmax, Nmax, st); }   // (never taken: s_fused is float only)
-
-template <class S, int NBN>
-static void launch_gain_w(const Dev<S>& d, int b0, int nb, hipStream_t st) {
-  // more workgroups per trajectory while the batch leaves CUs idle (the Cholesky of S is redone by each of them)
-  if (nb <= 64) hipLaunchKernelGGL((k_gain_w<S, NBN, 8>), dim3(8, nb), dim3(256), 0, st, d, b0);
-  else if (nb <= 128) hipLaunchKernelGGL((k_gain_w<S, NBN, 4>), dim3(4, nb), dim3(256), 0, st, d, b0);
-  else hipLaunchKernelGGL((k_gain_w<S, NBN, 2>), dim3(2, nb), dim3(256), 0, st, d, b0);
+template <class S>
+static void launch_gain_w(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::KalmanRoute& r) {
+  dispatch_int<4, 8, routes::reg_blocks_max(sizeof(S))>(r.nbn, [&](auto NBN) {
+    dispatch_int<8, 4, 2>(r.npart, [&](auto NPART) { hipLaunchKernelGGL((k_gain_w<S, NBN(), NPART()>), dim3(NPART(), nb), dim3(256), 0, st, d, b0); });
+  });
 }
-
-static bool gain_blocked(const Dev<float>& d, int b0, int nb, hipStream_t st) { return launch_chol_gain(d, b0, nb, st); }
-static bool gain_blocked(const Dev<double>&, int, int, hipStream_t) { return false; }
 
 // ---------------------------------------------------------------- k_update_small: the whole update of a SMALL window in one launch
 // Single filters with short windows (BASELINE.json configs[1]: 10 cameras, D = 75 .. 81) ran their update as a chain of six
@@ -976,20 +969,7 @@ void us_cycles_read(unsigned long long* out16, int reset) {
 template <class T> __device__ __forceinline__ T us_clamp();
 template <> __device__ __forceinline__ double us_clamp<double>() { return 1e-300; }
 template <> __device__ __forceinline__ float us_clamp<float>() { return 1e-30f; }
-constexpr int US_UMAX = 2;     // tasks per wavefront of the factorizations
-constexpr int US_SEG_E = 12;   // columns per task of chol(S) with its D + 1 riding rows (10 cameras: 3 row chunks x 5 segments = 15 tasks); chol(Lam^): SEGB = 4 (61 rows: one chunk, 15 tasks) or 8
-// scalars of the PHt / W block [15 + n_max][n_max | 1]: it also stages 24 rows of B^ (doubles, 16 ceil((n_max + 1) / 16) + 1 columns) in
-// phase A, the larger need for the first few frames of a window; and of the P staging block [n_max][(15 + n_max) | 1], later S [n_max][n_max | 1]
-__host__ __device__ inline size_t update_small_ph_elems(int n_max, size_t scalar) {
-  const size_t w = (size_t)(15 + n_max) * (n_max | 1), nb1 = 16 * (((size_t)n_max + 1 + 15) / 16) + 1, stg = (24 * nb1 * sizeof(double) + scalar - 1) / scalar;
-  return ((w > stg ? w : stg) + 3) & ~(size_t)3;
-}
-// (phase A keeps two ints per included track there: f_cap of them at most)
-__host__ __device__ inline size_t update_small_pt_elems(int n_max, int f_cap, size_t scalar) {
-  const size_t a = (size_t)n_max * ((15 + n_max) | 1), b = (size_t)n_max * (n_max | 1), c = ((size_t)f_cap * 2 * sizeof(int) + scalar - 1) / scalar;
-  const size_t m = a > b ? (a > c ? a : c) : (b > c ? b : c);
-  return (m + 3) & ~(size_t)3;
-}
+using routes::US_UMAX; using routes::US_SEG_E; using routes::update_small_ph_elems; using routes::update_small_pt_elems;   // update_routes.h: the host sizes the launch by them
 // one 16 x 16 tile of sum_k a(16 ti + m, k) b(k, 16 tj + c), k in [k0, k1) in steps of 4 (the functors return zero out of range)
 template <class T, class FA, class FB>
 __device__ __forceinline__ typename Mfma16<T>::V us_tile(int ti, int tj, int k0, int k1, int lane, FA&& fa, FB&& fb) {
@@ -1292,77 +1272,59 @@ __global__ __launch_bounds__(1024) void k_update_small(Dev<S> d, int b0, int n_m
 }
 
 static bool update_small_ok = false;   // the 160 KB attribute was granted (kalman_device_setup)
-size_t update_small_lds_bytes(int n_max, int f_cap, size_t scalar) {
-  const size_t n1 = (size_t)n_max + 1, LL = n1 | 1, Dm = 15 + (size_t)n_max, cstride = 2 * (size_t)n_max + 20;
-  return (n1 * LL + n1 + 1 + 2 * cstride) * sizeof(double) + (update_small_pt_elems(n_max, f_cap, scalar) + update_small_ph_elems(n_max, scalar) + n_max + 2 + Dm + 1) * scalar + 64;
-}
-// does a window of n_max camera columns fit k_update_small (its LDS, the tasks of its factorizations)?  Monotone in n_max.
-bool update_small_fits(int n_max, int f_cap, size_t scalar) {
-  const size_t lds = update_small_lds_bytes(n_max, f_cap, scalar);
-  // tasks of the factorizations: ceil(n / 12) x ceil((2 n + 16) / 64) and ceil(n / 4) x ceil((n + 1) / 64) <= 32; tiles of Lam^: <= 15 of the 16 wavefronts
-  const int ncs = (n_max + US_SEG_E - 1) / US_SEG_E, nrc = (2 * n_max + 16 + 63) / 64, nt1 = (n_max + 1 + 15) / 16;
-  const int nrcb = (n_max + 1 + 63) / 64;
-  const bool b4 = ((n_max + 3) / 4) * nrcb <= 16 * US_UMAX, b8 = ((n_max + 7) / 8) * nrcb <= 16 * US_UMAX;
-  return update_small_ok && lds <= 156 * 1024 && ncs * nrc <= 16 * US_UMAX && (b4 || b8) && nt1 * (nt1 + 1) / 2 <= 16 && (15 + n_max) * n_max <= 1024 * 7;
-}
+bool update_small_granted() { return update_small_ok; }
 template <class S>
-bool launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, int n_max) {
-  if (nb <= 0) return true;
-  if (!update_small_fits(n_max, d.f_cap, sizeof(S))) return false;
-  const size_t lds = update_small_lds_bytes(n_max, d.f_cap, sizeof(S));
-  const bool b4 = ((n_max + 3) / 4) * ((n_max + 1 + 63) / 64) <= 16 * US_UMAX;
-  if (b4) hipLaunchKernelGGL((k_update_small<S, 4>), dim3(nb), dim3(1024), lds, st, d, b0, n_max);
-  else hipLaunchKernelGGL((k_update_small<S, 8>), dim3(nb), dim3(1024), lds, st, d, b0, n_max);
-  return true;
+void launch_update_small(const Dev<S>& d, int b0, int nb, hipStream_t st, const routes::SmallRoute& r) {
+  if (nb <= 0) return;
+  const size_t lds = routes::update_small_lds_bytes(r.nsmall, d.f_cap, sizeof(S));
+  dispatch_int<4, 8>(r.segb, [&](auto SEGB) { hipLaunchKernelGGL((k_update_small<S, SEGB()>), dim3(nb), dim3(1024), lds, st, d, b0, r.nsmall); });
 }
-template bool launch_update_small<float>(const Dev<float>&, int, int, hipStream_t, int);
-template bool launch_update_small<double>(const Dev<double>&, int, int, hipStream_t, int);
+template void launch_update_small<float>(const Dev<float>&, int, int, hipStream_t, const routes::SmallRoute&);
+template void launch_update_small<double>(const Dev<double>&, int, int, hipStream_t, const routes::SmallRoute&);
 
 template <class S>
 void launch_kalman(const Dev<S>& d, int b0, int nb, hipStream_t st) {
   if (nb <= 0) return;
+  using namespace routes;
   const int n = d.n6cap, D = 15 + n;
+  const KalmanRoute r = kalman_route(sizeof(S), d.n_cap, d.B, nb, d.joseph, d.gain_fused_s, d.gain_parts, d.Mp2 != nullptr);
   // S: formed inside the blocked gain solve where that runs (float, square-root gain form, windows up to 32 cameras); nothing
   // then reads the column-major PHt, so only its row-major copy is written
-  const bool s_fused = sizeof(S) == 4 && d.joseph == 0 && d.gain_fused_s && (n + 15) / 16 <= 12;
-  if (s_fused) gemm_pht_rowmajor(d, b0, nb, D, n, st); else gemm<S, OP_PHT>(d, b0, nb, D, n, st);
-  if (!s_fused) gemm<S, OP_S>(d, b0, nb, n, n, st);
-  const int nbn = (n + 15) / 16;
-  const int nbn_max = sizeof(S) == 4 ? 12 : 8;
-  const size_t lds_chol = (size_t)n * (n + 1) * sizeof(S);
+  if constexpr (has_blocked_gain(sizeof(S))) { if (r.s_fused) gemm<S, OP_PHTT>(d, b0, nb, D, n, st); }
+  if (!r.s_fused) { gemm<S, OP_PHT>(d, b0, nb, D, n, st); gemm<S, OP_S>(d, b0, nb, n, n, st); }
   auto chol_inv = [&]() {
-    if (lds_chol <= 150 * 1024) hipLaunchKernelGGL((k_chol_inv<S, true>), dim3(nb), dim3(256), lds_chol, st, d, b0);
+    if (r.chol_inv_lds) hipLaunchKernelGGL((k_chol_inv<S, true>), dim3(nb), dim3(256), r.chol_inv_bytes, st, d, b0);
     else hipLaunchKernelGGL((k_chol_inv<S, false>), dim3(nb), dim3(256), 0, st, d, b0);
   };
-  if (d.joseph != 1) {
+  switch (r.solve) {
     // ---- square-root gain form: W = PHt L^-T, dx = W L^-1 r_n, P <- P - W W^T
-    if (d.joseph == 0 && gain_blocked(d, b0, nb, st)) {}   // float: blocked matrix-core Cholesky with appended rows
-    else if (nbn <= 4) launch_gain_w<S, 4>(d, b0, nb, st);
-    else if (nbn <= 8) launch_gain_w<S, 8>(d, b0, nb, st);
-    else if (nbn <= nbn_max) launch_gain_w<S, (sizeof(S) == 4 ? 12 : 8)>(d, b0, nb, st);
-    else if (d.joseph == 0 && nbn > 12 && launch_chol_gain_large<S>(d, b0, nb, st)) {}   // two-level blocked factorization + row solves
-    else {
+    case GAIN_BLOCKED: if constexpr (has_blocked_gain(sizeof(S))) launch_chol_gain(d, b0, nb, st, r); break;   // blocked matrix-core Cholesky with appended rows
+    case GAIN_W: launch_gain_w<S>(d, b0, nb, st, r); break;
+    case GAIN_LARGE: launch_chol_gain_large<S>(d, b0, nb, st, r); break;   // two-level blocked factorization + row solves
+    case GAIN_CHOL_INV:
       chol_inv();
       gemm<S, OP_W>(d, b0, nb, D, n, st);
       hipLaunchKernelGGL((k_dx_w<S>), dim3(nb), dim3(256), (size_t)2 * d.n6cap * sizeof(S), st, d, b0);
-    }
+      break;
+    // ---- Joseph form (the reference's literal sequence)
+    // K = PHt S^-1: register-resident factor/solve when the window fits the 16x16 thread grid, otherwise
+    // Cholesky + triangular inverse (LDS or global) followed by two GEMMs.
+    case GAIN_K:
+      dispatch_int<4, 8, 12>(r.nbn, [&](auto NBN) { hipLaunchKernelGGL((k_gain<S, NBN()>), dim3(nb), dim3(256), 0, st, d, b0); });
+      hipLaunchKernelGGL((k_inject<S, true>), dim3(nb), dim3(256), (size_t)d.ld * sizeof(S), st, d, b0);
+      break;
+    case GAIN_K_CHOL_INV:
+      chol_inv();
+      gemm<S, OP_W>(d, b0, nb, D, n, st);
+      gemm<S, OP_K>(d, b0, nb, D, n, st);
+      hipLaunchKernelGGL((k_inject<S, false>), dim3(nb), dim3(256), (size_t)(d.ld + d.n6cap) * sizeof(S), st, d, b0);
+      break;
+    case GAIN_NONE: break;
+  }
+  if (d.joseph != 1) {
     gemm<S, OP_DOWN>(d, b0, nb, D, D, st);   // its first tile's workgroup also applies dx to the state (inject_from_dx)
     return;
   }
-  // ---- Joseph form (the reference's literal sequence)
-  // K = PHt S^-1: register-resident factor/solve when the window fits the 16x16 thread grid, otherwise
-  // Cholesky + triangular inverse (LDS or global) followed by two GEMMs.
-  if (nbn <= nbn_max) {
-    if (nbn <= 4) hipLaunchKernelGGL((k_gain<S, 4>), dim3(nb), dim3(256), 0, st, d, b0);
-    else if (nbn <= 8) hipLaunchKernelGGL((k_gain<S, 8>), dim3(nb), dim3(256), 0, st, d, b0);
-    else hipLaunchKernelGGL((k_gain<S, 12>), dim3(nb), dim3(256), 0, st, d, b0);
-  } else {
-    chol_inv();
-    gemm<S, OP_W>(d, b0, nb, D, n, st);
-    gemm<S, OP_K>(d, b0, nb, D, n, st);
-  }
-  if (nbn <= nbn_max) hipLaunchKernelGGL((k_inject<S, true>), dim3(nb), dim3(256), (size_t)d.ld * sizeof(S), st, d, b0);
-  else hipLaunchKernelGGL((k_inject<S, false>), dim3(nb), dim3(256), (size_t)(d.ld + d.n6cap) * sizeof(S), st, d, b0);
   gemm<S, OP_A>(d, b0, nb, D, D, st);
   gemm<S, OP_AP>(d, b0, nb, D, D, st);
   gemm<S, OP_X>(d, b0, nb, D, D, st);

@@ -1083,15 +1083,11 @@ struct Batch : BatchCore {
   int alloc() override {
     h_imu.assign((size_t)B * IMU_STRIDE, S(0));
     d.B = B; d.n_cap = n_cap; d.f_cap = f_cap; d.m_cap = m_cap;
-    d.n6cap = 6 * n_cap;
-    d.ld = ((15 + 6 * n_cap + 15) / 16) * 16;
-    d.ldR = ((6 * n_cap + 1 + 63) / 64) * 64;
+    const routes::Geometry g = routes::geometry(B, n_cap, f_cap, m_cap, sizeof(S));   // update_routes.h: the routes read the same record
+    d.n6cap = g.n6cap; d.ld = g.ld; d.ldR = g.ldR; d.nchunk = g.nchunk;
     // 6 n_cap + 1 <= 384 (n_cap <= 63): the compression kernels' column capacity; it also bounds everything indexed by a state
     // column or a camera slot further down (k_prune_inplace keeps ceil(ld / 16) x ceil(ld / 256) <= 25 x 2 elements per thread: ld <= 400; 6-bit slot fields of trk_first)
-    if (d.ldR / 64 > 6) return fail(-ENOTSUP, "n_cap too large: 6*n_cap+1 must be <= 384 (at most 63 camera states)");
-    int nch = 1;
-    while (nch < 8 && (long)B * nch * 2 <= 256) nch *= 2;    // TSQR route: chunks x trajectories ~ one workgroup per CU
-    d.nchunk = nch;
+    if (g.refusal == routes::GEO_N_CAP) return fail(-ENOTSUP, "n_cap too large: 6*n_cap+1 must be <= 384 (at most 63 camera states)");
     const size_t Bz = B, pl = (size_t)d.ld * d.ld, nl = (size_t)d.n6cap * d.n6cap, dn = (size_t)d.ld * d.n6cap;
     const size_t TF = Bz * f_cap;
     int rc = 0;
@@ -1107,15 +1103,15 @@ struct Batch : BatchCore {
     rc |= dalloc(&d.row_start, Bz * (f_cap + 1)); rc |= dalloc(&d.trk_order, TF); rc |= dalloc(&d.stats, Bz * STAT_STRIDE);
     rc |= dalloc(&d.Rbuf, Bz * d.nchunk * (size_t)d.n6cap * d.ldR);
     // information-form compression (kernels_gram.hip + kernels_chol.hip)
-    d.compress = (d.ldR <= 384 && f_cap <= 1024) ? 3 : 0;   // blocked matrix-core Cholesky (kernels_chol.hip), two levels beyond 192 columns
+    d.compress = g.compress;   // blocked matrix-core Cholesky (kernels_chol.hip), two levels beyond 192 columns
     d.Mp = nullptr; d.Mp2 = nullptr;
-    if (d.n6cap > 192) rc |= dalloc(&d.Mp2, Bz * 24 * 256);
+    if (g.has_Mp2) rc |= dalloc(&d.Mp2, Bz * 24 * 256);
     if (d.compress) {
-      if (d.ldR > 192) rc |= dalloc(&d.Mp, Bz * 12 * 256);
+      if (g.has_Mp) rc |= dalloc(&d.Mp, Bz * 12 * 256);
       rc |= dalloc(&d.trk_B, TF * 3 * (size_t)d.ldR); rc |= dalloc(&d.trk_rw, TF * 2 * m_cap); rc |= dalloc(&d.trk_inv, TF * n_cap);
       rc |= dalloc(&d.Dg, Bz * n_cap * DG_STRIDE);
-      d.lam_part = d.ldR <= 192 ? (long)(Bz * (size_t)d.ldR * d.ldR) : 0;     // up to four copies of Lam^ for the split-K SYRK (windows up to 31 cameras)
-      d.gram_parts = 3;   // P = 4 (sixteen workgroups per trajectory) measured: k_gram 56 -> 54 us, the Cholesky's extra load round 64 -> 66 us
+      d.lam_part = g.lam_parts ? (long)(Bz * (size_t)d.ldR * d.ldR) : 0;     // up to four copies of Lam^ for the split-K SYRK (windows up to 31 cameras)
+      d.gram_parts = routes::GRAM_PARTS;   // P = 4 (sixteen workgroups per trajectory) measured: k_gram 56 -> 54 us, the Cholesky's extra load round 64 -> 66 us
       rc |= dalloc(&d.Lam, Bz * (size_t)d.ldR * d.ldR * (d.lam_part ? 4 : 1));
     }
     rc |= dalloc(&d.PHt, Bz * dn); rc |= dalloc(&d.Smat, Bz * nl); rc |= dalloc(&d.Linv, Bz * nl); rc |= dalloc(&d.W, Bz * dn);
@@ -1133,7 +1129,7 @@ struct Batch : BatchCore {
     dv_ncam = d.ncam; dv_nres = d.n_resid; dv_stats = d.stats; info_form = d.trk_B != nullptr;
     if (rc) return rc;
     use_single_worklists();
-    if (feature_lds_bytes(m_cap, sizeof(S)) > 160 * 1024) return fail(-EINVAL, "m_cap too large for the feature kernel's LDS budget");
+    if (g.refusal == routes::GEO_M_CAP) return fail(-EINVAL, "m_cap too large for the feature kernel's LDS budget");
     HIPCHK(hipStreamSynchronize(st));
     return 0;
   }
@@ -1142,8 +1138,7 @@ struct Batch : BatchCore {
     d.joseph = s.cov_update; d.gate_early = s.gate_early; d.gain_fused_s = s.fused_s; d.feat_pair = s.feat_pair; d.gain_parts = s.gain_parts;
     d.lit.serial = s.lit_serial; d.lit.route = s.lit_route;
     d.lit.tol = s.lit_tol >= 0 ? s.lit_tol : (sizeof(S) == 4 ? 8e-4 : 1e-10);
-    small_limit = 0;
-    for (int n = s.small_update / 6 * 6; n >= 6 && !small_limit; n -= 6) if (update_small_fits(n, f_cap, sizeof(S))) small_limit = n;
+    small_limit = routes::small_limit(s.small_update, f_cap, sizeof(S), update_small_granted());
   }
   void use_single_worklists() {
     d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
@@ -1470,16 +1465,9 @@ struct Batch : BatchCore {
     for (int f = f0; f < f1; ++f) flips += fuse_frame(f, f1) ? 1 : 0;
     if (flips & 1) std::swap(d.P, P_spare);
   }
-  // compression route of an update's launches (k_feature publishes B^ only for the information form): the handle's choice,
-  // except that a batch with a trajectory on the literal anisotropic route always takes the information form (that route hands
-  // over an information matrix: Cholesky tail).  Every launch of an update -- the early k_feature of the overlap path too --
-  // asks here.
-  int update_compress(int base) const {
-    int cmp = base;
-    if (settings.compress_route >= 0) cmp = (settings.compress_route && d.trk_B) ? 3 : 0;
-    if (n_lit > 0 && !cmp) cmp = d.compress;
-    return cmp;
-  }
+  // compression route of an update's launches (routes::effective_compress).  Every launch of an update -- the early k_feature of
+  // the overlap path too -- asks here.
+  int update_compress() const { return routes::effective_compress(d.compress, settings.compress_route, n_lit); }
   // ncam_ahead: run_frames advances its host mirror of the window sizes after the frame's launches (the frame's augmentState is
   // not in h_ncam yet when its update is enqueued).  Which route a TRAJECTORY takes depends on its own window size only -- never
   // on its neighbours in the range, on how a batch is cut into slices or a frame range into calls, or on the API used
@@ -1493,26 +1481,20 @@ struct Batch : BatchCore {
   void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
-    v.compress = update_compress(v.compress);
+    v.compress = update_compress();
     if (!feature_done) { stage_begin(2, q); launch_feature<S>(v, b0, nb, q); stage_end(2, q); }
     // information form: k_select and the block-diagonal reduction share a launch (both only read k_feature's outputs)
-    stage_begin(7, q); if (v.compress) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q);
+    const routes::CompressRoute cr = routes::compress_route(v.compress, d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts);
+    stage_begin(7, q); if (cr.select_diag) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q);
     // short windows (single filters, BASELINE configs[1]): everything after the selection in ONE launch (k_update_small)
-    if (small_limit && v.compress && n_lit == 0 && d.joseph == 0) {
-      int nmax = 0, nsmall = 0;                    // largest window of the range, largest one within the limit
-      for (int b = b0; b < b0 + nb; ++b) { const int n = 6 * std::min(h_ncam[b] + (cell_k && cell_k[b - b0] == IMU_SKIP ? 0 : ncam_ahead), n_cap); nmax = std::max(nmax, n); if (n > 0 && n <= small_limit) nsmall = std::max(nsmall, n); }
-      // (an empty window has no update: it makes no range mixed, and in a mixed one it is k_update_small's, 6 x 0 <= small_split)
-      const bool mixed = nsmall > 0 && nmax > small_limit;
-      if ((nmax > 0 && nmax <= small_limit) || mixed) {
-        if (mixed) v.small_split = small_limit;
-        stage_begin(5, q);
-        const bool ok = launch_update_small<S>(v, b0, nb, q, nsmall);
-        stage_end(5, q);
-        if (ok && !mixed) return;
-        if (!ok) v.small_split = 0;                // (not reached: small_limit fits) the chain takes everybody
-      }
+    const routes::SmallRoute sr = routes::small_route(nb, [&](int i) { return routes::window_cols(h_ncam[b0 + i], ncam_ahead, cell_k && cell_k[i] == IMU_SKIP, n_cap); },
+                                                      small_limit, v.compress, n_lit, d.joseph, f_cap, sizeof(S), update_small_granted());
+    if (sr.kind != routes::CHAIN_ONLY) {
+      v.small_split = sr.small_split;
+      stage_begin(5, q); launch_update_small<S>(v, b0, nb, q, sr); stage_end(5, q);
+      if (sr.kind == routes::SMALL_ONLY) return;
     }
-    if (v.compress) {
+    if (cr.info) {
       // anisotropic pixel noise, literal route: the information matrix of the reference's (T_H, r_n, R_n) replaces H_o^T H_o
       // for those trajectories (kernels_literal.hip)
       stage_begin(3, q);
@@ -1817,7 +1799,7 @@ struct Batch : BatchCore {
       (void)hipEventRecord(ev_fa[hh], q);
       (void)hipStreamWaitEvent(sty[hh], ev_fa[hh], 0);
       Dev<S> v2 = v; v2.ncam_bias = 1;
-      v2.compress = update_compress(v2.compress);
+      v2.compress = update_compress();
       launch_feature<S>(v2, b0, nb, sty[hh]);
       (void)hipEventRecord(ev_fb[hh], sty[hh]);
     }
