@@ -338,8 +338,21 @@ int msckf_hip_profile_read_ex(msckf_hip_handle h, double* ms, int* count, int ca
  * this.  (The reference's StageTiming message, asl_msckf.cpp:229-296, is host wall-clock and has no such term.) */
 int msckf_hip_profile_event_overhead(msckf_hip_handle h, double* ms);
 /* run_frames on n = 1..8 HIP streams: the batch is cut into n slices of independent trajectories that run the
- * same kernel sequence concurrently (latency-bound stages of one slice overlap chip-filling stages of another). */
+ * same kernel sequence concurrently (latency-bound stages of one slice overlap chip-filling stages of another).
+ * n is an upper bound: slices whose streams share a hardware queue run one after the other, slower than a single slice, so
+ * the handle runs as many slices as the process has queues for (msckf_hip_set_hw_queues), and the process's default stream
+ * holds one of those: with 4 queues a request for 4 slices runs 2; with 8, 4.  Results do not depend on the count. */
 int msckf_hip_set_streams(msckf_hip_handle h, int n);
+/* The hardware queues the HIP runtime gives this process, 1..32: GPU_MAX_HW_QUEUES as the process started with, 4 (the
+ * runtime's default and the handle's) where it was not set.  The library reads no variable of the runtime's and sets none:
+ * the caller says what its process has.  msckf_hip_parse_hw_queues turns the variable's text into that number (null, empty
+ * or no number: 4; a number is clamped to 1..32). */
+int msckf_hip_set_hw_queues(msckf_hip_handle h, int n);
+int msckf_hip_parse_hw_queues(const char* text);
+/* on != 0: the frame loops run exactly the slices msckf_hip_set_streams asked for, whatever the queues (A/B runs). */
+int msckf_hip_set_slices_exact(msckf_hip_handle h, int on);
+/* The slices msckf_hip_run_frames (streamed == 0) or msckf_hip_run_frames_streamed (streamed != 0) would run now. */
+int msckf_hip_get_effective_streams(msckf_hip_handle h, int streamed, int* out);
 /* Host cores for the threads of msckf_hip_run_frames / _streamed: cpus[0] for the calling thread while it uploads frames
  * (restored on return), cpus[1 + i] for the enqueue thread of slice i.  The hand-overs between them are spin waits; without
  * this the threads run wherever the scheduler puts them (n = 0 clears the list).  One core each, ideally on the GPU's NUMA

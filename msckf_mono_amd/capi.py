@@ -34,7 +34,7 @@ SYMBOLS = [
     "msckf_hip_scenario_pin", "msckf_hip_set_upload_ring", "msckf_hip_clear_error_flags",
     "msckf_hip_set_compression", "msckf_hip_set_covariance_update", "msckf_hip_set_feature_overlap", "msckf_hip_get_pruned_states", "msckf_hip_get_cam_meta", "msckf_hip_get_tracked_feature_ids",
     "msckf_hip_set_anisotropic_noise", "msckf_hip_literal_info", "msckf_hip_get_error_flags", "msckf_hip_copy_state", "msckf_hip_set_host_affinity",
-    "msckf_hip_image_cycle_range",
+    "msckf_hip_image_cycle_range", "msckf_hip_get_effective_streams", "msckf_hip_set_hw_queues", "msckf_hip_parse_hw_queues", "msckf_hip_set_slices_exact",
     "msckf_hip_frame_log_enable", "msckf_hip_frame_log_reset", "msckf_hip_frame_log_count", "msckf_hip_frame_log_read", "msckf_hip_frame_log_metrics",
     "msckf_hip_scenario_set_cell", "msckf_hip_propagate_range_counts", "msckf_hip_frame_log_metrics_ranges",
     "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
@@ -134,6 +134,12 @@ class Batch:
         self.h = C.c_void_p()
         self.B, self.n_cap, self.f_cap, self.m_cap, self.dtype = B, n_cap, f_cap, m_cap, dtype
         _chk(self.L.msckf_hip_create(B, n_cap, f_cap, m_cap, dtype, device, C.byref(self.h)))
+        # the hardware queues of this process, for the slice policy (csrc/slice_policy.h): the native library reads no variable
+        # of the runtime's, so its caller passes on what the runtime found when the process started
+        # (a library from before the policy, given through MSCKF_HIP_LIB for an A/B run, has no such entry)
+        if hasattr(self.L, "msckf_hip_set_hw_queues"):
+            text = os.environ.get("GPU_MAX_HW_QUEUES")
+            self.set_hw_queues(self.L.msckf_hip_parse_hw_queues(None if text is None else text.encode()))
 
     def close(self):
         if self.h:
@@ -365,6 +371,21 @@ class Batch:
 
     def set_streams(self, n):
         _chk(self.L.msckf_hip_set_streams(self.h, int(n)))
+
+    def set_hw_queues(self, n):
+        """hardware queues the runtime gives this process (GPU_MAX_HW_QUEUES when it started, 4 by default): 1..32"""
+        _chk(self.L.msckf_hip_set_hw_queues(self.h, int(n)))
+
+    def set_slices_exact(self, on):
+        """run exactly set_streams' slices whatever the hardware queues (A/B runs)"""
+        _chk(self.L.msckf_hip_set_slices_exact(self.h, 1 if on else 0))
+
+    def effective_streams(self, streamed=False):
+        """the slices run_frames (or, streamed, run_frames_streamed) runs now: set_streams' count is an upper bound that the
+        handle sizes to the process's hardware queues (csrc/slice_policy.h)"""
+        n = C.c_int(0)
+        _chk(self.L.msckf_hip_get_effective_streams(self.h, 1 if streamed else 0, C.byref(n)))
+        return int(n.value)
 
     def set_compression(self, route):
         """-1 default for the window size; 0 Householder TSQR; 3 information form chol(H_o^T H_o) with the blocked matrix-core

@@ -35,6 +35,7 @@
 #include "dev_common.h"
 #include "host_lists.h"
 #include "settings.h"
+#include "slice_policy.h"
 
 namespace {
 using namespace msckf;
@@ -265,6 +266,10 @@ struct BatchCore {
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     for (int i = 0; i < NSTG; ++i) HIPCHK(hipEventCreateWithFlags(&ev_stage[i], hipEventDisableTiming));
     stx[0] = st;
+    // every stream up front, in this order: the runtime places a stream on a hardware queue when it is made, and this order is
+    // the one whose placement is measured (the slices' streams on queues of their own as far as the budget goes).  Making them
+    // when a frame loop first needs them changed the placement: measured, 3 slices on 4 queues and 4 slices on 8 queues then
+    // lost a third of their rate (profiles/hw_queue_slices.md, "streams made on first use")
     for (int i = 1; i < MAXS; ++i) HIPCHK(hipStreamCreateWithFlags(&stx[i], hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     for (int i = 1; i < MAXS; ++i) HIPCHK(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
@@ -640,8 +645,20 @@ struct BatchCore {
   // the latency-bound stages of one slice (gain solve, Cholesky, propagate: one workgroup per trajectory) overlap with the
   // chip-filling stages of the others.  One host thread per slice enqueues that slice's kernels for all frames of the call
   // (~13 launches per frame and slice would otherwise serialise on one thread and make more than two slices launch-bound).
-  // Stage profiling forces a single stream.
-  int n_slices() const { return prof ? 1 : std::max(1, std::min(settings.nstreams, B)); }
+  // Stage profiling forces a single stream.  settings.nstreams is an upper bound: slices that would share a hardware queue run
+  // one after the other, so the count is sized to the queues the process has (slice_policy.h states the rule, nothing here decides)
+  // hw_queues: the hardware queues of the process, the runtime's default until the caller says otherwise (msckf_hip_set_hw_queues:
+  // the library reads no variable of the runtime's); slices_exact: run the request whatever the queues (A/B runs).  Both are
+  // plumbing of this process and stay with their handle when its state is copied.
+  int hw_queues = msckf::slices::HW_QUEUES_DEFAULT; bool slices_exact = false;
+  int n_slices(bool streamed) const {
+    return msckf::slices::effective_slices(settings.nstreams, B, msckf::slices::handle_queue_budget(hw_queues), streamed, slices_exact, prof);
+  }
+  int set_hw_queues(int n) {
+    if (n < 1 || n > msckf::slices::HW_QUEUES_MAX) return fail(-EINVAL, "1 to 32 hardware queues");
+    hw_queues = n;
+    return 0;
+  }
   // slice hh of nh on its enqueue thread: trajectories [b0, b0 + nb) on stream q.  A frame whose prune rides on the downdate
   // leaves the covariance in the other buffer (flipped: the slice's current one is the handle's spare) and the new window size
   // for the next k_propagate to commit (pending)
@@ -849,7 +866,7 @@ struct BatchCore {
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = reserve_logs(f0, f1)) return rc;
     if (int rc = enter()) return rc;
-    const int nh = n_slices();
+    const int nh = n_slices(false);
     const int rc = fork_slices(nh);
     if (rc) return rc;
     int slice_rc[MAXS] = {0};
@@ -892,7 +909,7 @@ struct BatchCore {
         for (int i = 0; i < MAXS; ++i) HIPCHK(hipEventCreateWithFlags(&ev_use[k][i], hipEventDisableTiming));
       }
     }
-    const int nh = n_slices();
+    const int nh = n_slices(true);
     const int R = settings.ring, mode = settings.up_mode;
     const int rc = fork_slices(nh, stc);
     if (rc) return rc;
@@ -2454,6 +2471,10 @@ int msckf_hip_profile_read_ex(msckf_hip_handle h, double* ms, int* count, int ca
 int msckf_hip_profile_event_overhead(msckf_hip_handle h, double* ms) { if (!h || !ms) return fail(-EINVAL, "null argument"); return H(h)->prof_event_overhead(ms); }
 int msckf_hip_set_host_affinity(msckf_hip_handle h, const int* cpus, int n) { if (!h || (n > 0 && !cpus)) return fail(-EINVAL, "null argument"); return H(h)->set_host_affinity(cpus, n); }
 int msckf_hip_set_streams(msckf_hip_handle h, int n) { return H(h)->set_streams(n); }
+int msckf_hip_get_effective_streams(msckf_hip_handle h, int streamed, int* out) { if (!h || !out) return fail(-EINVAL, "null argument"); *out = H(h)->n_slices(streamed != 0); return 0; }
+int msckf_hip_parse_hw_queues(const char* text) { return msckf::slices::parse_hw_queue_budget(text); }
+int msckf_hip_set_hw_queues(msckf_hip_handle h, int n) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_hw_queues(n); }
+int msckf_hip_set_slices_exact(msckf_hip_handle h, int on) { if (!h) return fail(-EINVAL, "null handle"); H(h)->slices_exact = on != 0; return 0; }
 int msckf_hip_scenario_pin(msckf_hip_handle h, int f0, int f1) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->scen_pin(f0, f1); }
 int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_upload_ring(depth, mode); }
 int msckf_hip_set_feature_overlap(msckf_hip_handle h, int on) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_feature_overlap(on); }
