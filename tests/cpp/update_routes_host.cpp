@@ -5,6 +5,7 @@
 // is the form of tests/golden/update_routes.txt: every threshold shows as the end of one run and the start of the next, and a
 // key that a route does not depend on shows as one run over all its values.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -98,7 +99,32 @@ static void small_case(Table& V, const char* name, const int* cols, int nb, int 
   V.add({sc(scalar), str(limit), str(compress), str(n_lit), str(joseph), name}, fmt("%s split=%d nsmall=%d segb=%d", kind, r.small_split, r.nsmall, r.segb));
 }
 
+// --handle scalar B nb n_cap f_cap m_cap form fused_s gain_parts small_update override cameras...: the routes of ONE update of ONE
+// handle, composed the way launch_update composes them (one line per stage: G geometry, F features, C compression, V the
+// small-window decision over the range's windows, K Kalman stage); tests/test_gpu_update_kernels.py asserts with it that each
+// of its cases reaches the kernels it was written for.  scalar: f | d; cameras: the window size of each trajectory of the range
+static int one_handle(int argc, char** argv) {
+  if (argc < 13) { std::fprintf(stderr, "--handle needs 11 values and the windows\n"); return 2; }
+  const size_t s = argv[2][0] == 'f' ? 4 : 8;
+  int a[10];
+  for (int i = 0; i < 10; ++i) a[i] = std::atoi(argv[3 + i]);
+  const int B = a[0], nb = a[1], n_cap = a[2], f_cap = a[3], m_cap = a[4], form = a[5], fused_s = a[6], gain_parts = a[7], small_update = a[8], ov = a[9];
+  std::vector<int> cols;
+  for (int i = 13; i < argc; ++i) cols.push_back(window_cols(std::atoi(argv[i]), 0, false, n_cap));
+  if ((int)cols.size() != nb) { std::fprintf(stderr, "--handle: %d windows for nb = %d\n", (int)cols.size(), nb); return 2; }
+  const Geometry g = geometry(B, n_cap, f_cap, m_cap, s);
+  const int cmp = effective_compress(g.compress, ov, 0), limit = small_limit(small_update, f_cap, s, true);
+  const SmallRoute r = small_route(nb, [&](int i) { return cols[i]; }, limit, cmp, 0, form, f_cap, s, true);
+  std::printf("G %s ld=%d ldR=%d compress=%d Mp=%d Mp2=%d lam_parts=%d\n", g.refusal == GEO_OK ? "ok" : "refused", g.ld, g.ldR, g.compress, g.has_Mp, g.has_Mp2, g.lam_parts);
+  std::printf("F %s\n", feature_text(feature_route(s, f_cap, m_cap, nb, 1, cmp)).c_str());
+  std::printf("C compress=%d %s\n", cmp, compress_text(compress_route(cmp, g.ldR, g.has_Mp, g.lam_parts, GRAM_PARTS)).c_str());
+  std::printf("V limit=%d %s split=%d nsmall=%d segb=%d\n", limit, r.kind == CHAIN_ONLY ? "chain" : r.kind == SMALL_ONLY ? "small" : "mixed", r.small_split, r.nsmall, r.segb);
+  std::printf("K %s\n", kalman_text(kalman_route(s, n_cap, B, nb, form, fused_s, gain_parts, g.has_Mp2), s).c_str());
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "--handle")) return one_handle(argc, argv);
   g_runs = argc > 1 && !std::strcmp(argv[1], "--runs");
   // G: what alloc derives from n_cap and f_cap; N: from B; A: what it refuses (the scalar and m_cap enter only there)
   Table G{"G", {"f_cap", "n_cap"}, {}}, N{"N", {"B"}, {}}, A{"A", {"scalar", "m_cap", "n_cap"}, {}};
