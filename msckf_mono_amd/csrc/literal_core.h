@@ -1936,8 +1936,11 @@ LIT_FN void compact_basis(const Ctx& c, const Args<HT>& a, const int m) {
     tick(c, 7);
     const int nab = na + nb;
     const int ldb = (nb + 7) & ~3;                  // the staged rows of the basis' columns, gathered, [l][k] (zero beyond nb)
-    const bool tiles = 33L * n1 + 104 + 30L * ldb <= c.lds_doubles;
-    double* sEg = sU + 16L * n1 + 104; double* sUg = sEg + 15L * ldb;
+    // (the list's nr ints lie between the staged rows and the tiles' copy: 104 doubles hold 208 of them; a basis of more rows -- from
+    // 33 cameras on, with 21 or more kept handed-through rows -- moves the copy up, or sB's tail would be overwritten by it)
+    const long lsb = nr <= 208 ? 104 : (((nr + 1) / 2 + 3) & ~3L);
+    const bool tiles = 33L * n1 + lsb + 30L * ldb <= c.lds_doubles;
+    double* sEg = sU + 16L * n1 + lsb; double* sUg = sEg + 15L * ldb;
     if (tiles) {
       par_for32(c, 15 * ldb, [&](int x) {
         const int l = x / ldb, k = x - l * ldb;

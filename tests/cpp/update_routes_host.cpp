@@ -102,8 +102,10 @@ static void small_case(Table& V, const char* name, const int* cols, int nb, int 
 // --handle scalar B nb n_cap f_cap m_cap form fused_s gain_parts small_update override cameras...: the routes of ONE update of ONE
 // handle, composed the way launch_update composes them (one line per stage: G geometry, F features, C compression, V the
 // small-window decision over the range's windows, K Kalman stage); tests/test_gpu_update_kernels.py asserts with it that each
-// of its cases reaches the kernels it was written for.  scalar: f | d; cameras: the window size of each trajectory of the range
-static int one_handle(int argc, char** argv) {
+// of its cases reaches the kernels it was written for.  scalar: f | d; cameras: the window size of each trajectory of the range.
+// --handle-lit: the same handle with a trajectory on the literal anisotropic route in it (n_lit > 0: no k_update_small, the
+// information form whatever the override says; tests/test_gpu_literal_kernels.py)
+static int one_handle(int argc, char** argv, int n_lit) {
   if (argc < 13) { std::fprintf(stderr, "--handle needs 11 values and the windows\n"); return 2; }
   const size_t s = argv[2][0] == 'f' ? 4 : 8;
   int a[10];
@@ -113,8 +115,8 @@ static int one_handle(int argc, char** argv) {
   for (int i = 13; i < argc; ++i) cols.push_back(window_cols(std::atoi(argv[i]), 0, false, n_cap));
   if ((int)cols.size() != nb) { std::fprintf(stderr, "--handle: %d windows for nb = %d\n", (int)cols.size(), nb); return 2; }
   const Geometry g = geometry(B, n_cap, f_cap, m_cap, s);
-  const int cmp = effective_compress(g.compress, ov, 0), limit = small_limit(small_update, f_cap, s, true);
-  const SmallRoute r = small_route(nb, [&](int i) { return cols[i]; }, limit, cmp, 0, form, f_cap, s, true);
+  const int cmp = effective_compress(g.compress, ov, n_lit), limit = small_limit(small_update, f_cap, s, true);
+  const SmallRoute r = small_route(nb, [&](int i) { return cols[i]; }, limit, cmp, n_lit, form, f_cap, s, true);
   std::printf("G %s ld=%d ldR=%d compress=%d Mp=%d Mp2=%d lam_parts=%d\n", g.refusal == GEO_OK ? "ok" : "refused", g.ld, g.ldR, g.compress, g.has_Mp, g.has_Mp2, g.lam_parts);
   std::printf("F %s\n", feature_text(feature_route(s, f_cap, m_cap, nb, 1, cmp)).c_str());
   std::printf("C compress=%d %s\n", cmp, compress_text(compress_route(cmp, g.ldR, g.has_Mp, g.lam_parts, GRAM_PARTS)).c_str());
@@ -124,7 +126,8 @@ static int one_handle(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-  if (argc > 1 && !std::strcmp(argv[1], "--handle")) return one_handle(argc, argv);
+  if (argc > 1 && !std::strcmp(argv[1], "--handle")) return one_handle(argc, argv, 0);
+  if (argc > 1 && !std::strcmp(argv[1], "--handle-lit")) return one_handle(argc, argv, 1);
   g_runs = argc > 1 && !std::strcmp(argv[1], "--runs");
   // G: what alloc derives from n_cap and f_cap; N: from B; A: what it refuses (the scalar and m_cap enter only there)
   Table G{"G", {"f_cap", "n_cap"}, {}}, N{"N", {"B"}, {}}, A{"A", {"scalar", "m_cap", "n_cap"}, {}};

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import literal_lab as LL
 from msckf_mono_amd import scenario as sc
 
 pytestmark = pytest.mark.gpu
@@ -62,6 +63,7 @@ def test_literal_route_double_vs_restatement_every_frame(capi, po, N, F, nf, tra
         H.oracle_frame(o, tr, k, N); H.device_frame(bt, 0, tr, k, N)
         e = _errs(bt, 0, o)
         assert H.worst(e) < 1e-6, (k, e)
+        assert H.cov_scaled_err(bt.covariance(0), o.getCovariance()) < 1e-6, k       # entry by entry: the norm above cannot see a wrong block
         if o.lastStats()["m_rows"]:
             info = bt.literal_info(0)
             assert info["m_rows"] == o.lastStats()["m_rows"] and info["kept_rows"] == o.lastStats()["r_rows"] and info["route"] == 3, (k, info, o.lastStats())
@@ -262,6 +264,8 @@ def test_literal_route_handed_through_rows_deep_in_the_sweep(capi, po, slot, dou
             continue
         e = _errs(bt, 0, o)
         assert H.worst(e) < bar, (k, e)
+        sc_err = H.cov_scaled_err(bt.covariance(0), o.getCovariance())              # entry by entry: 1e-6 in double, the lab's float bar in float
+        assert sc_err < (LL.BAR_F64 if double else LL.bars("f32")[0]), (k, sc_err)
         info = bt.literal_info(0)
         assert info["m_rows"] == o.lastStats()["m_rows"] > 4000 and abs(info["kept_rows"] - o.lastStats()["r_rows"]) <= (0 if double else 2) and info["route"] == 3
         assert info["kept_handed_through_rows"] >= 6, info
