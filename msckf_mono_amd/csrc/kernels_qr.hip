@@ -1,6 +1,7 @@
 // kernels_qr.hip -- Householder compression of the stacked projected Jacobian (msckf.h:1338-1366) as a streaming
-// TSQR on gfx950.  Route (b) of DESIGN.md section 4.4: used for windows with n + 1 > 192 and as the A/B reference of
-// the information-form route (kernels_gram.hip), which is the default below that size.
+// TSQR on gfx950.  Route (b) of DESIGN.md section 4.4: used when the handle holds more tracks than the information form
+// takes (f_cap > routes::INFO_F_CAP = 1024), on request (set_compression(0)), and as the A/B reference of the
+// information-form route (kernels_gram.hip), which is the default at every window size.
 //
 // The reference stacks H_o (m x D, m ~ 5 600 for 200 tracks in a 30-camera window), runs a dense
 // HouseholderQR, forms the FULL m x m Q and a dense m x m R_o (msckf.h:1343-1366).  Here H_o is never
@@ -65,8 +66,8 @@ struct Tri {
 // from wave to wave through LDS with a release/acquire progress word).  Inside a wavefront a step needs no
 // LDS exchange and no barrier: the pivot column is read from its owner lane with v_readlane, the dot
 // products are complete within the wave, the column norm is the pivot column's self product.
-constexpr int QR_NW = 12;        // wavefronts per workgroup = depth of the software pipeline
-constexpr int QR_MAXBLK = 512;   // ring of per-block progress words in LDS
+constexpr int QR_NW = routes::QR_PIPELINE;   // wavefronts per workgroup = depth of the software pipeline
+constexpr int QR_MAXBLK = routes::QR_RING;   // ring of per-block progress words in LDS
 
 template <class S, int NC, int RW, bool RLDS>
 __global__ __launch_bounds__(64 * QR_NW) void k_qr_update(Dev<S> d, int b0, int stage, int level) {
@@ -282,34 +283,24 @@ __global__ __launch_bounds__(64 * QR_NW) void k_qr_update(Dev<S> d, int b0, int 
   }
 }
 
+// routes::tsqr_route (update_routes.h) says which instantiation, its LDS and whether the merge runs; the launchers carry it out
 template <class S, int NC, bool RLDS>
-static void launch_compress_impl(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase, size_t lds) {
-  constexpr int RW = (sizeof(S) == 4 && NC <= 3) ? 32 : 16;
+static void launch_compress_impl(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase, const routes::TsqrRoute& r) {
+  constexpr int RW = routes::qr_rows_per_block(sizeof(S), NC);
   auto kern = k_qr_update<S, NC, RW, RLDS>;
-  if (phase != 2) hipLaunchKernelGGL(kern, dim3(d.nchunk, nb), dim3(64 * QR_NW), lds, st, d, b0, 1, 0);
+  if (phase != 2) hipLaunchKernelGGL(kern, dim3(r.nchunk, nb), dim3(64 * QR_NW), r.lds_bytes, st, d, b0, 1, 0);
   if (phase == 1) return;
-  if (d.nchunk > 1) hipLaunchKernelGGL(kern, dim3(1, nb), dim3(64 * QR_NW), lds, st, d, b0, 2, 0);
-}
-template <class S, int NC>
-static void launch_compress_nc(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase) {
-  const size_t base = 4 * QR_MAXBLK;
-  const size_t tri = sizeof(S) * (size_t)(d.n6cap + 1) * (d.n6cap + 2) / 2;
-  if (base + tri <= 150 * 1024) launch_compress_impl<S, NC, true>(d, b0, nb, st, phase, base + tri);
-  else launch_compress_impl<S, NC, false>(d, b0, nb, st, phase, base);
+  if (r.merge) hipLaunchKernelGGL(kern, dim3(1, nb), dim3(64 * QR_NW), r.lds_bytes, st, d, b0, 2, 0);
 }
 
 template <class S>
 void launch_compress(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase) {
   if (nb <= 0) return;
-  const int nc = d.ldR / 64;
-  switch (nc) {
-    case 1: launch_compress_nc<S, 1>(d, b0, nb, st, phase); break;
-    case 2: launch_compress_nc<S, 2>(d, b0, nb, st, phase); break;
-    case 3: launch_compress_nc<S, 3>(d, b0, nb, st, phase); break;
-    case 4: launch_compress_nc<S, 4>(d, b0, nb, st, phase); break;
-    case 5: launch_compress_nc<S, 5>(d, b0, nb, st, phase); break;
-    default: launch_compress_nc<S, 6>(d, b0, nb, st, phase); break;
-  }
+  const routes::TsqrRoute r = routes::tsqr_route(sizeof(S), d.n6cap, d.ldR, d.nchunk);
+  dispatch_int<1, 2, 3, 4, 5, routes::QR_NC_MAX>(r.nc, [&](auto NC) {
+    if (r.tri_lds) launch_compress_impl<S, NC(), true>(d, b0, nb, st, phase, r);
+    else launch_compress_impl<S, NC(), false>(d, b0, nb, st, phase, r);
+  });
 }
 
 #ifdef MSCKF_ABLATE
@@ -318,7 +309,7 @@ void qr_debug_set(int idx, int val) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_qr_db
 
 // one-time, per-device setup (called from msckf_hip_create after hipSetDevice): LDS limit of every instantiation
 template <class S, int NC> static void qr_setup_nc() {
-  constexpr int RW = (sizeof(S) == 4 && NC <= 3) ? 32 : 16;
+  constexpr int RW = routes::qr_rows_per_block(sizeof(S), NC);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_update<S, NC, RW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_qr_update<S, NC, RW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }

@@ -2,7 +2,7 @@
 //
 // A handle's geometry (what Batch<S>::alloc derives from B, n_cap, f_cap, m_cap and the scalar) and the route of each stage of
 // the update -- feature kernels, the one-launch update of short windows, compression, Kalman stage -- as pure functions that
-// return small PODs.  The launchers of kernels_feature / _gram / _chol / _kalman.hip and the head of launch_update
+// return small PODs.  The launchers of kernels_feature / _qr / _gram / _chol / _kalman.hip and the head of launch_update
 // (msckf_hip.hip) ask here and carry the answer out; none of them decides.  No HIP header, no heap, no lock (the functions
 // run on the enqueue threads and on the single-filter path): a host compiler accepts this file on its own, and
 // tests/cpp/update_routes_host.cpp prints the routes of a grid of handles for tests/test_update_routes.py.
@@ -205,6 +205,30 @@ inline CompressRoute compress_route(int compress, int ldR, bool has_Mp, bool lam
   }
   // split-K partial sums only where the consumer adds them up: the one-level Cholesky
   if (r.chol_levels == 1 && lam_parts) r.gram_parts = gram_parts_setting >= GRAM_PARTS ? gram_parts_setting : GRAM_PARTS;
+  return r;
+}
+
+// ---------------------------------------------------------------- Householder TSQR route (kernels_qr.hip)
+// k_qr_update<S, NC, RW, RLDS>: NC 64-column panels of [R | Q^T r] per lane, blocks of RW stacked rows per wavefront, the packed
+// work triangle in LDS (RLDS) or ldR-strided in global memory.  Stage 1 runs nchunk workgroups per trajectory, stage 2 merges
+// their triangles into chunk 0 (merge: it runs only where there is more than one chunk).
+constexpr int QR_PIPELINE = 12;             // wavefronts per workgroup = depth of the software pipeline over R's rows
+constexpr int QR_RING = 512;                // progress words per workgroup: block q of a chunk lives in slot q % QR_RING (a power of two)
+constexpr size_t QR_TRI_LDS = 150 * 1024;   // the progress ring + the packed triangle stay in LDS up to here, the triangle in global memory beyond
+constexpr int QR_RW_WIDE = 32, QR_RW = 16;  // rows per block: 32 where the registers hold them (float, up to QR_RW_WIDE_NC panels), else 16
+constexpr int QR_RW_WIDE_NC = 3;
+constexpr int QR_NC_MAX = 6;                // 384 columns (N_CAP_MAX)
+constexpr int qr_rows_per_block(size_t scalar, int nc) { return (scalar == 4 && nc <= QR_RW_WIDE_NC) ? QR_RW_WIDE : QR_RW; }
+struct TsqrRoute { int nc, rw; bool tri_lds; size_t lds_bytes; int nchunk; bool merge; };
+inline TsqrRoute tsqr_route(size_t scalar, int n6cap, int ldR, int nchunk) {
+  TsqrRoute r{};
+  r.nc = ldR / 64 < QR_NC_MAX ? ldR / 64 : QR_NC_MAX;
+  r.rw = qr_rows_per_block(scalar, r.nc);
+  const size_t ring = sizeof(int) * (size_t)QR_RING, tri = scalar * (size_t)(n6cap + 1) * (n6cap + 2) / 2;
+  r.tri_lds = ring + tri <= QR_TRI_LDS;
+  r.lds_bytes = r.tri_lds ? ring + tri : ring;
+  r.nchunk = nchunk;
+  r.merge = nchunk > 1;
   return r;
 }
 

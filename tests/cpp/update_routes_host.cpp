@@ -78,6 +78,9 @@ static std::string compress_text(const CompressRoute& r) {
   else s += "none";
   return s;
 }
+static std::string tsqr_text(const TsqrRoute& r) {
+  return fmt("tsqr NC=%d RW=%d tri=%s lds=%zu nchunk=%d merge=%d", r.nc, r.rw, r.tri_lds ? "lds" : "global", r.lds_bytes, r.nchunk, r.merge ? 1 : 0);
+}
 static std::string kalman_text(const KalmanRoute& r, size_t scalar) {
   const char* S = scalar == 4 ? "float" : "double";
   std::string s = fmt("fused=%d ", r.s_fused ? 1 : 0);
@@ -100,8 +103,9 @@ static void small_case(Table& V, const char* name, const int* cols, int nb, int 
 }
 
 // --handle scalar B nb n_cap f_cap m_cap form fused_s gain_parts small_update override cameras...: the routes of ONE update of ONE
-// handle, composed the way launch_update composes them (one line per stage: G geometry, F features, C compression, V the
-// small-window decision over the range's windows, K Kalman stage); tests/test_gpu_update_kernels.py asserts with it that each
+// handle, composed the way launch_update composes them (one line per stage: G geometry, F features, C compression, Q the
+// k_qr_update instantiation where the compression is the Householder TSQR, V the small-window decision over the range's
+// windows, K Kalman stage); tests/test_gpu_update_kernels.py asserts with it that each
 // of its cases reaches the kernels it was written for.  scalar: f | d; cameras: the window size of each trajectory of the range.
 // --handle-lit: the same handle with a trajectory on the literal anisotropic route in it (n_lit > 0: no k_update_small, the
 // information form whatever the override says; tests/test_gpu_literal_kernels.py)
@@ -120,6 +124,7 @@ static int one_handle(int argc, char** argv, int n_lit) {
   std::printf("G %s ld=%d ldR=%d compress=%d Mp=%d Mp2=%d lam_parts=%d\n", g.refusal == GEO_OK ? "ok" : "refused", g.ld, g.ldR, g.compress, g.has_Mp, g.has_Mp2, g.lam_parts);
   std::printf("F %s\n", feature_text(feature_route(s, f_cap, m_cap, nb, 1, cmp)).c_str());
   std::printf("C compress=%d %s\n", cmp, compress_text(compress_route(cmp, g.ldR, g.has_Mp, g.lam_parts, GRAM_PARTS)).c_str());
+  if (!cmp) std::printf("Q %s\n", tsqr_text(tsqr_route(s, g.n6cap, g.ldR, g.nchunk)).c_str());
   std::printf("V limit=%d %s split=%d nsmall=%d segb=%d\n", limit, r.kind == CHAIN_ONLY ? "chain" : r.kind == SMALL_ONLY ? "small" : "mixed", r.small_split, r.nsmall, r.segb);
   std::printf("K %s\n", kalman_text(kalman_route(s, n_cap, B, nb, form, fused_s, gain_parts, g.has_Mp2), s).c_str());
   return 0;
@@ -208,6 +213,16 @@ int main(int argc, char** argv) {
           C.add({str(ov), str(n_lit), str(f_cap), str(n_cap)}, fmt("compress=%d ", cmp) + compress_text(compress_route(cmp, g.ldR, g.has_Mp, g.lam_parts, GRAM_PARTS)));
         }
   C.print();
+  // Q: the Householder TSQR's instantiation (every window at one batch size; every batch size on either side of a chunk count at one window)
+  Table Q{"Q", {"scalar", "B", "n_cap"}, {}};
+  for (size_t s : SCALARS)
+    for (int B : {1, 32, 33, 64, 65, 128, 129, 130})
+      for (int n_cap = 1; n_cap <= N_CAP_MAX; ++n_cap)
+        if (B == 64 || n_cap == 22) {
+          const Geometry g = geometry(B, n_cap, 1025, 12, s);
+          Q.add({sc(s), str(B), str(n_cap)}, tsqr_text(tsqr_route(s, g.n6cap, g.ldR, g.nchunk)));
+        }
+  Q.print();
   // K: Kalman route (the window first: a bound in n_cap then shows once, over everything that does not move it)
   Table K{"K", {"n_cap", "scalar", "form", "fused_s", "gain_parts", "B,nb"}, {}};
   for (int n_cap = 1; n_cap <= N_CAP_MAX; ++n_cap)

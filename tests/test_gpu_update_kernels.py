@@ -21,7 +21,11 @@ Found while writing this suite: the one-launch update fits windows of at most 12
 not the 14 the setting asks for; 13 and 14 cameras take the chain.  Hence 12 among the sizes, and `mixed` from n_cap 14 on.
 
 Out of scope: the fp16-Jacobian dtype (an envelope of its own), the early-accept bound, tracks longer than 30 (the feature routes:
-tests/test_gpu_feature_kernels.py); the anisotropic and literal routes and aniso_mode == 1 are tests/test_gpu_literal_kernels.py's."""
+tests/test_gpu_feature_kernels.py); the anisotropic and literal routes and aniso_mode == 1 are tests/test_gpu_literal_kernels.py's.
+The `tsqr` variant below holds the Householder TSQR route on THESE lists only (every track from slot 0, all or none passing, at
+most 720 rows); everything else about that route -- every k_qr_update instantiation, the chunk counts, staggered first slots,
+compactions with holes, blind cameras, stacks deeper than the pipeline and longer than the progress ring, the route taken by
+geometry -- is tests/test_gpu_tsqr_kernels.py's (inputs: tests/tsqr_lab.py, tests/test_tsqr_inputs.py)."""
 import os
 import subprocess
 

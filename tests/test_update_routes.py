@@ -213,3 +213,49 @@ def test_couplings(table):
             flags = [f for _, f in fits]
             assert flags == sorted(flags, reverse=True) and flags[0], (s, f_cap, flags)
             assert route(table, "S", scalar=s, f_cap=f_cap, granted=0, n_cap=10).startswith("fits=0")
+
+
+# the Householder TSQR's instantiations, written down from the table of the suite's specification, NOT
+# computed from update_routes.h: per dtype the windows of each (NC, triangle in LDS | global memory) pair, first and last
+TSQR_PAIRS = {
+    "f": (((1, 10), 1, "lds"), ((11, 21), 2, "lds"), ((22, 31), 3, "lds"), ((32, 42), 4, "lds"), ((43, 45), 5, "lds"), ((46, 53), 5, "global"), ((54, 63), 6, "global")),
+    "d": (((1, 10), 1, "lds"), ((11, 21), 2, "lds"), ((22, 31), 3, "lds"), ((32, 32), 4, "lds"), ((33, 42), 4, "global"), ((43, 53), 5, "global"), ((54, 63), 6, "global")),
+}
+
+
+def test_tsqr_routes(table):
+    """(b) k_qr_update<S, NC, RW, RLDS>: seven reachable (NC, L | G) pairs per dtype, the LDS edges at float 45 | 46 and double
+    32 | 33 (4L exists in double at 32 cameras only: 151 816 bytes), RW 32 in float up to 31 cameras and 16 everywhere else, the
+    chunk count by the batch size alone, no merge launch for one chunk"""
+    for s, pairs in TSQR_PAIRS.items():
+        seen = []
+        for (lo, hi), nc, where in pairs:
+            for n in range(lo, hi + 1):
+                r = route(table, "Q", scalar=s, B=64, n_cap=n)
+                rw = 32 if s == "f" and n <= 31 else 16
+                assert r.startswith("tsqr NC=%d RW=%d tri=%s lds=" % (nc, rw, where)) and r.endswith(" nchunk=4 merge=1"), (s, n, r)
+                scalar = 4 if s == "f" else 8
+                tri = scalar * (6 * n + 1) * (6 * n + 2) // 2
+                assert (" lds=%d " % (2048 + tri if where == "lds" else 2048)) in r and (2048 + tri <= 150 * 1024) == (where == "lds"), (s, n, r)
+                seen.append(n)
+        assert seen == list(range(1, 64))
+    assert route(table, "Q", scalar="f", B=64, n_cap=45) == "tsqr NC=5 RW=16 tri=lds lds=149472 nchunk=4 merge=1"
+    assert route(table, "Q", scalar="f", B=64, n_cap=46) == "tsqr NC=5 RW=16 tri=global lds=2048 nchunk=4 merge=1"
+    assert route(table, "Q", scalar="d", B=64, n_cap=32) == "tsqr NC=4 RW=16 tri=lds lds=151816 nchunk=4 merge=1"
+    assert route(table, "Q", scalar="d", B=64, n_cap=33) == "tsqr NC=4 RW=16 tri=global lds=2048 nchunk=4 merge=1"
+    assert route(table, "Q", scalar="f", B=64, n_cap=31) == "tsqr NC=3 RW=32 tri=lds lds=72360 nchunk=4 merge=1"
+    assert route(table, "Q", scalar="f", B=64, n_cap=32) == "tsqr NC=4 RW=16 tri=lds lds=76932 nchunk=4 merge=1"
+    for s in "fd":
+        for B, nchunk in ((1, 8), (32, 8), (33, 4), (64, 4), (65, 2), (128, 2), (129, 1), (130, 1)):
+            assert route(table, "Q", scalar=s, B=B, n_cap=22).endswith(" nchunk=%d merge=%d" % (nchunk, 1 if nchunk > 1 else 0)), (s, B)
+
+
+def test_handle_prints_the_tsqr_line_only_on_that_route(program):
+    """--handle: the Q line with compress == 0 -- on request and by geometry (f_cap > 1024) -- and not on the information form"""
+    args = lambda s, B, n_cap, f_cap, ov: ["--handle", s, str(B), "1", str(n_cap), str(f_cap), "30", "0", "2", "0", "84", str(ov), str(n_cap)]
+    lines = lambda out: dict(line.split(" ", 1) for line in out.splitlines())
+    assert lines(run(program, *args("d", 24, 32, 32, 0)))["Q"] == "tsqr NC=4 RW=16 tri=lds lds=151816 nchunk=8 merge=1"
+    got = lines(run(program, *args("f", 2, 31, 1040, -1)))
+    assert got["C"] == "compress=0 select tsqr" and got["Q"] == "tsqr NC=3 RW=32 tri=lds lds=72360 nchunk=8 merge=1" and got["F"].startswith("k_feature<0> ")
+    assert lines(run(program, *args("f", 129, 30, 320, 0)))["Q"] == "tsqr NC=3 RW=32 tri=lds lds=67932 nchunk=1 merge=0"
+    assert "Q" not in lines(run(program, *args("f", 2, 31, 1024, -1))) and "Q" not in lines(run(program, *args("d", 24, 32, 32, 3)))
