@@ -6,7 +6,7 @@
 // Everything numerical (msckf.h:101-212, 336-449, 905-1423) runs in the HIP kernels of kernels_*.hip; there
 // is no CPU fallback: if no HIP device is usable msckf_hip_create fails.
 // A handle is a BatchCore -- everything that is the same for float and double: streams, staging, the frame loops run_frames /
-// run_frames_streamed, the work-list rules BatchCore::check_worklist -- with the typed half Batch<S> on top: the device
+// run_frames_streamed -- with the typed half Batch<S> on top: the device
 // buffers, the launches, the conversions between S and double.  What one frame of a scenario enqueues is
 // Batch<S>::enqueue_frame; the per-filter entries are the range entries with nb = 1.
 #include <hip/hip_runtime.h>
@@ -34,6 +34,7 @@
 #include "../../include/msckf_hip.h"
 #include "dev_common.h"
 #include "host_lists.h"
+#include "input_layouts.h"
 #include "settings.h"
 #include "slice_policy.h"
 
@@ -41,6 +42,8 @@ namespace {
 using namespace msckf;
 using namespace msckf_lists;
 using msckf_settings::Settings;
+namespace inputs = msckf_inputs;
+static_assert(inputs::RD_ROW == RD_STRIDE && inputs::NO_IMAGE == IMU_SKIP, "input_layouts.h restates the reading's stride and the skipped cell's count");
 static_assert(TRK_MOTION_OK == ST_MOTION_OK && TRK_TRI_VALID == ST_TRI_VALID && TRK_MOTION_SKIPPED == ST_MOTION_SKIPPED, "host_lists.h reads the feature kernel's status bits");
 
 // rocTX ranges under the reference's stage names (asl_msckf.cpp:229-296: imu_prop, msckf_augment_state, msckf_update,
@@ -154,9 +157,8 @@ struct BatchCore {
   static constexpr int NSTG = 8;
   unsigned char* h_stage[NSTG] = {nullptr}; size_t h_stage_bytes[NSTG] = {0}; hipEvent_t ev_stage[NSTG] = {nullptr}; bool stage_busy[NSTG] = {false};
   int stage_cur = 0;
-  // host mirror of ncam[] (every call that changes the window size updates it) and, per scenario cell, the largest camera
-  // slot its work-list touches: run_frames overlaps k_feature with propagate + augment when no track sees the newest camera
-  std::vector<int> h_ncam, h_maxslot;
+  // host mirror of ncam[] (every call that changes the window size updates it)
+  std::vector<int> h_ncam;
   hipStream_t sty[MAXS] = {nullptr}; hipEvent_t ev_fa[MAXS] = {nullptr}, ev_fb[MAXS] = {nullptr};
   // every tunable of the handle (settings.h: defaults, environment variables, what a copy takes over); the typed half's
   // apply_settings() carries them into the kernel argument
@@ -178,31 +180,23 @@ struct BatchCore {
   int* dv_ncam = nullptr; long long* dv_nres = nullptr; int* dv_stats = nullptr;
   int rd_cap = 0;   // samples per trajectory that the single-call staging of propagate holds
   void* h_rb = nullptr;   // page-locked landing area of the single-filter state read (get_cams_known): [n_cap][CAM_STRIDE] + [IMU_STRIDE] scalars
-  // single-call work-lists: per trajectory ONE block of ints [n, 0, 0, 0 | M[f4] | slots[f_cap][m_cap]] (wl_ib ints; one copy per
-  // set_tracks instead of three) and the observations [2 wl_ib] (the kernels index both with the same stride)
-  int* wl_i = nullptr; long wl_ib = 0; int wl_f4 = 0;
-  // scenario.  Work-lists are COMPACT: a cell (frame, trajectory) holds sum M_j (slot, observation) entries, track t of the
-  // cell starts at off[cell][t] counted from the frame's first entry (Dev::trk_off) -- not [f_cap][m_cap] padded rows (1.9x
-  // the payload at cfg3's track lengths, on the host, in HBM and in every per-frame upload).
-  // h_rd / sc_rd ([frames][B][K][RD_STRIDE]) and c_obs / sc_obs (coordinate pairs) hold scalars of esz bytes.
-  // h_k / sc_k: per cell its own number of IMU samples (0 .. sc_K; the rows beyond it are padding that nothing reads), or
-  // IMU_SKIP: the trajectory has no image on that frame (k_propagate's cnt)
-  int sc_frames = 0, sc_K = 0;
+  // single-call work-lists (input_layouts.h, SingleBlock): per trajectory wl_blk.ib ints on the device, the typed half's
+  // coordinates beside them
+  inputs::SingleBlock wl_blk; int* wl_i = nullptr;
+  // scenario (input_layouts.h): the staged cells and the frame index on the host (sc; sc.frames == 0: none), and the resident
+  // copy a commit makes of them, one device array per section (SECTIONS), sc_total entries in the two variable ones
+  inputs::ScenarioStore sc;
   bool committed = false;
-  unsigned char* sc_rd = nullptr; int* sc_n = nullptr; int* sc_M = nullptr; int* sc_off = nullptr; int* sc_drop = nullptr; int* sc_k = nullptr;
-  int* sc_slots = nullptr; unsigned char* sc_obs = nullptr; size_t sc_total = 0;      // sum over all cells
-  std::vector<unsigned char> h_rd; std::vector<int> h_n, h_M, h_off, h_drop, h_k;
-  std::vector<std::vector<int>> c_slots; std::vector<std::vector<unsigned char>> c_obs;   // per cell
-  std::vector<size_t> fr_base;                                             // [frames + 1] first entry of a frame in sc_slots / sc_obs
+  unsigned char* sc_dev[inputs::N_SECTIONS] = {nullptr}; size_t sc_total = 0;
   std::vector<void*> sc_allocs;
-  // streamed inputs (run_frames_streamed): frame f's block [rd | n | drop | k | M | off | slots | obs] is copied from page-locked
+  // streamed inputs (run_frames_streamed): frame f's block (input_layouts.h, FrameLayout) is copied from page-locked
   // host memory into one of `ring` device staging sets on a copy stream, `ring` - 1 frames ahead of the kernels that read it.
   // Page-locked blocks are built on demand (scen_pin, or the first streamed run over a frame), only for frames that are
   // streamed: a run_frames-only user never pays for them.
   static constexpr int RING_MAX = 8;
   hipStream_t stc = nullptr; hipEvent_t ev_up[RING_MAX] = {nullptr}; hipEvent_t ev_use[RING_MAX][MAXS] = {{nullptr}};
   unsigned char* sg_blk[RING_MAX] = {nullptr}; size_t sg_bytes = 0;
-  struct PinFrame { unsigned char* p = nullptr; size_t bytes = 0, off_obs = 0; int chunk = -1; };
+  struct PinFrame { unsigned char* p = nullptr; size_t bytes = 0; int chunk = -1; };
   struct PinChunk { void* p = nullptr; int live = 0; };   // page-locked block of several frames; freed when its last frame is invalidated
   std::vector<PinFrame> pinf; std::vector<PinChunk> pin_chunks;
   void unpin_frame(int f) {
@@ -219,7 +213,6 @@ struct BatchCore {
     pin_chunks.clear();
     for (auto& pf : pinf) pf = PinFrame();
   }
-  size_t pk_rd = 0, pk_n = 0, pk_drop = 0, pk_k = 0, pk_M = 0, pk_off = 0, pk_slots = 0;   // section offsets (256-byte aligned); obs follows the frame's slots
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
   // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
@@ -361,7 +354,6 @@ struct BatchCore {
     HIPCHK(hipStreamSynchronize(st));
     return 0;
   }
-  static size_t al256(size_t x) { return (x + 255) / 256 * 256; }   // sections of a streamed frame block
   // ---- profiling helpers
   void stage_begin(int s, hipStream_t q) {
     if (!prof) return;
@@ -377,23 +369,10 @@ struct BatchCore {
     ev_used[s]++;
   }
 
-  // a track observes a camera at most once (the kernels rely on it: slot -> observation map, contiguous-range test)
-  static bool repeated_slot(const int* s, int M) {
-    unsigned long long seen = 0;
-    for (int k = 0; k < M; ++k) { const unsigned long long bit = 1ull << (s[k] & 63); if (s[k] >= 0 && s[k] < 64 && (seen & bit)) return true; seen |= bit; }
-    return false;
-  }
-  // The rules for one trajectory's work-list (set_tracks, set_tracks_range, scenario_set), checked before anything of it is
-  // staged or written: the number of tracks, then every track's length, then track by track its slots' range and repetition
+  // the rules for one trajectory's work-list (input_layouts.h), checked before anything of it is staged or written
   int check_worklist(int F, const int* M, const int* slots) const {
-    if (F < 0 || F > f_cap) return fail(-E2BIG, "more tracks than f_cap");
-    for (int t = 0; t < F; ++t) if (M[t] > m_cap || M[t] < 0) return fail(-E2BIG, "track longer than m_cap");
-    size_t o = 0;
-    for (int t = 0; t < F; o += M[t++]) {
-      for (int k = 0; k < M[t]; ++k) if (slots[o + k] < 0 || slots[o + k] >= n_cap) return fail(-EINVAL, "camera slot out of range");
-      if (repeated_slot(slots + o, M[t])) return fail(-EINVAL, "camera slot repeated within a track");
-    }
-    return 0;
+    const inputs::Refusal r = inputs::worklist_refusal(F, M, slots, f_cap, m_cap, n_cap);
+    return r.code ? fail(r.code, r.why) : 0;
   }
   void invalidate_imu(int b0, int nb) { for (int b = b0; b < b0 + nb && b < B; ++b) h_imu_ok[b] = 0; }
   // Single-filter API (the shim's propagate(), one call per IMU sample, msckf.h:101): while the host copy of the IMU state is
@@ -406,7 +385,7 @@ struct BatchCore {
     const int b = pend_b; pend_b = -1;
     std::vector<double> rd; rd.swap(pend_rd);
     if (hipSetDevice(device) != hipSuccess) { h_imu_ok[b] = 0; return fail(-EIO, "hipSetDevice failed"); }
-    const int rc = propagate_device(b, 1, rd.data(), (int)(rd.size() / RD_STRIDE), then_augment);
+    const int rc = propagate_device(inputs::Readings(rd.data(), 1, (int)(rd.size() / RD_STRIDE)), b, then_augment);
     if (rc) h_imu_ok[b] = 0;   // the samples are gone and the device never saw them: the host copy is ahead of the filter, drop it (getImuState() re-reads the device)
     return rc;
   }
@@ -422,7 +401,7 @@ struct BatchCore {
     }
     if (!(mirror && nb == 1)) invalidate_imu(b0, nb);
     if (int rc = enter()) return rc;
-    return propagate_device(b0, nb, rd, K);
+    return propagate_device(inputs::Readings(rd, nb, K), b0);
   }
   // propagate() with a sample count per trajectory: rd holds K[0] rows, then K[1] rows, ...
   int propagate_counts(int b0, int nb, const double* rd, const int* K) {
@@ -431,7 +410,7 @@ struct BatchCore {
     for (int i = 0; i < nb; ++i) if (K[i] < 0) return fail(-EINVAL, "negative sample count K[" + std::to_string(i) + "]");
     for (int i = 0; i < nb; ++i) if (K[i] > 0) invalidate_imu(b0 + i, 1);
     if (int rc = enter()) return rc;
-    return propagate_device_counts(b0, nb, rd, K);
+    return propagate_device(inputs::Readings(rd, nb, K), b0);
   }
   // ---- the device's integer arrays
   // last_stats of a marginalize() that had nothing to residualize (the reference returns early, msckf.h:337)
@@ -487,7 +466,8 @@ struct BatchCore {
       allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end());
     }
     sc_allocs.clear();
-    sc_rd = nullptr; sc_n = sc_M = sc_off = sc_drop = sc_k = sc_slots = nullptr; sc_obs = nullptr; sc_total = 0;
+    for (auto& p : sc_dev) p = nullptr;
+    sc_total = 0;
   }
   template <class T> int sc_dalloc(T** p, size_t count, size_t elem = sizeof(T)) {
     const size_t mark = allocs.size();
@@ -500,83 +480,46 @@ struct BatchCore {
     if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(st));
     free_scenario_device();
-    sc_frames = 0; committed = false;
+    committed = false;
     unpin_host();
-    const size_t Bz = B, FB = (size_t)n_frames * Bz;
-    h_rd.assign(FB * K * RD_STRIDE * esz, 0); h_n.assign(FB, 0); h_M.assign(FB * f_cap, 0); h_off.assign(FB * f_cap, 0);
-    h_drop.assign(FB, 0); h_k.assign(FB, K); h_maxslot.assign(FB, -1);
-    c_slots.assign(FB, std::vector<int>()); c_obs.assign(FB, std::vector<unsigned char>());
-    fr_base.assign((size_t)n_frames + 1, 0);
+    sc.reset(n_frames, B, K, f_cap, esz);
     pinf.assign((size_t)n_frames, PinFrame());
     int rc = 0;
-    rc |= sc_dalloc(&sc_rd, FB * K * RD_STRIDE, esz); rc |= sc_dalloc(&sc_n, h_n.size()); rc |= sc_dalloc(&sc_M, h_M.size());
-    rc |= sc_dalloc(&sc_off, h_off.size()); rc |= sc_dalloc(&sc_drop, h_drop.size()); rc |= sc_dalloc(&sc_k, h_k.size());
-    if (rc) return rc;
-    // fixed sections of a streamed frame block; the frame's slots start at pk_slots, its observations follow them
-    pk_rd = 0; pk_n = al256(pk_rd + Bz * K * RD_STRIDE * esz); pk_drop = al256(pk_n + Bz * sizeof(int));
-    pk_k = al256(pk_drop + Bz * sizeof(int)); pk_M = al256(pk_k + Bz * sizeof(int)); pk_off = al256(pk_M + Bz * f_cap * sizeof(int)); pk_slots = al256(pk_off + Bz * f_cap * sizeof(int));
-    sc_frames = n_frames; sc_K = K;
-    return 0;
-  }
-  // the compact cells of frame f, trajectory after trajectory, as one contiguous block: slots to hs, coordinates to ho
-  void gather_frame(int f, int* hs, unsigned char* ho) const {
-    size_t o = 0;
-    for (int b = 0; b < B; ++b) {
-      const size_t cell = (size_t)f * B + b, n = c_slots[cell].size();
-      if (n) { std::memcpy(hs + o, c_slots[cell].data(), n * sizeof(int)); std::memcpy(ho + 2 * o * esz, c_obs[cell].data(), 2 * n * esz); }
-      o += n;
-    }
+    for (int s = 0; s < inputs::N_FIXED; ++s) rc |= sc_dalloc(&sc_dev[s], sc.fixed[s].size(), 1);
+    if (rc) sc.frames = 0;
+    return rc;
   }
   // H2D of everything staged.  The host copy is kept, so cells may be patched with scenario_set and committed again.
   int scen_commit() {
-    if (sc_frames <= 0) return fail(-EINVAL, "no scenario allocated");
+    using namespace inputs;
+    if (sc.frames <= 0) return fail(-EINVAL, "no scenario allocated");
     if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(st));
-    const size_t Bz = B;
-    size_t total = 0;
-    for (int f = 0; f < sc_frames; ++f) {
-      fr_base[f] = total;
-      size_t in_frame = 0;
-      for (size_t b = 0; b < Bz; ++b) {
-        const size_t cell = (size_t)f * Bz + b;
-        size_t o = in_frame;
-        for (int t = 0; t < f_cap; ++t) { h_off[cell * f_cap + t] = (int)o; o += h_M[cell * f_cap + t]; }
-        in_frame += c_slots[cell].size();
+    if (!sc.index()) return fail(-E2BIG, "a frame's work-lists exceed 2^31 observations");
+    const size_t total = sc.total(), per_entry = sc.lay.entry_bytes(SEC_SLOTS) + sc.lay.entry_bytes(SEC_OBS);
+    if (total != sc_total || !sc_dev[SEC_SLOTS]) {          // patched cells may have changed the compact size
+      int rc = 0;
+      for (int s = N_FIXED; s < N_SECTIONS; ++s) {
+        if (void* q = sc_dev[s]) { hipFree(q); allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end()); sc_allocs.erase(std::remove(sc_allocs.begin(), sc_allocs.end(), q), sc_allocs.end()); }
+        sc_dev[s] = nullptr;
       }
-      if (in_frame > 0x7fffffffu) return fail(-E2BIG, "a frame's work-lists exceed 2^31 observations");
-      total += in_frame;
-    }
-    fr_base[sc_frames] = total;
-    if (total != sc_total || !sc_slots) {          // patched cells may have changed the compact size
-      for (void* q : {(void*)sc_slots, (void*)sc_obs})
-        if (q) { hipFree(q); allocs.erase(std::remove(allocs.begin(), allocs.end(), q), allocs.end()); sc_allocs.erase(std::remove(sc_allocs.begin(), sc_allocs.end(), q), sc_allocs.end()); }
-      sc_slots = nullptr; sc_obs = nullptr;
-      int rc = sc_dalloc(&sc_slots, total); rc |= sc_dalloc(&sc_obs, 2 * total, esz);
+      for (int s = N_FIXED; s < N_SECTIONS; ++s) rc |= sc_dalloc(&sc_dev[s], total, sc.lay.entry_bytes(s));
       if (rc) return rc;
       sc_total = total;
     }
-    HIPCHK(hipMemcpyAsync(sc_rd, h_rd.data(), h_rd.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_n, h_n.data(), h_n.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_M, h_M.data(), h_M.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_off, h_off.data(), h_off.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_drop, h_drop.data(), h_drop.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(sc_k, h_k.data(), h_k.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    {   // size the pinned staging ring once, for the largest frame
-      size_t mx = 0;
-      for (int f = 0; f < sc_frames; ++f) mx = std::max(mx, fr_base[f + 1] - fr_base[f]);
-      const int rc = stage_reserve(mx * (sizeof(int) + 2 * esz));
-      if (rc) return rc;
-    }
-    for (int f = 0; f < sc_frames; ++f) {            // one frame at a time through the pinned staging area (bounded host memory)
-      const size_t nf = fr_base[f + 1] - fr_base[f];
+    for (int s = 0; s < N_FIXED; ++s) HIPCHK(hipMemcpyAsync(sc_dev[s], sc.fixed[s].data(), sc.fixed[s].size(), hipMemcpyHostToDevice, st));
+    if (int rc = stage_reserve(sc.largest_frame() * per_entry)) return rc;   // the pinned staging ring once, for the largest frame
+    for (int f = 0; f < sc.frames; ++f) {            // one frame at a time through the pinned staging area (bounded host memory)
+      const size_t nf = sc.entries(f);
       if (!nf) continue;
       unsigned char* raw = nullptr;
-      int rc = stage_acquire(nf * (sizeof(int) + 2 * esz), &raw);
+      int rc = stage_acquire(nf * per_entry, &raw);
       if (rc) return rc;
-      int* hs = reinterpret_cast<int*>(raw); unsigned char* ho = raw + nf * sizeof(int);
-      gather_frame(f, hs, ho);
-      HIPCHK(hipMemcpyAsync(sc_slots + fr_base[f], hs, nf * sizeof(int), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(sc_obs + 2 * fr_base[f] * esz, ho, 2 * nf * esz, hipMemcpyHostToDevice, st));
+      unsigned char* h[N_SECTIONS] = {nullptr};
+      h[SEC_SLOTS] = raw; h[SEC_OBS] = raw + nf * sc.lay.entry_bytes(SEC_SLOTS);
+      sc.gather(f, reinterpret_cast<int*>(h[SEC_SLOTS]), h[SEC_OBS]);
+      for (int s = N_FIXED; s < N_SECTIONS; ++s)
+        HIPCHK(hipMemcpyAsync(sc_dev[s] + sc.lay.resident_at(s, f, sc.fr_base[f]), h[s], nf * sc.lay.entry_bytes(s), hipMemcpyHostToDevice, st));
       rc = stage_release();
       if (rc) return rc;
     }
@@ -587,18 +530,16 @@ struct BatchCore {
   // page-locked per-frame blocks for run_frames_streamed, frames [f0, f1) that do not have one yet; also sizes the device
   // staging ring.  Called by run_frames_streamed itself; call it beforehand to keep the pinning out of a timed region.
   int scen_pin(int f0, int f1) {
-    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (f0 < 0 || f1 > sc.frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = enter()) return rc;
-    const size_t Bz = B;
     size_t need = 0, maxb = sg_bytes;
     std::vector<int> todo;
     for (int f = f0; f < f1; ++f) {
-      const size_t nf = fr_base[f + 1] - fr_base[f];
-      const size_t off_obs = al256(pk_slots + nf * sizeof(int)), bytes = al256(off_obs + 2 * nf * esz);
+      const size_t bytes = sc.lay.bytes(sc.entries(f));
       maxb = std::max(maxb, bytes);
       if (pinf[f].p) continue;
-      pinf[f].bytes = bytes; pinf[f].off_obs = off_obs;
+      pinf[f].bytes = bytes;
       need += bytes; todo.push_back(f);
     }
     if (!todo.empty()) {
@@ -614,14 +555,7 @@ struct BatchCore {
       size_t o = 0;
       for (int f : todo) {
         unsigned char* blk = chunk + o;
-        const size_t c0 = (size_t)f * Bz;
-        std::memcpy(blk + pk_rd, h_rd.data() + c0 * sc_K * RD_STRIDE * esz, Bz * sc_K * RD_STRIDE * esz);
-        std::memcpy(blk + pk_n, h_n.data() + c0, Bz * sizeof(int));
-        std::memcpy(blk + pk_drop, h_drop.data() + c0, Bz * sizeof(int));
-        std::memcpy(blk + pk_k, h_k.data() + c0, Bz * sizeof(int));
-        std::memcpy(blk + pk_M, h_M.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
-        std::memcpy(blk + pk_off, h_off.data() + c0 * f_cap, Bz * f_cap * sizeof(int));
-        gather_frame(f, reinterpret_cast<int*>(blk + pk_slots), blk + pinf[f].off_obs);
+        sc.write_block(f, blk);
         pinf[f].p = blk; pinf[f].chunk = ci;
         o += pinf[f].bytes;
       }
@@ -862,7 +796,7 @@ struct BatchCore {
   int pruned_log_counts(int b0, int nb, int* stored, int* found) { return cursor_log_counts(prn, b0, nb, stored, found); }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
-    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (f0 < 0 || f1 > sc.frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = reserve_logs(f0, f1)) return rc;
     if (int rc = enter()) return rc;
@@ -893,7 +827,7 @@ struct BatchCore {
   // the device-side hipStreamWaitEvent protocol, for comparison.
   int run_frames_streamed(int f0, int f1) {
     if (int rc = guard()) return rc;
-    if (f0 < 0 || f1 > sc_frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
+    if (f0 < 0 || f1 > sc.frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
     if (!committed) return fail(-EINVAL, "scenario not committed");
     if (int rc = reserve_logs(f0, f1)) return rc;
     if (int rc = enter()) return rc;
@@ -1029,8 +963,7 @@ struct BatchCore {
   virtual int init_core(int b, const double* cam, const double* noise, const double* q78, const double* P0, const double* params, const double* imu) = 0;
   virtual int init_full(int b, const double* cam, const double* uv2, const double* Q144, const double* P0_225, const double* params, const double* imu) = 0;
   virtual void mirror_advance(int b, const double* rd, int K) = 0;   // propagate()'s K samples on the host copy of the IMU state
-  virtual int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment = false) = 0;
-  virtual int propagate_device_counts(int b0, int nb, const double* rd, const int* K) = 0;
+  virtual int propagate_device(const inputs::Readings& in, int b0, bool then_augment = false) = 0;   // in.nb trajectories from b0 on
   virtual int augment(int b0, int nb) = 0;
   virtual int set_tracks(int b, int F, const int* M, const int* slots, const double* obs) = 0;
   virtual int marginalize(int b0, int nb, int mode = 0) = 0;   // mode 1: the second update of pruneRedundantStates (stored p_f_G per track, set_given_range)
@@ -1095,7 +1028,7 @@ struct Batch : BatchCore {
   S* d_rd = nullptr;                                // [B][rd_cap][7]
   int* d_cnt = nullptr;                             // [B] sample counts of a propagate_range_counts chunk
   S* d_pfin = nullptr;                              // [B][f_cap][4] stored feature positions (mode 1)
-  S* wl_obs = nullptr;         // the observations of the single-call work-lists: [B][2 wl_ib], beside the core's wl_i
+  S* wl_obs = nullptr;         // the coordinates of the single-call work-lists: [B][2 wl_blk.ib], beside the core's wl_i
 
   int alloc() override {
     h_imu.assign((size_t)B * IMU_STRIDE, S(0));
@@ -1141,8 +1074,8 @@ struct Batch : BatchCore {
     rd_cap = 64;
     rc |= dalloc(&d_rd, Bz * rd_cap * RD_STRIDE); rc |= dalloc(&d_cnt, Bz);
     HIPCHK(hipHostMalloc(&h_rb, ((size_t)n_cap * CAM_STRIDE + IMU_STRIDE) * sizeof(S), hipHostMallocDefault));
-    wl_f4 = (f_cap + 3) & ~3; wl_ib = (4 + wl_f4 + (long)f_cap * m_cap + 3) & ~3L;
-    rc |= dalloc(&wl_i, Bz * wl_ib); rc |= dalloc(&wl_obs, Bz * wl_ib * 2);
+    wl_blk = inputs::SingleBlock(f_cap, m_cap);
+    rc |= dalloc(&wl_i, Bz * wl_blk.ib); rc |= dalloc(&wl_obs, Bz * wl_blk.ib * 2);
     dv_ncam = d.ncam; dv_nres = d.n_resid; dv_stats = d.stats; info_form = d.trk_B != nullptr;
     if (rc) return rc;
     use_single_worklists();
@@ -1158,8 +1091,8 @@ struct Batch : BatchCore {
     small_limit = routes::small_limit(s.small_update, f_cap, sizeof(S), update_small_granted());
   }
   void use_single_worklists() {
-    d.trk_n = wl_i; d.trk_M = wl_i + 4; d.trk_slots = wl_i + 4 + wl_f4; d.trk_obs = wl_obs; d.trk_off = nullptr;
-    d.wl_stride_n = wl_ib; d.wl_stride_f = wl_ib; d.wl_stride_o = wl_ib;
+    d.trk_n = wl_i + wl_blk.N_AT; d.trk_M = wl_i + wl_blk.M_AT; d.trk_slots = wl_i + wl_blk.slots_at(); d.trk_obs = wl_obs; d.trk_off = nullptr;
+    d.wl_stride_n = wl_blk.ib; d.wl_stride_f = wl_blk.ib; d.wl_stride_o = wl_blk.ib;
   }
   // Dev view whose work-list pointers start at trajectory b0 (kernels index work-lists by b - b0)
   Dev<S> view(int b0) const {
@@ -1167,23 +1100,6 @@ struct Batch : BatchCore {
     v.trk_n += (long)b0 * d.wl_stride_n; v.trk_M += (long)b0 * d.wl_stride_f;
     v.trk_slots += (long)b0 * d.wl_stride_o; v.trk_obs += 2 * (long)b0 * d.wl_stride_o;
     return v;
-  }
-  // the device's padded single-call layout of one work-list, the F rows in use (all that is written): I = [F, 0, 0, 0 | M[f4] |
-  // F rows of m_cap slots], O = F rows of m_cap coordinate pairs
-  void pack_worklist(int* I, S* O, int F, const int* M, const int* slots, const double* obs) const {
-    std::memset(I, 0, (4 + (size_t)wl_f4 + (size_t)F * m_cap) * sizeof(int));
-    std::memset(O, 0, (size_t)F * m_cap * 2 * sizeof(S));
-    I[0] = F;
-    int* hM = I + 4; int* hS = I + 4 + wl_f4;
-    size_t o = 0;
-    for (int t = 0; t < F; o += M[t++]) {
-      hM[t] = M[t];
-      for (int k = 0; k < M[t]; ++k) {
-        hS[(size_t)t * m_cap + k] = slots[o + k];
-        O[((size_t)t * m_cap + k) * 2] = (S)obs[2 * (o + k)];
-        O[((size_t)t * m_cap + k) * 2 + 1] = (S)obs[2 * (o + k) + 1];
-      }
-    }
   }
 
   // The five derived noise parameters PRM_WU .. PRM_LIT of trajectory b for the batch's anisotropic-noise mode
@@ -1312,7 +1228,7 @@ struct Batch : BatchCore {
     h_ncam[b] = 0;
     HIPCHK(hipMemsetAsync(d.n_resid + b, 0, sizeof(long long), st));
     HIPCHK(hipMemsetAsync(d.stats + (size_t)b * STAT_STRIDE, 0, sizeof(int) * STAT_STRIDE, st));
-    HIPCHK(hipMemsetAsync(wl_i + (size_t)b * wl_ib, 0, sizeof(int), st));
+    HIPCHK(hipMemsetAsync(wl_i + (size_t)b * wl_blk.ib + wl_blk.N_AT, 0, sizeof(int), st));
     HIPCHK(hipStreamSynchronize(st));
     HostTraj& t = traj[b];
     t = HostTraj();
@@ -1365,49 +1281,22 @@ struct Batch : BatchCore {
     for (int k = 0; k < K; ++k) host_rk(h_imu.data() + (size_t)b * IMU_STRIDE, rd + (size_t)k * RD_STRIDE);
   }
   // then_augment: augmentState follows for the same trajectories -- k_propagate's fused variant on the last chunk (as run_frames)
-  int propagate_device(int b0, int nb, const double* rd, int K, bool then_augment) override {
-    for (int k0 = 0; k0 < K; k0 += rd_cap) {
-      const int kk = std::min(rd_cap, K - k0);
-      const size_t cnt = (size_t)nb * kk * RD_STRIDE;
+  // With a count per trajectory (in.Kb) a trajectory that has run out has none in the later chunks: k_propagate leaves it alone
+  int propagate_device(const inputs::Readings& in, int b0, bool then_augment) override {
+    const int nb = in.nb;
+    for (int k0 = 0; k0 < in.kmax; k0 += rd_cap) {
+      const int kk = in.rows(k0, rd_cap);
       unsigned char* raw = nullptr;
-      int rc = stage_acquire(cnt * sizeof(S), &raw);
+      int rc = stage_acquire(in.staged_bytes(kk, sizeof(S)), &raw);
       if (rc) return rc;
-      S* tmp = reinterpret_cast<S*>(raw);
-      for (int i = 0; i < nb; ++i)
-        for (int k = 0; k < kk; ++k)
-          for (int c = 0; c < RD_STRIDE; ++c) tmp[((size_t)i * kk + k) * RD_STRIDE + c] = (S)rd[((size_t)i * K + k0 + k) * RD_STRIDE + c];
-      HIPCHK(hipMemcpyAsync(d_rd, tmp, cnt * sizeof(S), hipMemcpyHostToDevice, st));
+      S* tmp = reinterpret_cast<S*>(raw); int* hc = reinterpret_cast<int*>(raw + in.counts_at(kk, sizeof(S)));
+      in.pack(tmp, hc, k0, kk, rd_cap);
+      HIPCHK(hipMemcpyAsync(d_rd, tmp, in.scalars(kk) * sizeof(S), hipMemcpyHostToDevice, st));
+      if (in.Kb) HIPCHK(hipMemcpyAsync(d_cnt, hc, nb * sizeof(int), hipMemcpyHostToDevice, st));
       rc = stage_release();
       if (rc) return rc;
-      launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, then_augment && k0 + kk >= K, qroute(b0, nb));
-      HIPCHK(hipGetLastError());
-    }
-    return 0;
-  }
-  // The rd_cap-sample staging chunks are cut per trajectory: in chunk c trajectory i has clamp(K[i] - rd_cap c, 0, rd_cap) samples --
-  // the chunks of its own propagate_device(b0 + i, 1, ., K[i]), so the same launches see the same samples -- and none once it
-  // has run out (k_propagate leaves a trajectory with no samples alone).  Rows padded to the chunk's longest trajectory.
-  int propagate_device_counts(int b0, int nb, const double* rd, const int* K) override {
-    int kmax = 0;
-    std::vector<size_t> row0(nb);                     // trajectory i's first row in rd
-    { size_t o = 0; for (int i = 0; i < nb; ++i) { row0[i] = o; o += K[i]; kmax = std::max(kmax, K[i]); } }
-    for (int k0 = 0; k0 < kmax; k0 += rd_cap) {
-      const int kk = std::min(rd_cap, kmax - k0);
-      const size_t cnt = (size_t)nb * kk * RD_STRIDE, off_c = (cnt * sizeof(S) + 15) / 16 * 16;
-      unsigned char* raw = nullptr;
-      int rc = stage_acquire(off_c + nb * sizeof(int), &raw);
-      if (rc) return rc;
-      S* tmp = reinterpret_cast<S*>(raw); int* hc = reinterpret_cast<int*>(raw + off_c);
-      for (int i = 0; i < nb; ++i) {
-        hc[i] = std::max(0, std::min(K[i] - k0, rd_cap));
-        for (int k = 0; k < kk; ++k)
-          for (int c = 0; c < RD_STRIDE; ++c) tmp[((size_t)i * kk + k) * RD_STRIDE + c] = k < hc[i] ? (S)rd[(row0[i] + k0 + k) * RD_STRIDE + c] : S(0);
-      }
-      HIPCHK(hipMemcpyAsync(d_rd, tmp, cnt * sizeof(S), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_cnt, hc, nb * sizeof(int), hipMemcpyHostToDevice, st));
-      rc = stage_release();
-      if (rc) return rc;
-      launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, false, qroute(b0, nb), d_cnt);
+      if (in.Kb) launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, false, qroute(b0, nb), d_cnt);
+      else launch_propagate<S>(d, b0, nb, d_rd, (long)kk * RD_STRIDE, kk, st, then_augment && k0 + kk >= in.K, qroute(b0, nb));
       HIPCHK(hipGetLastError());
     }
     return 0;
@@ -1432,17 +1321,16 @@ struct Batch : BatchCore {
     int rc = check_worklist(F, M, slots);
     if (rc) return rc;
     if (int rc = enter()) return rc;
-    // only the F rows in use travel, as the device holds them: [n, 0, 0, 0 | M[f4] | F rows of slots] in one copy, F rows of
-    // coordinates in a second one, both out of one pinned block
-    const size_t nI = 4 + (size_t)wl_f4 + (size_t)F * m_cap, nO = (size_t)F * m_cap * 2;
-    const size_t offO = ((nI * sizeof(int) + 15) / 16) * 16;
+    // only the F rows in use travel, as the device holds them: the ints in one copy, the coordinates in a second one, both out
+    // of one pinned block
+    const size_t nI = wl_blk.ints(F), nO = wl_blk.scalars(F);
     unsigned char* raw = nullptr;
-    rc = stage_acquire(offO + nO * sizeof(S) + 16, &raw);
+    rc = stage_acquire(wl_blk.staged_bytes(nI, nO, sizeof(S)), &raw);
     if (rc) return rc;
-    int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + offO);
-    pack_worklist(hI, hO, F, M, slots, obs);
-    HIPCHK(hipMemcpyAsync(wl_i + (size_t)b * wl_ib, hI, (F ? nI : 4) * sizeof(int), hipMemcpyHostToDevice, st));
-    if (F) HIPCHK(hipMemcpyAsync(wl_obs + (size_t)b * wl_ib * 2, hO, nO * sizeof(S), hipMemcpyHostToDevice, st));
+    int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + wl_blk.coords_at(nI));
+    wl_blk.pack(hI, hO, F, M, slots, obs);
+    HIPCHK(hipMemcpyAsync(wl_i + (size_t)b * wl_blk.ib, hI, (F ? nI : (size_t)wl_blk.M_AT) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (F) HIPCHK(hipMemcpyAsync(wl_obs + (size_t)b * wl_blk.ib * 2, hO, nO * sizeof(S), hipMemcpyHostToDevice, st));
     rc = stage_release();
     if (rc) return rc;
     traj[b].wl_F = F;
@@ -1452,20 +1340,19 @@ struct Batch : BatchCore {
     if (chk_range(b0, nb) || (int)wl.size() != nb) return fail(-EINVAL, "trajectory range out of bounds");
     for (int i = 0; i < nb; ++i) { const int rc = check_worklist((int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data()); if (rc) return rc; }
     if (int rc = enter()) return rc;
-    // the device's padded single-call layout for the whole range: [nb][wl_ib] ints ([n, 0, 0, 0 | M[f4] | f_cap rows of slots]) and
-    // [nb][wl_ib * 2] coordinates, out of one pinned block, two copies
-    const size_t nI = (size_t)nb * wl_ib, nO = (size_t)nb * wl_ib * 2;
-    const size_t offO = ((nI * sizeof(int) + 15) / 16) * 16;
+    // the device's padded single-call layout for the whole range: nb whole blocks of ints and of coordinates, out of one
+    // pinned block, two copies
+    const size_t nI = (size_t)nb * wl_blk.ib, nO = (size_t)nb * wl_blk.ib * 2;
     unsigned char* raw = nullptr;
-    int rc = stage_acquire(offO + nO * sizeof(S) + 16, &raw);
+    int rc = stage_acquire(wl_blk.staged_bytes(nI, nO, sizeof(S)), &raw);
     if (rc) return rc;
-    int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + offO);
+    int* hI = reinterpret_cast<int*>(raw); S* hO = reinterpret_cast<S*>(raw + wl_blk.coords_at(nI));
     parallel_for(nb, [&](int i) {
-      pack_worklist(hI + (size_t)i * wl_ib, hO + (size_t)i * wl_ib * 2, (int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data(), wl[i].obs.data());
+      wl_blk.pack(hI + (size_t)i * wl_blk.ib, hO + (size_t)i * wl_blk.ib * 2, (int)wl[i].M.size(), wl[i].M.data(), wl[i].slots.data(), wl[i].obs.data());
       return 0;
     });
-    HIPCHK(hipMemcpyAsync(wl_i + (size_t)b0 * wl_ib, hI, nI * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(wl_obs + (size_t)b0 * wl_ib * 2, hO, nO * sizeof(S), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(wl_i + (size_t)b0 * wl_blk.ib, hI, nI * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(wl_obs + (size_t)b0 * wl_blk.ib * 2, hO, nO * sizeof(S), hipMemcpyHostToDevice, st));
     rc = stage_release();
     if (rc) return rc;
     for (int i = 0; i < nb; ++i) traj[b0 + i].wl_F = (int)wl[i].M.size();
@@ -1494,7 +1381,7 @@ struct Batch : BatchCore {
   // (LDS strides, and the column-segment width of chol(Lam^): 4 up to 63 columns, 8 beyond); neither changes the order of the
   // operations on any matrix element -- every element takes its rank-1 updates pivot by pivot whichever task holds it -- so the
   // bits are the trajectory's own (tests/test_gpu_ragged.py holds it: 5 .. 14 cameras alone and beside each other).
-  // cell_k (run_frames: the frame's h_k from b0 on): a skipped cell has no augmentState ahead.
+  // cell_k (run_frames: the frame's sample counts from b0 on): a skipped cell has no augmentState ahead.
   void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
@@ -1750,43 +1637,24 @@ struct Batch : BatchCore {
     return D;
   }
   int scen_set(int f, int b, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) override {
-    if (f < 0 || f >= sc_frames || chk(b)) return fail(-EINVAL, "scenario cell out of range");
+    if (f < 0 || f >= sc.frames || chk(b)) return fail(-EINVAL, "scenario cell out of range");
     { const int rc = check_worklist(F, M, slots); if (rc) return rc; }   // before the staged cell is touched
     if (n_drop < 0) return fail(-EINVAL, "negative n_drop");
-    if (const char* why = cell_refusal(k, sc_K, F, n_drop, flags)) return fail(-EINVAL, why);
+    if (const char* why = cell_refusal(k, sc.lay.K, F, n_drop, flags)) return fail(-EINVAL, why);
     if (k > 0 && !rd) return fail(-EINVAL, "null readings for a cell with samples");
-    const bool skip = (flags & CELL_SKIP) != 0;
-    const size_t cell = (size_t)f * B + b;
-    size_t tot = 0;
-    for (int t = 0; t < F; ++t) tot += M[t];
-    S* hr = reinterpret_cast<S*>(h_rd.data()) + cell * sc_K * RD_STRIDE;   // (the core stores the cell's scalars as bytes)
-    for (int s = 0; s < sc_K; ++s) for (int c = 0; c < RD_STRIDE; ++c) hr[s * RD_STRIDE + c] = s < k ? (S)rd[s * RD_STRIDE + c] : S(0);   // (padding beyond k: never read again)
-    h_n[cell] = F; h_drop[cell] = n_drop; h_k[cell] = skip ? IMU_SKIP : k;
-    for (int t = 0; t < f_cap; ++t) h_M[cell * f_cap + t] = t < F ? M[t] : 0;
-    c_slots[cell].assign(slots, slots + tot);
-    c_obs[cell].resize(2 * tot * sizeof(S));
-    S* co = reinterpret_cast<S*>(c_obs[cell].data());
-    int mx = -1;
-    for (size_t e = 0; e < tot; ++e) { mx = std::max(mx, slots[e]); co[2 * e] = (S)obs[2 * e]; co[2 * e + 1] = (S)obs[2 * e + 1]; }
-    h_maxslot[cell] = mx;
+    sc.set_cell<S>(f, b, rd, k, (flags & CELL_SKIP) != 0, F, M, slots, obs, n_drop);
     committed = false;               // offsets move: the resident copy and the frame's page-locked block are stale until the next commit
     unpin_frame(f);                  // (its chunk is released with the last of its frames: patch -> commit -> stream cycles do not grow)
     return 0;
   }
-  // where a frame's inputs are on the device, for a slice that starts at trajectory b0: per-trajectory arrays already offset
-  // to b0, slots / obs the frame's compact entries (tracks find theirs through off)
-  struct FrameIn { const S* rd; const int* n; const int* M; const int* off; const int* slots; const S* obs; const int* drop; const int* k; };
+  // a frame's inputs on the device for a slice that starts at trajectory b0 (input_layouts.h, frame_in): resident, or as
+  // uploaded into staging set k
+  using FrameIn = inputs::FrameIn<S>;
   FrameIn resident_frame(int f, int b0) const {
-    const size_t c = (size_t)f * B + b0;
-    return FrameIn{reinterpret_cast<const S*>(sc_rd) + c * sc_K * RD_STRIDE, sc_n + c, sc_M + c * f_cap, sc_off + c * f_cap, sc_slots + fr_base[f],
-                   reinterpret_cast<const S*>(sc_obs) + 2 * fr_base[f], sc_drop + c, sc_k + c};
+    return inputs::frame_in<S>(sc.lay, b0, [&](int s) { return sc_dev[s] + sc.lay.resident_at(s, f, sc.fr_base[f]); });
   }
-  FrameIn staged_frame(int f, int k, int b0) const {   // frame f as uploaded into staging set k
-    unsigned char* blk = sg_blk[k];
-    return FrameIn{reinterpret_cast<S*>(blk + pk_rd) + (size_t)b0 * sc_K * RD_STRIDE, reinterpret_cast<int*>(blk + pk_n) + b0,
-                   reinterpret_cast<int*>(blk + pk_M) + (size_t)b0 * f_cap, reinterpret_cast<int*>(blk + pk_off) + (size_t)b0 * f_cap,
-                   reinterpret_cast<int*>(blk + pk_slots), reinterpret_cast<S*>(blk + pinf[f].off_obs), reinterpret_cast<int*>(blk + pk_drop) + b0,
-                   reinterpret_cast<int*>(blk + pk_k) + b0};
+  FrameIn staged_frame(int f, int k, int b0) const {
+    return inputs::frame_in<S>(sc.lay, b0, [&](int s) { return sg_blk[k] + sc.lay.block_at(s, sc.entries(f)); });
   }
   // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged` or (staged < 0) resident --
   // propagate + augmentState, the update, the prune (on the downdate or with its own launch, fuse_frame), the host mirror of
@@ -1801,6 +1669,7 @@ struct Batch : BatchCore {
     const bool may_overlap = staged < 0;
     hipStream_t q = s.q;
     const size_t cell0 = (size_t)f * B;
+    const int* cell_k = sc.ints(inputs::SEC_K) + cell0; const int* cell_drop = sc.ints(inputs::SEC_DROP) + cell0;   // the host's copy of the frame's cells
     Dev<S> v = d;
     v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
@@ -1810,7 +1679,7 @@ struct Batch : BatchCore {
     for (int b = b0; b < b0 + nb && early; ++b) {
       const int n_after = std::min(h_ncam[b] + 1, n_cap);
       // (a skipped cell gets no camera state: the early k_feature's window size, ncam_upd = "after the next augment", would be one too many)
-      early = h_ncam[b] < n_cap && h_maxslot[cell0 + b] <= n_after - 2 && h_k[cell0 + b] != IMU_SKIP;
+      early = h_ncam[b] < n_cap && sc.maxslot[cell0 + b] <= n_after - 2 && cell_k[b] != IMU_SKIP;
     }
     if (early) {
       (void)hipEventRecord(ev_fa[hh], q);
@@ -1823,13 +1692,13 @@ struct Batch : BatchCore {
     // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
     {
       StageRange r("imu_prop+msckf_augment_state");
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc_K * RD_STRIDE, sc_K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc.lay.K * RD_STRIDE, sc.lay.K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
       if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q, in.k); stage_end(1, q); }
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
     v.ncam_defer = 0;
     if (fuse) { v.Pout = s.flipped ? d.P : P_spare; v.fuse_drop = in.drop; }
-    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1, h_k.data() + cell0 + b0); }
+    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1, cell_k + b0); }
     if (fuse) s.flipped = !s.flipped;
     else {
       // pruned-state log: the states this frame drops, as the update left them (v.P: in place), with frame ordinal
@@ -1848,9 +1717,9 @@ struct Batch : BatchCore {
     // map.ordinal(f, f0), behind the trajectories' cursors; also outside the stage timers
     if (map.buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map.ordinal(f, f0), map.cap, static_cast<S*>(map.buf), map.found);
     for (int b = b0; b < b0 + nb; ++b) {   // host mirror of the window size: augment (not for a skipped cell), then drop n_drop (clamped as k_make_keep does)
-      const bool augmented = h_ncam[b] < n_cap && h_k[cell0 + b] != IMU_SKIP;
+      const bool augmented = h_ncam[b] < n_cap && cell_k[b] != IMU_SKIP;
       if (augmented) h_ncam[b]++;
-      const int nd = std::max(0, std::min(h_drop[cell0 + b], h_ncam[b]));
+      const int nd = std::max(0, std::min(cell_drop[b], h_ncam[b]));
       h_ncam[b] -= nd;
       if (prn.buf) prn_list.mirror(b, augmented, nd, prn.ordinal(f, f0), prn.cap);
     }
@@ -2454,7 +2323,7 @@ int msckf_hip_drop_oldest_range(msckf_hip_handle h, int b0, int nb, int n_drop) 
 int msckf_hip_scenario_alloc(msckf_hip_handle h, int n_frames, int K) { return H(h)->scen_alloc(n_frames, K); }
 int msckf_hip_scenario_set(msckf_hip_handle h, int frame, int b, const double* readings7, int F, const int* M, const int* slots, const double* obs2, int n_drop) {
   if (!h) return fail(-EINVAL, "null handle");
-  return H(h)->scen_set(frame, b, readings7, H(h)->sc_K, F, M, slots, obs2, n_drop, 0);
+  return H(h)->scen_set(frame, b, readings7, H(h)->sc.lay.K, F, M, slots, obs2, n_drop, 0);
 }
 static_assert(MSCKF_HIP_CELL_SKIP == CELL_SKIP, "host_lists.h states the cell rule with the header's flag bit");
 int msckf_hip_scenario_set_cell(msckf_hip_handle h, int frame, int b, const double* readings7, int k, int F, const int* M, const int* slots, const double* obs2, int n_drop, int flags) {
