@@ -234,6 +234,40 @@ int msckf_hip_scenario_pin(msckf_hip_handle h, int f0, int f1);
  * uploading thread and the slices' enqueue threads on the HOST (no stream waits for another stream's event on the device),
  * mode 1 uses hipStreamWaitEvent hand-overs.  Same results. */
 int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode);
+/* ---- Monte-Carlo replay: shared noise-free sequences, per-trajectory seeded noise added on the device -------------- */
+/* n_seq SEQUENCES of n_frames cells are staged once (sequence values are kept as doubles); each of the handle's B trajectories
+ * then names a sequence, a 64-bit seed and four noise levels, and before each frame one kernel launch per slice expands the
+ * frame's sequence cells into the ordinary per-trajectory frame block -- what msckf_hip_run_frames_streamed would have
+ * uploaded -- so that B trajectories cost the host store, the page-locked memory and the PCIe traffic of none.
+ * The noise is a pure function of (seed, frame, index), no state is carried between frames:
+ *   mix(s, i)  = value i (0-based) of splitmix64 seeded s: z = s + (i + 1) 0x9E3779B97F4A7C15, z = (z ^ z >> 30) 0xBF58476D1CE4E5B9,
+ *                z = (z ^ z >> 27) 0x94D049BB133111EB, z ^ z >> 31, modulo 2^64;   U(s, i) = (mix(s, i) >> 11) 2^-53
+ *   pair(s, j) = (r cos(2 pi u2), r sin(2 pi u2)) with u1 = 1 - U(s, 2 j), u2 = U(s, 2 j + 1), r = sqrt(-2 ln u1)
+ *   trajectory b with seed s_b on frame f: s_imu = mix(s_b, 2 f), s_obs = mix(s_b, 2 f + 1)
+ *   IMU sample i < k of the cell takes pairs 3 i, 3 i + 1, 3 i + 2 of s_imu = (g_x, g_y), (g_z, a_x), (a_y, a_z):
+ *     omega += sigma_g g, a += sigma_a a; dT is unchanged; rows from k on are zero
+ *   entry e of the cell (its e-th (slot, observation) pair) takes pair e of s_obs: obs += (sigma_u n_u, sigma_v n_v)
+ * Sums are formed in double and rounded once to the handle's scalar.  msckf_mono_amd/scenario.py holds the numpy twin.
+ * Not provided: bias random walks (they need carried state) and correlated Q_imu noise.
+ * msckf_hip_replay_alloc replaces a previous replay; a scenario staged with msckf_hip_scenario_* is independent of it. */
+int msckf_hip_replay_alloc(msckf_hip_handle h, int n_seq, int n_frames, int K);
+/* one (frame, sequence) cell: arguments and rules of msckf_hip_scenario_set_cell; un-commits the replay */
+int msckf_hip_replay_set_cell(msckf_hip_handle h, int frame, int seq, const double* readings7 /*[k][7]*/, int k, int F,
+                              const int* M, const int* slots, const double* obs2, int n_drop, int flags);
+/* seq_of[B], seed[B], sigma4[B][4] = sigma_g sigma_a sigma_u sigma_v per trajectory.  -EINVAL for a seq_of outside
+ * [0, n_seq) or a sigma that is negative or not finite; the assignment made before stays.  May be called again between runs. */
+int msckf_hip_replay_assign(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* sigma4);
+int msckf_hip_replay_commit(msckf_hip_handle h);   /* H2D of the sequences staged */
+/* msckf_hip_run_frames over the frames [f0, f1) of the replay: same kernels, same slices, same logs; a frame's inputs are
+ * expanded on the slice's own stream ahead of its propagate.  -EINVAL "frame range out of bounds", "replay not committed",
+ * "replay not assigned", in this order. */
+int msckf_hip_run_frames_replay(msckf_hip_handle h, int f0, int f1);
+/* What the expansion kernel writes for trajectory b on `frame`, from a launch of the same kernel for that trajectory alone into
+ * scratch memory: rd [K][7] and the cell's coordinate pairs obs2 [entries][2] as doubles (exact: the handle's scalar widened);
+ * _ints: ints [3 + 2 f_cap] = n, drop, k, M[f_cap], off[f_cap] and slots [entries].  Returns the cell's entries; -E2BIG when
+ * they exceed cap_entries.  Nothing of the handle's filters, inputs or logs changes. */
+int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd /*[K][7]*/, double* obs2, int cap_entries);
+int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints, int* slots, int cap_entries);
 int msckf_hip_sync(msckf_hip_handle h);
 /* ---- per-frame device log of msckf_hip_run_frames / _streamed (off by default) ------------------------ */
 /* Storage for capacity_frames records ("frame log record" above) of every trajectory, in the handle's dtype; 0 frees the
@@ -331,7 +365,8 @@ int msckf_hip_profile_enable(msckf_hip_handle h, int on);
 int msckf_hip_profile_read(msckf_hip_handle h, double* ms8, int* count8);
 /* The same with the stages beyond the first eight (cap >= 8 entries are written, unknown ones as zero): 8 k_lit_pre, 9 k_lit_gamma,
  * 10 k_literal -- the three launches of the literal anisotropic compression (u_var' != v_var', msckf.h:423-431, 1343-1366;
- * kernels_literal.hip), which a profiled run brackets one by one (stage 3 is then k_gram alone). */
+ * kernels_literal.hip), which a profiled run brackets one by one (stage 3 is then k_gram alone); 11 k_replay_expand, the
+ * expansion launches of msckf_hip_run_frames_replay. */
 int msckf_hip_profile_read_ex(msckf_hip_handle h, double* ms, int* count, int cap);
 /* Milliseconds an event pair with nothing between its two records reads on the handle's stream (mean of 64 pairs): every
  * stage timer above brackets its launches with such a pair, so a single-kernel stage reads the kernel's duration plus

@@ -39,6 +39,8 @@ SYMBOLS = [
     "msckf_hip_scenario_set_cell", "msckf_hip_propagate_range_counts", "msckf_hip_frame_log_metrics_ranges",
     "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
     "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
+    "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
+    "msckf_hip_replay_expand_ints",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -128,6 +130,7 @@ def full_noise(cfg):
 
 class Batch:
     """A batch of B independent filters resident on one GPU."""
+    _replay_K = 0   # K of the last replay_alloc
 
     def __init__(self, B, n_cap, f_cap, m_cap, dtype=F32, device=0):
         self.L = lib()
@@ -350,6 +353,44 @@ class Batch:
         """run_frames with per-frame asynchronous H2D of the inputs (copy stream, ring of staging sets, compact work-lists)"""
         _chk(self.L.msckf_hip_run_frames_streamed(self.h, f0, f1))
 
+    # ---- Monte-Carlo replay: shared noise-free sequences, per-trajectory seeded noise added on the device
+    def replay_alloc(self, n_seq, n_frames, K):
+        """n_seq sequences of n_frames cells with up to K IMU samples each (replaces a previous replay)"""
+        _chk(self.L.msckf_hip_replay_alloc(self.h, int(n_seq), int(n_frames), int(K)))
+        self._replay_K = int(K)
+
+    def replay_set_cell(self, frame, seq, readings, M, slots, obs, n_drop, skip=False):
+        """one (frame, sequence) cell, noise-free: the arguments and rules of scenario_set"""
+        r, pr = _d(np.asarray(readings, dtype=np.float64).reshape(-1, 7)); Ma, pM = _i(M); s, ps = _i(slots); o, po = _d(obs)
+        _chk(self.L.msckf_hip_replay_set_cell(self.h, int(frame), int(seq), pr, r.shape[0], len(Ma), pM, ps, po, int(n_drop), CELL_SKIP if skip else 0))
+
+    def replay_assign(self, seq_of, seeds, sigma4):
+        """per trajectory its sequence, its 64-bit seed and (sigma_g, sigma_a, sigma_u, sigma_v); sigma4 [4] serves every
+        trajectory.  May be called again between runs."""
+        q, pq = _i(seq_of)
+        sd = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        sg = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma4, dtype=np.float64), (self.B, 4)))
+        if q.shape != (self.B,) or sd.shape != (self.B,):
+            raise ValueError("seq_of and seeds must hold one value per trajectory")
+        _chk(self.L.msckf_hip_replay_assign(self.h, pq, sd.ctypes.data_as(_up), sg.ctypes.data_as(_dp)))
+
+    def replay_commit(self):
+        _chk(self.L.msckf_hip_replay_commit(self.h))
+
+    def run_frames_replay(self, f0, f1):
+        """run_frames over the replay's frames [f0, f1): each frame's inputs are expanded from the sequences on the device"""
+        _chk(self.L.msckf_hip_run_frames_replay(self.h, int(f0), int(f1)))
+
+    def replay_expand(self, frame, b):
+        """what the expansion kernel writes for trajectory b on `frame` (a launch of the same kernel into scratch memory): dict of
+        rd [K][7], obs [entries][2] (the handle's scalars as doubles), n, drop, k, M [f_cap], off [f_cap], slots [entries]"""
+        cap = self.f_cap * self.m_cap
+        rd = np.zeros((self._replay_K, 7)); obs = np.zeros((cap, 2)); ints = np.zeros(3 + 2 * self.f_cap, dtype=np.int32); slots = np.zeros(cap, dtype=np.int32)
+        n = _chk(self.L.msckf_hip_replay_expand(self.h, int(frame), int(b), rd.ctypes.data_as(_dp), obs.ctypes.data_as(_dp), cap))
+        _chk(self.L.msckf_hip_replay_expand_ints(self.h, int(frame), int(b), ints.ctypes.data_as(_ip), slots.ctypes.data_as(_ip), cap))
+        return dict(rd=rd, obs=obs[:n], n=int(ints[0]), drop=int(ints[1]), k=int(ints[2]), M=ints[3:3 + self.f_cap].copy(),
+                    off=ints[3 + self.f_cap:].copy(), slots=slots[:n])
+
     def scenario_pin(self, f0, f1):
         """page-lock the per-frame blocks of frames [f0, f1) ahead of a streamed run (outside any timed region)"""
         _chk(self.L.msckf_hip_scenario_pin(self.h, int(f0), int(f1)))
@@ -553,7 +594,7 @@ class Batch:
     def profile_read(self):
         ms = np.zeros(16); cnt = np.zeros(16, dtype=np.int32)
         _chk(self.L.msckf_hip_profile_read_ex(self.h, ms.ctypes.data_as(_dp), cnt.ctypes.data_as(_ip), 16))
-        names = ["propagate", "augment", "feature", "compress_stage1", "compress_merge", "kalman", "prune", "select", "lit_pre", "lit_gamma", "literal"]
+        names = ["propagate", "augment", "feature", "compress_stage1", "compress_merge", "kalman", "prune", "select", "lit_pre", "lit_gamma", "literal", "replay_expand"]
         return {n: (float(m), int(c)) for n, m, c in zip(names, ms, cnt)}
 
 

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
+#include <cstdint>
 #include <type_traits>
 
 #include "update_routes.h"
@@ -551,6 +552,15 @@ template <class S> void launch_map_metrics(const S* rec, const int* found, int c
 // records with prune ordinal in [q0, q1) against ground-truth poses gt[n_ord][B][7], matched through aug[B][cap], into out[B][10]
 template <class S> void launch_pruned_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop, int ordinal, int cap, S* rec, int* found);
 template <class S> void launch_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out, hipStream_t st);
+// kernels_replay.hip: the Monte-Carlo replay's expansion (replay_plan.h) of frame f for the trajectories [b0, b0 + nb) -- the
+// frame's S sequence cells (q: the sections of the sequence store from sequence 0, scalars double, slots / obs from the frame's
+// first sequence entry) through the assignment (t: seq_of[B], seed[B], sigma[B][4], and the frame's base[B]) into the ordinary
+// frame block (o: its sections from trajectory 0).  A workgroup takes REPLAY_CHUNK items of one trajectory.
+struct ReplaySeqIn { const double* rd; const int* n; const int* drop; const int* k; const int* M; const int* off; const int* slots; const double* obs; };
+struct ReplayTrajIn { const int* seq_of; const uint64_t* seed; const double* sigma; const int* base; };
+template <class S> struct ReplayOut { S* rd; int* n; int* drop; int* k; int* M; int* off; int* slots; S* obs; };
+constexpr int REPLAY_CHUNK = 256;
+template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();
 void qr_device_setup();

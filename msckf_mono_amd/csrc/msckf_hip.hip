@@ -35,6 +35,7 @@
 #include "dev_common.h"
 #include "host_lists.h"
 #include "input_layouts.h"
+#include "replay_plan.h"
 #include "settings.h"
 #include "slice_policy.h"
 
@@ -80,7 +81,7 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (e_ != hipSuccess) return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-constexpr int NSTAGE = 11;   // 0..7: msckf_hip_profile_read; 8 k_lit_pre, 9 k_lit_gamma, 10 k_literal (msckf_hip_profile_read_ex)
+constexpr int NSTAGE = 12;   // 0..7: msckf_hip_profile_read; 8 k_lit_pre, 9 k_lit_gamma, 10 k_literal, 11 k_replay_expand (msckf_hip_profile_read_ex)
 
 // Persistent enqueue threads of a batch (one per slice of run_frames / run_frames_streamed): a K-frame window is a few
 // milliseconds, creating and joining three std::threads per call was 1-2 % of it.
@@ -213,6 +214,18 @@ struct BatchCore {
     pin_chunks.clear();
     for (auto& pf : pinf) pf = PinFrame();
   }
+  // Monte-Carlo replay (replay_plan.h; kernels_replay.hip): the plan on the host; on the device the sequence store (one array
+  // per section as a resident scenario has them, scalars double), the assignment with every frame's bases, one expanded frame
+  // block per slice (rp_blk: slices are at different frames at the same time, and where a trajectory's entries start depends on
+  // the frame) and the scratch block of replay_expand.  rp_cells: per slice the host's k / drop / maxslot of the frame's cells,
+  // looked up through seq_of by the slice's enqueue thread.
+  msckf_replay::Plan rp;
+  unsigned char* rp_dev[inputs::N_SECTIONS] = {nullptr}; std::vector<int> rp_maxcell;   // rp_maxcell [frames]: entries of the frame's largest sequence cell
+  int* rp_seq_of = nullptr; uint64_t* rp_seed = nullptr; double* rp_sigma = nullptr; int* rp_base = nullptr; size_t rp_base_count = 0;
+  bool rp_uploaded = false;                                  // the assignment and the bases on the device are the plan's
+  unsigned char* rp_blk[MAXS] = {nullptr}; size_t rp_blk_bytes = 0;
+  unsigned char* rp_scratch = nullptr; size_t rp_scratch_bytes = 0;
+  std::vector<int> rp_cells[MAXS];
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
   // counts the records written; a run_frames / run_frames_streamed call over [f0, f1) writes the records log_base + (f - f0)
@@ -279,6 +292,7 @@ struct BatchCore {
     if (st) hipStreamSynchronize(st);
     for (void* p : allocs) hipFree(p);
     release_logs();
+    free_replay_device();
     if (h_rb) hipHostFree(h_rb);
     for (int s = 0; s < NSTAGE; ++s) for (auto& e : ev_pool[s]) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (int i = 1; i < MAXS; ++i) { if (stx[i]) hipStreamDestroy(stx[i]); if (ev_join[i]) hipEventDestroy(ev_join[i]); }
@@ -496,7 +510,7 @@ struct BatchCore {
     if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(st));
     if (!sc.index()) return fail(-E2BIG, "a frame's work-lists exceed 2^31 observations");
-    const size_t total = sc.total(), per_entry = sc.lay.entry_bytes(SEC_SLOTS) + sc.lay.entry_bytes(SEC_OBS);
+    const size_t total = sc.total();
     if (total != sc_total || !sc_dev[SEC_SLOTS]) {          // patched cells may have changed the compact size
       int rc = 0;
       for (int s = N_FIXED; s < N_SECTIONS; ++s) {
@@ -507,24 +521,31 @@ struct BatchCore {
       if (rc) return rc;
       sc_total = total;
     }
-    for (int s = 0; s < N_FIXED; ++s) HIPCHK(hipMemcpyAsync(sc_dev[s], sc.fixed[s].data(), sc.fixed[s].size(), hipMemcpyHostToDevice, st));
-    if (int rc = stage_reserve(sc.largest_frame() * per_entry)) return rc;   // the pinned staging ring once, for the largest frame
-    for (int f = 0; f < sc.frames; ++f) {            // one frame at a time through the pinned staging area (bounded host memory)
-      const size_t nf = sc.entries(f);
+    if (int rc = upload_store(sc, sc_dev)) return rc;
+    committed = true;
+    return 0;
+  }
+  // an indexed store's cells into its resident arrays dev[N_SECTIONS] (one per section, sized for it), and the wait for the copies
+  int upload_store(const inputs::ScenarioStore& q, unsigned char* const* dev) {
+    using namespace inputs;
+    const size_t per_entry = q.lay.entry_bytes(SEC_SLOTS) + q.lay.entry_bytes(SEC_OBS);
+    for (int s = 0; s < N_FIXED; ++s) HIPCHK(hipMemcpyAsync(dev[s], q.fixed[s].data(), q.fixed[s].size(), hipMemcpyHostToDevice, st));
+    if (int rc = stage_reserve(q.largest_frame() * per_entry)) return rc;   // the pinned staging ring once, for the largest frame
+    for (int f = 0; f < q.frames; ++f) {             // one frame at a time through the pinned staging area (bounded host memory)
+      const size_t nf = q.entries(f);
       if (!nf) continue;
       unsigned char* raw = nullptr;
       int rc = stage_acquire(nf * per_entry, &raw);
       if (rc) return rc;
       unsigned char* h[N_SECTIONS] = {nullptr};
-      h[SEC_SLOTS] = raw; h[SEC_OBS] = raw + nf * sc.lay.entry_bytes(SEC_SLOTS);
-      sc.gather(f, reinterpret_cast<int*>(h[SEC_SLOTS]), h[SEC_OBS]);
+      h[SEC_SLOTS] = raw; h[SEC_OBS] = raw + nf * q.lay.entry_bytes(SEC_SLOTS);
+      q.gather(f, reinterpret_cast<int*>(h[SEC_SLOTS]), h[SEC_OBS]);
       for (int s = N_FIXED; s < N_SECTIONS; ++s)
-        HIPCHK(hipMemcpyAsync(sc_dev[s] + sc.lay.resident_at(s, f, sc.fr_base[f]), h[s], nf * sc.lay.entry_bytes(s), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(dev[s] + q.lay.resident_at(s, f, q.fr_base[f]), h[s], nf * q.lay.entry_bytes(s), hipMemcpyHostToDevice, st));
       rc = stage_release();
       if (rc) return rc;
     }
     HIPCHK(hipStreamSynchronize(st));
-    committed = true;
     return 0;
   }
   // page-locked per-frame blocks for run_frames_streamed, frames [f0, f1) that do not have one yet; also sizes the device
@@ -893,6 +914,131 @@ struct BatchCore {
     if (rc_up) return poison(rc_up, "input upload failed");
     return finish_slices(nh, slice_rc, f0, f1, stc);
   }
+  // ---- Monte-Carlo replay (replay_plan.h): shared sequences, expanded per frame on the device (k_replay_expand)
+  int refuse(const inputs::Refusal& r) const { return r.code ? fail(r.code, r.why) : 0; }
+  void free_replay_device() {
+    for (auto& p : rp_dev) dfree(p);
+    dfree(rp_seq_of); dfree(rp_seed); dfree(rp_sigma); dfree(rp_base); rp_base_count = 0;
+    for (auto& p : rp_blk) dfree(p);
+    rp_blk_bytes = 0;
+    dfree(rp_scratch); rp_scratch_bytes = 0;
+    rp_uploaded = false;
+  }
+  int replay_alloc(int n_seq, int n_frames, int K) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(msckf_replay::Plan::alloc_refusal(n_seq, n_frames, K))) return rc;
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    free_replay_device();
+    rp.alloc(n_seq, n_frames, K, B, f_cap);
+    return 0;
+  }
+  int replay_set_cell(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) {
+    if (int rc = refuse(rp.cell_refusal(f, s, rd, k, F, M, slots, n_drop, flags, m_cap, n_cap))) return rc;
+    rp.set_cell(f, s, rd, k, F, M, slots, obs, n_drop, flags);
+    return 0;
+  }
+  // H2D of the sequences as they stand (the host copy is kept: cells may be patched and committed again)
+  int replay_commit() {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.commit_refusal())) return rc;
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));
+    if (int rc = refuse(rp.commit())) return rc;
+    rp.committed = false;                                    // until the device holds them
+    const ScenarioStore& q = rp.seq;
+    for (auto& p : rp_dev) dfree(p);
+    for (int s = 0; s < N_SECTIONS; ++s)
+      HIPCHK(hipMalloc((void**)&rp_dev[s], std::max<size_t>(s < N_FIXED ? q.fixed[s].size() : q.total() * q.lay.entry_bytes(s), 16)));
+    if (int rc = upload_store(q, rp_dev)) return rc;
+    rp_maxcell.assign(q.frames, 0);
+    for (int f = 0; f < q.frames; ++f) for (int s = 0; s < rp.S; ++s) rp_maxcell[f] = std::max(rp_maxcell[f], (int)rp.entries(s, f));
+    rp.committed = true;
+    rp_uploaded = false;
+    return 0;
+  }
+  // may be called again between runs
+  int replay_assign(const int* seq_of, const uint64_t* seed, const double* sigma4) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.assign_refusal(seq_of, sigma4))) return rc;
+    rp.assign(seq_of, seed, sigma4);
+    rp_uploaded = false;
+    return 0;
+  }
+  // before a run or an expansion (after enter()): the bases of every frame, and with the assignment on the device
+  int replay_upload_plan() {
+    if (rp.planned && rp_uploaded) return 0;
+    if (int rc = refuse(rp.index_trajectories())) return rc;
+    HIPCHK(hipStreamSynchronize(st));                        // the last run's kernels have read the old ones
+    if (!rp_seq_of) {
+      HIPCHK(hipMalloc((void**)&rp_seq_of, (size_t)B * sizeof(int))); HIPCHK(hipMalloc((void**)&rp_seed, (size_t)B * sizeof(uint64_t)));
+      HIPCHK(hipMalloc((void**)&rp_sigma, (size_t)B * msckf_replay::N_SIGMA * sizeof(double)));
+    }
+    if (rp.base.size() != rp_base_count) { dfree(rp_base); rp_base_count = 0; HIPCHK(hipMalloc((void**)&rp_base, rp.base.size() * sizeof(int))); rp_base_count = rp.base.size(); }
+    HIPCHK(hipMemcpy(rp_seq_of, rp.seq_of.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rp_seed, rp.seed.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rp_sigma, rp.sigma.data(), rp.sigma.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rp_base, rp.base.data(), rp.base.size() * sizeof(int), hipMemcpyHostToDevice));
+    rp_uploaded = true;
+    return 0;
+  }
+  // one expanded block per slice, each large enough for the largest expanded frame
+  int replay_blocks(int nh) {
+    const size_t need = rp.block_bytes(esz);
+    if (need > rp_blk_bytes) {
+      HIPCHK(hipStreamSynchronize(st));
+      for (auto& p : rp_blk) dfree(p);
+      rp_blk_bytes = need;
+    }
+    for (int i = 0; i < nh; ++i) if (!rp_blk[i]) HIPCHK(hipMalloc((void**)&rp_blk[i], rp_blk_bytes));
+    return 0;
+  }
+  // run_frames with each frame's block expanded on the device from the sequences, on the slice's own stream ahead of the frame's
+  // propagate; everything else is run_frames'
+  int run_frames_replay(int f0, int f1) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.run_refusal(f0, f1))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    const int nh = n_slices(false);
+    if (int rc = replay_blocks(nh)) return rc;
+    if (int rc = reserve_logs(f0, f1)) return rc;
+    for (int i = 0; i < nh; ++i) rp_cells[i].assign((size_t)3 * B, 0);
+    const int rc = fork_slices(nh);
+    if (rc) return rc;
+    int slice_rc[MAXS] = {0};
+    auto enqueue = [&](int hh) {
+      Slice s = begin_slice(hh, nh);
+      for (int f = f0; f < f1; ++f) enqueue_frame(s, f, f0, f1, IN_REPLAY);
+      slice_rc[hh] = (int)hipGetLastError();
+    };
+    if (nh == 1) enqueue(0);
+    else {
+      workers.start(nh - 1, [&](int idx) { enqueue(idx + 1); });
+      enqueue(0);
+      workers.wait();
+    }
+    return finish_slices(nh, slice_rc, f0, f1);
+  }
+  // where a frame's inputs are, as enqueue_frame's `staged` says: resident, expanded by the replay, or (>= 0) in that staging set
+  static constexpr int IN_RESIDENT = -1, IN_REPLAY = -2;
+  // The host's copy of the frame's cells, indexed by trajectory: the sample count k (or IMU_SKIP), the drop, the largest camera
+  // slot of the work-list.  A scenario's own cells, or for a replay those of each trajectory's sequence (slice hh's [b0, b0 + nb)).
+  struct FrameCells { const int* k; const int* drop; const int* maxslot; };
+  FrameCells frame_cells(int f, int staged, int hh, int b0, int nb) {
+    using namespace inputs;
+    if (staged != IN_REPLAY) {
+      const size_t cell0 = (size_t)f * B;
+      return FrameCells{sc.ints(SEC_K) + cell0, sc.ints(SEC_DROP) + cell0, sc.maxslot.data() + cell0};
+    }
+    int* c = rp_cells[hh].data();
+    for (int b = b0; b < b0 + nb; ++b) {
+      const size_t cell = rp.cell_of(f, b);
+      c[b] = rp.seq.ints(SEC_K)[cell]; c[B + b] = rp.seq.ints(SEC_DROP)[cell]; c[2 * B + b] = rp.seq.maxslot[cell];
+    }
+    return FrameCells{c, c + B, c + 2 * B};
+  }
   int sync() {
     if (int rc = enter()) return rc;
     HIPCHK(hipStreamSynchronize(st));
@@ -985,9 +1131,10 @@ struct BatchCore {
   virtual int track_info(int b, double* out, int cap) = 0;
   virtual int deltax(int b, double* out, int cap) = 0;
   virtual int scen_set(int f, int b, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) = 0;
-  // THE frame step of run_frames / run_frames_streamed: frame f of a call over [f0, f1) for slice s, inputs in staging set
-  // `staged` of the upload ring, or (staged < 0) resident
+  // THE frame step of run_frames / run_frames_streamed / run_frames_replay: frame f of a call over [f0, f1) for slice s, inputs
+  // in staging set `staged` of the upload ring, or resident (IN_RESIDENT), or expanded by the replay (IN_REPLAY)
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
+  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries) = 0;
   virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
   virtual void apply_settings() = 0;   // the one place where `settings` reaches the kernel argument
   virtual int set_aniso(int mode, double tol) = 0;
@@ -1656,7 +1803,67 @@ struct Batch : BatchCore {
   FrameIn staged_frame(int f, int k, int b0) const {
     return inputs::frame_in<S>(sc.lay, b0, [&](int s) { return sg_blk[k] + sc.lay.block_at(s, sc.entries(f)); });
   }
-  // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged` or (staged < 0) resident --
+  // the replay's three views of frame f: the sequence cells, the assignment with the frame's bases, and the sections of an
+  // expanded block (the ordinary frame block of rp.nf[f] entries) to write (replay_out) or to read (replay_frame)
+  ReplaySeqIn replay_seq(int f) const {
+    using namespace inputs;
+    const ScenarioStore& q = rp.seq;
+    auto at = [&](int s) { return rp_dev[s] + q.lay.resident_at(s, f, q.fr_base[f]); };
+    auto i = [&](int s) { return reinterpret_cast<const int*>(at(s)); };
+    return ReplaySeqIn{reinterpret_cast<const double*>(at(SEC_RD)), i(SEC_N), i(SEC_DROP), i(SEC_K), i(SEC_M), i(SEC_OFF), i(SEC_SLOTS), reinterpret_cast<const double*>(at(SEC_OBS))};
+  }
+  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B}; }
+  ReplayOut<S> replay_out(unsigned char* blk, int f) const {
+    using namespace inputs;
+    const FrameLayout L = rp.out_layout(sizeof(S));
+    auto at = [&](int s) { return blk + L.block_at(s, rp.nf[f]); };
+    auto i = [&](int s) { return reinterpret_cast<int*>(at(s)); };
+    return ReplayOut<S>{reinterpret_cast<S*>(at(SEC_RD)), i(SEC_N), i(SEC_DROP), i(SEC_K), i(SEC_M), i(SEC_OFF), i(SEC_SLOTS), reinterpret_cast<S*>(at(SEC_OBS))};
+  }
+  FrameIn replay_frame(int f, int hh, int b0) const {
+    const inputs::FrameLayout L = rp.out_layout(sizeof(S));
+    return inputs::frame_in<S>(L, b0, [&](int s) { return rp_blk[hh] + L.block_at(s, rp.nf[f]); });
+  }
+  // msckf_hip_replay_expand / _ints: k_replay_expand for trajectory b alone into the scratch block, and what it wrote there --
+  // rd [K][7] and the cell's coordinate pairs as doubles; ints [3 + 2 f_cap] = n, drop, k, M[f_cap], off[f_cap] and the cell's
+  // slots (each pair null or not).  Returns the cell's entries.  Nothing of the handle's filters, inputs or logs changes.
+  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries) override {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.expand_refusal(f, b))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    const int K = rp.K(), E = (int)rp.entries(rp.seq_of[b], f);
+    if (E > cap_entries) return fail(-E2BIG, "output buffer too small for the cell's entries");
+    const size_t need = rp.block_bytes(sizeof(S));
+    if (need > rp_scratch_bytes) {
+      HIPCHK(hipStreamSynchronize(st));
+      dfree(rp_scratch); rp_scratch_bytes = 0;
+      HIPCHK(hipMalloc((void**)&rp_scratch, need));
+      rp_scratch_bytes = need;
+    }
+    const ReplayOut<S> o = replay_out(rp_scratch, f);
+    launch_replay_expand<S>(replay_seq(f), replay_traj(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st);
+    HIPCHK(hipGetLastError());
+    const size_t base = (size_t)rp.base[(size_t)f * B + b];
+    std::vector<S> hr((size_t)K * RD_STRIDE), ho((size_t)2 * std::max(E, 1));
+    std::vector<int> hi((size_t)3 + 2 * f_cap), hs(std::max(E, 1));
+    HIPCHK(hipMemcpyAsync(hr.data(), o.rd + (size_t)b * K * RD_STRIDE, hr.size() * sizeof(S), hipMemcpyDeviceToHost, st));
+    if (E) HIPCHK(hipMemcpyAsync(ho.data(), o.obs + 2 * base, (size_t)2 * E * sizeof(S), hipMemcpyDeviceToHost, st));
+    if (E) HIPCHK(hipMemcpyAsync(hs.data(), o.slots + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hi[0], o.n + b, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hi[1], o.drop + b, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hi[2], o.k + b, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hi[3], o.M + (size_t)b * f_cap, (size_t)f_cap * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hi[3 + f_cap], o.off + (size_t)b * f_cap, (size_t)f_cap * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (rd) for (size_t i = 0; i < hr.size(); ++i) rd[i] = (double)hr[i];
+    if (obs) for (int i = 0; i < 2 * E; ++i) obs[i] = (double)ho[i];
+    if (ints) std::copy(hi.begin(), hi.end(), ints);
+    if (slots) std::copy(hs.begin(), hs.begin() + E, slots);
+    return E;
+  }
+  // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged`, resident or the replay's --
   // propagate + augmentState, the update, the prune (on the downdate or with its own launch, fuse_frame), the host mirror of
   // the window size.
   // may_overlap (resident inputs only): k_feature reads only what the previous frame's prune left behind -- camera states and
@@ -1665,11 +1872,15 @@ struct Batch : BatchCore {
   // for it (set_feature_overlap) it runs on a side stream concurrently with the latency-bound propagate + augment.
   void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) override {
     const int b0 = s.b0, nb = s.nb, hh = s.hh;
-    const FrameIn in = staged < 0 ? resident_frame(f, b0) : staged_frame(f, staged, b0);
-    const bool may_overlap = staged < 0;
+    const bool replay = staged == IN_REPLAY;
+    const FrameIn in = replay ? replay_frame(f, hh, b0) : staged == IN_RESIDENT ? resident_frame(f, b0) : staged_frame(f, staged, b0);
+    const bool may_overlap = staged == IN_RESIDENT;
     hipStream_t q = s.q;
-    const size_t cell0 = (size_t)f * B;
-    const int* cell_k = sc.ints(inputs::SEC_K) + cell0; const int* cell_drop = sc.ints(inputs::SEC_DROP) + cell0;   // the host's copy of the frame's cells
+    const FrameCells cells = frame_cells(f, staged, hh, b0, nb);   // the host's copy of the frame's cells
+    const int* cell_k = cells.k; const int* cell_drop = cells.drop;
+    const int K = replay ? rp.K() : sc.lay.K;
+    // replay: the slice's trajectories of this frame's block, from the sequences (outside the frame step's own stage timers)
+    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q); stage_end(11, q); }
     Dev<S> v = d;
     v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
@@ -1679,7 +1890,7 @@ struct Batch : BatchCore {
     for (int b = b0; b < b0 + nb && early; ++b) {
       const int n_after = std::min(h_ncam[b] + 1, n_cap);
       // (a skipped cell gets no camera state: the early k_feature's window size, ncam_upd = "after the next augment", would be one too many)
-      early = h_ncam[b] < n_cap && sc.maxslot[cell0 + b] <= n_after - 2 && cell_k[b] != IMU_SKIP;
+      early = h_ncam[b] < n_cap && cells.maxslot[b] <= n_after - 2 && cell_k[b] != IMU_SKIP;
     }
     if (early) {
       (void)hipEventRecord(ev_fa[hh], q);
@@ -1692,7 +1903,7 @@ struct Batch : BatchCore {
     // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
     {
       StageRange r("imu_prop+msckf_augment_state");
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)sc.lay.K * RD_STRIDE, sc.lay.K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
       if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q, in.k); stage_end(1, q); }
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
@@ -2333,6 +2544,16 @@ int msckf_hip_scenario_set_cell(msckf_hip_handle h, int frame, int b, const doub
 int msckf_hip_scenario_commit(msckf_hip_handle h) { return H(h)->scen_commit(); }
 int msckf_hip_run_frames(msckf_hip_handle h, int f0, int f1) { return H(h)->run_frames(f0, f1); }
 int msckf_hip_run_frames_streamed(msckf_hip_handle h, int f0, int f1) { return H(h)->run_frames_streamed(f0, f1); }
+int msckf_hip_replay_alloc(msckf_hip_handle h, int n_seq, int n_frames, int K) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_alloc(n_seq, n_frames, K); }
+int msckf_hip_replay_set_cell(msckf_hip_handle h, int frame, int seq, const double* readings7, int k, int F, const int* M, const int* slots, const double* obs2, int n_drop, int flags) {
+  if (!h) return fail(-EINVAL, "null handle");
+  return H(h)->replay_set_cell(frame, seq, readings7, k, F, M, slots, obs2, n_drop, flags);
+}
+int msckf_hip_replay_assign(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* sigma4) { if (!h || !seq_of || !seed || !sigma4) return fail(-EINVAL, "null argument"); return H(h)->replay_assign(seq_of, seed, sigma4); }
+int msckf_hip_replay_commit(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_commit(); }
+int msckf_hip_run_frames_replay(msckf_hip_handle h, int f0, int f1) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->run_frames_replay(f0, f1); }
+int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd, double* obs2, int cap_entries) { if (!h || !rd || !obs2) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, rd, obs2, nullptr, nullptr, cap_entries); }
+int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints, int* slots, int cap_entries) { if (!h || !ints || !slots) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, ints, slots, cap_entries); }
 int msckf_hip_sync(msckf_hip_handle h) { return H(h)->sync(); }
 int msckf_hip_profile_enable(msckf_hip_handle h, int on) { return H(h)->prof_enable(on); }
 int msckf_hip_profile_read(msckf_hip_handle h, double* ms7, int* count7) { return H(h)->prof_read(ms7, count7, 8); }

@@ -1,0 +1,161 @@
+// replay_plan.h -- the Monte-Carlo replay's host side, free of device calls: S noise-free SEQUENCES staged once, and B
+// trajectories that each name a sequence, a 64-bit seed and four noise levels.  Before a frame the kernel k_replay_expand
+// (kernels_replay.hip) turns the frame's S sequence cells into the ordinary per-trajectory frame block of input_layouts.h
+// (FrameLayout(B, K, f_cap, esz), sections [rd | n | drop | k | M | off | slots | obs]) -- what an upload would have put there.
+//
+// Stated once here:
+//   1. mix / U        the integer part of the random stream (value i of scenario.SplitMix64(seed) and the 53-bit uniform made of
+//                     it), constexpr, shared by this file's host users, the kernel and -- bit for bit -- the numpy twin
+//   2. the noise      which pair of which sub-seed a value takes (NOISE below)
+//   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record,
+//                     per frame each trajectory's first entry in the expanded block and the block's size, the largest expanded
+//                     frame, and every refusal with its code and text
+// Out of scope: bias random walks (they need state carried from frame to frame) and correlated Q_imu noise.
+// No HIP header, no batch type: a host compiler accepts this file on its own (tests/cpp/replay_plan_host.cpp).
+#ifndef MSCKF_REPLAY_PLAN_H
+#define MSCKF_REPLAY_PLAN_H
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "host_lists.h"
+#include "input_layouts.h"
+
+namespace msckf_replay {
+
+// ---- 1. the integer part
+constexpr uint64_t GAMMA = 0x9E3779B97F4A7C15ull;
+// value i (0-based) of scenario.SplitMix64(seed): the finalizer of seed + (i + 1) gamma, all modulo 2^64
+constexpr uint64_t mix(uint64_t seed, uint64_t i) {
+  uint64_t z = seed + (i + 1) * GAMMA;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// the uniform in [0, 1) of its upper 53 bits: exact in a double
+constexpr double U(uint64_t seed, uint64_t i) { return (double)(mix(seed, i) >> 11) * (1.0 / 9007199254740992.0); }
+
+// ---- 2. NOISE: which draws a value takes
+// pair(s, j) = (r cos(2 pi u2), r sin(2 pi u2)), u1 = 1 - U(s, 2 j), u2 = U(s, 2 j + 1), r = sqrt(-2 ln u1)      (Box-Muller)
+// Trajectory b with seed s_b on frame f: s_imu = mix(s_b, 2 f), s_obs = mix(s_b, 2 f + 1).
+//   IMU sample i < k of the cell: pairs 3 i, 3 i + 1, 3 i + 2 of s_imu = (g_x, g_y), (g_z, a_x), (a_y, a_z);
+//                                 omega += sigma_g g, a += sigma_a a, dT unchanged, rows from k on zero
+//   entry e of the cell:          pair e of s_obs = (n_u, n_v); obs += (sigma_u n_u, sigma_v n_v)
+// Sequence values are doubles; value + sigma * noise is formed in double (product rounded, then the sum) and rounded once to
+// the handle's scalar.
+constexpr uint64_t imu_seed(uint64_t s, int f) { return mix(s, 2 * (uint64_t)f); }
+constexpr uint64_t obs_seed(uint64_t s, int f) { return mix(s, 2 * (uint64_t)f + 1); }
+enum Sigma { SIG_G, SIG_A, SIG_U, SIG_V, N_SIGMA };
+constexpr int IMU_PAIRS = 3;   // pairs per IMU sample
+// column c (0 .. 5) of an IMU sample is half (c & 1) of its pair c / 2 and scales with sigma[c < 3 ? SIG_G : SIG_A]
+
+// ---- 3. the plan
+using msckf_inputs::FrameLayout;
+using msckf_inputs::Refusal;
+using msckf_inputs::ScenarioStore;
+
+struct Plan {
+  int S = 0, B = 0, f_cap = 0;
+  ScenarioStore seq;                 // the sequences' cells: seq.lay.B == S, scalars double; seq.frames == 0: no replay allocated
+  bool committed = false;            // the cells are indexed (and, for the caller, on the device) as they stand
+  bool assigned = false;
+  std::vector<int> seq_of;           // [B]
+  std::vector<uint64_t> seed;        // [B]
+  std::vector<double> sigma;         // [B][N_SIGMA]
+  // per frame and trajectory the first entry in the expanded block, [frames][B] (a prefix sum of entries(seq_of[b], f)), and the
+  // frame's entries; filled by index_trajectories()
+  std::vector<int> base; std::vector<size_t> nf;
+  size_t largest = 0;                // entries of the largest expanded frame
+  bool planned = false;              // base / nf / largest match the cells and the assignment
+
+  int frames() const { return seq.frames; }
+  int K() const { return seq.lay.K; }
+  size_t cell(int f, int s) const { return (size_t)f * S + s; }
+  size_t entries(int s, int f) const { return seq.slots[cell(f, s)].size(); }
+  // the ordinary frame block the kernel fills, for a handle whose scalars have esz bytes
+  FrameLayout out_layout(size_t esz) const { return FrameLayout(B, K(), f_cap, esz); }
+  size_t block_bytes(size_t esz) const { return out_layout(esz).bytes(largest); }
+
+  // -- staging the sequences
+  static Refusal alloc_refusal(int n_seq, int n_frames, int K) {
+    if (n_seq <= 0 || n_frames <= 0 || K <= 0) return {-EINVAL, "bad replay size"};
+    return {0, nullptr};
+  }
+  void alloc(int n_seq, int n_frames, int K, int B_, int f_cap_) {
+    S = n_seq; B = B_; f_cap = f_cap_;
+    seq.reset(n_frames, n_seq, K, f_cap_, sizeof(double));
+    committed = assigned = planned = false;
+    seq_of.clear(); seed.clear(); sigma.clear(); base.clear(); nf.clear(); largest = 0;
+  }
+  // the rules of one sequence cell, in scenario_set_cell's order: its place, the work-list rules, the drop, the cell rule, the readings
+  Refusal cell_refusal(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, int n_drop, int flags, int m_cap, int n_cap) const {
+    if (f < 0 || f >= seq.frames || s < 0 || s >= S) return {-EINVAL, "replay cell out of range"};
+    const Refusal r = msckf_inputs::worklist_refusal(F, M, slots, f_cap, m_cap, n_cap);
+    if (r.code) return r;
+    if (n_drop < 0) return {-EINVAL, "negative n_drop"};
+    if (const char* why = msckf_lists::cell_refusal(k, K(), F, n_drop, flags)) return {-EINVAL, why};
+    if (k > 0 && !rd) return {-EINVAL, "null readings for a cell with samples"};
+    return {0, nullptr};
+  }
+  void set_cell(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) {
+    seq.set_cell<double>(f, s, rd, k, (flags & msckf_lists::CELL_SKIP) != 0, F, M, slots, obs, n_drop);
+    committed = planned = false;
+  }
+  Refusal commit_refusal() const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    return {0, nullptr};
+  }
+  // every off and the frame index of the sequence store (ScenarioStore::index: a frame of S cells cannot pass 2^31 entries
+  // unless an expanded one does, which index_trajectories refuses)
+  Refusal commit() {
+    if (!seq.index()) return {-E2BIG, "a frame's sequence work-lists exceed 2^31 observations"};
+    committed = true; planned = false;
+    return {0, nullptr};
+  }
+
+  // -- the assignment
+  Refusal assign_refusal(const int* seq_of_, const double* sigma4) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    for (int b = 0; b < B; ++b) if (seq_of_[b] < 0 || seq_of_[b] >= S) return {-EINVAL, "seq_of names no sequence of the replay"};
+    for (int i = 0; i < B * N_SIGMA; ++i) if (!(sigma4[i] >= 0.0) || !std::isfinite(sigma4[i])) return {-EINVAL, "sigma must be finite and not negative"};
+    return {0, nullptr};
+  }
+  void assign(const int* seq_of_, const uint64_t* seed_, const double* sigma4) {
+    seq_of.assign(seq_of_, seq_of_ + B); seed.assign(seed_, seed_ + B); sigma.assign(sigma4, sigma4 + (size_t)B * N_SIGMA);
+    assigned = true; planned = false;
+  }
+
+  // -- a run
+  // in run_frames' order: the range, then what has to have happened before
+  Refusal run_refusal(int f0, int f1) const {
+    if (f0 < 0 || f1 > seq.frames || f0 > f1) return {-EINVAL, "frame range out of bounds"};
+    if (!committed) return {-EINVAL, "replay not committed"};
+    if (!assigned) return {-EINVAL, "replay not assigned"};
+    return {0, nullptr};
+  }
+  Refusal expand_refusal(int f, int b) const {
+    if (const Refusal r = run_refusal(0, seq.frames); r.code) return r;
+    if (f < 0 || f >= seq.frames || b < 0 || b >= B) return {-EINVAL, "replay cell out of range"};
+    return {0, nullptr};
+  }
+  // base, nf and largest from the committed cells and the assignment
+  Refusal index_trajectories() {
+    if (planned) return {0, nullptr};
+    base.assign((size_t)seq.frames * B, 0); nf.assign(seq.frames, 0); largest = 0;
+    for (int f = 0; f < seq.frames; ++f) {
+      size_t o = 0;
+      for (int b = 0; b < B; ++b) { base[(size_t)f * B + b] = (int)o; o += entries(seq_of[b], f); if (o > 0x7fffffffu) return {-E2BIG, "an expanded frame's work-lists exceed 2^31 observations"}; }
+      nf[f] = o;
+      largest = std::max(largest, o);
+    }
+    planned = true;
+    return {0, nullptr};
+  }
+  // what the frame step reads on the host of trajectory b's cell: its sequence's
+  size_t cell_of(int f, int b) const { return cell(f, seq_of[b]); }
+};
+
+}  // namespace msckf_replay
+
+#endif  // MSCKF_REPLAY_PLAN_H

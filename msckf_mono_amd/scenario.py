@@ -63,6 +63,70 @@ class SplitMix64:
         return (self.u64(n) % np.uint64(mod)).astype(np.int64)
 
 
+# ------------------------------------------------------------------ Monte-Carlo replay: the numpy twin of csrc/replay_plan.h
+# The noise a replay adds on the device is a pure function of (seed, frame, index); include/msckf_hip.h states it, this is its
+# twin.  The integer part (replay_mix, replay_uniform) agrees with the host and device code bit for bit; ln, sqrt, cos and sin
+# are numpy's.  Out of scope: bias random walks (they need state carried between frames) and correlated Q_imu noise.
+def replay_mix(seed, i):
+    """value i (0-based; an int or an array) of SplitMix64(seed), as uint64"""
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) + (np.asarray(i, dtype=np.uint64) + np.uint64(1)) * _GAMMA
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def replay_uniform(seed, i):
+    """U(seed, i) = (mix(seed, i) >> 11) 2^-53, in [0, 1)"""
+    return (replay_mix(seed, i) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def replay_pairs(seed, n):
+    """pairs 0 .. n - 1 of sub-seed `seed`, [n][2]: (r cos(2 pi u2), r sin(2 pi u2)), u1 = 1 - U(seed, 2 j), u2 = U(seed, 2 j + 1)"""
+    j = np.arange(n, dtype=np.uint64)
+    u1 = 1.0 - replay_uniform(seed, np.uint64(2) * j)
+    u2 = replay_uniform(seed, np.uint64(2) * j + np.uint64(1))
+    r = np.sqrt(-2.0 * np.log(u1))
+    return np.stack([r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2)], -1)
+
+
+def replay_subseeds(seed, frame):
+    """(s_imu, s_obs) of a trajectory's seed on a frame: mix(seed, 2 f), mix(seed, 2 f + 1)"""
+    return int(replay_mix(seed, 2 * int(frame))), int(replay_mix(seed, 2 * int(frame) + 1))
+
+
+def replay_noise(seed, frame, K, k, n_entries):
+    """unit-variance noise of one cell: (imu [K][6], rows from k on zero: g_x g_y g_z a_x a_y a_z of sample i from the pairs
+    3 i, 3 i + 1, 3 i + 2 of s_imu; obs [n_entries][2]: (n_u, n_v) of entry e from pair e of s_obs)"""
+    s_imu, s_obs = replay_subseeds(seed, frame)
+    imu = np.zeros((K, 6))
+    k = max(int(k), 0)                       # (a skipped cell's count is -1)
+    imu[:k] = replay_pairs(s_imu, 3 * k).reshape(k, 6)
+    return imu, replay_pairs(s_obs, n_entries).reshape(n_entries, 2)
+
+
+def replay_cell(readings, obs, frame, seed, sigma4, K=None):
+    """a noise-free cell (readings [k][7], obs [n][2]) as trajectory `seed` sees it on `frame` with sigma4 = (sigma_g, sigma_a,
+    sigma_u, sigma_v): (readings [K][7] with rows from k on zero, obs [n][2]), in double"""
+    rd = np.asarray(readings, dtype=np.float64).reshape(-1, 7)
+    ob = np.asarray(obs, dtype=np.float64).reshape(-1, 2)
+    k = len(rd)
+    K = k if K is None else int(K)
+    imu, nz = replay_noise(seed, frame, K, k, len(ob))
+    sg, sa, su, sv = (float(x) for x in sigma4)
+    out = np.zeros((K, 7))
+    out[:k] = rd
+    out[:, 0:3] += sg * imu[:, 0:3]
+    out[:, 3:6] += sa * imu[:, 3:6]
+    return out, ob + np.array([su, sv]) * nz
+
+
+def replay_expand(seq_traj, frame, seed, sigma4):
+    """frame `frame` of the noise-free Trajectory seq_traj (imu_noise_scale = 0, obs_noise_px = 0) with the replay's noise:
+    (readings [IMU_PER_FRAME][7], obs [n][2]); M and slots are the sequence's own"""
+    return replay_cell(seq_traj.imu_for_frame(frame), seq_traj.frames[frame]["obs"], frame, seed, sigma4)
+
+
 def rot_to_quat(R):
     """Rotation matrix -> (w,x,y,z) such that Eigen's toRotationMatrix() gives R back."""
     t = np.trace(R)
