@@ -236,7 +236,8 @@ int msckf_hip_scenario_pin(msckf_hip_handle h, int f0, int f1);
 int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode);
 /* ---- Monte-Carlo replay: shared noise-free sequences, per-trajectory seeded noise added on the device -------------- */
 /* n_seq SEQUENCES of n_frames cells are staged once (sequence values are kept as doubles); each of the handle's B trajectories
- * then names a sequence, a 64-bit seed and four noise levels, and before each frame one kernel launch per slice expands the
+ * then names a sequence, a 64-bit seed and a noise model (four white levels, or the filter's Q_imu with its bias random walks:
+ * msckf_hip_replay_assign_q below), and before each frame one kernel launch per slice expands the
  * frame's sequence cells into the ordinary per-trajectory frame block -- what msckf_hip_run_frames_streamed would have
  * uploaded -- so that B trajectories cost the host store, the page-locked memory and the PCIe traffic of none.
  * The noise is a pure function of (seed, frame, index), no state is carried between frames:
@@ -248,7 +249,6 @@ int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode);
  *     omega += sigma_g g, a += sigma_a a; dT is unchanged; rows from k on are zero
  *   entry e of the cell (its e-th (slot, observation) pair) takes pair e of s_obs: obs += (sigma_u n_u, sigma_v n_v)
  * Sums are formed in double and rounded once to the handle's scalar.  msckf_mono_amd/scenario.py holds the numpy twin.
- * Not provided: bias random walks (they need carried state) and correlated Q_imu noise.
  * msckf_hip_replay_alloc replaces a previous replay; a scenario staged with msckf_hip_scenario_* is independent of it. */
 int msckf_hip_replay_alloc(msckf_hip_handle h, int n_seq, int n_frames, int K);
 /* one (frame, sequence) cell: arguments and rules of msckf_hip_scenario_set_cell; un-commits the replay */
@@ -257,6 +257,33 @@ int msckf_hip_replay_set_cell(msckf_hip_handle h, int frame, int seq, const doub
 /* seq_of[B], seed[B], sigma4[B][4] = sigma_g sigma_a sigma_u sigma_v per trajectory.  -EINVAL for a seq_of outside
  * [0, n_seq) or a sigma that is negative or not finite; the assignment made before stays.  May be called again between runs. */
 int msckf_hip_replay_assign(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* sigma4);
+/* The Q_imu model in place of sigma4: the noise the filter assumes (msckf_hip_initialize_full's Q144), correlated, with the
+ * two bias random walks.  Per trajectory Q[b] (12 x 12, column-major, noise order n_g n_wg n_a n_wa, taken as its symmetric
+ * part 0.5 (Q + Q^T)), scale[b] >= 0 (the role of scenario.Trajectory's imu_noise_scale) and (sigma_u, sigma_v)[b].
+ *   L = chol_psd(Q_sym), lower triangular, on the host in double: for column c, d = Q_cc - s, s = sum_{j < c} L_cj^2 (ascending j
+ *     from 0); d < -1e-12 max_diag is refused; |d| <= 1e-12 max_diag makes the whole column zero (semi-definite input works: a
+ *     zero walk density is the common case); otherwise L_cc = sqrt(d), L_rc = (Q_rc - sum_{j < c} L_rj L_cj) / L_cc
+ *   IMU sample i < k of the cell takes pairs 6 i .. 6 i + 5 of s_imu as z[0 .. 11]: pair 6 i + p = (z[2 p], z[2 p + 1]);
+ *     w_r = sum_{c <= r} L_rc z_c, c ascending from 0, each product rounded, then added
+ *   with dT_i > 0: omega += (scale w[0:3]) / sqrt(dT_i), a += (scale w[6:9]) / sqrt(dT_i),
+ *     delta_g = (scale w[3:6]) sqrt(dT_i), delta_a = (scale w[9:12]) sqrt(dT_i); a sample with dT_i <= 0 gets neither
+ *   the walk, per component (gyro 0 .. 2, accelerometer 3 .. 5), summed sequentially in double: P(f, 0) = 0,
+ *     P(f, i + 1) = P(f, i) + delta(f, i); Wstart(0) = 0, Wstart(f + 1) = Wstart(f) + P(f, k_f); skipped cells and cells with
+ *     k = 0 add nothing.  Sample (f, i) stores (value + (Wstart(f) + P(f, i))) + noise: the bias starts at the sequence's constant
+ *     bias, what the filter is initialised with.  Rows from k on are zero.  Observations as above: obs += (sigma_u n_u, sigma_v n_v).
+ * Everything is summed in double and rounded once to the handle's scalar.  A one-off device scan tabulates Wstart (frames + 1
+ * rows per trajectory) when an assignment or a commit has changed it, so single frames and cut ranges expand as before.
+ * -EINVAL, in this order: "seq_of names no sequence of the replay", "Q, scale and sigma must be finite", "scale and sigma must
+ * not be negative", "Q is not positive semi-definite"; the assignment made before stays.  May be called between runs; a later
+ * msckf_hip_replay_assign returns the handle to the sigma4 model.  msckf_hip_run_frames_replay, msckf_hip_replay_expand and
+ * _expand_ints serve whichever model is assigned. */
+int msckf_hip_replay_assign_q(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* Q144 /*[B][144]*/,
+                              const double* scale /*[B]*/, const double* sigma_uv /*[B][2]*/);
+/* Rows [f0, f1) of Wstart, 0 <= f0 <= f1 <= frames + 1, for the trajectories [b0, b0 + nb): out [f1 - f0][nb][6] (gyro, then
+ * accelerometer bias offset).  Row f + 1 is the true bias offset at the time of frame f's log record.  Builds the table if
+ * needed.  -EINVAL "no replay allocated", "walk range out of bounds", "replay not committed", "replay not assigned through
+ * msckf_hip_replay_assign_q", in this order. */
+int msckf_hip_replay_walk(msckf_hip_handle h, int f0, int f1, int b0, int nb, double* out);
 int msckf_hip_replay_commit(msckf_hip_handle h);   /* H2D of the sequences staged */
 /* msckf_hip_run_frames over the frames [f0, f1) of the replay: same kernels, same slices, same logs; a frame's inputs are
  * expanded on the slice's own stream ahead of its propagate.  -EINVAL "frame range out of bounds", "replay not committed",
@@ -366,7 +393,7 @@ int msckf_hip_profile_read(msckf_hip_handle h, double* ms8, int* count8);
 /* The same with the stages beyond the first eight (cap >= 8 entries are written, unknown ones as zero): 8 k_lit_pre, 9 k_lit_gamma,
  * 10 k_literal -- the three launches of the literal anisotropic compression (u_var' != v_var', msckf.h:423-431, 1343-1366;
  * kernels_literal.hip), which a profiled run brackets one by one (stage 3 is then k_gram alone); 11 k_replay_expand, the
- * expansion launches of msckf_hip_run_frames_replay. */
+ * expansion launches of msckf_hip_run_frames_replay; 12 k_replay_walk_scan, the one-off scan of the Q_imu model's walk table. */
 int msckf_hip_profile_read_ex(msckf_hip_handle h, double* ms, int* count, int cap);
 /* Milliseconds an event pair with nothing between its two records reads on the handle's stream (mean of 64 pairs): every
  * stage timer above brackets its launches with such a pair, so a single-kernel stage reads the kernel's duration plus

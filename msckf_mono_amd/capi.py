@@ -40,7 +40,7 @@ SYMBOLS = [
     "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
     "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
-    "msckf_hip_replay_expand_ints",
+    "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -131,6 +131,7 @@ def full_noise(cfg):
 class Batch:
     """A batch of B independent filters resident on one GPU."""
     _replay_K = 0   # K of the last replay_alloc
+    _replay_frames = 0   # its frames
 
     def __init__(self, B, n_cap, f_cap, m_cap, dtype=F32, device=0):
         self.L = lib()
@@ -357,7 +358,7 @@ class Batch:
     def replay_alloc(self, n_seq, n_frames, K):
         """n_seq sequences of n_frames cells with up to K IMU samples each (replaces a previous replay)"""
         _chk(self.L.msckf_hip_replay_alloc(self.h, int(n_seq), int(n_frames), int(K)))
-        self._replay_K = int(K)
+        self._replay_K, self._replay_frames = int(K), int(n_frames)
 
     def replay_set_cell(self, frame, seq, readings, M, slots, obs, n_drop, skip=False):
         """one (frame, sequence) cell, noise-free: the arguments and rules of scenario_set"""
@@ -373,6 +374,29 @@ class Batch:
         if q.shape != (self.B,) or sd.shape != (self.B,):
             raise ValueError("seq_of and seeds must hold one value per trajectory")
         _chk(self.L.msckf_hip_replay_assign(self.h, pq, sd.ctypes.data_as(_up), sg.ctypes.data_as(_dp)))
+
+    def replay_assign_q(self, seq_of, seeds, Q, scale, sigma_uv):
+        """per trajectory its sequence, its 64-bit seed and the Q_imu noise model (include/msckf_hip.h): Q [12][12] (the
+        filter's Q_imu, noise order n_g n_wg n_a n_wa), scale (Trajectory's imu_noise_scale) and (sigma_u, sigma_v); one Q, scale
+        or sigma pair serves every trajectory.  A later replay_assign returns to the sigma4 model."""
+        q, pq = _i(seq_of)
+        sd = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        if q.shape != (self.B,) or sd.shape != (self.B,):
+            raise ValueError("seq_of and seeds must hold one value per trajectory")
+        Qa = np.broadcast_to(np.asarray(Q, dtype=np.float64), (self.B, 12, 12))
+        Qc = np.ascontiguousarray(np.swapaxes(Qa, 1, 2))                 # column-major, per trajectory
+        sc_ = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (self.B,)))
+        uv = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_uv, dtype=np.float64), (self.B, 2)))
+        _chk(self.L.msckf_hip_replay_assign_q(self.h, pq, sd.ctypes.data_as(_up), Qc.ctypes.data_as(_dp), sc_.ctypes.data_as(_dp), uv.ctypes.data_as(_dp)))
+
+    def replay_walk(self, f0=0, f1=None, b0=0, nb=None):
+        """the model's bias walk at the start of the frames [f0, f1) (default: all frames + 1 rows) for the trajectories
+        [b0, b0 + nb): [f1 - f0][nb][6], gyro then accelerometer bias offset; row f + 1 belongs to frame f's log record"""
+        f1 = self._replay_frames + 1 if f1 is None else int(f1)
+        nb = self.B - int(b0) if nb is None else int(nb)
+        out = np.zeros((max(f1 - int(f0), 0), max(nb, 0), 6))
+        _chk(self.L.msckf_hip_replay_walk(self.h, int(f0), f1, int(b0), nb, out.ctypes.data_as(_dp)))
+        return out
 
     def replay_commit(self):
         _chk(self.L.msckf_hip_replay_commit(self.h))
@@ -594,7 +618,7 @@ class Batch:
     def profile_read(self):
         ms = np.zeros(16); cnt = np.zeros(16, dtype=np.int32)
         _chk(self.L.msckf_hip_profile_read_ex(self.h, ms.ctypes.data_as(_dp), cnt.ctypes.data_as(_ip), 16))
-        names = ["propagate", "augment", "feature", "compress_stage1", "compress_merge", "kalman", "prune", "select", "lit_pre", "lit_gamma", "literal", "replay_expand"]
+        names = ["propagate", "augment", "feature", "compress_stage1", "compress_merge", "kalman", "prune", "select", "lit_pre", "lit_gamma", "literal", "replay_expand", "replay_walk_scan"]
         return {n: (float(m), int(c)) for n, m, c in zip(names, ms, cnt)}
 
 

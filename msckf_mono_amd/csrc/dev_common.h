@@ -560,7 +560,14 @@ struct ReplaySeqIn { const double* rd; const int* n; const int* drop; const int*
 struct ReplayTrajIn { const int* seq_of; const uint64_t* seed; const double* sigma; const int* base; };
 template <class S> struct ReplayOut { S* rd; int* n; int* drop; int* k; int* M; int* off; int* slots; S* obs; };
 constexpr int REPLAY_CHUNK = 256;
-template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st);
+constexpr int REPLAY_SCAN_CHUNK = 64;
+// Under the Q_imu model (replay_plan.h, MODEL) t.sigma is sigma_uv[B][2] and m holds the rest: the factors L[B][144], scale[B]
+// and the frame's row of the walk table, wstart[B][6]; m.L == nullptr: the sigma4 model.
+struct ReplayModelIn { const double* L; const double* scale; const double* wstart; };
+template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st);
+// the model's walk table wstart[frames + 1][B][6] for all B trajectories: one workgroup per trajectory, REPLAY_SCAN_CHUNK frames
+// at a time.  rd / k: the sequence store's readings [frames][S][K][7] and counts [frames][S]; t.sigma and t.base are not read.
+void launch_replay_walk_scan(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, double* wstart, int frames, int S, int K, int B, hipStream_t st);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();
 void qr_device_setup();

@@ -15,6 +15,11 @@
 // All arithmetic is double whatever the handle's scalar; a value is rounded once when it is stored.  A reading's row has seven
 // scalars, so only the coordinate pairs have an alignment to store vectors by (16 bytes in double, 8 in float); they are all but
 // 7 K of a trajectory's scalars.  No LDS, no exchange between lanes.
+//
+// Under the Q_imu model (replay_plan.h, MODEL; the kernel's second instantiation) the IMU noise is no item: a sample's reading
+// needs the walk's prefix over the samples before it, so a trajectory's first workgroup forms all of them together ahead of its
+// items (model_imu: one lane per pair, per row of w = L z, per walk component, per stored scalar, handed over through LDS).
+// k_replay_walk_scan tabulates the walk at every frame's start once per assignment.
 #include "dev_common.h"
 #include "replay_plan.h"
 
@@ -39,26 +44,123 @@ __device__ __forceinline__ double noisy(double v, double sigma, double g) {
 }
 template <class S> struct alignas(2 * sizeof(S)) Vec2 { S x, y; };
 
+// ---- the Q_imu model (replay_plan.h, MODEL): a cell's samples one after the other, by one lane (the scan's)
+// w = L z of sample i: z from the pairs 6 i .. 6 i + 5 of s_imu, w_r = sum_{c <= r} L_rc z_c with c ascending, product rounded, then added
+__device__ __forceinline__ void model_w(uint64_t s_imu, int i, const double* L, double* w) {
+#pragma clang fp contract(off)
+  double z[rp::NQ];
+#pragma unroll
+  for (int p = 0; p < rp::MODEL_PAIRS; ++p) {
+    const Pair g = box_muller(s_imu, (uint64_t)(rp::MODEL_PAIRS * i + p));
+    z[2 * p] = g.c; z[2 * p + 1] = g.s;
+  }
+#pragma unroll
+  for (int r = 0; r < rp::NQ; ++r) {
+    double a = 0.0;
+#pragma unroll
+    for (int c = 0; c <= r; ++c) { const double p = L[c * rp::NQ + r] * z[c]; a = a + p; }
+    w[r] = a;
+  }
+}
+// P(f, n) of a cell: the sequential sum of the first n samples' increments, per component; rd: the cell's readings [K][7]
+__device__ __forceinline__ void model_prefix(const double* rd, uint64_t s_imu, const double* L, double scale, int n, double* P) {
+#pragma clang fp contract(off)
+  for (int c = 0; c < rp::WALK_ROW; ++c) P[c] = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const double dT = rd[i * RD_STRIDE + 6];
+    if (!(dT > 0.0)) continue;
+    double w[rp::NQ];
+    model_w(s_imu, i, L, w);
+    const double sq = sqrt(dT);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double dg = (scale * w[3 + c]) * sq, da = (scale * w[9 + c]) * sq;
+      P[c] = P[c] + dg; P[3 + c] = P[3 + c] + da;
+    }
+  }
+}
+
+// The IMU readings of one trajectory under the model, by the whole workgroup, MODEL_TILE samples at a time:
+//   1. lane j draws pair j of the tile (sample j / 6, z[2 (j % 6)], z[2 (j % 6) + 1])
+//   2. lane j forms row j % 12 of sample j / 12: w_r = sum_{c <= r} L_rc z_c, c ascending
+//   3. six lanes, one per walk component, go through the samples in order: W(f, i) = Wstart(f) + P, then P = P + delta(f, i)
+//      (P is carried from tile to tile in LDS)
+//   4. lane j stores scalar j % 6 of sample j / 6: (value + W(f, i)) + noise; rows from k on are the sequence's
+// Every sum is the normative one (replay_plan.h): who forms it changes, its order does not.
+constexpr int MODEL_TILE = 32;
 template <class S>
-__global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand(ReplaySeqIn q, ReplayTrajIn t, ReplayOut<S> o, int f, int b0, int K, int f_cap) {
+__device__ __forceinline__ void model_imu(const double* cell, S* out, const double* L, double scale, const double* wstart, uint64_t s_imu, int K, int k) {
+#pragma clang fp contract(off)
+  __shared__ double z[MODEL_TILE][rp::NQ], w[MODEL_TILE][rp::NQ], W[MODEL_TILE][rp::WALK_ROW], P[rp::WALK_ROW];
+  const int lane = (int)threadIdx.x;
+  if (lane < rp::WALK_ROW) P[lane] = 0.0;
+  for (int i0 = 0; i0 < K; i0 += MODEL_TILE) {
+    const int rows = K - i0 < MODEL_TILE ? K - i0 : MODEL_TILE;         // samples of the tile, of which n carry noise
+    const int n = k - i0 < 0 ? 0 : k - i0 < rows ? k - i0 : rows;
+    for (int j = lane; j < rp::MODEL_PAIRS * n; j += REPLAY_CHUNK) {
+      const Pair g = box_muller(s_imu, (uint64_t)(rp::MODEL_PAIRS * i0 + j));
+      z[j / rp::MODEL_PAIRS][2 * (j % rp::MODEL_PAIRS)] = g.c; z[j / rp::MODEL_PAIRS][2 * (j % rp::MODEL_PAIRS) + 1] = g.s;
+    }
+    __syncthreads();
+    for (int j = lane; j < rp::NQ * n; j += REPLAY_CHUNK) {
+      const int i = j / rp::NQ, r = j % rp::NQ;
+      double a = 0.0;
+      for (int c = 0; c <= r; ++c) { const double p = L[c * rp::NQ + r] * z[i][c]; a = a + p; }
+      w[i][r] = a;
+    }
+    __syncthreads();
+    if (lane < rp::WALK_ROW) {
+      const int r = lane < 3 ? 3 + lane : 6 + lane;                     // n_wg: rows 3 .. 5, n_wa: rows 9 .. 11
+      const double start = wstart[lane];
+      double run = P[lane];
+      for (int i = 0; i < n; ++i) {
+        W[i][lane] = start + run;
+        const double dT = cell[(i0 + i) * RD_STRIDE + 6];
+        if (dT > 0.0) { const double d = (scale * w[i][r]) * sqrt(dT); run = run + d; }
+      }
+      P[lane] = run;
+    }
+    __syncthreads();
+    for (int j = lane; j < rp::WALK_ROW * rows; j += REPLAY_CHUNK) {
+      const int i = j / rp::WALK_ROW, c = j % rp::WALK_ROW;
+      const double* rd = cell + (i0 + i) * RD_STRIDE;
+      double v = rd[c];
+      if (i < n) {
+        v = v + W[i][c];
+        const double dT = rd[6];
+        if (dT > 0.0) { const double nz = (scale * w[i][c < 3 ? c : 3 + c]) / sqrt(dT); v = v + nz; }   // n_g: rows 0 .. 2, n_a: rows 6 .. 8
+      }
+      out[(i0 + i) * RD_STRIDE + c] = (S)v;
+    }
+    __syncthreads();                                                   // the next tile overwrites z, w and W
+  }
+}
+
+// MODEL: false the sigma4 noise (the items above), true the Q_imu model (no IMU items: model_imu; t.sigma is sigma_uv[B][2])
+template <class S, bool MODEL>
+__global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand(ReplaySeqIn q, ReplayTrajIn t, ReplayModelIn m, ReplayOut<S> o, int f, int b0, int K, int f_cap) {
   const int b = b0 + (int)blockIdx.y;
   const int s = t.seq_of[b];
   const uint64_t seed = t.seed[b];
-  const double* sg = t.sigma + (long)b * rp::N_SIGMA;
+  const double* sg = t.sigma + (long)b * (MODEL ? 2 : rp::N_SIGMA);
   const int* Ms = q.M + (long)s * f_cap;
   const int* offs = q.off + (long)s * f_cap;
   const int first = offs[0];                                           // the sequence cell's first entry among the frame's sequence entries
   const int E = offs[f_cap - 1] + Ms[f_cap - 1] - first;
   const int base = t.base[b];                                          // the trajectory's first entry in the expanded block
   const int kc = q.k[s];
-  const int imu0 = E, dt0 = E + rp::IMU_PAIRS * K, m0 = dt0 + K, last = m0 + f_cap;
+  if constexpr (MODEL) {                                               // (a skipped cell's k is IMU_SKIP: no noise)
+    if (blockIdx.x == 0)
+      model_imu<S>(q.rd + (long)s * K * RD_STRIDE, o.rd + (long)b * K * RD_STRIDE, m.L + (long)b * rp::L_SIZE, m.scale[b], m.wstart + (long)b * rp::WALK_ROW, rp::imu_seed(seed, f), K, kc < K ? kc : K);
+  }
+  const int imu0 = E, dt0 = E + (MODEL ? 0 : rp::IMU_PAIRS) * K, m0 = dt0 + K, last = m0 + f_cap;
   for (int it = (int)blockIdx.x * REPLAY_CHUNK + (int)threadIdx.x; it <= last; it += (int)gridDim.x * REPLAY_CHUNK) {
     if (it < imu0) {
       const Pair g = box_muller(rp::obs_seed(seed, f), (uint64_t)it);
       const double* z = q.obs + 2 * (long)(first + it);
       o.slots[(long)base + it] = q.slots[(long)first + it];
       Vec2<S> w;
-      w.x = (S)noisy(z[0], sg[rp::SIG_U], g.c); w.y = (S)noisy(z[1], sg[rp::SIG_V], g.s);
+      w.x = (S)noisy(z[0], sg[MODEL ? 0 : rp::SIG_U], g.c); w.y = (S)noisy(z[1], sg[MODEL ? 1 : rp::SIG_V], g.s);
       *reinterpret_cast<Vec2<S>*>(o.obs + 2 * ((long)base + it)) = w;
     } else if (it < dt0) {
       const int j = it - imu0, i = j / rp::IMU_PAIRS, c = 2 * (j % rp::IMU_PAIRS);
@@ -85,13 +187,55 @@ __global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand(ReplaySeqIn q, R
 
 // max_entries: the entries of the frame's largest sequence cell (the grid's width; a trajectory with fewer leaves its lanes idle)
 template <class S>
-void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st) {
+void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st) {
   if (nb <= 0) return;
-  const long items = (long)max_entries + (long)(rp::IMU_PAIRS + 1) * K + f_cap + 1;
+  const bool model = m.L != nullptr;
+  const long items = (long)max_entries + (long)((model ? 0 : rp::IMU_PAIRS) + 1) * K + f_cap + 1;
   const dim3 grid((unsigned)((items + REPLAY_CHUNK - 1) / REPLAY_CHUNK), (unsigned)nb);
-  hipLaunchKernelGGL(k_replay_expand<S>, grid, dim3(REPLAY_CHUNK), 0, st, q, t, o, f, b0, K, f_cap);
+  if (model) hipLaunchKernelGGL((k_replay_expand<S, true>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, o, f, b0, K, f_cap);
+  else hipLaunchKernelGGL((k_replay_expand<S, false>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, o, f, b0, K, f_cap);
 }
-template void launch_replay_expand<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayOut<float>&, int, int, int, int, int, int, hipStream_t);
-template void launch_replay_expand<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayOut<double>&, int, int, int, int, int, int, hipStream_t);
+template void launch_replay_expand<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<float>&, int, int, int, int, int, int, hipStream_t);
+template void launch_replay_expand<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<double>&, int, int, int, int, int, int, hipStream_t);
+
+// The walk table of the model, wstart[frames + 1][B][6], once per assignment: workgroup b takes trajectory b.  Per chunk of
+// REPLAY_SCAN_CHUNK frames lane j forms P(f, k_f) of frame f = chunk + j serially over the cell's samples into LDS; then six
+// lanes, one per component, add the chunk's increments in frame order onto their running sum and store the rows.  The order of
+// the additions is the normative one (no tree), the sum is carried in a register from chunk to chunk.
+__global__ __launch_bounds__(REPLAY_SCAN_CHUNK) void k_replay_walk_scan(const double* rd, const int* kcell, ReplayTrajIn t, ReplayModelIn m, double* wstart, int frames, int S, int K, int B) {
+#pragma clang fp contract(off)
+  __shared__ double inc[REPLAY_SCAN_CHUNK][rp::WALK_ROW];
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double* L = m.L + (long)b * rp::L_SIZE;
+  const double scale = m.scale[b];
+  double run = 0.0;
+  if (lane < rp::WALK_ROW) wstart[(long)b * rp::WALK_ROW + lane] = 0.0;
+  for (int c0 = 0; c0 < frames; c0 += REPLAY_SCAN_CHUNK) {
+    const int f = c0 + lane;
+    if (f < frames) {
+      const long cell = (long)f * S + s;
+      const int k = kcell[cell];                                       // (a skipped cell's k is IMU_SKIP: nothing)
+      double P[rp::WALK_ROW];
+      model_prefix(rd + cell * K * RD_STRIDE, rp::imu_seed(seed, f), L, scale, k < K ? k : K, P);
+      for (int c = 0; c < rp::WALK_ROW; ++c) inc[lane][c] = P[c];
+    }
+    __syncthreads();
+    if (lane < rp::WALK_ROW) {
+      const int n = frames - c0 < REPLAY_SCAN_CHUNK ? frames - c0 : REPLAY_SCAN_CHUNK;
+      for (int j = 0; j < n; ++j) {
+        run = run + inc[j][lane];
+        wstart[((long)(c0 + j + 1) * B + b) * rp::WALK_ROW + lane] = run;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+void launch_replay_walk_scan(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, double* wstart, int frames, int S, int K, int B, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_replay_walk_scan, dim3((unsigned)B), dim3(REPLAY_SCAN_CHUNK), 0, st, rd, k, t, m, wstart, frames, S, K, B);
+}
 
 }  // namespace msckf

@@ -81,7 +81,7 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
     if (e_ != hipSuccess) return fail(-EIO, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-constexpr int NSTAGE = 12;   // 0..7: msckf_hip_profile_read; 8 k_lit_pre, 9 k_lit_gamma, 10 k_literal, 11 k_replay_expand (msckf_hip_profile_read_ex)
+constexpr int NSTAGE = 13;   // 0..7: msckf_hip_profile_read; 8 k_lit_pre, 9 k_lit_gamma, 10 k_literal, 11 k_replay_expand, 12 k_replay_walk_scan (msckf_hip_profile_read_ex)
 
 // Persistent enqueue threads of a batch (one per slice of run_frames / run_frames_streamed): a K-frame window is a few
 // milliseconds, creating and joining three std::threads per call was 1-2 % of it.
@@ -218,11 +218,13 @@ struct BatchCore {
   // per section as a resident scenario has them, scalars double), the assignment with every frame's bases, one expanded frame
   // block per slice (rp_blk: slices are at different frames at the same time, and where a trajectory's entries start depends on
   // the frame) and the scratch block of replay_expand.  rp_cells: per slice the host's k / drop / maxslot of the frame's cells,
-  // looked up through seq_of by the slice's enqueue thread.
+  // looked up through seq_of by the slice's enqueue thread.  Under the Q_imu model (rp.model) rp_sigma holds sigma_uv, and the
+  // factors, the scales and the walk table [frames + 1][B][6] (k_replay_walk_scan; rp.walk_planned) are on the device as well.
   msckf_replay::Plan rp;
   unsigned char* rp_dev[inputs::N_SECTIONS] = {nullptr}; std::vector<int> rp_maxcell;   // rp_maxcell [frames]: entries of the frame's largest sequence cell
   int* rp_seq_of = nullptr; uint64_t* rp_seed = nullptr; double* rp_sigma = nullptr; int* rp_base = nullptr; size_t rp_base_count = 0;
   bool rp_uploaded = false;                                  // the assignment and the bases on the device are the plan's
+  double* rp_L = nullptr; double* rp_scale = nullptr; double* rp_wstart = nullptr; size_t rp_wstart_count = 0;
   unsigned char* rp_blk[MAXS] = {nullptr}; size_t rp_blk_bytes = 0;
   unsigned char* rp_scratch = nullptr; size_t rp_scratch_bytes = 0;
   std::vector<int> rp_cells[MAXS];
@@ -919,6 +921,7 @@ struct BatchCore {
   void free_replay_device() {
     for (auto& p : rp_dev) dfree(p);
     dfree(rp_seq_of); dfree(rp_seed); dfree(rp_sigma); dfree(rp_base); rp_base_count = 0;
+    dfree(rp_L); dfree(rp_scale); dfree(rp_wstart); rp_wstart_count = 0;
     for (auto& p : rp_blk) dfree(p);
     rp_blk_bytes = 0;
     dfree(rp_scratch); rp_scratch_bytes = 0;
@@ -966,6 +969,14 @@ struct BatchCore {
     rp_uploaded = false;
     return 0;
   }
+  // the Q_imu model's assignment (replay_plan.h, MODEL); a later replay_assign returns to the sigma4 model
+  int replay_assign_q(const int* seq_of, const uint64_t* seed, const double* Q144, const double* scale, const double* sigma_uv) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.assign_q_refusal(seq_of, Q144, scale, sigma_uv))) return rc;
+    rp.assign_q(seq_of, seed, Q144, scale, sigma_uv);
+    rp_uploaded = false;
+    return 0;
+  }
   // before a run or an expansion (after enter()): the bases of every frame, and with the assignment on the device
   int replay_upload_plan() {
     if (rp.planned && rp_uploaded) return 0;
@@ -978,9 +989,55 @@ struct BatchCore {
     if (rp.base.size() != rp_base_count) { dfree(rp_base); rp_base_count = 0; HIPCHK(hipMalloc((void**)&rp_base, rp.base.size() * sizeof(int))); rp_base_count = rp.base.size(); }
     HIPCHK(hipMemcpy(rp_seq_of, rp.seq_of.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(rp_seed, rp.seed.data(), (size_t)B * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(rp_sigma, rp.sigma.data(), rp.sigma.size() * sizeof(double), hipMemcpyHostToDevice));
+    const bool model = rp.model == msckf_replay::MODEL_Q;
+    const std::vector<double>& sg = model ? rp.sigma_uv : rp.sigma;   // (rp_sigma has room for the larger of the two)
+    HIPCHK(hipMemcpy(rp_sigma, sg.data(), sg.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(rp_base, rp.base.data(), rp.base.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (model) {
+      if (!rp_L) { HIPCHK(hipMalloc((void**)&rp_L, (size_t)B * msckf_replay::L_SIZE * sizeof(double))); HIPCHK(hipMalloc((void**)&rp_scale, (size_t)B * sizeof(double))); }
+      HIPCHK(hipMemcpy(rp_L, rp.L.data(), rp.L.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(rp_scale, rp.scale.data(), rp.scale.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
     rp_uploaded = true;
+    return 0;
+  }
+  // under the Q_imu model, after replay_upload_plan(): the walk table of the cells and the assignment as they stand, tabulated on
+  // the handle's stream (stage 12; the slices' streams fork from it) if it is not already
+  int replay_walk_table() {
+    using namespace inputs;
+    if (rp.model != msckf_replay::MODEL_Q || rp.walk_planned) return 0;
+    const size_t need = (size_t)(rp.frames() + 1) * B * msckf_replay::WALK_ROW;
+    if (need != rp_wstart_count) {
+      HIPCHK(hipStreamSynchronize(st));
+      dfree(rp_wstart); rp_wstart_count = 0;
+      HIPCHK(hipMalloc((void**)&rp_wstart, need * sizeof(double)));
+      rp_wstart_count = need;
+    }
+    stage_begin(12, st);
+    launch_replay_walk_scan(reinterpret_cast<const double*>(rp_dev[SEC_RD]), reinterpret_cast<const int*>(rp_dev[SEC_K]), ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base},
+                            replay_model(0), rp_wstart, rp.frames(), rp.S, rp.K(), B, st);
+    stage_end(12, st);
+    HIPCHK(hipGetLastError());
+    rp.walk_planned = true;
+    return 0;
+  }
+  // the model's part of the expansion's arguments on frame f (all null under the sigma4 model)
+  ReplayModelIn replay_model(int f) const {
+    if (rp.model != msckf_replay::MODEL_Q) return ReplayModelIn{nullptr, nullptr, nullptr};
+    return ReplayModelIn{rp_L, rp_scale, rp_wstart + (size_t)f * B * msckf_replay::WALK_ROW};
+  }
+  // msckf_hip_replay_walk: rows [f0, f1) of the walk table for the trajectories [b0, b0 + nb), out [f1 - f0][nb][6]
+  int replay_walk(int f0, int f1, int b0, int nb, double* out) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.walk_refusal(f0, f1, b0, nb))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    if (int rc = replay_walk_table()) return rc;
+    constexpr int W = msckf_replay::WALK_ROW;
+    std::vector<double> rows((size_t)(f1 - f0) * B * W);
+    if (!rows.empty()) HIPCHK(hipMemcpyAsync(rows.data(), rp_wstart + (size_t)f0 * B * W, rows.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int f = 0; f < f1 - f0; ++f) std::copy(rows.begin() + ((size_t)f * B + b0) * W, rows.begin() + ((size_t)f * B + b0 + nb) * W, out + (size_t)f * nb * W);
     return 0;
   }
   // one expanded block per slice, each large enough for the largest expanded frame
@@ -1001,6 +1058,7 @@ struct BatchCore {
     if (int rc = refuse(rp.run_refusal(f0, f1))) return rc;
     if (int rc = enter()) return rc;
     if (int rc = replay_upload_plan()) return rc;
+    if (int rc = replay_walk_table()) return rc;
     const int nh = n_slices(false);
     if (int rc = replay_blocks(nh)) return rc;
     if (int rc = reserve_logs(f0, f1)) return rc;
@@ -1833,6 +1891,7 @@ struct Batch : BatchCore {
     if (int rc = refuse(rp.expand_refusal(f, b))) return rc;
     if (int rc = enter()) return rc;
     if (int rc = replay_upload_plan()) return rc;
+    if (int rc = replay_walk_table()) return rc;
     const int K = rp.K(), E = (int)rp.entries(rp.seq_of[b], f);
     if (E > cap_entries) return fail(-E2BIG, "output buffer too small for the cell's entries");
     const size_t need = rp.block_bytes(sizeof(S));
@@ -1843,7 +1902,7 @@ struct Batch : BatchCore {
       rp_scratch_bytes = need;
     }
     const ReplayOut<S> o = replay_out(rp_scratch, f);
-    launch_replay_expand<S>(replay_seq(f), replay_traj(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st);
+    launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st);
     HIPCHK(hipGetLastError());
     const size_t base = (size_t)rp.base[(size_t)f * B + b];
     std::vector<S> hr((size_t)K * RD_STRIDE), ho((size_t)2 * std::max(E, 1));
@@ -1880,7 +1939,7 @@ struct Batch : BatchCore {
     const int* cell_k = cells.k; const int* cell_drop = cells.drop;
     const int K = replay ? rp.K() : sc.lay.K;
     // replay: the slice's trajectories of this frame's block, from the sequences (outside the frame step's own stage timers)
-    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q); stage_end(11, q); }
+    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q); stage_end(11, q); }
     Dev<S> v = d;
     v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
@@ -2550,6 +2609,11 @@ int msckf_hip_replay_set_cell(msckf_hip_handle h, int frame, int seq, const doub
   return H(h)->replay_set_cell(frame, seq, readings7, k, F, M, slots, obs2, n_drop, flags);
 }
 int msckf_hip_replay_assign(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* sigma4) { if (!h || !seq_of || !seed || !sigma4) return fail(-EINVAL, "null argument"); return H(h)->replay_assign(seq_of, seed, sigma4); }
+int msckf_hip_replay_assign_q(msckf_hip_handle h, const int* seq_of, const uint64_t* seed, const double* Q144, const double* scale, const double* sigma_uv) {
+  if (!h || !seq_of || !seed || !Q144 || !scale || !sigma_uv) return fail(-EINVAL, "null argument");
+  return H(h)->replay_assign_q(seq_of, seed, Q144, scale, sigma_uv);
+}
+int msckf_hip_replay_walk(msckf_hip_handle h, int f0, int f1, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_walk(f0, f1, b0, nb, out); }
 int msckf_hip_replay_commit(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_commit(); }
 int msckf_hip_run_frames_replay(msckf_hip_handle h, int f0, int f1) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->run_frames_replay(f0, f1); }
 int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd, double* obs2, int cap_entries) { if (!h || !rd || !obs2) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, rd, obs2, nullptr, nullptr, cap_entries); }

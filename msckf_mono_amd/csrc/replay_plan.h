@@ -1,16 +1,16 @@
 // replay_plan.h -- the Monte-Carlo replay's host side, free of device calls: S noise-free SEQUENCES staged once, and B
-// trajectories that each name a sequence, a 64-bit seed and four noise levels.  Before a frame the kernel k_replay_expand
+// trajectories that each name a sequence, a 64-bit seed and a noise model: four white levels (sigma4), or the filter's own
+// 12 x 12 Q_imu with its two bias random walks (MODEL below).  Before a frame the kernel k_replay_expand
 // (kernels_replay.hip) turns the frame's S sequence cells into the ordinary per-trajectory frame block of input_layouts.h
 // (FrameLayout(B, K, f_cap, esz), sections [rd | n | drop | k | M | off | slots | obs]) -- what an upload would have put there.
 //
 // Stated once here:
 //   1. mix / U        the integer part of the random stream (value i of scenario.SplitMix64(seed) and the 53-bit uniform made of
 //                     it), constexpr, shared by this file's host users, the kernel and -- bit for bit -- the numpy twin
-//   2. the noise      which pair of which sub-seed a value takes (NOISE below)
-//   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record,
-//                     per frame each trajectory's first entry in the expanded block and the block's size, the largest expanded
-//                     frame, and every refusal with its code and text
-// Out of scope: bias random walks (they need state carried from frame to frame) and correlated Q_imu noise.
+//   2. the noise      which pair of which sub-seed a value takes (NOISE and MODEL below), and chol_psd, the factor of Q_imu
+//   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record
+//                     of either model, per frame each trajectory's first entry in the expanded block and the block's size, the
+//                     largest expanded frame, and every refusal with its code and text
 // No HIP header, no batch type: a host compiler accepts this file on its own (tests/cpp/replay_plan_host.cpp).
 #ifndef MSCKF_REPLAY_PLAN_H
 #define MSCKF_REPLAY_PLAN_H
@@ -50,6 +50,52 @@ enum Sigma { SIG_G, SIG_A, SIG_U, SIG_V, N_SIGMA };
 constexpr int IMU_PAIRS = 3;   // pairs per IMU sample
 // column c (0 .. 5) of an IMU sample is half (c & 1) of its pair c / 2 and scales with sigma[c < 3 ? SIG_G : SIG_A]
 
+// ---- 2b. MODEL: noise drawn from Q_imu, with bias random walks (msckf_hip_replay_assign_q; normative, the header and DESIGN
+// section 4.13 state the same)
+// Trajectory b has Q[b] (12 x 12, column-major, noise order n_g n_wg n_a n_wa: the filter's own Q144, taken as its symmetric
+// part 0.5 (Q + Q^T)), scale[b] >= 0 (scenario.Trajectory's imu_noise_scale) and (sigma_u, sigma_v)[b].
+//   L = chol_psd(Q_sym), lower triangular, in double, in this order: for column c, d = Q_cc - s with s = sum_{j < c} L_cj^2
+//     (terms added in ascending j, from 0); d < -1e-12 max_diag is refused; |d| <= 1e-12 max_diag makes the whole column zero (a
+//     zero walk density is the common case); otherwise L_cc = sqrt(d), L_rc = (Q_rc - sum_{j < c} L_rj L_cj) / L_cc, the sum as s.
+//   sample i < k of the cell takes pairs 6 i .. 6 i + 5 of s_imu as z[0 .. 11]: pair 6 i + p = (z[2 p], z[2 p + 1]);
+//     w_r = sum_{c <= r} L_rc z_c, c ascending from 0.0, each product rounded, then added.
+//   with dT_i > 0 (sq = sqrt(dT_i)): n_r = (scale w_r) / sq for the white rows r = 0 .. 2 (omega), 6 .. 8 (a);
+//     delta_g = (scale w[3 .. 5]) sq, delta_a = (scale w[9 .. 11]) sq.  dT_i <= 0: no noise, no increment.
+//   the walk, per component (0 .. 2 gyro, 3 .. 5 accelerometer), in double: P(f, 0) = 0, P(f, i + 1) = P(f, i) + delta(f, i);
+//     Wstart(0) = 0, Wstart(f + 1) = Wstart(f) + P(f, k_f) (skipped cells and cells with k = 0 add nothing);
+//     W(f, i) = Wstart(f) + P(f, i).  The bias starts at the sequence's constant bias, what the filter is initialised with.
+//   sample i < k stores (value + W(f, i)) + n, rounded once to the handle's scalar (n absent when dT_i <= 0); rows from k on
+//     are the sequence's (zero).  Observations as under NOISE: pair e of s_obs, obs += (sigma_u n_u, sigma_v n_v).
+// Wstart has frames + 1 rows per trajectory: row f + 1 is the true bias offset at the time of frame f's log record.  A one-off
+// scan (k_replay_walk_scan) tabulates it, so no state is carried between frames at run time.
+constexpr int NQ = 12, L_SIZE = NQ * NQ;   // L is stored whole, column-major as Q: L_rc = L[c * NQ + r]
+constexpr int MODEL_PAIRS = 6;             // pairs per IMU sample under the model
+constexpr int WALK_ROW = 6;                // scalars of a walk row: gyro bias offset, accelerometer bias offset
+constexpr double PSD_TOL = 1e-12;          // the project's symmetry tolerance, relative to the largest diagonal entry
+enum Model { MODEL_SIGMA4, MODEL_Q };
+// false: Q_sym has a negative pivot.  Q and L column-major [144]; L's upper triangle is zero.
+inline bool chol_psd(const double* Q, double* L) {
+  double A[L_SIZE], top = 0.0;
+  for (int r = 0; r < NQ; ++r) for (int c = 0; c < NQ; ++c) A[c * NQ + r] = 0.5 * (Q[c * NQ + r] + Q[r * NQ + c]);
+  for (int c = 0; c < NQ; ++c) top = std::max(top, A[c * NQ + c]);
+  for (int i = 0; i < L_SIZE; ++i) L[i] = 0.0;
+  for (int c = 0; c < NQ; ++c) {
+    double s = 0.0;
+    for (int j = 0; j < c; ++j) s += L[j * NQ + c] * L[j * NQ + c];
+    const double d = A[c * NQ + c] - s;
+    if (d < -PSD_TOL * top) return false;
+    if (std::fabs(d) <= PSD_TOL * top) continue;
+    const double p = std::sqrt(d);
+    L[c * NQ + c] = p;
+    for (int r = c + 1; r < NQ; ++r) {
+      double t = 0.0;
+      for (int j = 0; j < c; ++j) t += L[j * NQ + r] * L[j * NQ + c];
+      L[c * NQ + r] = (A[c * NQ + r] - t) / p;
+    }
+  }
+  return true;
+}
+
 // ---- 3. the plan
 using msckf_inputs::FrameLayout;
 using msckf_inputs::Refusal;
@@ -60,14 +106,18 @@ struct Plan {
   ScenarioStore seq;                 // the sequences' cells: seq.lay.B == S, scalars double; seq.frames == 0: no replay allocated
   bool committed = false;            // the cells are indexed (and, for the caller, on the device) as they stand
   bool assigned = false;
+  Model model = MODEL_SIGMA4;        // which of the two assignment records is in force
   std::vector<int> seq_of;           // [B]
   std::vector<uint64_t> seed;        // [B]
-  std::vector<double> sigma;         // [B][N_SIGMA]
+  std::vector<double> sigma;         // [B][N_SIGMA]                                    (MODEL_SIGMA4)
+  std::vector<double> L, scale, sigma_uv;   // [B][L_SIZE], [B], [B][2]                 (MODEL_Q)
   // per frame and trajectory the first entry in the expanded block, [frames][B] (a prefix sum of entries(seq_of[b], f)), and the
   // frame's entries; filled by index_trajectories()
   std::vector<int> base; std::vector<size_t> nf;
   size_t largest = 0;                // entries of the largest expanded frame
   bool planned = false;              // base / nf / largest match the cells and the assignment
+  bool walk_planned = false;         // the caller's walk table (MODEL_Q) matches the cells and the assignment: set by the caller
+                                     // when it has tabulated it, cleared here by whatever the table depends on
 
   int frames() const { return seq.frames; }
   int K() const { return seq.lay.K; }
@@ -85,8 +135,8 @@ struct Plan {
   void alloc(int n_seq, int n_frames, int K, int B_, int f_cap_) {
     S = n_seq; B = B_; f_cap = f_cap_;
     seq.reset(n_frames, n_seq, K, f_cap_, sizeof(double));
-    committed = assigned = planned = false;
-    seq_of.clear(); seed.clear(); sigma.clear(); base.clear(); nf.clear(); largest = 0;
+    committed = assigned = planned = walk_planned = false; model = MODEL_SIGMA4;
+    seq_of.clear(); seed.clear(); sigma.clear(); L.clear(); scale.clear(); sigma_uv.clear(); base.clear(); nf.clear(); largest = 0;
   }
   // the rules of one sequence cell, in scenario_set_cell's order: its place, the work-list rules, the drop, the cell rule, the readings
   Refusal cell_refusal(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, int n_drop, int flags, int m_cap, int n_cap) const {
@@ -100,7 +150,7 @@ struct Plan {
   }
   void set_cell(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) {
     seq.set_cell<double>(f, s, rd, k, (flags & msckf_lists::CELL_SKIP) != 0, F, M, slots, obs, n_drop);
-    committed = planned = false;
+    committed = planned = walk_planned = false;
   }
   Refusal commit_refusal() const {
     if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
@@ -110,7 +160,7 @@ struct Plan {
   // unless an expanded one does, which index_trajectories refuses)
   Refusal commit() {
     if (!seq.index()) return {-E2BIG, "a frame's sequence work-lists exceed 2^31 observations"};
-    committed = true; planned = false;
+    committed = true; planned = walk_planned = false;
     return {0, nullptr};
   }
 
@@ -123,7 +173,24 @@ struct Plan {
   }
   void assign(const int* seq_of_, const uint64_t* seed_, const double* sigma4) {
     seq_of.assign(seq_of_, seq_of_ + B); seed.assign(seed_, seed_ + B); sigma.assign(sigma4, sigma4 + (size_t)B * N_SIGMA);
-    assigned = true; planned = false;
+    assigned = true; planned = walk_planned = false; model = MODEL_SIGMA4;
+  }
+  // the model's assignment, in this order: the sequence, every entry finite, nothing negative, Q positive semi-definite
+  Refusal assign_q_refusal(const int* seq_of_, const double* Q144, const double* scale_, const double* sigma_uv_) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    for (int b = 0; b < B; ++b) if (seq_of_[b] < 0 || seq_of_[b] >= S) return {-EINVAL, "seq_of names no sequence of the replay"};
+    for (size_t i = 0; i < (size_t)B * L_SIZE; ++i) if (!std::isfinite(Q144[i])) return {-EINVAL, "Q, scale and sigma must be finite"};
+    for (int b = 0; b < B; ++b) if (!std::isfinite(scale_[b]) || !std::isfinite(sigma_uv_[2 * b]) || !std::isfinite(sigma_uv_[2 * b + 1])) return {-EINVAL, "Q, scale and sigma must be finite"};
+    for (int b = 0; b < B; ++b) if (scale_[b] < 0.0 || sigma_uv_[2 * b] < 0.0 || sigma_uv_[2 * b + 1] < 0.0) return {-EINVAL, "scale and sigma must not be negative"};
+    double Lb[L_SIZE];
+    for (int b = 0; b < B; ++b) if (!chol_psd(Q144 + (size_t)b * L_SIZE, Lb)) return {-EINVAL, "Q is not positive semi-definite"};
+    return {0, nullptr};
+  }
+  void assign_q(const int* seq_of_, const uint64_t* seed_, const double* Q144, const double* scale_, const double* sigma_uv_) {
+    seq_of.assign(seq_of_, seq_of_ + B); seed.assign(seed_, seed_ + B); scale.assign(scale_, scale_ + B); sigma_uv.assign(sigma_uv_, sigma_uv_ + (size_t)2 * B);
+    L.assign((size_t)B * L_SIZE, 0.0);
+    for (int b = 0; b < B; ++b) (void)chol_psd(Q144 + (size_t)b * L_SIZE, L.data() + (size_t)b * L_SIZE);
+    assigned = true; planned = walk_planned = false; model = MODEL_Q;
   }
 
   // -- a run
@@ -137,6 +204,14 @@ struct Plan {
   Refusal expand_refusal(int f, int b) const {
     if (const Refusal r = run_refusal(0, seq.frames); r.code) return r;
     if (f < 0 || f >= seq.frames || b < 0 || b >= B) return {-EINVAL, "replay cell out of range"};
+    return {0, nullptr};
+  }
+  // rows [f0, f1) of the walk table (frames + 1 rows) for the trajectories [b0, b0 + nb): the ranges, then what has to have happened
+  Refusal walk_refusal(int f0, int f1, int b0, int nb) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    if (f0 < 0 || f1 > seq.frames + 1 || f0 > f1 || b0 < 0 || nb < 0 || b0 + nb > B) return {-EINVAL, "walk range out of bounds"};
+    if (!committed) return {-EINVAL, "replay not committed"};
+    if (!assigned || model != MODEL_Q) return {-EINVAL, "replay not assigned through msckf_hip_replay_assign_q"};
     return {0, nullptr};
   }
   // base, nf and largest from the committed cells and the assignment

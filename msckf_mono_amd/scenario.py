@@ -66,7 +66,8 @@ class SplitMix64:
 # ------------------------------------------------------------------ Monte-Carlo replay: the numpy twin of csrc/replay_plan.h
 # The noise a replay adds on the device is a pure function of (seed, frame, index); include/msckf_hip.h states it, this is its
 # twin.  The integer part (replay_mix, replay_uniform) agrees with the host and device code bit for bit; ln, sqrt, cos and sin
-# are numpy's.  Out of scope: bias random walks (they need state carried between frames) and correlated Q_imu noise.
+# are numpy's.  Two noise models: four white levels (replay_noise / replay_cell / replay_expand), or the filter's Q_imu with its
+# bias random walks (replay_noise_factor / replay_model_* / replay_walk / replay_bias_gt, further down).
 def replay_mix(seed, i):
     """value i (0-based; an int or an array) of SplitMix64(seed), as uint64"""
     with np.errstate(over="ignore"):
@@ -125,6 +126,122 @@ def replay_expand(seq_traj, frame, seed, sigma4):
     """frame `frame` of the noise-free Trajectory seq_traj (imu_noise_scale = 0, obs_noise_px = 0) with the replay's noise:
     (readings [IMU_PER_FRAME][7], obs [n][2]); M and slots are the sequence's own"""
     return replay_cell(seq_traj.imu_for_frame(frame), seq_traj.frames[frame]["obs"], frame, seed, sigma4)
+
+
+# ---- the Q_imu model (csrc/replay_plan.h, MODEL; include/msckf_hip.h, msckf_hip_replay_assign_q): correlated noise drawn from
+# the filter's own 12 x 12 Q_imu (noise order n_g n_wg n_a n_wa) and the two bias random walks.  Every sum below is formed in the
+# order the header states, one rounded operation after the other, so that given the same draws the device's bits are these.
+REPLAY_PSD_TOL = 1e-12
+
+
+def replay_noise_factor(Q):
+    """L = chol_psd(0.5 (Q + Q^T)), [12][12] lower triangular, as replay_plan.h forms it: column by column, d = Q_cc - sum_j L_cj^2
+    (ascending j); d < -1e-12 max_diag raises ValueError, |d| <= 1e-12 max_diag leaves the column zero"""
+    Q = np.asarray(Q, dtype=np.float64).reshape(12, 12)
+    A = 0.5 * (Q + Q.T)
+    top = max(0.0, float(np.max(np.diag(A))))
+    L = np.zeros((12, 12))
+    for c in range(12):
+        s = 0.0
+        for j in range(c):
+            s = s + L[c, j] * L[c, j]
+        d = A[c, c] - s
+        if d < -REPLAY_PSD_TOL * top:
+            raise ValueError("Q is not positive semi-definite")
+        if abs(d) <= REPLAY_PSD_TOL * top:
+            continue
+        p = np.sqrt(d)
+        L[c, c] = p
+        for r in range(c + 1, 12):
+            t = 0.0
+            for j in range(c):
+                t = t + L[r, j] * L[c, j]
+            L[r, c] = (A[r, c] - t) / p
+    return L
+
+
+def replay_model_draws(seed, frame, k, L, pairs_per_sample=6):
+    """w [k][12] of a cell's samples: z[i] = pairs 6 i .. 6 i + 5 of s_imu, w_r = sum_{c <= r} L_rc z_c with c ascending from 0.0"""
+    k = max(int(k), 0)
+    s_imu = replay_subseeds(seed, frame)[0]
+    j = (np.uint64(pairs_per_sample) * np.arange(k, dtype=np.uint64))[:, None] + np.arange(6, dtype=np.uint64)[None, :]
+    u1 = 1.0 - replay_uniform(s_imu, np.uint64(2) * j)
+    u2 = replay_uniform(s_imu, np.uint64(2) * j + np.uint64(1))
+    r = np.sqrt(-2.0 * np.log(u1))
+    z = np.stack([r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2)], -1).reshape(k, 12)
+    L = np.asarray(L, dtype=np.float64)
+    w = np.zeros((k, 12))
+    for row in range(12):
+        a = np.zeros(k)
+        for c in range(row + 1):
+            a = a + L[row, c] * z[:, c]
+        w[:, row] = a
+    return w
+
+
+def replay_model_increments(dT, w, scale):
+    """(noise [k][6] on omega and a, delta [k][6] of the gyro and accelerometer bias) of samples with steps dT [k] and draws
+    w [k][12]: (scale w) / sqrt(dT) of rows 0:3, 6:9 and (scale w) sqrt(dT) of rows 3:6, 9:12; both zero where dT <= 0"""
+    dT = np.asarray(dT, dtype=np.float64)
+    ok = dT > 0.0
+    sq = np.sqrt(np.where(ok, dT, 1.0))[:, None]
+    sw = float(scale) * w
+    noise = np.where(ok[:, None], sw[:, [0, 1, 2, 6, 7, 8]] / sq, 0.0)
+    delta = np.where(ok[:, None], sw[:, [3, 4, 5, 9, 10, 11]] * sq, 0.0)
+    return noise, delta
+
+
+def replay_model_cell(readings, obs, frame, seed, L, scale, sigma_uv, w_start, K=None):
+    """a noise-free cell (readings [k][7], obs [n][2]) as trajectory `seed` sees it on `frame` under the model, the walk standing
+    at w_start [6] when the frame begins: (readings [K][7] with rows from k on zero, obs [n][2], w_end [6] = the walk after the
+    cell's k samples, Wstart of the next frame)"""
+    rd = np.asarray(readings, dtype=np.float64).reshape(-1, 7)
+    ob = np.asarray(obs, dtype=np.float64).reshape(-1, 2)
+    k = len(rd)
+    K = k if K is None else int(K)
+    noise, delta = replay_model_increments(rd[:, 6], replay_model_draws(seed, frame, k, L), scale)
+    P = np.zeros((k + 1, 6))
+    for i in range(k):
+        P[i + 1] = P[i] + delta[i]
+    w_start = np.asarray(w_start, dtype=np.float64)
+    out = np.zeros((K, 7))
+    out[:k] = rd
+    out[:k, :6] = (rd[:, :6] + (w_start + P[:k])) + noise
+    nz = replay_pairs(replay_subseeds(seed, frame)[1], len(ob))
+    return out, ob + np.array([float(sigma_uv[0]), float(sigma_uv[1])]) * nz, w_start + P[k]
+
+
+def _replay_cells(seq_traj_or_cells):
+    if hasattr(seq_traj_or_cells, "imu_for_frame"):
+        return [seq_traj_or_cells.imu_for_frame(f) for f in range(seq_traj_or_cells.n_frames)]
+    return [np.zeros((0, 7)) if c is None else np.asarray(c, dtype=np.float64).reshape(-1, 7) for c in seq_traj_or_cells]
+
+
+def replay_walk(seq_traj_or_cells, seed, L, scale):
+    """Wstart [frames + 1][6] of a trajectory that replays a noise-free Trajectory, or a list of per-frame readings [k][7] (None
+    or empty: a skipped cell or one without samples): Wstart[0] = 0, Wstart[f + 1] = Wstart[f] + P(f, k_f)"""
+    cells = _replay_cells(seq_traj_or_cells)
+    W = np.zeros((len(cells) + 1, 6))
+    for f, rd in enumerate(cells):
+        W[f + 1] = replay_model_cell(rd, np.zeros((0, 2)), f, seed, L, scale, (0.0, 0.0), W[f])[2]
+    return W
+
+
+def replay_model_expand(seq_traj, frame, seed, L, scale, sigma_uv, w_start=None):
+    """frame `frame` of the noise-free Trajectory seq_traj under the model: (readings [IMU_PER_FRAME][7], obs [n][2]);
+    w_start: the frame's row of replay_walk (computed here when not given)"""
+    if w_start is None:
+        w_start = replay_walk(seq_traj, seed, L, scale)[frame]
+    return replay_model_cell(seq_traj.imu_for_frame(frame), seq_traj.frames[frame]["obs"], frame, seed, L, scale, sigma_uv, w_start)[:2]
+
+
+def replay_bias_gt(trajs, walks):
+    """the true b_g, b_a at each frame-log record: [frames][B][6] = trajs[b]'s constant biases + walks[f + 1][b] (walks
+    [frames + 1][B][6]: Batch.replay_walk() or the stacked replay_walk of each trajectory), to take bias errors and bias NEES
+    from frame_log_read by"""
+    walks = np.asarray(walks, dtype=np.float64)
+    const = np.stack([np.concatenate([tr.b_g, tr.b_a]) for tr in trajs])
+    return const[None, :, :] + walks[1:]
 
 
 def rot_to_quat(R):

@@ -7,7 +7,11 @@ Both handles run the same frames on the same inputs (checked: the final IMU stat
 each, alternating in one process; every window starts from freshly initialised filters brought through the fill frames on the
 path that is timed.  Prints one JSON line: median and all window times, frames/s, the bytes per frame each path keeps on the
 host, page-locks and sends over PCIe (computed from the shapes), and the expansion kernel's time per frame from the library's
-stage timers (a run of its own: profiling forces one slice)."""
+stage timers (a run of its own: profiling forces one slice).
+
+--model q: the Q_imu noise model against the sigma4 one instead (no streamed handle): two replay handles on the same sequences,
+one assigned through replay_assign (sigma4), one through replay_assign_q (the filter's diagonal Q_imu with both walks, scale
+0.05), windows alternating in one process; the expansion's stage time for each, and the one-off walk scan's (stage 12)."""
 import argparse
 import json
 import os
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--fill", type=int, default=30)
     ap.add_argument("--timed", type=int, default=40)
     ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--model", choices=("sigma4", "q"), default="sigma4")
     args = ap.parse_args()
     N, F, S, B, fill, nf = args.window, args.tracks, args.sequences, args.sequences * args.seeds, args.fill, args.fill + args.timed
     K, esz = sc.IMU_PER_FRAME, 4
@@ -80,6 +85,8 @@ def main():
     rp.replay_assign(seq_of, seeds, sigma)
     rp.replay_commit()
     t_replay_setup = time.time() - t0
+    if args.model == "q":
+        return model_q(args, rp, handle, reinit, seqs, seq_of, seeds, sigma, cfg)
     t0 = time.time()
     st = handle()
     st.scenario_alloc(nf, K)
@@ -140,6 +147,57 @@ def main():
     print(json.dumps(out))
     st.close()
     rp.close()
+
+
+def model_q(args, rp, handle, reinit, seqs, seq_of, seeds, sigma, cfg):
+    """the sigma4 replay handle rp against a second one under the Q_imu model"""
+    fill, nf, K = args.fill, args.fill + args.timed, sc.IMU_PER_FRAME
+    Q = np.diag(np.asarray(cfg["Q_imu_diag"], dtype=np.float64))
+    rq = handle()
+    rq.replay_alloc(len(seqs), nf, K)
+    for f in range(nf):
+        for s, tr in enumerate(seqs):
+            fr = tr.frames[f]
+            rq.replay_set_cell(f, s, tr.imu_for_frame(f), fr["M"], fr["slots"], fr["obs"], 1 if fr["Nw"] == args.window else 0)
+    rq.replay_assign_q(seq_of, seeds, Q, 0.05, sigma[2:])
+    rq.replay_commit()
+    paths = {"replay": rp, "replay_q": rq}
+    times = {k: [] for k in paths}
+    for w in range(args.windows + 1):                       # window 0 warms both paths up and is not reported
+        for name, bt in paths.items():
+            reinit(bt)
+            bt.run_frames_replay(0, fill)
+            bt.sync()
+            t0 = time.perf_counter()
+            bt.run_frames_replay(fill, nf)
+            bt.sync()
+            if w:
+                times[name].append(time.perf_counter() - t0)
+    stages = {}
+    for name, bt in paths.items():
+        reinit(bt)
+        bt.run_frames_replay(0, fill)
+        bt.profile_enable(True)
+        if name == "replay_q":
+            rq.replay_assign_q(seq_of, seeds, Q, 0.05, sigma[2:])     # the same assignment again: the next run tabulates the walk anew
+        bt.run_frames_replay(fill, nf)
+        prof = bt.profile_read()
+        stages[name] = dict(expand_ms_per_frame=prof["replay_expand"][0] / max(prof["replay_expand"][1], 1), expand_launches=prof["replay_expand"][1],
+                            walk_scan_ms=prof["replay_walk_scan"][0], walk_scan_launches=prof["replay_walk_scan"][1], event_pair_overhead_ms=bt.profile_event_overhead())
+        bt.profile_enable(False)
+    walk = rq.replay_walk()
+    med = {k: statistics.median(v) for k, v in times.items()}
+    entries = sum(int(seqs[s].frames[nf - 1]["M"].sum()) for s in seq_of)
+    print(json.dumps({
+        "shape": dict(dtype="f32", window=args.window, tracks=args.tracks, sequences=len(seqs), trajectories=len(seq_of), fill_frames=fill, timed_frames=args.timed, windows=args.windows),
+        "slices": {k: bt.effective_streams(False) for k, bt in paths.items()},
+        "window_s": times, "median_window_s": med, "ms_per_frame": {k: 1e3 * v / args.timed for k, v in med.items()},
+        "model_over_sigma4_time": med["replay_q"] / med["replay"], "stages": stages,
+        "items_per_frame": {"entries": entries, "imu_sigma4": 3 * K * len(seq_of), "imu_model": K * len(seq_of)},
+        "walk_table_bytes": int(walk.nbytes), "walk_rms_last_row": float(np.sqrt(np.mean(walk[-1] ** 2))),
+    }))
+    rp.close()
+    rq.close()
 
 
 if __name__ == "__main__":
