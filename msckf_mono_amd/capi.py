@@ -40,7 +40,7 @@ SYMBOLS = [
     "msckf_hip_map_log_enable", "msckf_hip_map_log_reset", "msckf_hip_map_log_frames", "msckf_hip_map_log_counts", "msckf_hip_map_log_read", "msckf_hip_map_log_metrics",
     "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
-    "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk",
+    "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -280,6 +280,15 @@ class Batch:
 
     def last_tracks(self, b):
         o = np.zeros((self.f_cap, 8)); n = _chk(self.L.msckf_hip_last_tracks(self.h, b, o.ctypes.data_as(_dp), self.f_cap)); return o[:n]
+
+    def last_track_blocks(self, b):
+        """per track of the last marginalize, as the feature kernels stored it for the information form: dict of first [F], last [F]
+        (camera slots), Hx [F][m_cap][2][6], rw [F][m_cap][2], B [F][3][6 n_cap + 1] (stale where a track has no observation / slot)"""
+        F, m, nc = self.f_cap, self.m_cap, 6 * self.n_cap + 1
+        first, Hx, rw, Bh = np.zeros(F, np.int32), np.zeros((F, m, 2, 6)), np.zeros((F, m, 2)), np.zeros((F, 3, nc))
+        n = _chk(self.L.msckf_hip_last_track_blocks(self.h, int(b), first.ctypes.data_as(_ip), Hx.ctypes.data_as(_dp), rw.ctypes.data_as(_dp),
+                                                    Bh.ctypes.data_as(_dp), F))
+        return dict(first=first[:n] & 255, last=first[:n] >> 8, Hx=Hx[:n], rw=rw[:n], B=Bh[:n])
 
     def last_deltax(self, b):
         cap = 15 + 6 * self.n_cap

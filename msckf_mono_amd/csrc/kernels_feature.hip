@@ -1039,13 +1039,18 @@ __device__ unsigned long long g_featp_cycles[8];
 #define FP_TICK(slot) do { } while (0)
 #endif
 
-// Register budget: three wavefronts per SIMD (168 registers, 5 values per lane in scratch).  At four (128 registers) 34 live values
-// per lane sit in scratch: 56 MB of the launch's 96 MB of writes at 64 trajectories (166 MB of traffic per launch instead of 64),
-// ~70 scratch instructions per wavefront.  Throughput: the three-wavefront build was ahead while the slices ran the one-track form
-// (185-189 k -> 192-193 k updates/s), with pairs in the slices the four-wavefront build is (medians 203.8 / 204.6 k vs 207.2 /
-// 208.6 k, alternating runs on one lease: 1.5 %, inside what leases differ by) -- the build that moves a third of the bytes ships.
-// (Both side by side, picked by launch size: the 128-register one then reads 95 us for the large launches, warm or not.)
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_feature_pair(Dev<float> d, int b0, int nb, int lm, int m_lo, int m_hi, int s_cap, int items, int single) {
+// Register budget: routes::PAIR_WAVES_PER_SIMD = four wavefronts per SIMD, 128 registers, nothing in scratch.  A slice of 32
+// trajectories is 3 200 pair-wavefronts; at three per SIMD (168 registers, what shipped before) the chip has 3 072 slots and the
+// other slice's Choleskys hold part of them, so the launch ran a second, partial residency (routes::feature_pair_residency).
+// At 128 registers the kernel used to keep 33 values per lane in scratch (136 bytes; 22 + 25 scratch instructions per wavefront,
+// 56 MB of the launch's 96 MB of writes at 64 trajectories).  None of them came from the G assembly's 6 x 6 blocks: the compiler
+// had (1) formed the rows, columns and packed offsets of gate_chol_dpp's 36 blocks, which depend on the lane alone, once in
+// front of the pass loop -- about thirty registers alive through the G assembly -- and (2) formed the nine f64 sums of normal_eq
+// once for the early accept and the tail, 18 registers alive through both factorizations.  The two empty asm statements below
+// (at the factorization and at the tail) end both; no sum changes (profiles/feature_pair_residency.md).
+// (One build only.  Two register budgets side by side, picked by launch size, once made the 128-register one read 95 us for the
+// large launches, warm or not: never understood, not brought back.)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(routes::PAIR_WAVES_PER_SIMD, routes::PAIR_WAVES_PER_SIMD))) void k_feature_pair(Dev<float> d, int b0, int nb, int lm, int m_lo, int m_hi, int s_cap, int items, int single) {
   typedef float S;
   int bi, w;
   if (!xcd_item(nb, items, bi, w)) return;
@@ -1457,15 +1462,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
       const S* G = sG + (s ? offB : 0);
       const int R2 = 2 * (s ? MB : MA), nbr = (R2 + 4 + 7) >> 3;   // 8 x 8 blocks in use (wave-uniform)
       bool ok;
+      // (the lane is held opaque per factorization: the rows, columns and packed offsets gate_chol_dpp derives from it depend on
+      // nothing else, and the compiler otherwise forms them once in front of the pass loop -- about thirty registers that live
+      // through the G assembly for a few hundred instructions saved)
+      int lane_f = lane;
+      asm volatile("" : "+v"(lane_f));
       switch (nbr) {
-        case 1: ok = gate_chol_dpp<1>(G, sC, lane, R2, sig2); break;
-        case 2: ok = gate_chol_dpp<2>(G, sC, lane, R2, sig2); break;
-        case 3: ok = gate_chol_dpp<3>(G, sC, lane, R2, sig2); break;
-        case 4: ok = gate_chol_dpp<4>(G, sC, lane, R2, sig2); break;
-        case 5: ok = gate_chol_dpp<5>(G, sC, lane, R2, sig2); break;
-        case 6: ok = gate_chol_dpp<6>(G, sC, lane, R2, sig2); break;
-        case 7: ok = gate_chol_dpp<7>(G, sC, lane, R2, sig2); break;
-        default: ok = gate_chol_dpp<8>(G, sC, lane, R2, sig2); break;
+        case 1: ok = gate_chol_dpp<1>(G, sC, lane_f, R2, sig2); break;
+        case 2: ok = gate_chol_dpp<2>(G, sC, lane_f, R2, sig2); break;
+        case 3: ok = gate_chol_dpp<3>(G, sC, lane_f, R2, sig2); break;
+        case 4: ok = gate_chol_dpp<4>(G, sC, lane_f, R2, sig2); break;
+        case 5: ok = gate_chol_dpp<5>(G, sC, lane_f, R2, sig2); break;
+        case 6: ok = gate_chol_dpp<6>(G, sC, lane_f, R2, sig2); break;
+        case 7: ok = gate_chol_dpp<7>(G, sC, lane_f, R2, sig2); break;
+        default: ok = gate_chol_dpp<8>(G, sC, lane_f, R2, sig2); break;
       }
       const S gm = ok ? gate_gamma_from_corner<S>(sC) : S(0);
       if (g == s) { spd = ok; gamma = gm; }
@@ -1489,6 +1499,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
   // spilled register -- waited for all of them to drain (the kernel published H_x and B^ before the gate to shorten B^'s 36
   // registers' lives: 14 us of the launch went into those waits)
   {
+    // (the sums of normal_eq are redone from H_x and r here: were the compiler to see that they are the early accept's, it would
+    // form them once in front of the gate and carry nine doubles, 18 registers, through both factorizations)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      asm volatile("" : "+v"(r[i]));
+#pragma unroll
+      for (int k = 3; k < 6; ++k) asm volatile("" : "+v"(hx[i][k]));
+    }
     const Lq q = normal_eq();
     double Bq[3][6];
     const double f0[3] = {-(double)hx[0][3], -(double)hx[0][4], -(double)hx[0][5]}, f1[3] = {-(double)hx[1][3], -(double)hx[1][4], -(double)hx[1][5]};
@@ -1842,9 +1860,8 @@ void launch_feature(const Dev<S>& d, int b0, int nb, hipStream_t st) {
     const routes::FeatureLaunch& l = r.l[i];
     if (l.pair) {
       if constexpr (sizeof(S) == 4) {
-        int s_cap = 0;
-        const size_t lds = routes::feature_pair_lds_bytes(l.lm, s_cap);
-        hipLaunchKernelGGL(k_feature_pair, dim3(xcd_grid(nb, l.items)), dim3(64), lds, st, d, b0, nb, l.lm, l.m_lo, l.m_hi, s_cap, l.items, l.single);
+        const routes::PairResidency res = routes::feature_pair_residency(l.lm);   // lm <= M_REG: sixteen wavefronts' LDS fits a compute unit
+        hipLaunchKernelGGL(k_feature_pair, dim3(xcd_grid(nb, l.items)), dim3(64), res.lds_bytes, st, d, b0, nb, l.lm, l.m_lo, l.m_hi, res.s_cap, l.items, l.single);
       }
       continue;
     }

@@ -1187,6 +1187,7 @@ struct BatchCore {
   virtual int get_cov(int b, double* P, int ldo) = 0;
   virtual int set_cov(int b, const double* P, int D) = 0;
   virtual int track_info(int b, double* out, int cap) = 0;
+  virtual int track_blocks(int b, int* first, double* Hx, double* rw, double* Bh, int cap) = 0;
   virtual int deltax(int b, double* out, int cap) = 0;
   virtual int scen_set(int f, int b, const double* rd, int k, int F, const int* M, const int* slots, const double* obs, int n_drop, int flags) = 0;
   // THE frame step of run_frames / run_frames_streamed / run_frames_replay: frame f of a call over [f0, f1) for slice s, inputs
@@ -1828,6 +1829,28 @@ struct Batch : BatchCore {
       o[1] = (stt[t] & ST_TRI_VALID) ? 1 : 0; o[2] = (stt[t] & ST_GATE_PASS) ? 1 : 0; o[3] = (stt[t] & ST_INCLUDED) ? 1 : 0;
       o[4] = (double)gm[t]; o[5] = (double)pf[4 * t]; o[6] = (double)pf[4 * t + 1]; o[7] = (double)pf[4 * t + 2];
     }
+    return F;
+  }
+  // what the feature kernels left per track for the information form, as stored (entries beyond a track's observations or
+  // outside its slot range are whatever the buffers held): first [F], Hx [F][m_cap][12], rw [F][m_cap][2], Bh [F][3][6 n_cap + 1]
+  int track_blocks(int b, int* first, double* Hx, double* rw, double* Bh, int cap) override {
+    if (int rc = enter_traj(b)) return rc;
+    if (!d.trk_B || !d.trk_Hx || !d.trk_rw) return fail(-ENOTSUP, "the per-track blocks exist on the information-form route with an f32 / f64 Jacobian only");
+    int tmp[STAT_STRIDE];
+    if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
+    const int F = tmp[STAT_NTRACKS];
+    if (F > cap) return fail(-E2BIG, "output buffer too small");
+    if (!F) return 0;
+    const size_t tb = (size_t)b * f_cap, nh = (size_t)F * m_cap * 12, nr = (size_t)F * 2 * m_cap, ldR = (size_t)d.ldR, nB = (size_t)F * 3 * ldR, nc = 6 * (size_t)n_cap + 1;
+    std::vector<S> hx(nh), r(nr); std::vector<double> bb(nB);
+    HIPCHK(hipMemcpyAsync(first, d.trk_first + tb, F * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hx.data(), d.trk_Hx + tb * m_cap * 12, nh * sizeof(S), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(r.data(), d.trk_rw + tb * 2 * m_cap, nr * sizeof(S), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bb.data(), d.trk_B + tb * 3 * ldR, nB * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t i = 0; i < nh; ++i) Hx[i] = (double)hx[i];
+    for (size_t i = 0; i < nr; ++i) rw[i] = (double)r[i];
+    for (size_t q = 0; q < (size_t)F * 3; ++q) for (size_t c = 0; c < nc; ++c) Bh[q * nc + c] = bb[q * ldR + c];
     return F;
   }
   int deltax(int b, double* out, int cap) override {
@@ -2579,6 +2602,7 @@ int msckf_hip_last_stats(msckf_hip_handle h, int b, int* out7) { return H(h)->st
 int msckf_hip_clear_error_flags(msckf_hip_handle h, int b) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->clear_errors(b); }
 int msckf_hip_last_tracks(msckf_hip_handle h, int b, double* out8, int cap) { return H(h)->track_info(b, out8, cap); }
 int msckf_hip_last_deltax(msckf_hip_handle h, int b, double* dx, int cap) { return H(h)->deltax(b, dx, cap); }
+int msckf_hip_last_track_blocks(msckf_hip_handle h, int b, int* first, double* Hx, double* rw, double* Bh, int cap) { return H(h)->track_blocks(b, first, Hx, rw, Bh, cap); }
 
 int msckf_hip_set_tracks(msckf_hip_handle h, int b, int F, const int* M, const int* slots, const double* obs2) { return H(h)->set_tracks(b, F, M, slots, obs2); }
 int msckf_hip_propagate_range(msckf_hip_handle h, int b0, int nb, const double* readings7, int K) { return H(h)->propagate(b0, nb, readings7, K); }

@@ -28,6 +28,7 @@ constexpr int M_STAGED = 62;                // float: longest track whose gate m
 constexpr int LONG_BIN_SPLIT = 16;          // long tracks without the staged kernel: two bins once the range beyond M_REG spans this many lengths
 constexpr int PAIR_F_CAP = 512;             // k_feature_pair: track capacity (its NC = 8 status words per lane)
 constexpr int PAIR_SINGLE_TRACKS = 1024;    // k_feature_pair: a launch of at most this many tracks takes one track per wavefront
+constexpr int PAIR_WAVES_PER_SIMD = 4;      // k_feature_pair: wavefronts per SIMD its register budget is held to (the kernel's attribute reads this)
 constexpr int INFO_F_CAP = 1024;            // information-form compression: track capacity
 constexpr int BLOCKS_ONE_LEVEL = 12;        // blocked matrix-core Cholesky: 16-column blocks in one level (192 columns)
 constexpr int BLOCKS_TWO_LEVELS = 24;       // ... in two levels (384 columns)
@@ -51,6 +52,26 @@ inline size_t feature_pair_lds_bytes(int lm, int& s_cap) {
   s_cap = r2 * (r2 + 1) / 2 + 12 * 13 / 2;            // the longest track + a 4-observation partner
   if (s_cap < 64) s_cap = 64;                          // the prologue's histogram lives there
   return ((size_t)s_cap + 16) * sizeof(float) + 2 * (size_t)lm * sizeof(int) + 16;
+}
+// Slots of k_feature_pair: its workgroups are single wavefronts, so a compute unit holds waves_per_simd of them on each of its
+// four SIMDs as far as its LDS holds that many.  PAIR_WAVES_PER_SIMD is four because a slice of 32 trajectories x 200 tracks
+// is 3 200 pair-wavefronts: three per SIMD are 3 072 slots on 256 compute units, one residency does not take the launch even on
+// an empty chip; four are 4 096 (tests/test_feature_residency.py).
+constexpr int SIMDS_PER_CU = 4;
+struct PairResidency {
+  int s_cap; size_t lds_bytes;   // what the launch asks for (feature_pair_lds_bytes)
+  bool lds_fits;                 // SIMDS_PER_CU x waves_per_simd wavefronts' LDS fits FEATURE_LDS: the registers bound the residency
+  int waves_per_cu;              // the smaller of the two bounds
+  long slots(int cus) const { return (long)cus * waves_per_cu; }
+  bool one_residency(long wavefronts, int cus) const { return wavefronts <= slots(cus); }
+};
+inline PairResidency feature_pair_residency(int lm, int waves_per_simd = PAIR_WAVES_PER_SIMD) {
+  PairResidency r{};
+  r.lds_bytes = feature_pair_lds_bytes(lm, r.s_cap);
+  const size_t by_regs = (size_t)SIMDS_PER_CU * waves_per_simd, by_lds = FEATURE_LDS / r.lds_bytes;
+  r.lds_fits = by_regs <= by_lds;
+  r.waves_per_cu = (int)(r.lds_fits ? by_regs : by_lds);
+  return r;
 }
 
 // ---------------------------------------------------------------- geometry of a handle
