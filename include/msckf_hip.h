@@ -449,6 +449,17 @@ int msckf_hip_set_covariance_update(msckf_hip_handle h, int form);
  * frame left behind).  Bit-identical results; OFF by default -- on MI355X at the benchmark configuration the per-track
  * kernel starves the latency-bound propagate/augment workgroups of CUs (100 k -> 82 k updates/s). */
 int msckf_hip_set_feature_overlap(msckf_hip_handle h, int on);
+/* run_frames (resident, streamed and replay inputs): the order of a frame's first launches.  1 (default): on a frame where
+ * no track of the slice observes the camera state that augmentState adds, every window of the slice has room for it and no
+ * cell is skipped, the per-track kernel runs FIRST, from what the previous frame's prune left, and the track selection shares
+ * ONE launch with propagate + augmentState on the slice's own stream -- one launch less on the frame's latency chain.  Float
+ * handles on the information-form route; never the first frame of a call, never while the stage profile is on; every other
+ * frame, and every frame of a double handle, takes order 0: propagate + augmentState, per-track kernel, selection.
+ * Bit-identical results either way.  -EINVAL for any other value.
+ * msckf_hip_get_frame_order_count: how many frames took order 1 since the handle was created, counted once per slice
+ * (msckf_hip_set_streams) and frame. */
+int msckf_hip_set_frame_order(msckf_hip_handle h, int order);
+int msckf_hip_get_frame_order_count(msckf_hip_handle h, long long* count);
 /* Anisotropic pixel noise, u_var_prime != v_var_prime (see the header comment): mode 0 (default) the reference's
  * R_o_j = A_j^T R_j A_j / HouseholderQR in column order / R_n = Q_1^T R_o Q_1 on the device (msckf.h:423-431, 1343-1366;
  * f64: the Householder sweep for its decisions, the result as a projection onto range(Q_1), kernels_literal.hip), handed to the

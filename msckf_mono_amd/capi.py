@@ -41,6 +41,7 @@ SYMBOLS = [
     "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
+    "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -473,6 +474,17 @@ class Batch:
 
     def set_feature_overlap(self, on):
         _chk(self.L.msckf_hip_set_feature_overlap(self.h, 1 if on else 0))
+
+    def set_frame_order(self, order):
+        """run_frames: 1 (default) feature kernel first and selection beside propagate + augmentState in one launch on the
+        frames that allow it, 0 propagate first on every frame; same bits either way."""
+        _chk(self.L.msckf_hip_set_frame_order(self.h, int(order)))
+
+    def frame_order_count(self):
+        """frames (one count per slice and frame) that took order 1 since the handle was created"""
+        n = C.c_longlong(0)
+        _chk(self.L.msckf_hip_get_frame_order_count(self.h, C.byref(n)))
+        return n.value
 
     def set_gate_early_accept(self, on):
         _chk(self.L.msckf_hip_set_gate_early_accept(self.h, 1 if on else 0))

@@ -525,6 +525,8 @@ template <class S> void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_
 template <class S> void launch_feature(const Dev<S>& d, int b0, int nb, hipStream_t st);
 template <class S> void launch_select(const Dev<S>& d, int b0, int nb, hipStream_t st);
 template <class S> void launch_select_diag(const Dev<S>& d, int b0, int nb, hipStream_t st);   // k_select + block-diagonal part of Lam^ in one launch
+// launch_select_diag's workgroups and launch_propagate's (then_augment, qroute 0 | 2) in ONE launch (k_propagate's HEAD instance, kernels_state.hip; float only)
+template <class S> void launch_frame_head(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, int qroute, const int* cnt);
 // phase: 0 = stage 1 + merges, 1 = stage 1 only (chunk-local QR updates), 2 = merge tree only
 template <class S> void launch_compress(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase);
 // phase: 0 = both, 1 = Gram accumulation only, 2 = Cholesky only, 3 = SYRK only (the block-diagonal part came with launch_select_diag)

@@ -12,6 +12,7 @@
 // augmentation uses the 6 non-zero 3x3 blocks of J instead of two dense (D+6) x D GEMMs and never
 // computes the unused determinant of msckf.h:176.
 #include "dev_common.h"
+#include "select_diag.h"
 
 namespace msckf {
 
@@ -163,10 +164,34 @@ __global__ __launch_bounds__(256) void k_augment(Dev<S> d, int b0, const int* cn
 // launch's i-th trajectory -- uniform over its workgroup; only that many rows of its readings are read.  0: nothing is propagated
 // (state and covariance are not rewritten), the fused augment still runs: bit for bit k_augment alone.  IMU_SKIP (< 0): the
 // trajectory has no image on this frame -- a deferred window size is committed (the frame's later kernels read ncam), nothing else.
-template <class S, bool AUGMENT, int QM>
-__global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K, const int* cnt) {
-  const int b = b0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (cnt) K = cnt[blockIdx.x];
+//
+// HEAD (k_propagate<float, true, QM, true>, launch_frame_head): the frame step's feature-first order (routes::frame_order,
+// frame_order.h).  The frame's k_feature has run in front of this launch, from what the previous frame's prune left, and the
+// launch holds what comes next on the chain in ONE grid of (ndiag + 2) x nb workgroups: for trajectory y of the launch,
+// workgroups x < ndiag are k_select_diag's block-diagonal sums, x == ndiag is its selection (select_diag_body, select_diag.h:
+// the body k_select_diag runs), x == ndiag + 1 is this kernel's own propagate + augmentState workgroup.  No workgroup waits for
+// another one, and the update's next launch (k_gram) is the first to read what either half wrote.  The propagate body is not
+// factored out into a function of its own: inlined from one, the compiler contracted and shared its float products differently
+// (8 FMAs fewer in the float instance) and the filter's bits moved; left in place, the instances without HEAD compile to the
+// instruction stream they had, and the HEAD instances to the same float operations beside the selection's branch.
+// Words of trajectory b that more than one role of a HEAD launch touches (R read, W write):
+//   ncam[b]      propagate W (the deferred commit, then augmentState's increment); selection and sums take the window size
+//                from ncam_upd[b] instead (update_ncam, d.ncam_bias = 1 in this launch), the value ncam[b] has when this
+//                launch has ended -- the host takes this order only for a frame whose augmentState does add a camera state
+//   ncam_upd[b]  R by all three (propagate: the deferred commit); written by the previous and by this frame's prune only
+//   n_resid[b]   selection R W; the sums read nres_upd[b], k_feature's copy of it; propagate neither
+//   stats[b]     selection W (STAT_NTRACKS .. STAT_RROWS); augmentState ORs STAT_ERR only for a full window, which the host
+//                keeps on the other order; the sums and propagate neither
+//   trk_status   selection R W, sums R (they re-derive the decision from the bits k_feature left: k_select_diag's rule)
+//   imu[b], P, cam[b][ncam]   propagate / augmentState W; selection and sums read none of them (k_feature, the launch before,
+//                read IG of imu, the P blocks and the camera states below the newest slot)
+//   Dg, row_start, trk_order  sums W / selection W; propagate neither
+// nb, ndiag: read by a HEAD launch only.
+template <class S, bool AUGMENT, int QM, bool HEAD = false>
+__global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K, const int* cnt, int nb, int ndiag) {
+  if (HEAD && (int)blockIdx.x <= ndiag) { select_diag_body<S>(d, b0, nb, ndiag, (int)blockIdx.x, (int)blockIdx.y); return; }
+  const int b = b0 + (HEAD ? blockIdx.y : blockIdx.x), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (cnt) K = cnt[HEAD ? blockIdx.y : blockIdx.x];
   constexpr bool FULLQ = QM == 2;
   if (QM != 0 && (d.qf[(long)b * QF_STRIDE + QF_FLAG] != S(0)) != FULLQ) return;   // the other instantiation's trajectory
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
@@ -534,7 +559,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
 #ifdef MSCKF_ABLATE
   __syncthreads();
   PR_TICK(4);
-  if (tid == 0 && blockIdx.x == 0) { for (int q = 0; q < 5; ++q) atomicAdd(&g_prop_cycles[q], (unsigned long long)pcyc[q]); atomicAdd(&g_prop_cycles[5], 1ull); }
+  if (tid == 0 && b == b0) { for (int q = 0; q < 5; ++q) atomicAdd(&g_prop_cycles[q], (unsigned long long)pcyc[q]); atomicAdd(&g_prop_cycles[5], 1ull); }
 #endif
   if (AUGMENT) {
     // the state and the IMU rows of P just written by this workgroup are read back by other threads of it: work-group scope
@@ -599,8 +624,8 @@ __global__ __launch_bounds__(1024) void k_prune_inplace(Dev<S> d, int b0, const 
 
 template <class S, int QM>
 static void launch_propagate_q(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, const int* cnt) {
-  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true, QM>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K, cnt);
-  else hipLaunchKernelGGL((k_propagate<S, false, QM>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K, cnt);
+  if (then_augment) hipLaunchKernelGGL((k_propagate<S, true, QM>), dim3(nb), dim3(256), (size_t)6 * d.ld * sizeof(S), st, d, b0, readings, rd_stride, K, cnt, 0, 0);
+  else hipLaunchKernelGGL((k_propagate<S, false, QM>), dim3(nb), dim3(256), 0, st, d, b0, readings, rd_stride, K, cnt, 0, 0);
 }
 template <class S>
 void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, bool then_augment, int qroute, const int* cnt) {
@@ -609,6 +634,19 @@ void launch_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long r
   if (qroute == 0) { launch_propagate_q<S, 0>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt); return; }
   if (qroute == 1) launch_propagate_q<S, 1>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt);   // disjoint trajectories: same stream, either order
   launch_propagate_q<S, 2>(d, b0, nb, readings, rd_stride, K, st, then_augment, cnt);
+}
+// d.ncam_bias = 1 (the caller's); qroute 0 or 2: one instantiation takes every trajectory of the range.  Float handles only
+// (routes::frame_order): the double propagate body needs 254 registers.
+template <class S>
+void launch_frame_head(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, int qroute, const int* cnt) {
+  if (nb <= 0) return;
+  if constexpr (sizeof(S) == 4) {
+    const int ndiag = (d.n_cap + 3) / 4;
+    const dim3 grid(ndiag + 2, nb);
+    const size_t lds = (size_t)6 * d.ld * sizeof(S);
+    if (qroute == 0) hipLaunchKernelGGL((k_propagate<S, true, 0, true>), grid, dim3(256), lds, st, d, b0, readings, rd_stride, K, cnt, nb, ndiag);
+    else hipLaunchKernelGGL((k_propagate<S, true, 2, true>), grid, dim3(256), lds, st, d, b0, readings, rd_stride, K, cnt, nb, ndiag);
+  }
 }
 template <class S>
 void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* cnt) {
@@ -629,6 +667,8 @@ void launch_prune(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* dr
 
 template void launch_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, bool, int, const int*);
 template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool, int, const int*);
+template void launch_frame_head<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, int, const int*);
+template void launch_frame_head<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, int, const int*);
 template void launch_augment<float>(const Dev<float>&, int, int, hipStream_t, const int*);
 template void launch_augment<double>(const Dev<double>&, int, int, hipStream_t, const int*);
 template void launch_prune<float>(const Dev<float>&, int, int, hipStream_t, const int*, int);

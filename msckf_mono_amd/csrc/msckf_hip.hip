@@ -33,6 +33,7 @@
 
 #include "../../include/msckf_hip.h"
 #include "dev_common.h"
+#include "frame_order.h"
 #include "host_lists.h"
 #include "input_layouts.h"
 #include "replay_plan.h"
@@ -164,6 +165,10 @@ struct BatchCore {
   // every tunable of the handle (settings.h: defaults, environment variables, what a copy takes over); the typed half's
   // apply_settings() carries them into the kernel argument
   Settings settings;
+  msckf_settings::FrameSettings frame_settings;   // the frame step's launch order (settings.h)
+  // frames of a slice (one count per slice and frame) that took the feature-first order (routes::frame_order) since the handle
+  // was created; the slices' enqueue threads count concurrently
+  std::atomic<long long> n_feature_first{0};
   int small_limit = 0;       // settings.small_update as far as it fits k_update_small at this handle's dtype and f_cap (apply_settings): the per-trajectory limit launch_update routes by
   bool info_form = false;    // the information form's buffers exist (Dev::trk_B; set by the typed half's create)
   std::vector<double> h_uv;  // [B][2] u_var', v_var' as initialize() got them
@@ -1105,6 +1110,11 @@ struct BatchCore {
   // the setters of the C interface: validate, store, apply
   int store(int Settings::* field, int v) { settings.*field = v; apply_settings(); return 0; }
   int set_feature_overlap(int on) { return store(&Settings::overlap_feature, on ? 1 : 0); }
+  int set_frame_order(int order) {
+    if (order != 0 && order != 1) return fail(-EINVAL, "order: 0 propagate first on every frame, 1 feature first where the frame allows it");
+    frame_settings.order = order;
+    return 0;
+  }
   int set_compression(int route) {
     if (route < -1 || route > 3) return fail(-EINVAL, "route: -1 default, 0 Householder TSQR, 1..3 information form (blocked matrix-core Cholesky; 1 and 2 named retired factorizations)");
     if (route >= 1 && !info_form) return fail(-ENOTSUP, "information form not available for this window size (6 n_cap + 1 > 384 or f_cap > 1024)");
@@ -1588,14 +1598,15 @@ struct Batch : BatchCore {
   // operations on any matrix element -- every element takes its rank-1 updates pivot by pivot whichever task holds it -- so the
   // bits are the trajectory's own (tests/test_gpu_ragged.py holds it: 5 .. 14 cameras alone and beside each other).
   // cell_k (run_frames: the frame's sample counts from b0 on): a skipped cell has no augmentState ahead.
-  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr) {
+  // select_done (the frame step's feature-first order): k_propagate's HEAD instance has run the selection and the block-diagonal sums already.
+  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr, bool select_done = false) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
     v.compress = update_compress();
     if (!feature_done) { stage_begin(2, q); launch_feature<S>(v, b0, nb, q); stage_end(2, q); }
     // information form: k_select and the block-diagonal reduction share a launch (both only read k_feature's outputs)
     const routes::CompressRoute cr = routes::compress_route(v.compress, d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts);
-    stage_begin(7, q); if (cr.select_diag) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q);
+    if (!select_done) { stage_begin(7, q); if (cr.select_diag) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q); }
     // short windows (single filters, BASELINE configs[1]): everything after the selection in ONE launch (k_update_small)
     const routes::SmallRoute sr = routes::small_route(nb, [&](int i) { return routes::window_cols(h_ncam[b0 + i], ncam_ahead, cell_k && cell_k[i] == IMU_SKIP, n_cap); },
                                                       small_limit, v.compress, n_lit, d.joseph, f_cap, sizeof(S), update_small_granted());
@@ -1803,7 +1814,7 @@ struct Batch : BatchCore {
     HIPCHK(cp(d.ncam, o->d.ncam, Bz * sizeof(int))); HIPCHK(cp(d.n_resid, o->d.n_resid, Bz * sizeof(long long)));
     HIPCHK(cp(d.stats, o->d.stats, Bz * STAT_STRIDE * sizeof(int))); HIPCHK(cp(d.ncam_upd, o->d.ncam_upd, Bz * sizeof(int)));
     traj = o->traj; h_ncam = o->h_ncam; h_uv = o->h_uv; h_imu = o->h_imu; h_imu_ok = o->h_imu_ok; h_qfull = o->h_qfull;
-    settings.take_over(o->settings);
+    settings.take_over(o->settings); frame_settings.take_over(o->frame_settings);
     prn_list.forget(h_ncam);   // (the log stays with its handle; the states taken over are none of its images)
     HIPCHK(hipStreamSynchronize(st));
     std::fill(h_lit.begin(), h_lit.end(), 0); n_lit = 0;   // which trajectories run the literal route is re-derived from the copied parameters
@@ -1952,6 +1963,10 @@ struct Batch : BatchCore {
   // P blocks of slots below the newest one, the constant gravity vector -- unless a track observes the camera this frame's
   // augmentState adds.  When none does (host mirror of the window sizes, slots known since scenario_set) and the handle asks
   // for it (set_feature_overlap) it runs on a side stream concurrently with the latency-bound propagate + augment.
+  // The same condition, for resident, staged and replay inputs alike (frame_cells has every kind's largest slot), lets a float
+  // handle take the feature-first order (routes::frame_order; frame_settings.order, the default): k_feature, then ONE launch
+  // with the selection and propagate + augmentState side by side, on the slice's own stream -- no second stream, no event, and
+  // the frame's prune rides on the downdate as on every other frame (fuse_frame does not ask about the order).
   void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) override {
     const int b0 = s.b0, nb = s.nb, hh = s.hh;
     const bool replay = staged == IN_REPLAY;
@@ -1968,11 +1983,23 @@ struct Batch : BatchCore {
     const bool fuse = fuse_frame(f, f1);
     v.trk_n = in.n; v.trk_M = in.M; v.trk_off = in.off; v.trk_slots = in.slots; v.trk_obs = in.obs;
     v.wl_stride_n = 1; v.wl_stride_f = f_cap; v.wl_stride_o = 0;
-    bool early = may_overlap && settings.overlap_feature && !prof && f > f0;   // f0: the previous call need not have ended with a prune (ncam_upd)
-    for (int b = b0; b < b0 + nb && early; ++b) {
-      const int n_after = std::min(h_ncam[b] + 1, n_cap);
-      // (a skipped cell gets no camera state: the early k_feature's window size, ncam_upd = "after the next augment", would be one too many)
-      early = h_ncam[b] < n_cap && cells.maxslot[b] <= n_after - 2 && cell_k[b] != IMU_SKIP;
+    // may k_feature run before this frame's augmentState?  (frame_order.h: never on the call's first frame -- the previous call need
+    // not have ended with a prune -- nor beside a skipped cell, which gets no camera state: ncam_upd would be one too many)
+    const int q_route = qroute(b0, nb);
+    const bool select_diag = routes::compress_route(update_compress(), d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts).select_diag;
+    const bool feature_first = routes::frame_order(frame_settings.order, settings.overlap_feature, sizeof(S), select_diag, q_route, nb, h_ncam.data() + b0,
+                                                   cells.maxslot + b0, cell_k + b0, IMU_SKIP, n_cap, f == f0, prof) == routes::FO_TAKEN;
+    const bool early = may_overlap && settings.overlap_feature &&
+                       routes::feature_ahead(nb, h_ncam.data() + b0, cells.maxslot + b0, cell_k + b0, IMU_SKIP, n_cap, f == f0, prof) == routes::FO_TAKEN;
+    if (feature_first) {
+      // feature-first order, on the slice's own stream: k_feature from what the previous frame's prune left (window size from ncam_upd),
+      // then the selection's workgroups and propagate + augmentState side by side in one launch (k_propagate's HEAD instance), then the rest of the update
+      StageRange r("msckf_marginalize(features)+imu_prop+msckf_augment_state");
+      Dev<S> v2 = v; v2.ncam_bias = 1;
+      v2.compress = update_compress();
+      launch_feature<S>(v2, b0, nb, q);
+      launch_frame_head<S>(v2, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, q_route, in.k);
+      n_feature_first.fetch_add(1, std::memory_order_relaxed);
     }
     if (early) {
       (void)hipEventRecord(ev_fa[hh], q);
@@ -1983,15 +2010,15 @@ struct Batch : BatchCore {
       (void)hipEventRecord(ev_fb[hh], sty[hh]);
     }
     // propagate and augmentState are always back to back here: one launch (the per-stage profile keeps them apart)
-    {
+    if (!feature_first) {
       StageRange r("imu_prop+msckf_augment_state");
-      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, !prof, qroute(b0, nb), in.k); stage_end(0, q);
+      stage_begin(0, q); launch_propagate<S>(v, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, !prof, q_route, in.k); stage_end(0, q);
       if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q, in.k); stage_end(1, q); }
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
     v.ncam_defer = 0;
     if (fuse) { v.Pout = s.flipped ? d.P : P_spare; v.fuse_drop = in.drop; }
-    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early, 1, cell_k + b0); }
+    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early || feature_first, 1, cell_k + b0, feature_first); }
     if (fuse) s.flipped = !s.flipped;
     else {
       // pruned-state log: the states this frame drops, as the update left them (v.P: in place), with frame ordinal
@@ -2656,6 +2683,12 @@ int msckf_hip_set_slices_exact(msckf_hip_handle h, int on) { if (!h) return fail
 int msckf_hip_scenario_pin(msckf_hip_handle h, int f0, int f1) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->scen_pin(f0, f1); }
 int msckf_hip_set_upload_ring(msckf_hip_handle h, int depth, int mode) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_upload_ring(depth, mode); }
 int msckf_hip_set_feature_overlap(msckf_hip_handle h, int on) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_feature_overlap(on); }
+int msckf_hip_set_frame_order(msckf_hip_handle h, int order) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_frame_order(order); }
+int msckf_hip_get_frame_order_count(msckf_hip_handle h, long long* count) {
+  if (!h || !count) return fail(-EINVAL, "null handle or null count");
+  *count = H(h)->n_feature_first.load(std::memory_order_relaxed);
+  return 0;
+}
 int msckf_hip_set_covariance_update(msckf_hip_handle h, int form) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_cov_update(form); }
 int msckf_hip_set_compression(msckf_hip_handle h, int route) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_compression(route); }
 int msckf_hip_set_gate_early_accept(msckf_hip_handle h, int on) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_gate_early(on); }

@@ -81,6 +81,15 @@ inline void Settings::take_over(const Settings& o) {
   }
 }
 
+// The order of a frame's first launches in run_frames (msckf_hip_set_frame_order; routes::frame_order in frame_order.h reads
+// it).  A record of its own beside Settings, whose fields, size and table tests/cpp/settings_host.cpp holds as they are: no
+// environment variable, only the setter changes it, and a copy of the handle takes it over like every setting that decides
+// which kernels run (same bits either way).
+struct FrameSettings {
+  int order = 1;   // 1: k_feature first, then selection and propagate + augmentState in one launch, on the frames that allow it; 0: propagate first on every frame
+  void take_over(const FrameSettings& o) { order = o.order; }
+};
+
 // the environment's say on a new handle's settings; false: a value was refused, err says which
 inline bool settings_from_env(Settings& s, std::string& err) {
   for (const SettingRow& r : SETTINGS_TABLE) {
