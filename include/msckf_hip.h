@@ -53,6 +53,13 @@
  *            30    k: the state is the k-th oldest of those the frame drops (its camera slot before the prune)
  *            31    0
  *            (7, 29, 30 are integers below 2^24: exact in a float)
+ *   NEES log record, 8 doubles per frame and trajectory whatever the handle's dtype, from the state the frame leaves and the
+ *            frame's row of the truth table (msckf_hip_truth_set):
+ *            0     NEES of the 15-state: e^T P_II^-1 e, e = [e_th ; b_g - b_g* ; v - v* ; b_a - b_a* ; p - p*] in P's own order
+ *            1-5   NEES of the 3 x 3 diagonal blocks th, b_g, v, b_a, p on their own
+ *            6     frame index f
+ *            7     flags: 1 a diagonal entry or a pivot of P_II was not positive, 2 the cell was skipped (either: 0-5 are 0),
+ *                  4 the trajectory's sticky error flags are set (0-5 are computed all the same)
  *
  * Pixel noise: with u_var_prime == v_var_prime (the configuration the throughput metric is quoted on) the update is
  * independent of the null-space basis and of the compression order and matches the reference to rounding.  With
@@ -389,6 +396,43 @@ int msckf_hip_pruned_log_read(msckf_hip_handle h, int b, int r0, int n, double* 
  * Sums and counts, so that ranks combine by addition: position ATE = sqrt(col 2 / col 1), mean NEES = col 6 / col 7 (6 for a
  * consistent filter). */
 int msckf_hip_pruned_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_pose, int n_ord, double* out);
+/* ---- full-state NEES log of the frame loops, reduced per frame across trajectories (off by default) ------------------- */
+/* The truth the NEES log is taken against, resident on the device: truth16[n_frames][n_rows][16] holds the first 16 entries of
+ * imu29 (q_IG b_g v b_a p), the true state at the time of frame f's log record, in double; row_of[B] names each trajectory's
+ * row in [0, n_rows) -- its sequence for a replay, itself for a plain scenario.  add_walk = 1: row f + 1 of the replay's walk
+ * table (msckf_hip_replay_walk) is added to the true b_g and b_a of frame f; accepted only while a msckf_hip_replay_assign_q
+ * assignment is in force and honoured only by msckf_hip_run_frames_replay.  n_frames = 0 frees the table.
+ * -EINVAL: "truth table: row_of names no row of the table", "truth table: entry not finite", "truth table: quaternion norm off
+ * by more than 1e-6", "truth table: add_walk needs an assignment through msckf_hip_replay_assign_q"; the table set before stays. */
+int msckf_hip_truth_set(msckf_hip_handle h, int n_frames, int n_rows, const double* truth16, const int* row_of, int add_walk);
+/* Storage for capacity_frames records ("NEES log record" above) of every trajectory, always doubles; 0 frees the log and
+ * disables it.  Any call drops the records written so far.  -ENOMEM when the allocation fails: the log is then off and the
+ * handle as usable as before.  A dense log like the frame log: while it is on, every frame of a run_frames / _streamed / _replay
+ * call ends with one more small launch per stream, after the frame log's, that reads the state and the truth and writes only
+ * the log -- the filter computes the same bits with and without it -- and a call over [f0, f1) writes the records count ..
+ * count + (f1 - f0) - 1.  The head of such a call reserves the log fourth, after the frame, map and pruned-state logs, before
+ * anything of its frames is enqueued: -EINVAL "NEES log on without a truth table", "the truth table does not cover the call's
+ * frames", "the truth table adds the replay's walk, only msckf_hip_run_frames_replay honours it" (run_frames / _streamed),
+ * -ENOSPC when the frames do not fit behind the records written; nothing was run.
+ * The record: e_th is the error-state angle of the filter's own update (buildUpdateQuat, msckf.h:851-872), q_IG =
+ * buildUpdateQuat(e_th) * q_IG*, e_th = -2 vec(q_IG * q_IG*^-1) with a non-negative scalar part, as msckf_hip_pruned_log_metrics
+ * defines it for q_CG.  With D = diag P_II the correlation matrix C = D^-1/2 P_II D^-1/2 = L L^T is factored in double and
+ * NEES = |L^-1 D^-1/2 e|^2; each 3 x 3 diagonal block of P_II gets a Cholesky factorisation of its own.  P_II's upper
+ * triangle is read.  msckf_hip_copy_state copies neither the log nor the truth table. */
+int msckf_hip_nees_log_enable(msckf_hip_handle h, int capacity_frames);
+int msckf_hip_nees_log_reset(msckf_hip_handle h);   /* records written <- 0 (the storage stays) */
+int msckf_hip_nees_log_count(msckf_hip_handle h);   /* records written; advances when a frame loop's call has succeeded */
+/* Records [r0, r0 + n) of trajectories [b0, b0 + nb), out[n][nb][8]: one strided copy; waits for the handle's stream.
+ * -EINVAL for a range beyond the records written, -EIO on a handle that a failed run_frames call left unusable. */
+int msckf_hip_nees_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out);
+/* The records [r0, r1) reduced across trajectories on the device, per record and group: group_of[B] in [-1, n_groups) names a
+ * trajectory's group (the seeds of one sequence), -1 leaves it out.  out[r1 - r0][n_groups][14] = 0 members with flags = 0,
+ * 1 members left out for a flag, 2-7 the sums of columns 0-5 over the unflagged members, 8-13 the sums of their squares; an
+ * empty group gives zeros.  Accumulated in a fixed order: the same log gives the same bits.  Sums and counts, so that ranks
+ * combine by addition; ANEES = column 2 / column 0, consistent over n seeds when n ANEES lies between the chi-square(15 n)
+ * quantiles the caller chooses.  -EINVAL "record range beyond the records written", "NEES ensemble: group_of outside
+ * [-1, n_groups)", "NEES ensemble: at least one group". */
+int msckf_hip_nees_log_ensemble(msckf_hip_handle h, int r0, int r1, const int* group_of, int n_groups, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

@@ -42,6 +42,7 @@ SYMBOLS = [
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
     "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
+    "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -67,6 +68,14 @@ PRUNED_LOG_FIELDS = {"q": slice(0, 4), "p": slice(4, 7), "frame": slice(7, 8), "
                      "n_cam": slice(29, 30), "k": slice(30, 31), "pad": slice(31, 32)}
 # columns of pruned_log_metrics' result
 PRUNED_LOG_METRICS = ("n", "n_matched", "sum_sq_pos_err", "max_pos_err", "sum_sq_ang_err", "max_ang_err", "sum_nees", "n_nees", "n_bad_pivot", "n_unmatched")
+# fields of a NEES log record (include/msckf_hip.h, "NEES log record"): name -> slice of its 8 doubles
+NEES_LOG_STRIDE = 8
+NEES_LOG_FIELDS = {"nees": slice(0, 1), "nees_theta": slice(1, 2), "nees_b_g": slice(2, 3), "nees_v": slice(3, 4), "nees_b_a": slice(4, 5),
+                   "nees_p": slice(5, 6), "frame": slice(6, 7), "flags": slice(7, 8)}
+NEES_FLAG_NOT_PD, NEES_FLAG_SKIPPED, NEES_FLAG_STAT_ERR = 1, 2, 4   # bits of "flags"
+# columns of nees_log_ensemble's sums, per (record, group); the six of each run over NEES_LOG_FIELDS' first six
+NEES_ENSEMBLE_STRIDE = 14
+NEES_ENSEMBLE_FIELDS = {"n": slice(0, 1), "n_flagged": slice(1, 2), "sum": slice(2, 8), "sum_sq": slice(8, 14)}
 
 
 def build():
@@ -627,6 +636,54 @@ class Batch:
             raise ValueError("gt_pose must be [n_ord][B][7]")
         _chk(self.L.msckf_hip_pruned_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), int(g.shape[0]), o.ctypes.data_as(_dp)))
         return o
+
+    # ---- full-state NEES log of the frame loops, and its reduction per frame across trajectories
+    def truth_set(self, truth16, row_of=None, add_walk=False):
+        """the truth the NEES log is taken against: truth16 [n_frames][n_rows][16] (scenario.imu_state_gt), row_of [B] each
+        trajectory's row (default: itself), add_walk: row f + 1 of the replay's walk table is added to the true biases of frame
+        f (run_frames_replay under replay_assign_q only).  None frees the table."""
+        if truth16 is None:
+            _chk(self.L.msckf_hip_truth_set(self.h, 0, 0, None, None, 0))
+            return
+        t = np.ascontiguousarray(truth16, dtype=np.float64)
+        if t.ndim != 3 or t.shape[2] != 16:
+            raise ValueError("truth16 must be [n_frames][n_rows][16]")
+        r, pr = _i(np.arange(self.B) if row_of is None else row_of)
+        if r.shape != (self.B,):
+            raise ValueError("row_of must hold one row per trajectory")
+        _chk(self.L.msckf_hip_truth_set(self.h, int(t.shape[0]), int(t.shape[1]), t.ctypes.data_as(_dp), pr, 1 if add_walk else 0))
+
+    def nees_log_enable(self, capacity_frames):
+        """storage for capacity_frames records per trajectory (0: free the log and switch it off); drops the records written"""
+        _chk(self.L.msckf_hip_nees_log_enable(self.h, int(capacity_frames)))
+
+    def nees_log_reset(self):
+        _chk(self.L.msckf_hip_nees_log_reset(self.h))
+
+    def nees_log_count(self):
+        return _chk(self.L.msckf_hip_nees_log_count(self.h))
+
+    def nees_log_read(self, r0=0, n=None, b0=0, nb=None):
+        """records [r0, r0 + n) (default: all written) of trajectories [b0, b0 + nb) (default: all): the array [n][nb][8] and
+        a dict of views into it by field name (NEES_LOG_FIELDS)"""
+        n = self.nees_log_count() - r0 if n is None else int(n)
+        nb = self.B - b0 if nb is None else int(nb)
+        o = np.zeros((max(n, 0), max(nb, 0), NEES_LOG_STRIDE))
+        _chk(self.L.msckf_hip_nees_log_read(self.h, int(r0), n, int(b0), nb, o.ctypes.data_as(_dp)))
+        return o, {k: o[:, :, s] for k, s in NEES_LOG_FIELDS.items()}
+
+    def nees_log_ensemble(self, r0, r1, group_of, n_groups):
+        """records [r0, r1) reduced on the device over the groups group_of [B] (-1: left out): (sums [r1 - r0][n_groups][14],
+        columns NEES_ENSEMBLE_FIELDS -- sums and counts, ranks combine by addition -- and the ANEES curves [r1 - r0][n_groups][6]
+        = sum / n over the unflagged members, NaN for a group without one)"""
+        g, pg = _i(group_of)
+        if g.shape != (self.B,):
+            raise ValueError("group_of must hold one group per trajectory")
+        o = np.zeros((max(int(r1) - int(r0), 0), max(int(n_groups), 0), NEES_ENSEMBLE_STRIDE))
+        _chk(self.L.msckf_hip_nees_log_ensemble(self.h, int(r0), int(r1), pg, int(n_groups), o.ctypes.data_as(_dp)))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            anees = np.where(o[:, :, 0:1] > 0, o[:, :, 2:8] / o[:, :, 0:1], np.nan)
+        return o, anees
 
     def profile_enable(self, on=True):
         _chk(self.L.msckf_hip_profile_enable(self.h, 1 if on else 0))

@@ -554,6 +554,12 @@ template <class S> void launch_map_metrics(const S* rec, const int* found, int c
 // records with prune ordinal in [q0, q1) against ground-truth poses gt[n_ord][B][7], matched through aug[B][cap], into out[B][10]
 template <class S> void launch_pruned_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* drop, int ordinal, int cap, S* rec, int* found);
 template <class S> void launch_pruned_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, const int* aug, const double* gt, int n_ord, double* out, hipStream_t st);
+// the NEES record `rec` ([B][8] doubles, indexed by trajectory) of a frame from the state after it -- P the covariance buffer that
+// is current, k the frame's sample counts (offset to b0), truth the frame's rows of the truth table with row_of[B], walk the
+// frame's row of the replay's walk table ([B][6]) or null -- and the reduction of the records [r0, r1) over the groups
+// group_of[B] into out[r1 - r0][n_groups][14] (all device pointers; csrc/nees_plan.h has the columns)
+template <class S> void launch_nees_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, const int* k, const double* truth, const int* row_of, const double* walk, int frame, double* rec);
+void launch_nees_ensemble(const double* rec, int B, int r0, int r1, int n_groups, const int* group_of, double* out, hipStream_t st);
 // kernels_replay.hip: the Monte-Carlo replay's expansion (replay_plan.h) of frame f for the trajectories [b0, b0 + nb) -- the
 // frame's S sequence cells (q: the sections of the sequence store from sequence 0, scalars double, slots / obs from the frame's
 // first sequence entry) through the assignment (t: seq_of[B], seed[B], sigma[B][4], and the frame's base[B]) into the ordinary

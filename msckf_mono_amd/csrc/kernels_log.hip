@@ -10,7 +10,11 @@
 // k_pruned_log records the camera states a frame is about to prune, between the frame's update and its prune launch: the
 // posterior pose with its 6 x 6 covariance block, the fixed-lag smoothed trajectory; k_pruned_metrics reduces them against
 // ground-truth poses.
+// k_nees_log is the consistency counterpart of k_frame_log: the 15-state NEES of the IMU state against a resident truth table,
+// whole and per 3 x 3 block, one record of 8 doubles per frame and trajectory; k_nees_ensemble reduces those records over groups
+// of trajectories (the seeds of a sequence) at each frame: the sums behind the ANEES curves.
 #include "dev_common.h"
+#include "nees_plan.h"
 
 namespace msckf {
 
@@ -35,6 +39,20 @@ __device__ __forceinline__ void cursor_store(int* found, int b, int lane, long e
 // What the metrics kernels of a cursor log walk: the records stored, and of those the ones stamped with an ordinal in [q0, q1)
 __device__ __forceinline__ int cursor_stored(const int* found, int b, int cap) { return min(max(found[b], 0), cap); }
 __device__ __forceinline__ bool ordinal_in(int fr, int q0, int q1) { return fr >= q0 && fr < q1; }
+
+// The error-state angle e_th of an attitude estimate q against the truth q_gt, both (w, x, y, z): the small angle with which the
+// filter's own injection (k_inject: q <- update_quat(dtheta) * q) turns the truth into the estimate, q = update_quat(e_th) * q_gt.
+// update_quat(x) is the unit quaternion (sqrt(1 - |x / 2|^2), -x / 2), so e_th = -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign
+// of q that makes the scalar part >= 0.  q * q_gt^-1 = s (1 + dq * q_gt^-1) with dq = s q - q_gt, s the sign of q . q_gt: the
+// products are of the small difference, so that e_th keeps its relative precision where a plain q * q_gt^-1 cancels down to it.
+__device__ __forceinline__ V3<double> error_angle(Q4<double> qh, Q4<double> qg) {
+  const double sg = qh.w * qg.w + qh.x * qg.x + qh.y * qg.y + qh.z * qg.z < 0 ? -1.0 : 1.0;
+  Q4<double> dq; dq.w = sg * qh.w - qg.w; dq.x = sg * qh.x - qg.x; dq.y = sg * qh.y - qg.y; dq.z = sg * qh.z - qg.z;
+  Q4<double> u = qmul(dq, qinverse(qg));
+  u.w += 1.0;
+  const double sc = -2.0 / sqrt(u.w * u.w + u.x * u.x + u.y * u.y + u.z * u.z);
+  return mk3(sc * u.x, sc * u.y, sc * u.z);
+}
 
 // One wavefront per trajectory, four per workgroup.  Record index (include/msckf_hip.h, "frame log record"):
 //   0..15 imu[0..15] | 16..30 diag P_II | 31..36 P_pp xx xy xz yy yz zz | 37 window size | 38..40 STAT_NTRACKS, _PASSED, _ERR |
@@ -238,10 +256,7 @@ __global__ __launch_bounds__(256) void k_pruned_log(Dev<S> d, int b0, int nb, co
 // One workgroup (one wavefront) per trajectory over the stored records of the pruned-state log whose prune ordinal lies in
 // [q0, q1).  aug[B][cap]: per stored record the ordinal of the frame that augmented its camera state, or -1; a record with
 // 0 <= ordinal < n_ord is matched to the ground-truth pose gt[ordinal][B][7] (q_CG p_C_G), any other is unmatched.
-// Pose error e = [e_th ; e_p]: e_p = p - p_gt, e_th the small angle with which the filter's own injection (k_inject:
-// q <- update_quat(dtheta) * q) turns the ground truth into the estimate, q = update_quat(e_th) * q_gt: update_quat(x) is the
-// unit quaternion (sqrt(1 - |x / 2|^2), -x / 2), so e_th = -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign of q that makes the
-// scalar part >= 0.
+// Pose error e = [e_th ; e_p]: e_p = p - p_gt, e_th the error-state angle of q_CG against the ground truth (error_angle).
 // out[b][10] = records in range, matched, sum |e_p|^2, max |e_p|, sum |e_th|^2, max |e_th|, sum e^T P6^-1 e over the matched
 // records whose logged block factors (6 x 6 Cholesky in registers, P6 = L L^T, |L^-1 e|^2), their number, the matched records
 // with a non-positive pivot (left out of that sum), unmatched.  All in f64; lane l takes the records l, l + 64, ... in
@@ -266,15 +281,8 @@ __global__ __launch_bounds__(64) void k_pruned_metrics(const S* rec, const int* 
     const int ord = aug[(long)b * cap + rr];
     if (ord < 0 || ord >= n_ord) { un += 1.0; continue; }
     const double* g = gt + ((long)ord * B + b) * 7;
-    // q * q_gt^-1 = s (1 + dq * q_gt^-1) with dq = s q - q_gt, s the sign of q . q_gt: the products are of the small
-    // difference, so that e_th keeps its relative precision where a plain q * q_gt^-1 cancels down to it
-    const Q4<double> qh = ldq(x + PRN_Q), qg = ldq(g);
-    const double sg = qh.w * qg.w + qh.x * qg.x + qh.y * qg.y + qh.z * qg.z < 0 ? -1.0 : 1.0;
-    Q4<double> dq; dq.w = sg * qh.w - qg.w; dq.x = sg * qh.x - qg.x; dq.y = sg * qh.y - qg.y; dq.z = sg * qh.z - qg.z;
-    Q4<double> u = qmul(dq, qinverse(qg));
-    u.w += 1.0;
-    const double sc = -2.0 / sqrt(u.w * u.w + u.x * u.x + u.y * u.y + u.z * u.z);
-    double e[6] = {sc * u.x, sc * u.y, sc * u.z, x[PRN_P] - g[4], x[PRN_P + 1] - g[5], x[PRN_P + 2] - g[6]};
+    const V3<double> th = error_angle(ldq(x + PRN_Q), ldq(g));
+    double e[6] = {th.x, th.y, th.z, x[PRN_P] - g[4], x[PRN_P + 1] - g[5], x[PRN_P + 2] - g[6]};
     const double t2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2], p2 = e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
     const double dt = sqrt(t2), dp = sqrt(p2);
     nm += 1.0; sp += p2; sth += t2;
@@ -311,6 +319,129 @@ __global__ __launch_bounds__(64) void k_pruned_metrics(const S* rec, const int* 
     double* o = out + (long)b * 10;
     o[0] = cnt; o[1] = nm; o[2] = sp; o[3] = mp; o[4] = sth; o[5] = mth; o[6] = nees; o[7] = nn; o[8] = bad; o[9] = un;
   }
+}
+
+// The NEES log: the normalised estimation error squared of the IMU state after a frame against the resident truth table, one
+// record of msckf_nees::REC doubles per trajectory whatever the handle's dtype (include/msckf_hip.h, "NEES log record"):
+//   0 NEES of the 15-state | 1..5 NEES of the blocks theta, b_g, v, b_a, p | 6 frame index | 7 flags
+// One wavefront per trajectory, four per workgroup, after the frame log's launch.  P: the covariance buffer that is current
+// after the frame (P_II sits at the same place whatever the window, so a pending window size does not matter here).
+// k (offset to b0): the cell's sample count, IMU_SKIP for a skipped cell.  truth: the frame's rows [n_rows][16] of the truth
+// table, trajectory b's is row_of[b]; walk: row frame + 1 of the replay's walk table, [B][6], added to the true b_g and b_a,
+// or null.  imu[0..15], P_II's upper triangle, the truth row and the walk row are widened to double once; all arithmetic is f64.
+//   e = [e_th ; b_g - b_g* ; v - v* ; b_a - b_a* ; p - p*], P's own order; e_th = error_angle(q_IG, q_IG*)
+//   D = diag P_II, C = D^-1/2 P_II D^-1/2 (diagonal exactly 1), z = D^-1/2 e; NEES = |L^-1 z|^2 with C = L L^T
+// Lane r < 15 owns row r of C, lane 15 the riding row z: the left-looking factorisation of [C ; z^T] leaves L^-1 z in lane 15's
+// row (column j: s_r = A_rj - sum_{k < j} L_rk L_jk with L_jk handed over from lane j by wave_bcast, pivot s_j, L_rj = s_r /
+// sqrt(s_j)).  15 pivot steps, no LDS, no atomics.  Lane g < 5 factors the 3 x 3 block g of P_II itself as k_log_metrics does
+// P_pp.  Flags: FLAG_NOT_PD a diagonal entry or a pivot (of either factorisation) is not positive, FLAG_SKIPPED the cell was
+// skipped -- either zeroes columns 0..5 --, FLAG_STAT_ERR the trajectory's STAT_ERR is set.
+template <class S>
+__global__ __launch_bounds__(256) void k_nees_log(Dev<S> d, int b0, int nb, const S* P, const int* k, const double* truth, const int* row_of, const double* walk, int frame, double* rec) {
+  using namespace msckf_nees;
+  int lane, i;
+  if (!log_wave(nb, lane, i)) return;
+  const int b = b0 + i;
+  const S* Pb = P + (long)b * d.ld * d.ld;
+  const S* xs = d.imu + (long)b * IMU_STRIDE;
+  const double* tr = truth + (long)row_of[b] * TRUTH_ROW;
+  double x[TRUTH_ROW], g[TRUTH_ROW], e[NX];
+#pragma unroll
+  for (int c = 0; c < TRUTH_ROW; ++c) { x[c] = (double)xs[c]; g[c] = tr[c]; }
+  if (walk) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { g[IBG + c] += walk[(long)b * WALK_ROW + c]; g[IBA + c] += walk[(long)b * WALK_ROW + 3 + c]; }
+  }
+  const V3<double> th = error_angle(ldq(x + IQ), ldq(g + IQ));
+  e[0] = th.x; e[1] = th.y; e[2] = th.z;
+#pragma unroll
+  for (int c = 3; c < NX; ++c) e[c] = x[c + 1] - g[c + 1];            // b_g v b_a p follow q in the state as in the error state
+  // row min(lane, 14) of P_II's upper triangle mirrored: entry c <= r is element (c, r)
+  const int r = lane < NX ? lane : NX - 1;
+  double row[NX], er = 0.0;
+#pragma unroll
+  for (int c = 0; c < NX; ++c) { row[c] = (double)Pb[(long)r * d.ld + c]; if (lane == c) er = e[c]; }
+  const double dg = (double)Pb[(long)r * d.ld + r];
+  bool bad = !(dg > 0.0);
+  const double dinv = 1.0 / sqrt(dg), zr = er * dinv;
+#pragma unroll
+  for (int c = 0; c < NX; ++c) {
+    const double dc = wave_bcast(dinv, c), zc = wave_bcast(zr, c);
+    row[c] = lane < NX ? (lane == c ? 1.0 : row[c] * dinv * dc) : zc;
+  }
+  double L[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    double s = row[j];
+#pragma unroll
+    for (int c = 0; c < j; ++c) s -= L[c] * wave_bcast(L[c], j);
+    const double piv = wave_bcast(s, j);
+    bad = bad || !(piv > 0.0);
+    L[j] = s / sqrt(piv);
+  }
+  double nees = 0.0;
+#pragma unroll
+  for (int j = 0; j < NX; ++j) nees += L[j] * L[j];
+  nees = wave_bcast(nees, NX);                                         // lane 15's row is L^-1 z
+  // block min(lane, 4) of P_II, upper triangle xx xy xz yy yz zz, and its part of e
+  const int o = 3 * (lane < NBLK ? lane : NBLK - 1);
+  double e0 = 0.0, e1 = 0.0, e2 = 0.0;
+#pragma unroll
+  for (int c = 0; c < NBLK; ++c) if (o == 3 * c) { e0 = e[3 * c]; e1 = e[3 * c + 1]; e2 = e[3 * c + 2]; }
+  const double pxx = (double)Pb[(long)o * d.ld + o], pxy = (double)Pb[(long)(o + 1) * d.ld + o], pxz = (double)Pb[(long)(o + 2) * d.ld + o];
+  const double pyy = (double)Pb[(long)(o + 1) * d.ld + o + 1], pyz = (double)Pb[(long)(o + 2) * d.ld + o + 1], pzz = (double)Pb[(long)(o + 2) * d.ld + o + 2];
+  const double l00 = sqrt(pxx), l10 = pxy / l00, l20 = pxz / l00;
+  const double d11 = pyy - l10 * l10, l11 = sqrt(d11), l21 = (pyz - l20 * l10) / l11;
+  const double d22 = pzz - l20 * l20 - l21 * l21, l22 = sqrt(d22);
+  const double y0 = e0 / l00, y1 = (e1 - l10 * y0) / l11, y2 = (e2 - l20 * y0 - l21 * y1) / l22;
+  const double blk = y0 * y0 + y1 * y1 + y2 * y2;
+  bad = bad || !(pxx > 0.0) || !(d11 > 0.0) || !(d22 > 0.0);
+  const bool not_pd = __ballot(bad ? 1 : 0) != 0ull;
+  const bool skipped = k[i] == IMU_SKIP;
+  const int flags = (not_pd ? FLAG_NOT_PD : 0) | (skipped ? FLAG_SKIPPED : 0) | (d.stats[(long)b * STAT_STRIDE + STAT_ERR] != 0 ? FLAG_STAT_ERR : 0);
+  // lanes 0..7 store the record: lane l in 1..5 takes block l - 1 from lane l - 1 (every lane takes part in the exchange)
+  const double from_below = lane_gather(blk, ((lane - 1) & 63) << 2);
+  double v = lane == REC_NEES ? nees : (lane < REC_FRAME ? from_below : (lane == REC_FRAME ? (double)frame : (double)flags));
+  if ((not_pd || skipped) && lane < REC_FRAME) v = 0.0;
+  if (lane < REC) rec[(long)b * REC + lane] = v;
+}
+
+// One wavefront (one workgroup) per (record, group) over the records [r0, r0 + gridDim.x / n_groups) of the NEES log
+// ([.][B][8] doubles): group_of[b] in [-1, n_groups) names trajectory b's group, -1 none.  out[record - r0][group][14] =
+// members with flags == 0, members left out for a flag, the sums of columns 0..5 over the former, the sums of their squares.
+// Lane l takes the trajectories l, l + 64, ... in ascending order and the lanes are combined by wave_sum's fixed tree: the same
+// log gives the same bits on every call.  An empty group gives zeros.
+__global__ __launch_bounds__(64) void k_nees_ensemble(const double* rec, int B, int r0, int n_groups, const int* group_of, double* out) {
+  using namespace msckf_nees;
+  const int lane = threadIdx.x, r = r0 + (int)blockIdx.x / n_groups, g = (int)blockIdx.x % n_groups;
+  double n_ok = 0, n_out = 0, s[REC_FRAME] = {0}, q[REC_FRAME] = {0};
+  for (int b = lane; b < B; b += 64) {
+    if (group_of[b] != g) continue;
+    const double* x = rec + ((long)r * B + b) * REC;
+    if (x[REC_FLAGS] != 0.0) { n_out += 1.0; continue; }
+    n_ok += 1.0;
+#pragma unroll
+    for (int c = 0; c < REC_FRAME; ++c) { s[c] += x[c]; q[c] += x[c] * x[c]; }
+  }
+  n_ok = wave_sum(n_ok); n_out = wave_sum(n_out);
+#pragma unroll
+  for (int c = 0; c < REC_FRAME; ++c) { s[c] = wave_sum(s[c]); q[c] = wave_sum(q[c]); }
+  if (lane == 0) {
+    double* o = out + (long)blockIdx.x * ENS;
+    o[ENS_N] = n_ok; o[ENS_FLAGGED] = n_out;
+#pragma unroll
+    for (int c = 0; c < REC_FRAME; ++c) { o[ENS_SUM + c] = s[c]; o[ENS_SUMSQ + c] = q[c]; }
+  }
+}
+
+template <class S>
+void launch_nees_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, const int* k, const double* truth, const int* row_of, const double* walk, int frame, double* rec) {
+  if (nb <= 0) return;
+  hipLaunchKernelGGL(k_nees_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, P, k, truth, row_of, walk, frame, rec);
+}
+void launch_nees_ensemble(const double* rec, int B, int r0, int r1, int n_groups, const int* group_of, double* out, hipStream_t st) {
+  if (r1 <= r0 || n_groups <= 0) return;
+  hipLaunchKernelGGL(k_nees_ensemble, dim3((unsigned)(r1 - r0) * n_groups), dim3(64), 0, st, rec, B, r0, n_groups, group_of, out);
 }
 
 template <class S>
@@ -352,7 +483,8 @@ void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, con
   template void launch_map_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, const int*, int, int, S*, int*);   \
   template void launch_map_metrics<S>(const S*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t); \
   template void launch_pruned_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, int, int, S*, int*);            \
-  template void launch_pruned_metrics<S>(const S*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t);
+  template void launch_pruned_metrics<S>(const S*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t); \
+  template void launch_nees_log<S>(const Dev<S>&, int, int, hipStream_t, const S*, const int*, const double*, const int*, const double*, int, double*);
 MSCKF_LOG_LAUNCHERS(float)
 MSCKF_LOG_LAUNCHERS(double)
 

@@ -36,6 +36,7 @@
 #include "frame_order.h"
 #include "host_lists.h"
 #include "input_layouts.h"
+#include "nees_plan.h"
 #include "replay_plan.h"
 #include "settings.h"
 #include "slice_policy.h"
@@ -255,6 +256,13 @@ struct BatchCore {
   // of enqueue_frame that mirrors augment and drop into h_ncam).
   CursorLog prn{PRN_STRIDE, "pruned-state log", "msckf_hip_pruned_log"};
   PrunedFifo prn_list;
+  // NEES log (msckf_hip_nees_log_*; nees_plan.h, kernels_log.hip): dense like the frame log, [nees_cap][B][REC] doubles whatever
+  // the handle's dtype, null unless enabled; nees_n / nees_base as log_n / log_base.  The truth table it is taken against
+  // (msckf_hip_truth_set): tru [tru_frames][tru_rows][TRUTH_ROW] doubles and tru_row_of[B] on the device, tru_frames == 0: none;
+  // tru_walk: row f + 1 of the replay's walk table is added to the true biases of frame f (run_frames_replay only).
+  // nees_replay: the call in flight is the replay's (set by the reserve, read by the slices' enqueue threads)
+  double* nees_buf = nullptr; int nees_cap = 0, nees_n = 0, nees_base = 0; bool nees_replay = false;
+  double* tru = nullptr; int* tru_row_of = nullptr; int tru_frames = 0, tru_rows = 0; bool tru_walk = false;
   // profiling
   bool prof = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool[NSTAGE];
@@ -680,21 +688,24 @@ struct BatchCore {
     if (cursors) *cursors = static_cast<int*>(c);
     return 0;
   }
-  // head of run_frames / run_frames_streamed, before anything is enqueued, in the order frame, map, pruned: a log that refuses
-  // the call leaves the later ones untouched
-  int reserve_logs(int f0, int f1) {
+  // head of run_frames / run_frames_streamed / run_frames_replay (replay_loop), before anything of the call's frames is enqueued,
+  // in the order frame, map, pruned, NEES: a log that refuses the call leaves the later ones untouched
+  int reserve_logs(int f0, int f1, bool replay_loop = false) {
     if (int rc = frame_log_reserve(f0, f1)) return rc;
     if (int rc = cursor_log_reserve(map, f0, f1)) return rc;
-    return pruned_log_reserve(f0, f1);
+    if (int rc = pruned_log_reserve(f0, f1)) return rc;
+    return nees_log_reserve(f0, f1, replay_loop);
   }
   // finish_slices, when the call's frames have succeeded
   void advance_logs(int frames) {
     if (log_buf) log_n += frames;
     for (CursorLog* g : {&map, &prn}) if (g->buf) g->ord += frames;
+    if (nees_buf) nees_n += frames;
   }
   void release_logs() {
     dfree(log_buf);
     for (CursorLog* g : {&map, &prn}) { dfree(g->buf); dfree(g->found); }
+    dfree(nees_buf); dfree(tru); dfree(tru_row_of);
   }
   // ---- frame log
   int frame_log_enable(int capacity_frames) {
@@ -822,6 +833,74 @@ struct BatchCore {
     return 0;
   }
   int pruned_log_counts(int b0, int nb, int* stored, int* found) { return cursor_log_counts(prn, b0, nb, stored, found); }
+  // ---- NEES log and its truth table (nees_plan.h has every check)
+  bool replay_model_q() const { return rp.assigned && rp.model == msckf_replay::MODEL_Q; }
+  // truth16 [n_frames][n_rows][16] and row_of[B] to the device; n_frames == 0 frees the table.  A refused or failed call leaves
+  // the table that was there
+  int truth_set(int n_frames, int n_rows, const double* truth16, const int* row_of, int add_walk) {
+    using namespace msckf_nees;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(truth_refusal(n_frames, n_rows, truth16, row_of, B, add_walk, replay_model_q()))) return rc;
+    if (int rc = enter()) return rc;
+    HIPCHK(hipStreamSynchronize(st));                        // the last run's log launches have read the old table
+    double* t = nullptr; int* r = nullptr;
+    if (n_frames) {
+      const size_t bytes = (size_t)n_frames * n_rows * TRUTH_ROW * sizeof(double);
+      if (hipMalloc((void**)&t, bytes) != hipSuccess || hipMalloc((void**)&r, (size_t)B * sizeof(int)) != hipSuccess) {
+        (void)hipGetLastError();
+        dfree(t);
+        return fail(-ENOMEM, "could not allocate the truth table (the one set before stays)");
+      }
+      if (hipMemcpy(t, truth16, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(r, row_of, (size_t)B * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+        dfree(t); dfree(r);
+        return fail(-EIO, "could not copy the truth table to the device (the one set before stays)");
+      }
+    }
+    dfree(tru); dfree(tru_row_of);
+    tru = t; tru_row_of = r; tru_frames = n_frames; tru_rows = n_frames ? n_rows : 0; tru_walk = n_frames && add_walk;
+    return 0;
+  }
+  int nees_log_enable(int capacity_frames) {
+    if (int rc = log_enable_enter(capacity_frames)) return rc;
+    dfree(nees_buf); nees_cap = 0; nees_n = 0;
+    if (!capacity_frames) return 0;
+    void* q = nullptr;
+    if (int rc = log_alloc("NEES log", (size_t)capacity_frames * B * msckf_nees::REC * sizeof(double), &q, nullptr)) return rc;
+    nees_buf = static_cast<double*>(q); nees_cap = capacity_frames;
+    return 0;
+  }
+  int nees_log_reset() { nees_n = 0; return 0; }
+  int nees_log_count() const { return nees_n; }
+  // the call's frames are covered by the truth table and their records fit, starting at nees_n
+  int nees_log_reserve(int f0, int f1, bool replay_loop) {
+    if (!nees_buf) return 0;
+    if (int rc = refuse(msckf_nees::reserve_refusal(f0, f1, tru_frames, tru_walk ? 1 : 0, replay_loop, replay_model_q(), nees_n, nees_cap))) return rc;
+    nees_base = nees_n; nees_replay = replay_loop;
+    return 0;
+  }
+  // records [r0, r0 + n) of trajectories [b0, b0 + nb), out [n][nb][8]: one strided copy, one wait
+  int nees_log_read(int r0, int n, int b0, int nb, double* out) {
+    using namespace msckf_nees;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(read_refusal(r0, n, nees_n))) return rc;
+    if (int rc = enter_range(b0, nb)) return rc;
+    if (n && nb)
+      HIPCHK(hipMemcpy2DAsync(out, (size_t)nb * REC * sizeof(double), nees_buf + record_at(r0, b0, B), (size_t)B * REC * sizeof(double),
+                              (size_t)nb * REC * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return 0;
+  }
+  // the records [r0, r1) reduced over the groups of trajectories on the device (k_nees_ensemble): out [r1 - r0][n_groups][14]
+  int nees_log_ensemble(int r0, int r1, const int* group_of, int n_groups, double* out) {
+    using namespace msckf_nees;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(ensemble_refusal(r0, r1, nees_n, group_of, B, n_groups))) return rc;
+    if (int rc = enter()) return rc;
+    if (r1 == r0) return 0;
+    return log_metrics_call("nees_log_ensemble", nullptr, 0, group_of, (size_t)B, out, (size_t)(r1 - r0) * n_groups * ENS, [&](const double*, double* dout, const int* dgroup) {
+      launch_nees_ensemble(nees_buf, B, r0, r1, n_groups, dgroup, dout, st);
+    });
+  }
   int run_frames(int f0, int f1) {
     if (int rc = guard()) return rc;
     if (f0 < 0 || f1 > sc.frames || f0 > f1) return fail(-EINVAL, "frame range out of bounds");
@@ -1066,7 +1145,7 @@ struct BatchCore {
     if (int rc = replay_walk_table()) return rc;
     const int nh = n_slices(false);
     if (int rc = replay_blocks(nh)) return rc;
-    if (int rc = reserve_logs(f0, f1)) return rc;
+    if (int rc = reserve_logs(f0, f1, true)) return rc;
     for (int i = 0; i < nh; ++i) rp_cells[i].assign((size_t)3 * B, 0);
     const int rc = fork_slices(nh);
     if (rc) return rc;
@@ -2033,6 +2112,11 @@ struct Batch : BatchCore {
     // frame log: the state the frame leaves -- the covariance buffer that is current after the flip, the window size where the
     // prune left it (ncam_upd while it is pending) -- as record log_base + (f - f0); outside the stage timers
     if (log_buf) launch_frame_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, s.pending, static_cast<S*>(log_buf) + (size_t)(log_base + (f - f0)) * B * LOG_STRIDE);
+    // NEES log: the same state against frame f's rows of the truth table (and, for a replay whose table asks for it, row f + 1 of
+    // the walk table) as record nees_base + (f - f0); the reserve has checked that the table covers f
+    if (nees_buf)
+      launch_nees_log<S>(d, b0, nb, q, s.flipped ? P_spare : d.P, in.k, tru + msckf_nees::truth_at(f, 0, tru_rows), tru_row_of,
+                         tru_walk && nees_replay ? rp_wstart + (size_t)(f + 1) * B * msckf_replay::WALK_ROW : nullptr, f, nees_buf + msckf_nees::record_at(nees_base + (f - f0), 0, B));
     // map log: the tracks of the work-list the update read (in.n, in.M: resident or staged) with frame ordinal
     // map.ordinal(f, f0), behind the trajectories' cursors; also outside the stage timers
     if (map.buf) launch_map_log<S>(d, b0, nb, q, in.n, in.M, map.ordinal(f, f0), map.cap, static_cast<S*>(map.buf), map.found);
@@ -2713,6 +2797,12 @@ int msckf_hip_pruned_log_frames(msckf_hip_handle h) { if (!h) return fail(-EINVA
 int msckf_hip_pruned_log_counts(msckf_hip_handle h, int b0, int nb, int* stored, int* found) { if (!h || !stored || !found) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_counts(b0, nb, stored, found); }
 int msckf_hip_pruned_log_read(msckf_hip_handle h, int b, int r0, int n, double* out, int* aug_ord) { if (!h || !out || !aug_ord) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_read(b, r0, n, out, aug_ord); }
 int msckf_hip_pruned_log_metrics(msckf_hip_handle h, int q0, int q1, const double* gt_pose, int n_ord, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->pruned_log_metrics(q0, q1, gt_pose, n_ord, out); }
+int msckf_hip_truth_set(msckf_hip_handle h, int n_frames, int n_rows, const double* truth16, const int* row_of, int add_walk) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->truth_set(n_frames, n_rows, truth16, row_of, add_walk); }
+int msckf_hip_nees_log_enable(msckf_hip_handle h, int capacity_frames) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->nees_log_enable(capacity_frames); }
+int msckf_hip_nees_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->nees_log_reset(); }
+int msckf_hip_nees_log_count(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->nees_log_count(); }
+int msckf_hip_nees_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->nees_log_read(r0, n, b0, nb, out); }
+int msckf_hip_nees_log_ensemble(msckf_hip_handle h, int r0, int r1, const int* group_of, int n_groups, double* out) { if (!h || !group_of || !out) return fail(-EINVAL, "null argument"); return H(h)->nees_log_ensemble(r0, r1, group_of, n_groups, out); }
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"

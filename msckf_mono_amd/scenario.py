@@ -134,30 +134,36 @@ def replay_expand(seq_traj, frame, seed, sigma4):
 REPLAY_PSD_TOL = 1e-12
 
 
-def replay_noise_factor(Q):
-    """L = chol_psd(0.5 (Q + Q^T)), [12][12] lower triangular, as replay_plan.h forms it: column by column, d = Q_cc - sum_j L_cj^2
+def chol_psd(A, what="Q"):
+    """L = chol_psd(0.5 (A + A^T)), [n][n] lower triangular, as replay_plan.h forms it: column by column, d = A_cc - sum_j L_cj^2
     (ascending j); d < -1e-12 max_diag raises ValueError, |d| <= 1e-12 max_diag leaves the column zero"""
-    Q = np.asarray(Q, dtype=np.float64).reshape(12, 12)
-    A = 0.5 * (Q + Q.T)
+    A = np.asarray(A, dtype=np.float64)
+    n = A.shape[0]
+    A = 0.5 * (A + A.T)
     top = max(0.0, float(np.max(np.diag(A))))
-    L = np.zeros((12, 12))
-    for c in range(12):
+    L = np.zeros((n, n))
+    for c in range(n):
         s = 0.0
         for j in range(c):
             s = s + L[c, j] * L[c, j]
         d = A[c, c] - s
         if d < -REPLAY_PSD_TOL * top:
-            raise ValueError("Q is not positive semi-definite")
+            raise ValueError("%s is not positive semi-definite" % what)
         if abs(d) <= REPLAY_PSD_TOL * top:
             continue
         p = np.sqrt(d)
         L[c, c] = p
-        for r in range(c + 1, 12):
+        for r in range(c + 1, n):
             t = 0.0
             for j in range(c):
                 t = t + L[r, j] * L[c, j]
             L[r, c] = (A[r, c] - t) / p
     return L
+
+
+def replay_noise_factor(Q):
+    """L = chol_psd(0.5 (Q + Q^T)), [12][12] lower triangular: the factor of the Q_imu model's noise"""
+    return chol_psd(np.asarray(Q, dtype=np.float64).reshape(12, 12))
 
 
 def replay_model_draws(seed, frame, k, L, pairs_per_sample=6):
@@ -378,6 +384,114 @@ def camera_pose_gt(trajs, f0, f1):
         for b, tr in enumerate(trajs):
             out[k - f0, b, 0:4], out[k - f0, b, 4:7] = rot_to_quat(tr.C_CG[k]), tr.p_C[k]
     return out
+
+
+# ------------------------------------------------------------------ full-state NEES: the numpy twin of k_nees_log (csrc/kernels_log.hip)
+def imu_state_gt(trajs, f0, f1):
+    """The truth table of the frames [f0, f1) of a batch (or of a replay's sequences), as Batch.truth_set takes it:
+    [f1 - f0][len(trajs)][16] = q_IG b_g v b_a p at the time of each frame's log record, from trajs[b].gt_frames and its constant
+    biases (a replay adds its walk on the device: truth_set's add_walk)"""
+    out = np.zeros((max(f1 - f0, 0), len(trajs), 16))
+    for b, tr in enumerate(trajs):
+        g = tr.gt_frames
+        out[:, b, 0:4], out[:, b, 4:7], out[:, b, 7:10] = g["q_IG"][f0:f1], tr.b_g, g["v"][f0:f1]
+        out[:, b, 10:13], out[:, b, 13:16] = tr.b_a, g["p"][f0:f1]
+    return out
+
+
+def quat_mul(a, b):
+    """Hamilton product of (w, x, y, z) quaternions, Eigen's operator*"""
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return np.array([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by + ay * bw + az * bx - ax * bz, aw * bz + az * bw + ax * by - ay * bx])
+
+
+def update_quat(dtheta):
+    """buildUpdateQuat (msckf.h:851-872): the unit quaternion (sqrt(1 - |dtheta / 2|^2), -dtheta / 2), normalised"""
+    dq = 0.5 * np.asarray(dtheta, dtype=np.float64)
+    cs = float(dq @ dq)
+    q = np.concatenate([[1.0 if cs > 1.0 else np.sqrt(1.0 - cs)], -dq])
+    return q / np.linalg.norm(q)
+
+
+def error_angle(q, q_gt):
+    """e_th with q = update_quat(e_th) * q_gt: -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign of q that makes the scalar part
+    non-negative, formed from the small difference s q - q_gt as the device forms it"""
+    q, g = np.asarray(q, dtype=np.float64), np.asarray(q_gt, dtype=np.float64)
+    s = -1.0 if q @ g < 0 else 1.0
+    g_inv = np.concatenate([[g[0]], -g[1:]]) / (g @ g)
+    u = quat_mul(s * q - g, g_inv)
+    u[0] += 1.0
+    return -2.0 * u[1:] / np.linalg.norm(u)
+
+
+def nees_error(imu16, truth16):
+    """e [15] = [e_th ; b_g - b_g* ; v - v* ; b_a - b_a* ; p - p*], the error state in P's own order"""
+    x, g = np.asarray(imu16, dtype=np.float64), np.asarray(truth16, dtype=np.float64)
+    return np.concatenate([error_angle(x[0:4], g[0:4]), x[4:16] - g[4:16]])
+
+
+def _solve_sq(A, e):
+    """|L^-1 e|^2 with A = L L^T by Cholesky, column by column; None when a pivot is not positive"""
+    n = len(e)
+    L, y = np.zeros((n, n)), np.zeros(n)
+    for j in range(n):
+        s = A[j, j] - L[j, :j] @ L[j, :j]
+        if not s > 0.0:
+            return None
+        L[j, j] = np.sqrt(s)
+        for r in range(j + 1, n):
+            L[r, j] = (A[r, j] - L[r, :j] @ L[j, :j]) / L[j, j]
+        y[j] = (e[j] - L[j, :j] @ y[:j]) / L[j, j]
+    return float(y @ y)
+
+
+def nees_record(imu16, P_II, truth16):
+    """Columns 0..5 of a NEES log record and whether flag 1 is set, as k_nees_log forms them: the 15-state NEES through the
+    correlation matrix C = D^-1/2 P_II D^-1/2 (D = diag P_II, C's diagonal exactly 1), NEES = |L^-1 D^-1/2 e|^2 with C = L L^T, then
+    the NEES of the 3 x 3 diagonal blocks th, b_g, v, b_a, p through a Cholesky factorisation of each.  P_II's upper triangle
+    is read.  A diagonal entry or a pivot that is not positive: (zeros, True)."""
+    e = nees_error(imu16, truth16)
+    U = np.triu(np.asarray(P_II, dtype=np.float64)[:15, :15])
+    P = U + np.triu(U, 1).T
+    d = np.diag(P)
+    if not np.all(d > 0.0):
+        return np.zeros(6), True
+    s = 1.0 / np.sqrt(d)
+    C = P * s[:, None] * s[None, :]
+    np.fill_diagonal(C, 1.0)
+    cols = [_solve_sq(C, e * s)] + [_solve_sq(P[o:o + 3, o:o + 3], e[o:o + 3]) for o in range(0, 15, 3)]
+    if any(c is None for c in cols):
+        return np.zeros(6), True
+    return np.array(cols), False
+
+
+def replay_initial_error(seed, P0):
+    """e0 [15] ~ N(0, P0) of a trajectory's seed: z = the first 15 normals of replay_pairs(replay_mix(seed, 2^63), 8) (a sub-seed no
+    frame index reaches: frames use mix(seed, 2 f) and mix(seed, 2 f + 1)), e0 = L0 z with L0 = chol_psd(P0), each row summed
+    in ascending column order"""
+    P0 = np.asarray(P0, dtype=np.float64)
+    n = P0.shape[0]
+    z = replay_pairs(int(replay_mix(seed, 2 ** 63)), (n + 1) // 2).reshape(-1)[:n]
+    L0 = chol_psd(P0, "P0")
+    e0 = np.zeros(n)
+    for r in range(n):
+        a = 0.0
+        for c in range(r + 1):
+            a = a + L0[r, c] * z[c]
+        e0[r] = a
+    return e0
+
+
+def perturbed_imu29(imu29, e0):
+    """imu29 moved by the error state e0 [15] (th b_g v b_a p): q <- update_quat(e_th) * q, the rest additive; the null-space
+    anchors q_null, v_null, p_null are set to the perturbed values, as imu29_from_gt sets them to the state"""
+    s, e0 = np.array(imu29, dtype=np.float64), np.asarray(e0, dtype=np.float64)
+    s[0:4] = quat_mul(update_quat(e0[0:3]), s[0:4])
+    s[4:16] = s[4:16] + e0[3:15]
+    s[19:23], s[23:26], s[26:29] = s[0:4], s[7:10], s[13:16]
+    return s
 
 
 class Trajectory:
