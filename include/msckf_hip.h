@@ -433,6 +433,39 @@ int msckf_hip_nees_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, d
  * quantiles the caller chooses.  -EINVAL "record range beyond the records written", "NEES ensemble: group_of outside
  * [-1, n_groups)", "NEES ensemble: at least one group". */
 int msckf_hip_nees_log_ensemble(msckf_hip_handle h, int r0, int r1, const int* group_of, int n_groups, double* out);
+/* ---- aligned trajectory error on the device: yaw and SE(3) ATE, and the relative pose error -------------------------- */
+/* The frame log's records [r0, r1) against ground-truth poses gt_pose7[r1 - r0][B][7] (q_IG w x y z, then p; indexed from r0),
+ * reduced on the device after an alignment g ~ R p + t of each trajectory's estimate p onto its ground truth g: mode 0 none
+ * (R = I, t = 0), 1 a rotation about the global z axis (gravity is (0, 0, -9.81)) plus a translation -- the gauge of a VIO --,
+ * 2 a rotation and a translation (SE(3)); no scale.  r0b / r1b (both NULL: [r0, r1) for every trajectory): the trajectory's own
+ * range [r0b[b], r1b[b]) inside [r0, r1), as msckf_hip_frame_log_metrics_ranges takes it.
+ * out[B][20] = per trajectory: 0 records n, 1-9 R row by row, 10-12 t, 13 cond, and over e = R p + t - g: 14 sum |e|^2, 15 max |e|,
+ * 16 |e| at the last record; over the error-state angle e_th (msckf_hip_pruned_log_metrics defines it) of the aligned attitude
+ * C(q_IG) R^T against the truth: 17 sum |e_th|^2, 18 max |e_th|; 19 sum |p - g|^2 before alignment (column 1 of
+ * msckf_hip_frame_log_metrics).  Yaw: theta = atan2(W10 - W01, W00 + W11) of W = sum g_c p_c^T (_c: centred on its own mean),
+ * cond = hypot(W10 - W01, W00 + W11) / sqrt(sum |p_c,xy|^2 sum |g_c,xy|^2).  SE(3): R from the eigenvector of largest
+ * eigenvalue of Horn's 4 x 4 matrix (Jacobi, in double), always a proper rotation, cond = (l1 - l2) / l1.  cond lies in [0, 1];
+ * 0: the data do not fix R -- n <= 1, no extent (yaw: no horizontal extent) give R = I; collinear points under SE(3) give one
+ * of the minimisers.  t = mean g - R mean p.  The sums are centred in a pass of their own, not expanded from raw moments.
+ * Accumulated in double in a fixed order: the same input gives the same bits.  Sums and counts, so that ranks, sequences and
+ * seeds combine by addition (aligned ATE = sqrt(col 14 / col 0)).
+ * -EINVAL, in this order: "null argument"; "record range beyond the records written"; "trajectory alignment: mode is ...";
+ * "trajectory ranges: r0b and r1b, both or neither"; "trajectory ranges: a trajectory's range lies outside [r0, r1)";
+ * "ground-truth poses: entry not finite"; "ground-truth poses: quaternion norm off by more than 1e-6".  -EIO on a handle that a
+ * failed run_frames call left unusable.  Nothing of the handle's filters, inputs or logs changes. */
+int msckf_hip_frame_log_align(msckf_hip_handle h, int r0, int r1, const int* r0b, const int* r1b, const double* gt_pose7, int mode, double* out);
+/* The relative pose error of the same records over lags[n_lags] (1 <= n_lags <= 8, every lag >= 1 record), gauge-free: over
+ * the pairs (r, r + lag) inside the trajectory's range, e_t = C(q_r) (p_{r+lag} - p_r) - C(g_r) (g_{r+lag} - g_r) (each
+ * displacement in its own body frame at r) and e_th the error-state angle of q_{r+lag} * q_r^-1 against the truth's.
+ * out[B][n_lags][4] = 0 pairs, 1 sum |e_t|^2, 2 sum |e_th|^2, 3 max |e_t|; a lag longer than the range gives zeros.
+ * -EINVAL as above with "relative pose error: between 1 and 8 lags" / "... a lag is at least 1 record" in the mode's place. */
+int msckf_hip_frame_log_rpe(msckf_hip_handle h, int r0, int r1, const int* r0b, const int* r1b, const double* gt_pose7, const int* lags, int n_lags, double* out);
+/* The same two reductions on poses the caller hands over -- a pruned-state log's read-back, another run's outputs, a trajectory
+ * from elsewhere: est_pose7 and gt_pose7 [n_rec][n_traj][7], r0b / r1b inside [0, n_rec) or both NULL, out[n_traj][20] and
+ * out[n_traj][n_lags][4].  n_traj is free of the handle's B: the handle supplies the device and the stream.  -EINVAL "pose
+ * arrays: n_rec >= 0 and n_traj >= 1 are needed" takes the place of the record range. */
+int msckf_hip_traj_align(msckf_hip_handle h, int n_rec, int n_traj, const double* est_pose7, const double* gt_pose7, const int* r0b, const int* r1b, int mode, double* out);
+int msckf_hip_traj_rpe(msckf_hip_handle h, int n_rec, int n_traj, const double* est_pose7, const double* gt_pose7, const int* r0b, const int* r1b, const int* lags, int n_lags, double* out);
 /* HIP-event stage timing: enable, run, sync, then read accumulated milliseconds and launch counts for
  * stages 0 propagate, 1 augment, 2 k_feature, 3 compression A (k_gram | TSQR stage 1), 4 compression B
  * (k_chol_mfma | TSQR merge), 5 kalman, 6 prune, 7 k_select (information form: k_select_diag, which also reduces the

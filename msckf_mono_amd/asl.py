@@ -286,3 +286,21 @@ def ate(traj_out, ds):
         e = s[13:16] - gt["p"][j]
         se += float(e @ e); n += 1
     return (np.sqrt(se / max(n, 1)), se, n)
+
+
+def ate_aligned(traj_out, ds, mode):
+    """`ate` after an alignment of the estimate onto the ground truth (trajeval: 1 yaw about gravity plus translation, 2
+    SE(3); 0 none, which is `ate`): the counterpart for a runner that does not start from ground truth -- the stand-still
+    initialisation lives in its own gravity-aligned frame, and an unaligned ATE measures that frame's offset, not the filter.
+    Same association of image times with ground-truth entries as `ate`.  Returns (ate_m, row) with row the 20 columns of
+    trajeval.align (capi.ALIGN_FIELDS: sums and counts, R, t, cond)."""
+    from . import trajeval
+    gt = ds["gt"]
+    est7, gt7 = np.zeros((len(traj_out), 7)), np.zeros((len(traj_out), 7))
+    for k, (t, s) in enumerate(traj_out):
+        i = max(int(np.searchsorted(gt["t"], t, side="right")) - 1, 0)
+        j = min(i + 1, len(gt["t"]) - 1)
+        est7[k, 0:4], est7[k, 4:7] = s[0:4], s[13:16]
+        gt7[k, 0:4], gt7[k, 4:7] = gt["q_IG"][j] / np.linalg.norm(gt["q_IG"][j]), gt["p"][j]
+    row = trajeval.align(est7, gt7, mode)
+    return (float(np.sqrt(row[14] / max(row[0], 1.0))), row)

@@ -43,6 +43,7 @@ SYMBOLS = [
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
     "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
+    "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -76,6 +77,14 @@ NEES_FLAG_NOT_PD, NEES_FLAG_SKIPPED, NEES_FLAG_STAT_ERR = 1, 2, 4   # bits of "f
 # columns of nees_log_ensemble's sums, per (record, group); the six of each run over NEES_LOG_FIELDS' first six
 NEES_ENSEMBLE_STRIDE = 14
 NEES_ENSEMBLE_FIELDS = {"n": slice(0, 1), "n_flagged": slice(1, 2), "sum": slice(2, 8), "sum_sq": slice(8, 14)}
+# the aligned trajectory error (csrc/traj_plan.h): the modes, and the columns of an alignment row and of an RPE row
+ALIGN_NONE, ALIGN_YAW, ALIGN_SE3 = 0, 1, 2
+ALIGN_STRIDE = 20
+ALIGN_FIELDS = {"n": slice(0, 1), "R": slice(1, 10), "t": slice(10, 13), "cond": slice(13, 14), "sum_sq_err": slice(14, 15), "max_err": slice(15, 16),
+                "final_err": slice(16, 17), "sum_sq_ang_err": slice(17, 18), "max_ang_err": slice(18, 19), "sum_sq_err_unaligned": slice(19, 20)}
+RPE_STRIDE = 4
+RPE_MAX_LAGS = 8
+RPE_FIELDS = {"n_pairs": slice(0, 1), "sum_sq_trans_err": slice(1, 2), "sum_sq_ang_err": slice(2, 3), "max_trans_err": slice(3, 4)}
 
 
 def build():
@@ -636,6 +645,74 @@ class Batch:
             raise ValueError("gt_pose must be [n_ord][B][7]")
         _chk(self.L.msckf_hip_pruned_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), int(g.shape[0]), o.ctypes.data_as(_dp)))
         return o
+
+    # ---- aligned trajectory error on the device: yaw and SE(3) ATE, and the relative pose error
+    def _traj_ranges(self, r0b, r1b, n_traj):
+        """(keep-alive, pointer, pointer) of the per-trajectory ranges, or nulls when neither is given"""
+        if r0b is None and r1b is None:
+            return None, None, None
+        if r0b is None or r1b is None:
+            raise ValueError("r0b and r1b: both or neither")
+        a0, p0 = _i(r0b); a1, p1 = _i(r1b)
+        if a0.shape != (n_traj,) or a1.shape != (n_traj,):
+            raise ValueError("r0b and r1b must hold one record index per trajectory")
+        return (a0, a1), p0, p1
+
+    @staticmethod
+    def _traj_lags(lags):
+        a, p = _i(np.atleast_1d(lags))
+        if a.ndim != 1:
+            raise ValueError("lags must be a list of record counts")
+        return a, p
+
+    def frame_log_align(self, r0, r1, gt_pose7, mode, r0b=None, r1b=None):
+        """the frame log's records [r0, r1) against ground-truth poses gt_pose7 [r1 - r0][B][7] (trajeval.gt_pose7), after the
+        alignment `mode` (ALIGN_NONE, ALIGN_YAW, ALIGN_SE3) of each trajectory, reduced on the device: [B][20], columns
+        ALIGN_FIELDS (sums and counts).  r0b / r1b: a record range per trajectory inside [r0, r1)"""
+        g = np.ascontiguousarray(gt_pose7, dtype=np.float64)
+        if g.shape != (int(r1) - int(r0), self.B, 7):
+            raise ValueError("gt_pose7 must be [r1 - r0][B][7]")
+        keep, p0, p1 = self._traj_ranges(r0b, r1b, self.B)
+        o = np.zeros((self.B, ALIGN_STRIDE))
+        _chk(self.L.msckf_hip_frame_log_align(self.h, int(r0), int(r1), p0, p1, g.ctypes.data_as(_dp), int(mode), o.ctypes.data_as(_dp)))
+        return o
+
+    def frame_log_rpe(self, r0, r1, gt_pose7, lags, r0b=None, r1b=None):
+        """the relative pose error of the frame log's records [r0, r1) over `lags` (at most RPE_MAX_LAGS, in records), reduced on
+        the device: [B][len(lags)][4], columns RPE_FIELDS (sums and counts)"""
+        g = np.ascontiguousarray(gt_pose7, dtype=np.float64)
+        if g.shape != (int(r1) - int(r0), self.B, 7):
+            raise ValueError("gt_pose7 must be [r1 - r0][B][7]")
+        keep, p0, p1 = self._traj_ranges(r0b, r1b, self.B)
+        la, pl = self._traj_lags(lags)
+        o = np.zeros((self.B, max(len(la), 1), RPE_STRIDE))
+        _chk(self.L.msckf_hip_frame_log_rpe(self.h, int(r0), int(r1), p0, p1, g.ctypes.data_as(_dp), pl, len(la), o.ctypes.data_as(_dp)))
+        return o[:, :len(la)]
+
+    @staticmethod
+    def _traj_poses(est_pose7, gt_pose7):
+        e = np.ascontiguousarray(est_pose7, dtype=np.float64); g = np.ascontiguousarray(gt_pose7, dtype=np.float64)
+        if e.ndim != 3 or e.shape[1] < 1 or e.shape[2] != 7 or g.shape != e.shape:
+            raise ValueError("est_pose7 and gt_pose7 must both be [n_rec][n_traj][7]")
+        return e, g
+
+    def traj_align(self, est_pose7, gt_pose7, mode, r0b=None, r1b=None):
+        """frame_log_align on poses the caller hands over, est_pose7 and gt_pose7 [n_rec][n_traj][7] (q w x y z, then p; n_traj is
+        free of B): [n_traj][20], columns ALIGN_FIELDS"""
+        e, g = self._traj_poses(est_pose7, gt_pose7)
+        keep, p0, p1 = self._traj_ranges(r0b, r1b, e.shape[1])
+        o = np.zeros((e.shape[1], ALIGN_STRIDE))
+        _chk(self.L.msckf_hip_traj_align(self.h, e.shape[0], e.shape[1], e.ctypes.data_as(_dp), g.ctypes.data_as(_dp), p0, p1, int(mode), o.ctypes.data_as(_dp)))
+        return o
+
+    def traj_rpe(self, est_pose7, gt_pose7, lags, r0b=None, r1b=None):
+        """frame_log_rpe on poses the caller hands over: [n_traj][len(lags)][4], columns RPE_FIELDS"""
+        e, g = self._traj_poses(est_pose7, gt_pose7)
+        keep, p0, p1 = self._traj_ranges(r0b, r1b, e.shape[1])
+        la, pl = self._traj_lags(lags)
+        o = np.zeros((e.shape[1], max(len(la), 1), RPE_STRIDE))
+        _chk(self.L.msckf_hip_traj_rpe(self.h, e.shape[0], e.shape[1], e.ctypes.data_as(_dp), g.ctypes.data_as(_dp), p0, p1, pl, len(la), o.ctypes.data_as(_dp)))
+        return o[:, :len(la)]
 
     # ---- full-state NEES log of the frame loops, and its reduction per frame across trajectories
     def truth_set(self, truth16, row_of=None, add_walk=False):

@@ -322,6 +322,20 @@ template <class S> __device__ __forceinline__ Q4<S> update_quat(V3<S> dtheta) {
   return qnormalized(q);
 }
 
+// The error-state angle e_th of an attitude estimate q against the truth q_gt, both (w, x, y, z): the small angle with which the
+// filter's own injection (k_inject: q <- update_quat(dtheta) * q) turns the truth into the estimate, q = update_quat(e_th) * q_gt.
+// update_quat(x) is the unit quaternion (sqrt(1 - |x / 2|^2), -x / 2), so e_th = -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign
+// of q that makes the scalar part >= 0.  q * q_gt^-1 = s (1 + dq * q_gt^-1) with dq = s q - q_gt, s the sign of q . q_gt: the
+// products are of the small difference, so that e_th keeps its relative precision where a plain q * q_gt^-1 cancels down to it.
+__device__ __forceinline__ V3<double> error_angle(Q4<double> qh, Q4<double> qg) {
+  const double sg = qh.w * qg.w + qh.x * qg.x + qh.y * qg.y + qh.z * qg.z < 0 ? -1.0 : 1.0;
+  Q4<double> dq; dq.w = sg * qh.w - qg.w; dq.x = sg * qh.x - qg.x; dq.y = sg * qh.y - qg.y; dq.z = sg * qh.z - qg.z;
+  Q4<double> u = qmul(dq, qinverse(qg));
+  u.w += 1.0;
+  const double sc = -2.0 / sqrt(u.w * u.w + u.x * u.x + u.y * u.y + u.z * u.z);
+  return mk3(sc * u.x, sc * u.y, sc * u.z);
+}
+
 // ---------------------------------------------------------------- wave64 helpers
 __device__ __forceinline__ float wave_bcast(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -560,6 +574,14 @@ template <class S> void launch_pruned_metrics(const S* rec, const int* found, in
 // group_of[B] into out[r1 - r0][n_groups][14] (all device pointers; csrc/nees_plan.h has the columns)
 template <class S> void launch_nees_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, const int* k, const double* truth, const int* row_of, const double* walk, int frame, double* rec);
 void launch_nees_ensemble(const double* rec, int B, int r0, int r1, int n_groups, const int* group_of, double* out, hipStream_t st);
+// kernels_traj.hip: the aligned trajectory error (csrc/traj_plan.h has the modes and the columns) of the records [r0, r1) of a
+// frame log, or of the poses est[n_rec][n_traj][7], against ground-truth poses gt[.][.][7] indexed from the first record:
+// out[.][20] after the alignment `mode`, and the relative pose error over lags[n_lags] into out[.][n_lags][4].  r0b / r1b (both
+// or neither): a range per trajectory.  All device pointers.
+template <class S> void launch_traj_align_log(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, int mode, double* out, hipStream_t st);
+template <class S> void launch_traj_rpe_log(const S* log, int B, int r0, int r1, const int* r0b, const int* r1b, const double* gt, const int* lags, int n_lags, double* out, hipStream_t st);
+void launch_traj_align_pose(const double* est, int n_traj, int n_rec, const int* r0b, const int* r1b, const double* gt, int mode, double* out, hipStream_t st);
+void launch_traj_rpe_pose(const double* est, int n_traj, int n_rec, const int* r0b, const int* r1b, const double* gt, const int* lags, int n_lags, double* out, hipStream_t st);
 // kernels_replay.hip: the Monte-Carlo replay's expansion (replay_plan.h) of frame f for the trajectories [b0, b0 + nb) -- the
 // frame's S sequence cells (q: the sections of the sequence store from sequence 0, scalars double, slots / obs from the frame's
 // first sequence entry) through the assignment (t: seq_of[B], seed[B], sigma[B][4], and the frame's base[B]) into the ordinary

@@ -40,20 +40,6 @@ __device__ __forceinline__ void cursor_store(int* found, int b, int lane, long e
 __device__ __forceinline__ int cursor_stored(const int* found, int b, int cap) { return min(max(found[b], 0), cap); }
 __device__ __forceinline__ bool ordinal_in(int fr, int q0, int q1) { return fr >= q0 && fr < q1; }
 
-// The error-state angle e_th of an attitude estimate q against the truth q_gt, both (w, x, y, z): the small angle with which the
-// filter's own injection (k_inject: q <- update_quat(dtheta) * q) turns the truth into the estimate, q = update_quat(e_th) * q_gt.
-// update_quat(x) is the unit quaternion (sqrt(1 - |x / 2|^2), -x / 2), so e_th = -2 vec(q * q_gt^-1) / |q * q_gt^-1| with the sign
-// of q that makes the scalar part >= 0.  q * q_gt^-1 = s (1 + dq * q_gt^-1) with dq = s q - q_gt, s the sign of q . q_gt: the
-// products are of the small difference, so that e_th keeps its relative precision where a plain q * q_gt^-1 cancels down to it.
-__device__ __forceinline__ V3<double> error_angle(Q4<double> qh, Q4<double> qg) {
-  const double sg = qh.w * qg.w + qh.x * qg.x + qh.y * qg.y + qh.z * qg.z < 0 ? -1.0 : 1.0;
-  Q4<double> dq; dq.w = sg * qh.w - qg.w; dq.x = sg * qh.x - qg.x; dq.y = sg * qh.y - qg.y; dq.z = sg * qh.z - qg.z;
-  Q4<double> u = qmul(dq, qinverse(qg));
-  u.w += 1.0;
-  const double sc = -2.0 / sqrt(u.w * u.w + u.x * u.x + u.y * u.y + u.z * u.z);
-  return mk3(sc * u.x, sc * u.y, sc * u.z);
-}
-
 // One wavefront per trajectory, four per workgroup.  Record index (include/msckf_hip.h, "frame log record"):
 //   0..15 imu[0..15] | 16..30 diag P_II | 31..36 P_pp xx xy xz yy yz zz | 37 window size | 38..40 STAT_NTRACKS, _PASSED, _ERR |
 //   41..47 cam slot 0 (zeros when the window is empty)

@@ -37,6 +37,7 @@
 #include "host_lists.h"
 #include "input_layouts.h"
 #include "nees_plan.h"
+#include "traj_plan.h"
 #include "replay_plan.h"
 #include "settings.h"
 #include "slice_policy.h"
@@ -899,6 +900,55 @@ struct BatchCore {
     if (r1 == r0) return 0;
     return log_metrics_call("nees_log_ensemble", nullptr, 0, group_of, (size_t)B, out, (size_t)(r1 - r0) * n_groups * ENS, [&](const double*, double* dout, const int* dgroup) {
       launch_nees_ensemble(nees_buf, B, r0, r1, n_groups, dgroup, dout, st);
+    });
+  }
+  // ---- aligned trajectory error (traj_plan.h has the modes, the rows and every check; kernels_traj.hip the kernels).  None of
+  // the four calls touches filters, inputs or logs.
+  // The ints of one call, [r0b | r1b | lags]: on the device r0b sits at 0, r1b at nt, the lags behind the ranges given
+  static std::vector<int> traj_ints(const int* r0b, const int* r1b, int nt, const int* lags, int n_lags) {
+    std::vector<int> v;
+    if (r0b) { v.assign(r0b, r0b + nt); v.insert(v.end(), r1b, r1b + nt); }
+    if (lags) v.insert(v.end(), lags, lags + n_lags);
+    return v;
+  }
+  // the frame log's records [r0, r1) against gt_pose7 [r1 - r0][B][7]: lags null: the alignment `mode`, out [B][20]; else the
+  // relative pose error, out [B][n_lags][4].  The record range is refused as frame_log_metrics refuses it
+  int frame_log_traj(const char* what, int r0, int r1, const int* r0b, const int* r1b, const double* gt, int mode, const int* lags, int n_lags, double* out) {
+    using namespace msckf_traj;
+    if (int rc = guard()) return rc;
+    if (r0 < 0 || r1 < r0 || r1 > log_n) return fail(-EINVAL, "record range beyond the records written (msckf_hip_frame_log_count)");
+    if (int rc = refuse(lags ? rpe_refusal(r0, r1, r0b, r1b, B, gt, lags, n_lags) : align_refusal(r0, r1, r0b, r1b, B, gt, mode))) return rc;
+    if (int rc = enter()) return rc;
+    const std::vector<int> ints = traj_ints(r0b, r1b, B, lags, n_lags);
+    const size_t no = lags ? (size_t)B * n_lags * RPE_ROW : (size_t)B * ALIGN_ROW;
+    return log_metrics_call(what, gt, (size_t)(r1 - r0) * B * POSE, ints.data(), ints.size(), out, no, [&](const double* dg, double* dout, const int* di) {
+      const int* d0 = r0b ? di : nullptr; const int* d1 = r0b ? di + B : nullptr; const int* dl = di + (r0b ? 2 * B : 0);
+      if (esz == sizeof(float)) {
+        if (lags) launch_traj_rpe_log<float>(static_cast<const float*>(log_buf), B, r0, r1, d0, d1, dg, dl, n_lags, dout, st);
+        else launch_traj_align_log<float>(static_cast<const float*>(log_buf), B, r0, r1, d0, d1, dg, mode, dout, st);
+      } else {
+        if (lags) launch_traj_rpe_log<double>(static_cast<const double*>(log_buf), B, r0, r1, d0, d1, dg, dl, n_lags, dout, st);
+        else launch_traj_align_log<double>(static_cast<const double*>(log_buf), B, r0, r1, d0, d1, dg, mode, dout, st);
+      }
+    });
+  }
+  // the same on poses the caller hands over, est and gt [n_rec][n_traj][7]; n_traj is free of the handle's B, which only supplies
+  // the device and the stream.  The block on the device is [gt | est]
+  int pose_traj(const char* what, int n_rec, int nt, const double* est, const double* gt, const int* r0b, const int* r1b, int mode, const int* lags, int n_lags, double* out) {
+    using namespace msckf_traj;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(shape_refusal(n_rec, nt))) return rc;
+    if (int rc = refuse(lags ? rpe_refusal(0, n_rec, r0b, r1b, nt, gt, lags, n_lags) : align_refusal(0, n_rec, r0b, r1b, nt, gt, mode))) return rc;
+    if (int rc = enter()) return rc;
+    const size_t np = (size_t)n_rec * nt * POSE;
+    std::vector<double> both(gt, gt + np);
+    both.insert(both.end(), est, est + np);
+    const std::vector<int> ints = traj_ints(r0b, r1b, nt, lags, n_lags);
+    const size_t no = lags ? (size_t)nt * n_lags * RPE_ROW : (size_t)nt * ALIGN_ROW;
+    return log_metrics_call(what, both.data(), both.size(), ints.data(), ints.size(), out, no, [&](const double* dg, double* dout, const int* di) {
+      const int* d0 = r0b ? di : nullptr; const int* d1 = r0b ? di + nt : nullptr; const int* dl = di + (r0b ? 2 * nt : 0);
+      if (lags) launch_traj_rpe_pose(dg + np, nt, n_rec, d0, d1, dg, dl, n_lags, dout, st);
+      else launch_traj_align_pose(dg + np, nt, n_rec, d0, d1, dg, mode, dout, st);
     });
   }
   int run_frames(int f0, int f1) {
@@ -2803,6 +2853,22 @@ int msckf_hip_nees_log_reset(msckf_hip_handle h) { if (!h) return fail(-EINVAL, 
 int msckf_hip_nees_log_count(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->nees_log_count(); }
 int msckf_hip_nees_log_read(msckf_hip_handle h, int r0, int n, int b0, int nb, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->nees_log_read(r0, n, b0, nb, out); }
 int msckf_hip_nees_log_ensemble(msckf_hip_handle h, int r0, int r1, const int* group_of, int n_groups, double* out) { if (!h || !group_of || !out) return fail(-EINVAL, "null argument"); return H(h)->nees_log_ensemble(r0, r1, group_of, n_groups, out); }
+int msckf_hip_frame_log_align(msckf_hip_handle h, int r0, int r1, const int* r0b, const int* r1b, const double* gt_pose7, int mode, double* out) {
+  if (const auto r = msckf_traj::pointer_refusal({h, gt_pose7, out}); r.code) return fail(r.code, r.why);
+  return H(h)->frame_log_traj("frame_log_align", r0, r1, r0b, r1b, gt_pose7, mode, nullptr, 0, out);
+}
+int msckf_hip_frame_log_rpe(msckf_hip_handle h, int r0, int r1, const int* r0b, const int* r1b, const double* gt_pose7, const int* lags, int n_lags, double* out) {
+  if (const auto r = msckf_traj::pointer_refusal({h, gt_pose7, lags, out}); r.code) return fail(r.code, r.why);
+  return H(h)->frame_log_traj("frame_log_rpe", r0, r1, r0b, r1b, gt_pose7, 0, lags, n_lags, out);
+}
+int msckf_hip_traj_align(msckf_hip_handle h, int n_rec, int n_traj, const double* est_pose7, const double* gt_pose7, const int* r0b, const int* r1b, int mode, double* out) {
+  if (const auto r = msckf_traj::pointer_refusal({h, est_pose7, gt_pose7, out}); r.code) return fail(r.code, r.why);
+  return H(h)->pose_traj("traj_align", n_rec, n_traj, est_pose7, gt_pose7, r0b, r1b, mode, nullptr, 0, out);
+}
+int msckf_hip_traj_rpe(msckf_hip_handle h, int n_rec, int n_traj, const double* est_pose7, const double* gt_pose7, const int* r0b, const int* r1b, const int* lags, int n_lags, double* out) {
+  if (const auto r = msckf_traj::pointer_refusal({h, est_pose7, gt_pose7, lags, out}); r.code) return fail(r.code, r.why);
+  return H(h)->pose_traj("traj_rpe", n_rec, n_traj, est_pose7, gt_pose7, r0b, r1b, 0, lags, n_lags, out);
+}
 int msckf_hip_literal_info(msckf_hip_handle h, int b, int* out8) { if (!h || !out8) return fail(-EINVAL, "null argument"); return H(h)->lit_info(b, out8); }
 
 }  // extern "C"
