@@ -308,6 +308,48 @@ int msckf_hip_run_frames_replay(msckf_hip_handle h, int f0, int f1);
  * they exceed cap_entries.  Nothing of the handle's filters, inputs or logs changes. */
 int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd /*[K][7]*/, double* obs2, int cap_entries);
 int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints, int* slots, int cap_entries);
+/* Seeded front-end faults on top of either noise model: missed observations and outliers, per trajectory
+ * fault4[b] = (p_miss, p_out, rho_u, rho_v) -- two probabilities in [0, 1], two radii in normalised image units, finite and >= 0.
+ *   s_flt(f) = mix(mix(s_b, 2^63 + 1), f).  Frames use mix(s_b, 2 f) and mix(s_b, 2 f + 1), replay_initial_error (the twin)
+ *     uses mix(s_b, 2^63): no frame index reaches either.
+ *   entry e (0-based among the SEQUENCE cell's entries, in sequence order) takes u_miss = U(s_flt, 3 e), u_out = U(s_flt, 3 e + 1),
+ *     u_ang = U(s_flt, 3 e + 2)
+ *   raw_miss(e) = u_miss < p_miss.  A track that would keep fewer than two observations loses none: if M - #raw_miss < 2 then
+ *     miss = false on the whole track (so the sequence's own tracks with M < 2 pass through unchanged); otherwise
+ *     miss = raw_miss.  A tracker hands the filter no track of one observation.
+ *   out(e) = !miss(e) && u_out < p_out
+ *   obs = value + sigma noise exactly as without faults (pair e of s_obs, indexed by the sequence entry: a trajectory's Gaussian
+ *     noise does not depend on its faults); where out(e) the pair becomes (x + rho_u cos a, y + rho_v sin a), a the rounded
+ *     product 6.283185307179586 u_ang, each product rounded, then added, all in double, rounded once to the handle's scalar.
+ *     A displacement of fixed size at a uniform angle, so that detection rate against outlier size is a clean curve.
+ *   the expanded block: off[t], the trajectory's base, the frame's entry count, n, drop, k and rd are unchanged -- a track's
+ *     range keeps the sequence's length.  M[t] is the number of surviving observations; the range is a stable partition, the
+ *     survivors in sequence order, then the missed entries in sequence order; every entry carries its slot and coordinates.
+ *     Nothing downstream reads beyond off[t] + M[t].
+ * With NULL, or every trajectory at p_miss = p_out = 0, the expansion launched and every bit are those without faults.
+ * -EINVAL, in this order: "no replay allocated", "fault probabilities must lie in [0, 1]", "fault radii must be finite and not
+ * negative"; a refused call leaves the previous setting in force.  May be called between runs; survives msckf_hip_replay_assign,
+ * _assign_q and _commit; msckf_hip_replay_alloc clears it.  msckf_hip_replay_expand / _expand_ints return what the faulted
+ * kernel wrote: M = survivors, slots and coordinates in partition order; their return value is still the cell's entries. */
+int msckf_hip_replay_set_faults(msckf_hip_handle h, const double* fault4 /*[B][4], NULL: none*/);
+/* per SEQUENCE entry of trajectory b's cell on `frame`: 0 kept, 1 outlier, 2 missed, from the same launch as
+ * msckf_hip_replay_expand.  Returns the cell's entries; -E2BIG when they exceed cap_entries. */
+int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* code /*[entries]*/, int cap_entries);
+/* The faults of the frames [f0, f1) per trajectory, counted on the device from the sequences, the seeds and the fault record
+ * alone (no run, no log): out [B][6] = entries, missed, outliers, tracks, tracks that lost at least one observation, tracks that
+ * carry at least one outlier.  Integers: they equal the twin's exactly.  Refusals as msckf_hip_run_frames_replay. */
+int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long* out /*[B][6]*/);
+/* The gate against the faults: the stored map-log records with ordinal in [q0, q1), where the record with ordinal q belongs to
+ * replay frame f0 + (q - q0) -- the caller states that msckf_hip_run_frames_replay wrote the log contiguously from f0.  Whether
+ * a record's track carries an outlier is recomputed on the device from (seed, frame, the sequence's off / M, fault4).
+ * out [B][8] = 0 records in range, 1 clean and gate passed, 2 clean and rejected, 3 contaminated and passed, 4 contaminated and
+ * rejected, 5 sum of gamma and 6 sum of 2 M - 3 over the clean gate-passed records without flag 4 (the mean of 5 / 6 is 1 for a
+ * consistent filter), 7 records whose track index is >= the cell's n (unmatched, counted nowhere else).  Sums in double, in a
+ * fixed order: the same log gives the same bits; sums and counts, so ranks add.  Contaminated tracks that fail the motion or
+ * triangulation check are never logged: column 5 of msckf_hip_replay_fault_counts minus columns 3 + 4 here is their number.
+ * -EINVAL while the map log is off, for ordinals beyond those handed out, for a frame outside the replay ("frame range out of
+ * bounds"), and while the replay is not committed or not assigned. */
+int msckf_hip_map_log_fault_metrics(msckf_hip_handle h, int q0, int q1, int f0, double* out /*[B][8]*/);
 int msckf_hip_sync(msckf_hip_handle h);
 /* ---- per-frame device log of msckf_hip_run_frames / _streamed (off by default) ------------------------ */
 /* Storage for capacity_frames records ("frame log record" above) of every trajectory, in the handle's dtype; 0 frees the

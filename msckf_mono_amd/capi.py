@@ -41,6 +41,7 @@ SYMBOLS = [
     "msckf_hip_pruned_log_enable", "msckf_hip_pruned_log_reset", "msckf_hip_pruned_log_frames", "msckf_hip_pruned_log_counts", "msckf_hip_pruned_log_read", "msckf_hip_pruned_log_metrics",
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
+    "msckf_hip_replay_set_faults", "msckf_hip_replay_expand_faults", "msckf_hip_replay_fault_counts", "msckf_hip_map_log_fault_metrics",
     "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
     "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
@@ -63,6 +64,10 @@ MAP_LOG_FIELDS = {"p": slice(0, 3), "gamma": slice(3, 4), "frame": slice(4, 5), 
 MAP_FLAG_PASS, MAP_FLAG_INCLUDED, MAP_FLAG_BOUND = 1, 2, 4   # bits of "flags": gate passed, included in the update, gamma is the early-accept bound
 # columns of map_log_metrics' result
 MAP_LOG_METRICS = ("n", "n_matched", "sum_sq_err", "max_err", "n_gated", "sum_gamma", "sum_dof", "n_unmatched")
+# columns of replay_fault_counts' and of map_log_fault_metrics' result, and replay_expand_faults' codes
+REPLAY_FAULT_COUNTS = ("entries", "missed", "outliers", "tracks", "tracks_shortened", "tracks_contaminated")
+MAP_LOG_FAULT_METRICS = ("n", "clean_passed", "clean_rejected", "contaminated_passed", "contaminated_rejected", "sum_gamma", "sum_dof", "n_unmatched")
+FAULT_KEPT, FAULT_OUTLIER, FAULT_MISSED = 0, 1, 2
 # fields of a pruned-state log record (include/msckf_hip.h, "pruned-state log record"): name -> slice of its 32 scalars
 PRUNED_LOG_STRIDE = 32
 PRUNED_LOG_FIELDS = {"q": slice(0, 4), "p": slice(4, 7), "frame": slice(7, 8), "cov": slice(8, 29),   # cov: upper triangle of the 6 x 6 block, row by row
@@ -443,6 +448,30 @@ class Batch:
         return dict(rd=rd, obs=obs[:n], n=int(ints[0]), drop=int(ints[1]), k=int(ints[2]), M=ints[3:3 + self.f_cap].copy(),
                     off=ints[3 + self.f_cap:].copy(), slots=slots[:n])
 
+    def replay_set_faults(self, fault4):
+        """seeded missed observations and outliers (include/msckf_hip.h): per trajectory (p_miss, p_out, rho_u, rho_v), one row
+        serves every trajectory; None: no faults.  Stays through replay_assign, replay_assign_q and replay_commit."""
+        if fault4 is None:
+            _chk(self.L.msckf_hip_replay_set_faults(self.h, None))
+            return
+        ft = np.ascontiguousarray(np.broadcast_to(np.asarray(fault4, dtype=np.float64), (self.B, 4)))
+        _chk(self.L.msckf_hip_replay_set_faults(self.h, ft.ctypes.data_as(_dp)))
+
+    def replay_expand_faults(self, frame, b):
+        """per sequence entry of trajectory b's cell on `frame`: FAULT_KEPT, FAULT_OUTLIER or FAULT_MISSED"""
+        cap = self.f_cap * self.m_cap
+        code = np.zeros(cap, dtype=np.int32)
+        n = _chk(self.L.msckf_hip_replay_expand_faults(self.h, int(frame), int(b), code.ctypes.data_as(_ip), cap))
+        return code[:n]
+
+    def replay_fault_counts(self, f0=0, f1=None):
+        """the faults of the frames [f0, f1) (default: all) per trajectory, counted on the device: int64 [B][6], columns
+        REPLAY_FAULT_COUNTS"""
+        f1 = self._replay_frames if f1 is None else int(f1)
+        out = np.zeros((self.B, 6), dtype=np.int64)
+        _chk(self.L.msckf_hip_replay_fault_counts(self.h, int(f0), f1, out.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return out
+
     def scenario_pin(self, f0, f1):
         """page-lock the per-frame blocks of frames [f0, f1) ahead of a streamed run (outside any timed region)"""
         _chk(self.L.msckf_hip_scenario_pin(self.h, int(f0), int(f1)))
@@ -608,6 +637,13 @@ class Batch:
         if off.shape != ((int(q1) - int(q0)) * self.B + 1,) or (off.size and int(off[-1]) > len(g)):
             raise ValueError("gt_off must hold (q1 - q0) * B + 1 offsets into gt_xyz")
         _chk(self.L.msckf_hip_map_log_metrics(self.h, int(q0), int(q1), g.ctypes.data_as(_dp), po, o.ctypes.data_as(_dp)))
+        return o
+
+    def map_log_fault_metrics(self, q0, q1, f0):
+        """the stored records with frame ordinal in [q0, q1) -- written by run_frames_replay contiguously from replay frame f0 --
+        against the faults of their tracks, reduced on the device: [B][8], columns MAP_LOG_FAULT_METRICS"""
+        o = np.zeros((self.B, 8))
+        _chk(self.L.msckf_hip_map_log_fault_metrics(self.h, int(q0), int(q1), int(f0), o.ctypes.data_as(_dp)))
         return o
 
     # ---- pruned-state device log of run_frames / run_frames_streamed: the smoothed camera poses

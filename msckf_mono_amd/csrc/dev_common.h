@@ -587,14 +587,23 @@ void launch_traj_rpe_pose(const double* est, int n_traj, int n_rec, const int* r
 // first sequence entry) through the assignment (t: seq_of[B], seed[B], sigma[B][4], and the frame's base[B]) into the ordinary
 // frame block (o: its sections from trajectory 0).  A workgroup takes REPLAY_CHUNK items of one trajectory.
 struct ReplaySeqIn { const double* rd; const int* n; const int* drop; const int* k; const int* M; const int* off; const int* slots; const double* obs; };
-struct ReplayTrajIn { const int* seq_of; const uint64_t* seed; const double* sigma; const int* base; };
+// t.fault: fault4[B][4] (replay_plan.h, FAULTS), or null: no faults, the unfaulted form is launched
+struct ReplayTrajIn { const int* seq_of; const uint64_t* seed; const double* sigma; const int* base; const double* fault = nullptr; };
 template <class S> struct ReplayOut { S* rd; int* n; int* drop; int* k; int* M; int* off; int* slots; S* obs; };
 constexpr int REPLAY_CHUNK = 256;
 constexpr int REPLAY_SCAN_CHUNK = 64;
 // Under the Q_imu model (replay_plan.h, MODEL) t.sigma is sigma_uv[B][2] and m holds the rest: the factors L[B][144], scale[B]
 // and the frame's row of the walk table, wstart[B][6]; m.L == nullptr: the sigma4 model.
 struct ReplayModelIn { const double* L; const double* scale; const double* wstart; };
-template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st);
+// With t.fault the faulted form runs: a group of fault_group(m_cap) lanes per track, the grid sized from f_cap tracks; code (or
+// null): per entry of the block, at base[b] + the entry's index in the sequence cell, 0 kept, 1 outlier, 2 missed.
+template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st, int m_cap = 0, int* code = nullptr);
+// the faults of the frames [f0, f1) counted per trajectory, out[B][6] (replay_plan.h, FaultCount): n / M / off are the sequence
+// store's sections from frame 0, t.fault is not null; one workgroup per trajectory.  And the map log's records with ordinal in
+// [q0, q1) -- record ordinal q belongs to replay frame f0 + (q - q0) -- against the faults of their tracks, recomputed from
+// (seed, frame, the sequence's off / M, fault4): out[B][8] (replay_plan.h, FaultMetric); t.fault null: every track is clean.
+void launch_replay_fault_counts(const int* n, const int* M, const int* off, const ReplayTrajIn& t, int f0, int f1, int S, int f_cap, int B, long long* out, hipStream_t st);
+template <class S> void launch_map_fault_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, int f0, const int* n, const int* M, const int* off, const ReplayTrajIn& t, int n_seq, int f_cap, double* out, hipStream_t st);
 // the model's walk table wstart[frames + 1][B][6] for all B trajectories: one workgroup per trajectory, REPLAY_SCAN_CHUNK frames
 // at a time.  rd / k: the sequence store's readings [frames][S][K][7] and counts [frames][S]; t.sigma and t.base are not read.
 void launch_replay_walk_scan(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, double* wstart, int frames, int S, int K, int B, hipStream_t st);

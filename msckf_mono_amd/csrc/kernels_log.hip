@@ -15,6 +15,7 @@
 // of trajectories (the seeds of a sequence) at each frame: the sums behind the ANEES curves.
 #include "dev_common.h"
 #include "nees_plan.h"
+#include "replay_plan.h"
 
 namespace msckf {
 
@@ -188,6 +189,47 @@ __global__ __launch_bounds__(64) void k_map_metrics(const S* rec, const int* fou
   if (lane == 0) {
     double* o = out + (long)b * 8;
     o[0] = cnt; o[1] = nm; o[2] = s2; o[3] = mx; o[4] = ng; o[5] = sg; o[6] = sd; o[7] = un;
+  }
+}
+
+// The gate's confusion table under the replay's faults (msckf_hip_map_log_fault_metrics; replay_plan.h, FAULTS): one workgroup
+// (one wavefront) per trajectory over the stored records with frame ordinal in [q0, q1); the record with ordinal q belongs to
+// replay frame f0 + (q - q0).  Whether its track carries an outlier is recomputed from (seed, frame, the sequence cell's
+// off / M, fault4) with rp::track_faults; fault == null: nothing does.  n / M / off: the sequence store's sections from frame 0.
+// out[b][8] = records in range, clean and passed, clean and rejected, contaminated and passed, contaminated and rejected,
+// sum gamma and sum 2 M - 3 (M: the record's, the survivors) over the clean passed records whose gamma is not the early-accept
+// bound, records whose track index is >= the cell's n (unmatched, counted in column 0 only).  All in f64, records l, l + 64, ...
+// in ascending order per lane, the lanes combined by wave_sum's fixed tree: the same log gives the same bits on every call.
+template <class S>
+__global__ __launch_bounds__(64) void k_map_fault_metrics(const S* rec, const int* found, int cap, int q0, int q1, int f0, const int* n, const int* M, const int* off,
+                                                          const int* seq_of, const uint64_t* seed, const double* fault, int n_seq, int f_cap, double* out) {
+  namespace rp = msckf_replay;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int stored = cursor_stored(found, b, cap);
+  const int s = seq_of[b];
+  const uint64_t sd = seed[b];
+  const double p_miss = fault ? fault[(long)b * rp::N_FAULT + rp::FLT_P_MISS] : 0.0, p_out = fault ? fault[(long)b * rp::N_FAULT + rp::FLT_P_OUT] : 0.0;
+  double c[rp::N_FAULT_METRIC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int r = lane; r < stored; r += 64) {
+    const Vec4<S>* q = reinterpret_cast<const Vec4<S>*>(rec + ((long)b * cap + r) * MAP_STRIDE);
+    const Vec4<S> a = q[0], w = q[1];
+    const int fr = (int)w.x[0], trk = (int)w.x[1], flags = (int)w.x[2];
+    if (!ordinal_in(fr, q0, q1)) continue;
+    c[rp::FM_RECORDS] += 1.0;
+    const int f = f0 + (fr - q0);
+    const long cell = (long)f * n_seq + s;
+    if (trk < 0 || trk >= n[cell]) { c[rp::FM_UNMATCHED] += 1.0; continue; }
+    const int e0 = off[cell * f_cap + trk] - off[cell * f_cap];
+    const bool dirty = p_out > 0.0 && rp::track_faults(rp::fault_seed(sd, f), (uint64_t)e0, M[cell * f_cap + trk], p_miss, p_out).outliers > 0;
+    const bool pass = (flags & MAP_FLAG_PASS) != 0;
+    c[rp::FM_CLEAN_PASS] += !dirty && pass ? 1.0 : 0.0; c[rp::FM_CLEAN_REJ] += !dirty && !pass ? 1.0 : 0.0;
+    c[rp::FM_CONT_PASS] += dirty && pass ? 1.0 : 0.0; c[rp::FM_CONT_REJ] += dirty && !pass ? 1.0 : 0.0;
+    if (!dirty && pass && !(flags & MAP_FLAG_BOUND)) { c[rp::FM_SUM_GAMMA] += (double)a.x[3]; c[rp::FM_SUM_DOF] += 2.0 * (double)w.x[3] - 3.0; }
+  }
+#pragma unroll
+  for (int i = 0; i < rp::N_FAULT_METRIC; ++i) {
+    const double v = wave_sum(c[i]);
+    if (lane == 0) out[(long)b * rp::N_FAULT_METRIC + i] = v;
   }
 }
 
@@ -453,6 +495,12 @@ void launch_map_metrics(const S* rec, const int* found, int cap, int B, int q0, 
 }
 
 template <class S>
+void launch_map_fault_metrics(const S* rec, const int* found, int cap, int B, int q0, int q1, int f0, const int* n, const int* M, const int* off, const ReplayTrajIn& t, int n_seq, int f_cap, double* out, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_map_fault_metrics<S>, dim3(B), dim3(64), 0, st, rec, found, cap, q0, q1, f0, n, M, off, t.seq_of, t.seed, t.fault, n_seq, f_cap, out);
+}
+
+template <class S>
 void launch_frame_log(const Dev<S>& d, int b0, int nb, hipStream_t st, const S* P, bool pending, S* rec) {
   if (nb <= 0) return;
   hipLaunchKernelGGL(k_frame_log<S>, dim3((nb + 3) / 4), dim3(256), 0, st, d, b0, nb, P, pending ? 1 : 0, rec);
@@ -468,6 +516,7 @@ void launch_log_metrics(const S* log, int B, int r0, int r1, const int* r0b, con
   template void launch_log_metrics<S>(const S*, int, int, int, const int*, const int*, const double*, double*, hipStream_t); \
   template void launch_map_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, const int*, int, int, S*, int*);   \
   template void launch_map_metrics<S>(const S*, const int*, int, int, int, int, const double*, const int*, double*, hipStream_t); \
+  template void launch_map_fault_metrics<S>(const S*, const int*, int, int, int, int, int, const int*, const int*, const int*, const ReplayTrajIn&, int, int, double*, hipStream_t); \
   template void launch_pruned_log<S>(const Dev<S>&, int, int, hipStream_t, const int*, int, int, S*, int*);            \
   template void launch_pruned_metrics<S>(const S*, const int*, int, int, int, int, const int*, const double*, int, double*, hipStream_t); \
   template void launch_nees_log<S>(const Dev<S>&, int, int, hipStream_t, const S*, const int*, const double*, const int*, const double*, int, double*);

@@ -20,6 +20,12 @@
 // needs the walk's prefix over the samples before it, so a trajectory's first workgroup forms all of them together ahead of its
 // items (model_imu: one lane per pair, per row of w = L z, per walk component, per stored scalar, handed over through LDS).
 // k_replay_walk_scan tabulates the walk at every frame's start once per assignment.
+//
+// With a fault record (replay_plan.h, FAULTS) k_replay_expand_faults runs in its place: the same fixed items, and track items
+// instead of entry items -- a group of lanes per track drops the missed observations behind the survivors and displaces the
+// outliers.  k_replay_fault_counts counts a frame range's faults without expanding anything.
+#include <type_traits>
+
 #include "dev_common.h"
 #include "replay_plan.h"
 
@@ -136,6 +142,55 @@ __device__ __forceinline__ void model_imu(const double* cell, S* out, const doub
   }
 }
 
+// One entry's coordinate pair, stated once for both forms of the expansion: value + sigma * noise with pair e of s_obs (e: the
+// entry's index in the SEQUENCE cell), and for an outlier (replay_plan.h, FAULTS) the ring term on top of it -- a = the rounded
+// product 2 pi u_ang, each product rounded, then added -- all in double, rounded once.  out == false: flt and u_ang are not read.
+template <class S, bool MODEL>
+__device__ __forceinline__ Vec2<S> entry_obs(const double* z, const double* sg, uint64_t s_obs, uint64_t e, bool out, double u_ang, const double* flt) {
+  const Pair g = box_muller(s_obs, e);
+  double x = noisy(z[0], sg[MODEL ? 0 : rp::SIG_U], g.c), y = noisy(z[1], sg[MODEL ? 1 : rp::SIG_V], g.s);
+  if (out) {
+    double sn, cs;
+    sincos(6.283185307179586 * u_ang, &sn, &cs);
+    x = noisy(x, flt[rp::FLT_RHO_U], cs); y = noisy(y, flt[rp::FLT_RHO_V], sn);
+  }
+  Vec2<S> w;
+  w.x = (S)x; w.y = (S)y;
+  return w;
+}
+
+// The fixed items of a trajectory, j counted from the first of them (the list at the top of the file without the entries):
+// IMU noise pairs (sigma4 model only), dT, M[t] / off[t], and n / drop / k.  with_M == false: M[t] is somebody else's (the
+// faulted form's track items store the survivors).
+struct ReplayCell { int s, b, kc, first, base; uint64_t seed; const double* sg; const int* Ms; const int* offs; };
+template <class S, bool MODEL>
+__device__ __forceinline__ void fixed_item(const ReplaySeqIn& q, const ReplayOut<S>& o, const ReplayCell& c, int j, int f, int K, int f_cap, bool with_M) {
+  const int dt0 = (MODEL ? 0 : rp::IMU_PAIRS) * K, m0 = dt0 + K, last = m0 + f_cap;
+  const int s = c.s, b = c.b;
+  if (j < dt0) {
+    const int i = j / rp::IMU_PAIRS, cc = 2 * (j % rp::IMU_PAIRS);
+    const double* r = q.rd + ((long)s * K + i) * RD_STRIDE;
+    S* w = o.rd + ((long)b * K + i) * RD_STRIDE;
+    double v0 = r[cc], v1 = r[cc + 1];
+    if (i < c.kc) {                                                    // (a skipped cell's k is IMU_SKIP: no noise; rows from k on stay zero)
+      const Pair g = box_muller(rp::imu_seed(c.seed, f), (uint64_t)j);
+      v0 = noisy(v0, c.sg[cc < 3 ? rp::SIG_G : rp::SIG_A], g.c); v1 = noisy(v1, c.sg[cc + 1 < 3 ? rp::SIG_G : rp::SIG_A], g.s);
+    }
+    w[cc] = (S)v0; w[cc + 1] = (S)v1;
+  } else if (j < m0) {
+    const int i = j - dt0;
+    o.rd[((long)b * K + i) * RD_STRIDE + 6] = (S)q.rd[((long)s * K + i) * RD_STRIDE + 6];
+  } else if (j < last) {
+    const int tr = j - m0;
+    if (with_M) o.M[(long)b * f_cap + tr] = c.Ms[tr];
+    o.off[(long)b * f_cap + tr] = c.offs[tr] - c.first + c.base;
+  } else {
+    o.n[b] = q.n[s]; o.drop[b] = q.drop[s]; o.k[b] = c.kc;
+  }
+}
+// fixed items of a trajectory: IMU pairs (sigma4 model only), dT, tracks, the last
+constexpr int fixed_items(bool model, int K, int f_cap) { return ((model ? 0 : rp::IMU_PAIRS) + 1) * K + f_cap + 1; }
+
 // MODEL: false the sigma4 noise (the items above), true the Q_imu model (no IMU items: model_imu; t.sigma is sigma_uv[B][2])
 template <class S, bool MODEL>
 __global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand(ReplaySeqIn q, ReplayTrajIn t, ReplayModelIn m, ReplayOut<S> o, int f, int b0, int K, int f_cap) {
@@ -153,50 +208,133 @@ __global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand(ReplaySeqIn q, R
     if (blockIdx.x == 0)
       model_imu<S>(q.rd + (long)s * K * RD_STRIDE, o.rd + (long)b * K * RD_STRIDE, m.L + (long)b * rp::L_SIZE, m.scale[b], m.wstart + (long)b * rp::WALK_ROW, rp::imu_seed(seed, f), K, kc < K ? kc : K);
   }
-  const int imu0 = E, dt0 = E + (MODEL ? 0 : rp::IMU_PAIRS) * K, m0 = dt0 + K, last = m0 + f_cap;
+  const ReplayCell c{s, b, kc, first, base, seed, sg, Ms, offs};
+  const int last = E + fixed_items(MODEL, K, f_cap) - 1;
   for (int it = (int)blockIdx.x * REPLAY_CHUNK + (int)threadIdx.x; it <= last; it += (int)gridDim.x * REPLAY_CHUNK) {
-    if (it < imu0) {
-      const Pair g = box_muller(rp::obs_seed(seed, f), (uint64_t)it);
-      const double* z = q.obs + 2 * (long)(first + it);
+    if (it < E) {
       o.slots[(long)base + it] = q.slots[(long)first + it];
-      Vec2<S> w;
-      w.x = (S)noisy(z[0], sg[MODEL ? 0 : rp::SIG_U], g.c); w.y = (S)noisy(z[1], sg[MODEL ? 1 : rp::SIG_V], g.s);
-      *reinterpret_cast<Vec2<S>*>(o.obs + 2 * ((long)base + it)) = w;
-    } else if (it < dt0) {
-      const int j = it - imu0, i = j / rp::IMU_PAIRS, c = 2 * (j % rp::IMU_PAIRS);
-      const double* r = q.rd + ((long)s * K + i) * RD_STRIDE;
-      S* w = o.rd + ((long)b * K + i) * RD_STRIDE;
-      double v0 = r[c], v1 = r[c + 1];
-      if (i < kc) {                                                    // (a skipped cell's k is IMU_SKIP: no noise; rows from k on stay zero)
-        const Pair g = box_muller(rp::imu_seed(seed, f), (uint64_t)j);
-        v0 = noisy(v0, sg[c < 3 ? rp::SIG_G : rp::SIG_A], g.c); v1 = noisy(v1, sg[c + 1 < 3 ? rp::SIG_G : rp::SIG_A], g.s);
-      }
-      w[c] = (S)v0; w[c + 1] = (S)v1;
-    } else if (it < m0) {
-      const int i = it - dt0;
-      o.rd[((long)b * K + i) * RD_STRIDE + 6] = (S)q.rd[((long)s * K + i) * RD_STRIDE + 6];
-    } else if (it < last) {
-      const int tr = it - m0;
-      o.M[(long)b * f_cap + tr] = Ms[tr];
-      o.off[(long)b * f_cap + tr] = offs[tr] - first + base;
-    } else {
-      o.n[b] = q.n[s]; o.drop[b] = q.drop[s]; o.k[b] = kc;
-    }
+      *reinterpret_cast<Vec2<S>*>(o.obs + 2 * ((long)base + it)) = entry_obs<S, MODEL>(q.obs + 2 * (long)(first + it), sg, rp::obs_seed(seed, f), (uint64_t)it, false, 0.0, nullptr);
+    } else fixed_item<S, MODEL>(q, o, c, it - E, f, K, f_cap, true);
   }
 }
 
-// max_entries: the entries of the frame's largest sequence cell (the grid's width; a trajectory with fewer leaves its lanes idle)
+// The faulted form (replay_plan.h, FAULTS; t.fault is fault4[B][4]): the fixed items stay, the entry items become TRACK items --
+// a group of G lanes takes one track, one lane per entry (G = 16, 32 or 64 >= m_cap, chosen at launch, so that short-track
+// handles do not idle three quarters of a wavefront).  The lane draws its three uniforms and its noise pair; the group cuts its
+// part out of the wavefront's ballot of raw_miss, applies the "fewer than two" rule on the popcount, and each lane ranks itself
+// with mbcnt among the survivors or among the missed entries (as k_map_log ranks its records): slot and coordinate pair go to
+// base + off[t] - first + rank (+ survivors for a missed entry), the group's first lane stores M[t] = survivors.  The track items
+// [0, f_cap G) are padded to whole wavefronts, so a wavefront is either all track items or all fixed items.  code (null in the
+// frame loop): per entry of the block, at base + the entry's SEQUENCE index, 0 kept, 1 outlier, 2 missed.
+// No LDS, no atomics, no exchange between wavefronts.
+template <class S, bool MODEL, int G>
+__global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand_faults(ReplaySeqIn q, ReplayTrajIn t, ReplayModelIn m, ReplayOut<S> o, int* code, int f, int b0, int K, int f_cap) {
+  const int b = b0 + (int)blockIdx.y;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double* sg = t.sigma + (long)b * (MODEL ? 2 : rp::N_SIGMA);
+  const double* flt = t.fault + (long)b * rp::N_FAULT;
+  const int* Ms = q.M + (long)s * f_cap;
+  const int* offs = q.off + (long)s * f_cap;
+  const int first = offs[0];
+  const int base = t.base[b];
+  const int kc = q.k[s];
+  if constexpr (MODEL) {
+    if (blockIdx.x == 0)
+      model_imu<S>(q.rd + (long)s * K * RD_STRIDE, o.rd + (long)b * K * RD_STRIDE, m.L + (long)b * rp::L_SIZE, m.scale[b], m.wstart + (long)b * rp::WALK_ROW, rp::imu_seed(seed, f), K, kc < K ? kc : K);
+  }
+  const ReplayCell c{s, b, kc, first, base, seed, sg, Ms, offs};
+  const double p_miss = flt[rp::FLT_P_MISS], p_out = flt[rp::FLT_P_OUT];
+  const uint64_t s_flt = rp::fault_seed(seed, f), s_obs = rp::obs_seed(seed, f);
+  const int lane = (int)threadIdx.x & 63;
+  const int T = (f_cap * G + 63) & ~63;                                // REPLAY_CHUNK is a multiple of 64: `it < T` is the same for a whole wavefront
+  const int end = T + fixed_items(MODEL, K, f_cap);
+  for (int it = (int)blockIdx.x * REPLAY_CHUNK + (int)threadIdx.x; it < end; it += (int)gridDim.x * REPLAY_CHUNK) {
+    if (it < T) {
+      const int tr = it / G, l = it % G;
+      const int M = tr < f_cap ? Ms[tr] : 0;                           // (M <= m_cap <= G)
+      const bool have = l < M;
+      const int e = have ? offs[tr] - first + l : 0;                   // the entry's index in the sequence cell
+      const bool raw = have && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e) < p_miss;
+      unsigned long long gm = __ballot(raw ? 1 : 0);
+      if constexpr (G < 64) gm &= ((1ull << G) - 1) << (lane & ~(G - 1));
+      if (M - __popcll(gm) < 2) gm = 0;                                // a track keeps two observations or loses none
+      const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(gm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)gm, 0u));   // missed entries of the track before this one
+      const int surv = M - __popcll(gm);
+      if (have) {
+        const bool miss = (gm >> lane) & 1;
+        const bool out = !miss && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 1) < p_out;
+        const long dst = (long)base + (offs[tr] - first) + (miss ? surv + below : l - below);
+        o.slots[dst] = q.slots[(long)first + e];
+        *reinterpret_cast<Vec2<S>*>(o.obs + 2 * dst) = entry_obs<S, MODEL>(q.obs + 2 * (long)(first + e), sg, s_obs, (uint64_t)e, out, rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 2), flt);
+        if (code) code[(long)base + e] = miss ? rp::FAULT_MISSED : out ? rp::FAULT_OUTLIER : rp::FAULT_KEPT;
+      }
+      if (l == 0 && tr < f_cap) o.M[(long)b * f_cap + tr] = surv;
+    } else fixed_item<S, MODEL>(q, o, c, it - T, f, K, f_cap, false);
+  }
+}
+
+// max_entries: the entries of the frame's largest sequence cell (the unfaulted grid's width; a trajectory with fewer leaves its
+// lanes idle).  t.fault != nullptr: the faulted form, its grid sized from f_cap tracks of G lanes, G from m_cap.
+template <class S, bool MODEL, int G>
+static void launch_faulted(const dim3& grid, hipStream_t st, const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int* code, int f, int b0, int K, int f_cap) {
+  hipLaunchKernelGGL((k_replay_expand_faults<S, MODEL, G>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, o, code, f, b0, K, f_cap);
+}
 template <class S>
-void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st) {
+void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st, int m_cap, int* code) {
   if (nb <= 0) return;
   const bool model = m.L != nullptr;
-  const long items = (long)max_entries + (long)((model ? 0 : rp::IMU_PAIRS) + 1) * K + f_cap + 1;
+  if (t.fault) {
+    const int G = rp::fault_group(m_cap);
+    const long items = (long)((f_cap * G + 63) & ~63) + fixed_items(model, K, f_cap);
+    const dim3 grid((unsigned)((items + REPLAY_CHUNK - 1) / REPLAY_CHUNK), (unsigned)nb);
+    auto go = [&](auto mdl) {
+      constexpr bool MD = decltype(mdl)::value;
+      if (G == 16) launch_faulted<S, MD, 16>(grid, st, q, t, m, o, code, f, b0, K, f_cap);
+      else if (G == 32) launch_faulted<S, MD, 32>(grid, st, q, t, m, o, code, f, b0, K, f_cap);
+      else launch_faulted<S, MD, 64>(grid, st, q, t, m, o, code, f, b0, K, f_cap);
+    };
+    if (model) go(std::true_type{}); else go(std::false_type{});
+    return;
+  }
+  const long items = (long)max_entries + fixed_items(model, K, f_cap);
   const dim3 grid((unsigned)((items + REPLAY_CHUNK - 1) / REPLAY_CHUNK), (unsigned)nb);
   if (model) hipLaunchKernelGGL((k_replay_expand<S, true>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, o, f, b0, K, f_cap);
   else hipLaunchKernelGGL((k_replay_expand<S, false>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, o, f, b0, K, f_cap);
 }
-template void launch_replay_expand<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<float>&, int, int, int, int, int, int, hipStream_t);
-template void launch_replay_expand<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<double>&, int, int, int, int, int, int, hipStream_t);
+template void launch_replay_expand<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<float>&, int, int, int, int, int, int, hipStream_t, int, int*);
+template void launch_replay_expand<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayOut<double>&, int, int, int, int, int, int, hipStream_t, int, int*);
+
+// msckf_hip_replay_fault_counts: the faults of the frames [f0, f1) counted without expanding anything -- one workgroup (one
+// wavefront) per trajectory, lane l takes the (frame, track) pairs l, l + 64, ... and goes through a track's entries with
+// rp::track_faults (the rule stated serially); the lanes are combined by wave_sum.  Integers below 2^53 in doubles: exact.
+// n / M / off: the sequence store's sections from frame 0 ([frames][S], [frames][S][f_cap]); out [B][6] (replay_plan.h, FaultCount).
+__global__ __launch_bounds__(64) void k_replay_fault_counts(const int* n, const int* M, const int* off, ReplayTrajIn t, int f0, int f1, int S, int f_cap, long long* out) {
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double p_miss = t.fault[(long)b * rp::N_FAULT + rp::FLT_P_MISS], p_out = t.fault[(long)b * rp::N_FAULT + rp::FLT_P_OUT];
+  double c[rp::N_FAULT_COUNT] = {0, 0, 0, 0, 0, 0};
+  const long items = (long)(f1 - f0) * f_cap;
+  for (long it = lane; it < items; it += 64) {
+    const int f = f0 + (int)(it / f_cap), tr = (int)(it % f_cap);
+    const long cell = (long)f * S + s;
+    if (tr >= n[cell]) continue;
+    const int Mt = M[cell * f_cap + tr], e0 = off[cell * f_cap + tr] - off[cell * f_cap];
+    const rp::TrackFaults tf = rp::track_faults(rp::fault_seed(seed, f), (uint64_t)e0, Mt, p_miss, p_out);
+    c[rp::FC_ENTRIES] += Mt; c[rp::FC_MISSED] += tf.missed; c[rp::FC_OUTLIERS] += tf.outliers;
+    c[rp::FC_TRACKS] += 1.0; c[rp::FC_TRACKS_SHORTENED] += tf.missed > 0; c[rp::FC_TRACKS_CONTAMINATED] += tf.outliers > 0;
+  }
+#pragma unroll
+  for (int i = 0; i < rp::N_FAULT_COUNT; ++i) {
+    const double v = wave_sum(c[i]);
+    if (lane == 0) out[(long)b * rp::N_FAULT_COUNT + i] = (long long)v;
+  }
+}
+void launch_replay_fault_counts(const int* n, const int* M, const int* off, const ReplayTrajIn& t, int f0, int f1, int S, int f_cap, int B, long long* out, hipStream_t st) {
+  if (B <= 0) return;
+  hipLaunchKernelGGL(k_replay_fault_counts, dim3((unsigned)B), dim3(64), 0, st, n, M, off, t, f0, f1, S, f_cap, out);
+}
 
 // The walk table of the model, wstart[frames + 1][B][6], once per assignment: workgroup b takes trajectory b.  Per chunk of
 // REPLAY_SCAN_CHUNK frames lane j forms P(f, k_f) of frame f = chunk + j serially over the cell's samples into LDS; then six

@@ -234,6 +234,9 @@ struct BatchCore {
   double* rp_L = nullptr; double* rp_scale = nullptr; double* rp_wstart = nullptr; size_t rp_wstart_count = 0;
   unsigned char* rp_blk[MAXS] = {nullptr}; size_t rp_blk_bytes = 0;
   unsigned char* rp_scratch = nullptr; size_t rp_scratch_bytes = 0;
+  // the fault record fault4[B][4] (zeros while none is set; rp.faults_uploaded) and replay_expand_faults' codes, one per entry of
+  // the largest expanded frame
+  double* rp_fault = nullptr; int* rp_code = nullptr; size_t rp_code_count = 0;
   std::vector<int> rp_cells[MAXS];
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
@@ -1059,6 +1062,7 @@ struct BatchCore {
     for (auto& p : rp_blk) dfree(p);
     rp_blk_bytes = 0;
     dfree(rp_scratch); rp_scratch_bytes = 0;
+    dfree(rp_fault); dfree(rp_code); rp_code_count = 0;
     rp_uploaded = false;
   }
   int replay_alloc(int n_seq, int n_frames, int K) {
@@ -1111,14 +1115,23 @@ struct BatchCore {
     rp_uploaded = false;
     return 0;
   }
-  // before a run or an expansion (after enter()): the bases of every frame, and with the assignment on the device
+  // the fault record (replay_plan.h, FAULTS), or null for none; may be called between runs, stays through assign, assign_q and
+  // commit, and replay_alloc clears it.  A refused call leaves the previous record in force.
+  int replay_set_faults(const double* fault4) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.faults_refusal(fault4))) return rc;
+    rp.set_faults(fault4);
+    return 0;
+  }
+  // before a run or an expansion (after enter()): the bases of every frame, and with the assignment and the fault record on the device
   int replay_upload_plan() {
-    if (rp.planned && rp_uploaded) return 0;
+    if (rp.planned && rp_uploaded && rp.faults_uploaded) return 0;
     if (int rc = refuse(rp.index_trajectories())) return rc;
     HIPCHK(hipStreamSynchronize(st));                        // the last run's kernels have read the old ones
     if (!rp_seq_of) {
       HIPCHK(hipMalloc((void**)&rp_seq_of, (size_t)B * sizeof(int))); HIPCHK(hipMalloc((void**)&rp_seed, (size_t)B * sizeof(uint64_t)));
       HIPCHK(hipMalloc((void**)&rp_sigma, (size_t)B * msckf_replay::N_SIGMA * sizeof(double)));
+      HIPCHK(hipMalloc((void**)&rp_fault, (size_t)B * msckf_replay::N_FAULT * sizeof(double)));
     }
     if (rp.base.size() != rp_base_count) { dfree(rp_base); rp_base_count = 0; HIPCHK(hipMalloc((void**)&rp_base, rp.base.size() * sizeof(int))); rp_base_count = rp.base.size(); }
     HIPCHK(hipMemcpy(rp_seq_of, rp.seq_of.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
@@ -1132,8 +1145,36 @@ struct BatchCore {
       HIPCHK(hipMemcpy(rp_L, rp.L.data(), rp.L.size() * sizeof(double), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(rp_scale, rp.scale.data(), rp.scale.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    rp_uploaded = true;
+    if (rp.fault.empty()) HIPCHK(hipMemset(rp_fault, 0, (size_t)B * msckf_replay::N_FAULT * sizeof(double)));
+    else HIPCHK(hipMemcpy(rp_fault, rp.fault.data(), rp.fault.size() * sizeof(double), hipMemcpyHostToDevice));
+    rp_uploaded = rp.faults_uploaded = true;
     return 0;
+  }
+  // msckf_hip_replay_fault_counts: the faults of the frames [f0, f1) per trajectory, out [B][6], counted on the device from the
+  // sequences, the seeds and the fault record alone (k_replay_fault_counts): no run, no log
+  int replay_fault_counts(int f0, int f1, long long* out) {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.run_refusal(f0, f1))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    constexpr size_t W = msckf_replay::N_FAULT_COUNT;
+    long long* dout = nullptr;
+    HIPCHK(hipMalloc((void**)&dout, (size_t)B * W * sizeof(long long)));
+    auto i = [&](int s) { return reinterpret_cast<const int*>(rp_dev[s]); };
+    launch_replay_fault_counts(i(SEC_N), i(SEC_M), i(SEC_OFF), ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base, rp_fault}, f0, f1, rp.S, f_cap, B, dout, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)B * W * sizeof(long long), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dout);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("replay_fault_counts: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // what map_log_fault_metrics checks before anything reaches the device: the log and its ordinals, then the replay frames
+  // [f0, f0 + (q1 - q0)) as a run would check them
+  int map_log_check_faults(int q0, int q1, int f0) {
+    if (int rc = cursor_log_check_ordinals(map, q0, q1)) return rc;
+    return refuse(rp.run_refusal(f0, f0 + (q1 - q0)));
   }
   // under the Q_imu model, after replay_upload_plan(): the walk table of the cells and the assignment as they stand, tabulated on
   // the handle's stream (stage 12; the slices' streams fork from it) if it is not already
@@ -1332,7 +1373,8 @@ struct BatchCore {
   // THE frame step of run_frames / run_frames_streamed / run_frames_replay: frame f of a call over [f0, f1) for slice s, inputs
   // in staging set `staged` of the upload ring, or resident (IN_RESIDENT), or expanded by the replay (IN_REPLAY)
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
-  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries) = 0;
+  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr) = 0;
+  virtual int map_log_fault_metrics(int q0, int q1, int f0, double* out) = 0;                  // out [B][8]
   virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
   virtual void apply_settings() = 0;   // the one place where `settings` reaches the kernel argument
   virtual int set_aniso(int mode, double tol) = 0;
@@ -2033,7 +2075,8 @@ struct Batch : BatchCore {
     auto i = [&](int s) { return reinterpret_cast<const int*>(at(s)); };
     return ReplaySeqIn{reinterpret_cast<const double*>(at(SEC_RD)), i(SEC_N), i(SEC_DROP), i(SEC_K), i(SEC_M), i(SEC_OFF), i(SEC_SLOTS), reinterpret_cast<const double*>(at(SEC_OBS))};
   }
-  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B}; }
+  // (the fault record only while some trajectory has a non-zero probability: otherwise the unfaulted form is launched)
+  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B, rp.faulted ? rp_fault : nullptr}; }
   ReplayOut<S> replay_out(unsigned char* blk, int f) const {
     using namespace inputs;
     const FrameLayout L = rp.out_layout(sizeof(S));
@@ -2047,8 +2090,10 @@ struct Batch : BatchCore {
   }
   // msckf_hip_replay_expand / _ints: k_replay_expand for trajectory b alone into the scratch block, and what it wrote there --
   // rd [K][7] and the cell's coordinate pairs as doubles; ints [3 + 2 f_cap] = n, drop, k, M[f_cap], off[f_cap] and the cell's
-  // slots (each pair null or not).  Returns the cell's entries.  Nothing of the handle's filters, inputs or logs changes.
-  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries) override {
+  // slots (each pair null or not); code (or null): per SEQUENCE entry 0 kept, 1 outlier, 2 missed, from the same launch.  Under
+  // faults M holds the survivors and slots / obs are in partition order.  Returns the cell's entries.  Nothing of the handle's
+  // filters, inputs or logs changes.
+  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr) override {
     using namespace inputs;
     if (int rc = guard()) return rc;
     if (int rc = refuse(rp.expand_refusal(f, b))) return rc;
@@ -2064,8 +2109,15 @@ struct Batch : BatchCore {
       HIPCHK(hipMalloc((void**)&rp_scratch, need));
       rp_scratch_bytes = need;
     }
+    const bool coded = code && rp.faulted;                     // (without faults every code is 0: FAULT_KEPT)
+    if (coded && rp.largest > rp_code_count) {
+      HIPCHK(hipStreamSynchronize(st));
+      dfree(rp_code); rp_code_count = 0;
+      HIPCHK(hipMalloc((void**)&rp_code, rp.largest * sizeof(int)));
+      rp_code_count = rp.largest;
+    }
     const ReplayOut<S> o = replay_out(rp_scratch, f);
-    launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st);
+    launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st, m_cap, coded ? rp_code : nullptr);
     HIPCHK(hipGetLastError());
     const size_t base = (size_t)rp.base[(size_t)f * B + b];
     std::vector<S> hr((size_t)K * RD_STRIDE), ho((size_t)2 * std::max(E, 1));
@@ -2073,6 +2125,8 @@ struct Batch : BatchCore {
     HIPCHK(hipMemcpyAsync(hr.data(), o.rd + (size_t)b * K * RD_STRIDE, hr.size() * sizeof(S), hipMemcpyDeviceToHost, st));
     if (E) HIPCHK(hipMemcpyAsync(ho.data(), o.obs + 2 * base, (size_t)2 * E * sizeof(S), hipMemcpyDeviceToHost, st));
     if (E) HIPCHK(hipMemcpyAsync(hs.data(), o.slots + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (code) std::fill(code, code + E, (int)msckf_replay::FAULT_KEPT);
+    if (coded && E) HIPCHK(hipMemcpyAsync(code, rp_code + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[0], o.n + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[1], o.drop + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[2], o.k + b, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2106,7 +2160,7 @@ struct Batch : BatchCore {
     const int* cell_k = cells.k; const int* cell_drop = cells.drop;
     const int K = replay ? rp.K() : sc.lay.K;
     // replay: the slice's trajectories of this frame's block, from the sequences (outside the frame step's own stage timers)
-    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q); stage_end(11, q); }
+    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q, m_cap); stage_end(11, q); }
     Dev<S> v = d;
     v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
@@ -2227,6 +2281,19 @@ struct Batch : BatchCore {
     const size_t cells = (size_t)(q1 - q0) * B, noff = gt_off ? cells + 1 : 0, ng = gt_off ? (size_t)gt_off[cells] * 3 : 0;
     return log_metrics_call("map_log_metrics", gt_xyz, ng, gt_off, noff, out, (size_t)B * 8, [&](const double* dg, double* dout, const int* doff) {
       launch_map_metrics<S>(static_cast<const S*>(map.buf), map.found, map.cap, B, q0, q1, gt_off ? dg : nullptr, gt_off ? doff : nullptr, dout, st);
+    });
+  }
+  // the stored records with frame ordinal in [q0, q1), written by run_frames_replay contiguously from replay frame f0, against
+  // the faults of their tracks (k_map_fault_metrics): per trajectory the gate's confusion table and the clean passed gamma sums
+  int map_log_fault_metrics(int q0, int q1, int f0, double* out) override {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = map_log_check_faults(q0, q1, f0)) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    auto i = [&](int s) { return reinterpret_cast<const int*>(rp_dev[s]); };
+    return log_metrics_call("map_log_fault_metrics", nullptr, 0, nullptr, 0, out, (size_t)B * msckf_replay::N_FAULT_METRIC, [&](const double*, double* dout, const int*) {
+      launch_map_fault_metrics<S>(static_cast<const S*>(map.buf), map.found, map.cap, B, q0, q1, f0, i(SEC_N), i(SEC_M), i(SEC_OFF), replay_traj(0), rp.S, f_cap, dout, st);
     });
   }
   // the map log's read, and the augment ordinal of each record from the host mirror
@@ -2803,6 +2870,10 @@ int msckf_hip_replay_commit(msckf_hip_handle h) { if (!h) return fail(-EINVAL, "
 int msckf_hip_run_frames_replay(msckf_hip_handle h, int f0, int f1) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->run_frames_replay(f0, f1); }
 int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd, double* obs2, int cap_entries) { if (!h || !rd || !obs2) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, rd, obs2, nullptr, nullptr, cap_entries); }
 int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints, int* slots, int cap_entries) { if (!h || !ints || !slots) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, ints, slots, cap_entries); }
+int msckf_hip_replay_set_faults(msckf_hip_handle h, const double* fault4) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_faults(fault4); }
+int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* code, int cap_entries) { if (!h || !code) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, code); }
+int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_fault_counts(f0, f1, out); }
+int msckf_hip_map_log_fault_metrics(msckf_hip_handle h, int q0, int q1, int f0, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_fault_metrics(q0, q1, f0, out); }
 int msckf_hip_sync(msckf_hip_handle h) { return H(h)->sync(); }
 int msckf_hip_profile_enable(msckf_hip_handle h, int on) { return H(h)->prof_enable(on); }
 int msckf_hip_profile_read(msckf_hip_handle h, double* ms7, int* count7) { return H(h)->prof_read(ms7, count7, 8); }

@@ -1,6 +1,7 @@
 // replay_plan.h -- the Monte-Carlo replay's host side, free of device calls: S noise-free SEQUENCES staged once, and B
 // trajectories that each name a sequence, a 64-bit seed and a noise model: four white levels (sigma4), or the filter's own
-// 12 x 12 Q_imu with its two bias random walks (MODEL below).  Before a frame the kernel k_replay_expand
+// 12 x 12 Q_imu with its two bias random walks (MODEL below), and optionally a fault record: seeded missed observations and
+// outliers (FAULTS below).  Before a frame the kernel k_replay_expand
 // (kernels_replay.hip) turns the frame's S sequence cells into the ordinary per-trajectory frame block of input_layouts.h
 // (FrameLayout(B, K, f_cap, esz), sections [rd | n | drop | k | M | off | slots | obs]) -- what an upload would have put there.
 //
@@ -8,6 +9,8 @@
 //   1. mix / U        the integer part of the random stream (value i of scenario.SplitMix64(seed) and the 53-bit uniform made of
 //                     it), constexpr, shared by this file's host users, the kernel and -- bit for bit -- the numpy twin
 //   2. the noise      which pair of which sub-seed a value takes (NOISE and MODEL below), and chol_psd, the factor of Q_imu
+//                     and the faults on top of either model: missed observations and outliers (FAULTS below), the rule on a
+//                     track stated serially (track_faults), the lane group of the faulted expansion
 //   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record
 //                     of either model, per frame each trajectory's first entry in the expanded block and the block's size, the
 //                     largest expanded frame, and every refusal with its code and text
@@ -96,6 +99,50 @@ inline bool chol_psd(const double* Q, double* L) {
   return true;
 }
 
+// ---- 2c. FAULTS: seeded missed observations and outliers (msckf_hip_replay_set_faults; normative, the header, DESIGN section
+// 4.13 and the twin state the same).  Independent of the noise model: it composes with NOISE and with MODEL.
+// Trajectory b has fault4[b] = (p_miss, p_out, rho_u, rho_v): two probabilities in [0, 1], two radii in normalised image
+// units, finite and >= 0.
+//   sub-seed   s_flt(f) = mix(mix(s_b, 2^63 + 1), f).  Frames use mix(s_b, 2 f) and mix(s_b, 2 f + 1), replay_initial_error
+//              uses mix(s_b, 2^63): no frame index reaches either.
+//   draws      entry e (0-based among the SEQUENCE cell's entries, in sequence order) takes u_miss = U(s_flt, 3 e),
+//              u_out = U(s_flt, 3 e + 1), u_ang = U(s_flt, 3 e + 2).
+//   missed     raw_miss(e) = u_miss < p_miss.  A track that would keep fewer than two observations loses none: if
+//              M - #raw_miss < 2 then miss = false on the whole track (the sequence's own tracks with M < 2 pass through
+//              unchanged); otherwise miss = raw_miss.  A tracker hands the filter no track of one observation.
+//   outliers   out(e) = !miss(e) && u_out < p_out.
+//   values     obs = value + sigma noise exactly as without faults: pair e of s_obs, indexed by the sequence entry, so a
+//              trajectory's Gaussian noise does not depend on its faults.  Where out(e): (x + rho_u cos a, y + rho_v sin a),
+//              a the rounded product 6.283185307179586 u_ang, each product rounded, then added, all in double, rounded once to
+//              the handle's scalar.
+//   the block  off[t], the trajectory's base, the frame's entry count, n, drop, k and rd are unchanged: a track's range keeps
+//              the sequence's length.  M[t] is the number of survivors; the range is a stable partition -- the survivors in
+//              sequence order, then the missed entries in sequence order -- and every entry carries its slot and coordinates.
+//              Nothing downstream reads beyond off[t] + M[t] (the kernels find a track through trk_off / trk_M alone).
+// The host keeps the sequence's maxslot: an upper bound, which is all the frame step asks of it.  With no faults set, or
+// every trajectory at p_miss = p_out = 0, the expansion launched is the unfaulted one.
+constexpr uint64_t FAULT_STREAM = 0x8000000000000001ull;   // 2^63 + 1
+constexpr uint64_t fault_seed(uint64_t s, int f) { return mix(mix(s, FAULT_STREAM), (uint64_t)f); }
+enum Fault { FLT_P_MISS, FLT_P_OUT, FLT_RHO_U, FLT_RHO_V, N_FAULT };
+enum FaultCode { FAULT_KEPT = 0, FAULT_OUTLIER = 1, FAULT_MISSED = 2 };   // msckf_hip_replay_expand_faults, per sequence entry
+constexpr int FAULT_DRAWS = 3;             // uniforms per entry
+// lanes per track of the faulted expansion: the smallest of 16, 32, 64 that holds a track of m_cap observations
+constexpr int fault_group(int m_cap) { return m_cap <= 16 ? 16 : m_cap <= 32 ? 32 : 64; }
+// the rule on one track, stated serially: its M entries start at entry e0 of the sequence cell; how many of them are missed
+// and how many are outliers (what the expansion's lane groups decide by ballot, and what the two reductions recompute)
+struct TrackFaults { int missed, outliers; };
+constexpr TrackFaults track_faults(uint64_t s_flt, uint64_t e0, int M, double p_miss, double p_out) {
+  int raw = 0;
+  for (int l = 0; l < M; ++l) raw += U(s_flt, FAULT_DRAWS * (e0 + l)) < p_miss ? 1 : 0;
+  const bool none = M - raw < 2;             // a track keeps two observations or loses none
+  int out = 0;
+  for (int l = 0; l < M; ++l) out += (none || !(U(s_flt, FAULT_DRAWS * (e0 + l)) < p_miss)) && U(s_flt, FAULT_DRAWS * (e0 + l) + 1) < p_out ? 1 : 0;
+  return TrackFaults{none ? 0 : raw, out};
+}
+// columns of msckf_hip_replay_fault_counts and of msckf_hip_map_log_fault_metrics
+enum FaultCount { FC_ENTRIES, FC_MISSED, FC_OUTLIERS, FC_TRACKS, FC_TRACKS_SHORTENED, FC_TRACKS_CONTAMINATED, N_FAULT_COUNT };
+enum FaultMetric { FM_RECORDS, FM_CLEAN_PASS, FM_CLEAN_REJ, FM_CONT_PASS, FM_CONT_REJ, FM_SUM_GAMMA, FM_SUM_DOF, FM_UNMATCHED, N_FAULT_METRIC };
+
 // ---- 3. the plan
 using msckf_inputs::FrameLayout;
 using msckf_inputs::Refusal;
@@ -118,6 +165,9 @@ struct Plan {
   bool planned = false;              // base / nf / largest match the cells and the assignment
   bool walk_planned = false;         // the caller's walk table (MODEL_Q) matches the cells and the assignment: set by the caller
                                      // when it has tabulated it, cleared here by whatever the table depends on
+  // the fault record (FAULTS above): [B][N_FAULT], empty: none set; faulted: some trajectory has a non-zero probability;
+  // faults_uploaded: the caller's device copy is this record (set by the caller, cleared here)
+  std::vector<double> fault; bool faulted = false, faults_uploaded = false;
 
   int frames() const { return seq.frames; }
   int K() const { return seq.lay.K; }
@@ -137,6 +187,7 @@ struct Plan {
     seq.reset(n_frames, n_seq, K, f_cap_, sizeof(double));
     committed = assigned = planned = walk_planned = false; model = MODEL_SIGMA4;
     seq_of.clear(); seed.clear(); sigma.clear(); L.clear(); scale.clear(); sigma_uv.clear(); base.clear(); nf.clear(); largest = 0;
+    fault.clear(); faulted = faults_uploaded = false;
   }
   // the rules of one sequence cell, in scenario_set_cell's order: its place, the work-list rules, the drop, the cell rule, the readings
   Refusal cell_refusal(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, int n_drop, int flags, int m_cap, int n_cap) const {
@@ -191,6 +242,21 @@ struct Plan {
     L.assign((size_t)B * L_SIZE, 0.0);
     for (int b = 0; b < B; ++b) (void)chol_psd(Q144 + (size_t)b * L_SIZE, L.data() + (size_t)b * L_SIZE);
     assigned = true; planned = walk_planned = false; model = MODEL_Q;
+  }
+  // the fault record (FAULTS), fault4 [B][N_FAULT] or null for none, in this order: the replay, the probabilities, the radii
+  Refusal faults_refusal(const double* fault4) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    if (!fault4) return {0, nullptr};
+    for (int b = 0; b < B; ++b) for (int c : {FLT_P_MISS, FLT_P_OUT}) if (!(fault4[b * N_FAULT + c] >= 0.0 && fault4[b * N_FAULT + c] <= 1.0)) return {-EINVAL, "fault probabilities must lie in [0, 1]"};
+    for (int b = 0; b < B; ++b) for (int c : {FLT_RHO_U, FLT_RHO_V}) if (!(fault4[b * N_FAULT + c] >= 0.0) || !std::isfinite(fault4[b * N_FAULT + c])) return {-EINVAL, "fault radii must be finite and not negative"};
+    return {0, nullptr};
+  }
+  // independent of the assignment and of the cells: it stays through assign, assign_q and commit, and alloc() clears it
+  void set_faults(const double* fault4) {
+    if (fault4) fault.assign(fault4, fault4 + (size_t)B * N_FAULT); else fault.clear();
+    faulted = false;
+    for (size_t b = 0; b * N_FAULT < fault.size(); ++b) faulted = faulted || fault[b * N_FAULT + FLT_P_MISS] > 0.0 || fault[b * N_FAULT + FLT_P_OUT] > 0.0;
+    faults_uploaded = false;
   }
 
   // -- a run

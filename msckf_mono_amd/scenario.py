@@ -250,6 +250,139 @@ def replay_bias_gt(trajs, walks):
     return const[None, :, :] + walks[1:]
 
 
+# ---- seeded front-end faults (csrc/replay_plan.h, FAULTS; include/msckf_hip.h, msckf_hip_replay_set_faults): missed
+# observations and outliers per trajectory, fault4 = (p_miss, p_out, rho_u, rho_v), on top of either noise model
+REPLAY_FAULT_STREAM = (1 << 63) + 1
+FAULT_KEPT, FAULT_OUTLIER, FAULT_MISSED = 0, 1, 2
+
+
+def replay_fault_seed(seed, frame):
+    """s_flt = mix(mix(seed, 2^63 + 1), frame): frames use mix(seed, 2 f) and mix(seed, 2 f + 1), replay_initial_error uses
+    mix(seed, 2^63); no frame index reaches either"""
+    return int(replay_mix(int(replay_mix(seed, REPLAY_FAULT_STREAM)), int(frame)))
+
+
+def replay_fault_draws(seed, frame, n_entries):
+    """(u_miss, u_out, u_ang), each [n_entries]: entry e of the sequence cell takes U(s_flt, 3 e), U(s_flt, 3 e + 1), U(s_flt, 3 e + 2)"""
+    s = replay_fault_seed(seed, frame)
+    e = np.uint64(3) * np.arange(int(n_entries), dtype=np.uint64)
+    return replay_uniform(s, e), replay_uniform(s, e + np.uint64(1)), replay_uniform(s, e + np.uint64(2))
+
+
+def replay_fault_code(M, draws, p_miss, p_out):
+    """per entry of a cell with track lengths M (entries in sequence order): FAULT_MISSED where u_miss < p_miss -- unless the
+    track would keep fewer than two observations, then it loses none -- else FAULT_OUTLIER where u_out < p_out, else FAULT_KEPT"""
+    u_miss, u_out = np.asarray(draws[0]), np.asarray(draws[1])
+    code = np.zeros(len(u_miss), dtype=np.int32)
+    o = 0
+    for m in (int(x) for x in M):
+        miss = u_miss[o:o + m] < float(p_miss)
+        if m - int(miss.sum()) < 2:
+            miss = np.zeros(m, dtype=bool)
+        code[o:o + m] = np.where(miss, FAULT_MISSED, np.where(u_out[o:o + m] < float(p_out), FAULT_OUTLIER, FAULT_KEPT))
+        o += m
+    assert o == len(code)
+    return code
+
+
+def replay_fault_cell(M, slots, obs_noisy, code, u_ang, rho_u, rho_v):
+    """what the faulted expansion writes for a cell whose noisy coordinates are obs_noisy [n][2]: (M' = survivors per track,
+    slots [n], obs [n][2]) with every track's range a stable partition -- survivors in sequence order, then the missed entries
+    in sequence order -- and the outliers displaced by (rho_u cos a, rho_v sin a), a = the rounded product 2 pi u_ang"""
+    M = np.asarray(M, dtype=np.int32)
+    slots = np.asarray(slots, dtype=np.int32)
+    code = np.asarray(code)
+    ob = np.array(obs_noisy, dtype=np.float64).reshape(-1, 2)
+    a = 6.283185307179586 * np.asarray(u_ang, dtype=np.float64)
+    out = code == FAULT_OUTLIER
+    ob[out, 0] = ob[out, 0] + float(rho_u) * np.cos(a[out])
+    ob[out, 1] = ob[out, 1] + float(rho_v) * np.sin(a[out])
+    order, Mp, o = [], np.zeros_like(M), 0
+    for t, m in enumerate(int(x) for x in M):
+        miss = code[o:o + m] == FAULT_MISSED
+        order += list(o + np.nonzero(~miss)[0]) + list(o + np.nonzero(miss)[0])
+        Mp[t] = m - int(miss.sum())
+        o += m
+    order = np.asarray(order, dtype=np.int64)
+    return Mp, slots[order], ob[order]
+
+
+def replay_fault_survivors(M, Mp, slots, obs):
+    """the survivors of replay_fault_cell's (or the device's) partitioned cell, compact: (M', slots, obs) with no slack -- what a
+    caller without slack (the CPU oracle, an ordinary scenario) is handed"""
+    M, Mp = np.asarray(M, dtype=np.int64), np.asarray(Mp, dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(M)])[:len(M)]
+    keep = np.concatenate([np.arange(o, o + m) for o, m in zip(off, Mp)]).astype(np.int64) if len(M) else np.zeros(0, np.int64)
+    return Mp.astype(np.int32), np.asarray(slots)[keep], np.asarray(obs).reshape(-1, 2)[keep]
+
+
+def _replay_faulted(frame, seed, M, slots, obs, fault4):
+    p_miss, p_out, rho_u, rho_v = (float(x) for x in fault4)
+    draws = replay_fault_draws(seed, frame, len(obs))
+    code = replay_fault_code(M, draws, p_miss, p_out)
+    return replay_fault_cell(M, slots, obs, code, draws[2], rho_u, rho_v) + (code,)
+
+
+def replay_expand_faulted(seq_traj, frame, seed, sigma4, fault4):
+    """replay_expand with faults: (readings, M', slots, obs, code) in the expanded block's partition order"""
+    rd, obs = replay_expand(seq_traj, frame, seed, sigma4)
+    fr = seq_traj.frames[frame]
+    return (rd,) + _replay_faulted(frame, seed, fr["M"], fr["slots"], obs, fault4)
+
+
+def replay_model_expand_faulted(seq_traj, frame, seed, L, scale, sigma_uv, fault4, w_start=None):
+    """replay_model_expand with faults: (readings, M', slots, obs, code) in the expanded block's partition order"""
+    rd, obs = replay_model_expand(seq_traj, frame, seed, L, scale, sigma_uv, w_start)
+    fr = seq_traj.frames[frame]
+    return (rd,) + _replay_faulted(frame, seed, fr["M"], fr["slots"], obs, fault4)
+
+
+def replay_fault_counts(cells_M, seed, fault4, f0=0, f1=None):
+    """msckf_hip_replay_fault_counts for one trajectory: cells_M[f] the track lengths of its sequence's cell on frame f (None or
+    empty: no track); int64 [6] = entries, missed, outliers, tracks, tracks that lost an observation, tracks with an outlier"""
+    f1 = len(cells_M) if f1 is None else int(f1)
+    c = np.zeros(6, dtype=np.int64)
+    for f in range(int(f0), f1):
+        M = np.zeros(0, np.int64) if cells_M[f] is None else np.asarray(cells_M[f], dtype=np.int64)
+        n = int(M.sum())
+        code = replay_fault_code(M, replay_fault_draws(seed, f, n), fault4[0], fault4[1])
+        o = 0
+        c[0] += n; c[1] += int((code == FAULT_MISSED).sum()); c[2] += int((code == FAULT_OUTLIER).sum()); c[3] += len(M)
+        for m in (int(x) for x in M):
+            c[4] += bool((code[o:o + m] == FAULT_MISSED).any()); c[5] += bool((code[o:o + m] == FAULT_OUTLIER).any())
+            o += m
+    return c
+
+
+def replay_gate_confusion(records, cells_M, seed, fault4, q0, q1, f0):
+    """msckf_hip_map_log_fault_metrics for one trajectory: records [n][8] (map-log records: gamma 3, frame ordinal 4, track 5,
+    flags 6, M 7), the record with ordinal q belonging to replay frame f0 + (q - q0); cells_M as in replay_fault_counts.
+    float64 [8] = records in range, clean passed, clean rejected, contaminated passed, contaminated rejected, sum gamma and
+    sum 2 M - 3 over the clean passed records without flag 4, unmatched (track index >= the cell's tracks)"""
+    out = np.zeros(8)
+    codes = {}
+    for r in np.asarray(records, dtype=np.float64).reshape(-1, 8):
+        q, trk, flags = int(r[4]), int(r[5]), int(r[6])
+        if not q0 <= q < q1:
+            continue
+        out[0] += 1
+        f = f0 + (q - q0)
+        M = np.zeros(0, np.int64) if cells_M[f] is None else np.asarray(cells_M[f], dtype=np.int64)
+        if trk >= len(M):
+            out[7] += 1
+            continue
+        if f not in codes:
+            codes[f] = replay_fault_code(M, replay_fault_draws(seed, f, int(M.sum())), fault4[0], fault4[1])
+        o = int(M[:trk].sum())
+        dirty = bool((codes[f][o:o + int(M[trk])] == FAULT_OUTLIER).any())
+        ok = bool(flags & 1)
+        out[1 + 2 * dirty + (not ok)] += 1
+        if not dirty and ok and not flags & 4:
+            out[5] += r[3]
+            out[6] += 2.0 * r[7] - 3.0
+    return out
+
+
 def rot_to_quat(R):
     """Rotation matrix -> (w,x,y,z) such that Eigen's toRotationMatrix() gives R back."""
     t = np.trace(R)

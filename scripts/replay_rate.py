@@ -11,7 +11,9 @@ stage timers (a run of its own: profiling forces one slice).
 
 --model q: the Q_imu noise model against the sigma4 one instead (no streamed handle): two replay handles on the same sequences,
 one assigned through replay_assign (sigma4), one through replay_assign_q (the filter's diagonal Q_imu with both walks, scale
-0.05), windows alternating in one process; the expansion's stage time for each, and the one-off walk scan's (stage 12)."""
+0.05), windows alternating in one process; the expansion's stage time for each, and the one-off walk scan's (stage 12).
+--faults P (with --model q): both handles under replay_set_faults((P, P, 3 px, 3 px)), the faulted form of the expansion; the
+JSON line then carries the fault counts of the timed frames and the lane group G the form was launched with."""
 import argparse
 import json
 import os
@@ -55,6 +57,7 @@ def main():
     ap.add_argument("--timed", type=int, default=40)
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--model", choices=("sigma4", "q"), default="sigma4")
+    ap.add_argument("--faults", type=float, default=0.0)
     args = ap.parse_args()
     N, F, S, B, fill, nf = args.window, args.tracks, args.sequences, args.sequences * args.seeds, args.fill, args.fill + args.timed
     K, esz = sc.IMU_PER_FRAME, 4
@@ -162,6 +165,14 @@ def model_q(args, rp, handle, reinit, seqs, seq_of, seeds, sigma, cfg):
     rq.replay_assign_q(seq_of, seeds, Q, 0.05, sigma[2:])
     rq.replay_commit()
     paths = {"replay": rp, "replay_q": rq}
+    faults = {}
+    if args.faults > 0.0:
+        for bt in paths.values():
+            bt.replay_set_faults((args.faults, args.faults, 3.0 / cfg["f_u"], 3.0 / cfg["f_v"]))
+        cnt = rp.replay_fault_counts(fill, nf).sum(0)
+        G = 16 if args.window <= 16 else 32 if args.window <= 32 else 64
+        faults = dict(p_miss=args.faults, p_out=args.faults, counts_timed_frames=dict(zip(capi.REPLAY_FAULT_COUNTS, (int(x) for x in cnt))), lane_group=G,
+                      wavefronts_per_trajectory=dict(tracks=(args.tracks * G + 63) // 64, fixed_sigma4=(4 * K + args.tracks + 1 + 63) // 64))
     times = {k: [] for k in paths}
     for w in range(args.windows + 1):                       # window 0 warms both paths up and is not reported
         for name, bt in paths.items():
@@ -192,7 +203,7 @@ def model_q(args, rp, handle, reinit, seqs, seq_of, seeds, sigma, cfg):
         "shape": dict(dtype="f32", window=args.window, tracks=args.tracks, sequences=len(seqs), trajectories=len(seq_of), fill_frames=fill, timed_frames=args.timed, windows=args.windows),
         "slices": {k: bt.effective_streams(False) for k, bt in paths.items()},
         "window_s": times, "median_window_s": med, "ms_per_frame": {k: 1e3 * v / args.timed for k, v in med.items()},
-        "model_over_sigma4_time": med["replay_q"] / med["replay"], "stages": stages,
+        "model_over_sigma4_time": med["replay_q"] / med["replay"], "stages": stages, "faults": faults,
         "items_per_frame": {"entries": entries, "imu_sigma4": 3 * K * len(seq_of), "imu_model": K * len(seq_of)},
         "walk_table_bytes": int(walk.nbytes), "walk_rms_last_row": float(np.sqrt(np.mean(walk[-1] ** 2))),
     }))
