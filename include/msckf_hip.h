@@ -350,6 +350,37 @@ int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long*
  * -EINVAL while the map log is off, for ordinals beyond those handed out, for a frame outside the replay ("frame range out of
  * bounds"), and while the replay is not committed or not assigned. */
 int msckf_hip_map_log_fault_metrics(msckf_hip_handle h, int q0, int q1, int f0, double* out /*[B][8]*/);
+/* per trajectory, over the non-skipped cells of frames [f0, f1) as msckf_hip_run_frames_replay would expand them (either
+ * noise model, walk included; faults do not touch IMU rows): out[B][8] = 0 samples, 1-3 sum omega, 4-6 sum a, 7 sum dT.
+ * Each sample is the value the expansion writes -- rounded to the handle's scalar, widened to double -- summed in double in a
+ * fixed order (same inputs, same bits).  Sums and counts: intervals add.  Refusals as msckf_hip_run_frames_replay.
+ * One wavefront per trajectory: a lane takes the frames f0 + lane, f0 + lane + 64, ... in ascending order and a frame's
+ * samples in ascending order, the 64 partial sums are combined by a fixed tree.  What a per-seed stand-still initialisation
+ * needs (mean omega = the gyro bias, mean a = the attitude against gravity and the accelerometer bias), from samples that
+ * exist only on the device.  Nothing of the handle's filters, inputs or logs changes. */
+int msckf_hip_replay_imu_sums(msckf_hip_handle h, int f0, int f1, double* out /*[B][8]*/);
+/* ---- the track compiler: a recorded feature-id stream into the cells of the frame loops (host code, no device) -------- */
+/* The frame loops take positional work-lists per frame, (M, slots, obs2, n_drop); a recording is an id stream, the tracked and
+ * the new features of every image.  Without pruneRedundantStates the bookkeeping that turns one into the other -- update(),
+ * addFeatures(), marginalize()'s feature_tracks_to_residualize_, pruneEmptyStates() (msckf.h:215-332, 336-371, 685-717) -- reads
+ * ids and max_cam_states / min_track_length / max_track_length and nothing of the estimate, so a recording compiles once,
+ * offline, with the same host code msckf_hip_image_cycle_range (flags = 2) runs per image: the cycle of the reference's live
+ * node (ros_interface.cpp never prunes redundant states).  pruneRedundantStates cannot be compiled: it selects keyframes from
+ * the ESTIMATED camera poses (msckf.h:1049-1098); a run with it stays on msckf_hip_image_cycle_range.
+ * These four calls need no GPU and no handle and work on a machine without a GPU, as msckf_hip_last_error does.
+ * -EINVAL for non-positive parameters, negative counts or null pointers with positive counts; -EEXIST when a new id is already
+ * tracked ("added new feature that was already being tracked": the features before it stay added, as in the reference), after
+ * which the compiler is unusable (-EIO, "the compiler is unusable after a refused image").  Every refusal leaves its text
+ * with msckf_hip_last_error(). */
+typedef struct msckf_hip_compiler_s* msckf_hip_compiler;
+int msckf_hip_compile_create(int max_cam_states, int min_track_length, int max_track_length, msckf_hip_compiler* out);
+int msckf_hip_compile_destroy(msckf_hip_compiler c);
+/* one image = augmentState, update, addFeatures, marginalize's work-list, pruneEmptyStates.
+ * out5 = F tracks, entries (sum M), n_drop, window after the augment (before the drop), tracks still live */
+int msckf_hip_compile_image(msckf_hip_compiler c, const double* upd_meas2, const uint64_t* upd_ids, int upd_n,
+                            const double* new_meas2, const uint64_t* new_ids, int new_n, int* out5);
+/* the last image's work-list, in feature_tracks_to_residualize_ order; returns F, -E2BIG beyond the caps */
+int msckf_hip_compile_cell(msckf_hip_compiler c, int* M, int* slots, double* obs2, uint64_t* ids, int cap_tracks, int cap_entries);
 int msckf_hip_sync(msckf_hip_handle h);
 /* ---- per-frame device log of msckf_hip_run_frames / _streamed (off by default) ------------------------ */
 /* Storage for capacity_frames records ("frame log record" above) of every trajectory, in the handle's dtype; 0 frees the

@@ -189,7 +189,15 @@ def standstill_initial_state(ds, calib_start_ns, calib_end_ns):
     if not np.any(m):
         raise ValueError("no IMU samples inside the stand-still interval")
     rd = np.asarray(ds["readings"])[m]
-    gyro_mean, accel_mean = rd[:, 0:3].mean(0), rd[:, 3:6].mean(0)
+    return standstill_state(rd[:, 0:3].mean(0), rd[:, 3:6].mean(0))
+
+
+def standstill_state(gyro_mean, accel_mean):
+    """The closing maths of the stand-still initialisation (asl_msckf_no_ground_truth.cpp:150-173) from the two means alone:
+    gyro bias = gyro_mean, q_IG = FromTwoVectors(-g, accel_mean), accelerometer bias = q_IG g + accel_mean, zero position and
+    velocity.  Whoever holds the means calls it: standstill_initial_state from a dataset, capi.Batch.replay_standstill from the
+    sums of each seed's own noisy samples."""
+    gyro_mean, accel_mean = np.asarray(gyro_mean, dtype=np.float64), np.asarray(accel_mean, dtype=np.float64)
     g = np.array(sc.GRAVITY, dtype=float)
     q = _from_two_vectors(-g, accel_mean)
     w, x, y, z = q
@@ -262,6 +270,70 @@ def run(ds, flt, cfg, start_ns=None, prune_redundant=False, on_frame=None, stage
     if pend:
         flt.propagate(np.array(pend))
     return out
+
+
+def compile_sequence(ds, cfg, start_ns=None):
+    """The dataset's id stream (`tracks0`) compiled into the cells the frame loops take (capi.TrackCompiler, host code alone):
+    the dataset is walked exactly as `run` walks it -- same t_begin, same state_k, the IMU samples pending at an image handed
+    over with it -- and every image goes through augmentState / update / addFeatures / marginalize's work-list /
+    pruneEmptyStates with cfg's max_cam_states, min_track_length and max_track_length: `run(prune_redundant=False)`, the cycle
+    of the reference's live node.  pruneRedundantStates reads estimated poses and cannot be compiled.
+    Returns a dict: "images", per image a dict of stamp, state_k, readings [k][7], M, slots, obs, ids, n_drop, window;
+    "trailing", the IMU samples behind the last image [.][7]; and the maxima a handle needs: "K" (samples per image), "n_cap"
+    (window), "f_cap" (tracks per image), "m_cap" (observations per track)."""
+    from . import capi
+    comp = capi.TrackCompiler(cfg["max_cam_states"], cfg["min_track_length"], cfg["max_track_length"])
+    cam_set = set(int(t) for t in ds["cam_t"])
+    images = []
+    state_k = 0
+    t_begin = ds["imu_t"][0] if start_ns is None else start_ns
+    pend = []
+    for t, rd in zip(ds["imu_t"], ds["readings"]):
+        if t < t_begin:
+            continue
+        state_k += 1
+        pend.append(rd)
+        if int(t) in cam_set:
+            tr = ds["tracks"].get(int(t), {"cur": ([], []), "new": ([], [])})
+            cell = comp.image(tr["cur"], tr["new"])
+            cell.update(stamp=int(t), state_k=state_k, readings=np.array(pend, dtype=np.float64).reshape(-1, 7))
+            images.append(cell)
+            pend = []
+    comp.close()
+    return dict(images=images, trailing=np.array(pend, dtype=np.float64).reshape(-1, 7),
+                K=max([len(c["readings"]) for c in images] + [1]), n_cap=max([c["window"] for c in images] + [1]),
+                f_cap=max([len(c["M"]) for c in images] + [1]), m_cap=max([int(c["M"].max()) for c in images if len(c["M"])] + [1]))
+
+
+def _check_cell_fits(batch, cell, K):
+    """raises with the image's stamp when a compiled cell exceeds the handle's capacities (K: the staged store's, or None)"""
+    over = []
+    if cell["window"] > batch.n_cap:
+        over.append("a window of %d camera states exceeds n_cap = %d" % (cell["window"], batch.n_cap))
+    if len(cell["M"]) > batch.f_cap:
+        over.append("%d tracks exceed f_cap = %d" % (len(cell["M"]), batch.f_cap))
+    if len(cell["M"]) and int(cell["M"].max()) > batch.m_cap:
+        over.append("a track of %d observations exceeds m_cap = %d" % (int(cell["M"].max()), batch.m_cap))
+    if K is not None and len(cell["readings"]) > K:
+        over.append("%d IMU samples exceed K = %d" % (len(cell["readings"]), K))
+    if over:
+        raise ValueError("image %d: %s" % (cell["stamp"], "; ".join(over)))
+
+
+def stage_scenario(batch, compiled, b, K=None):
+    """the compiled images as trajectory b's cells of frames 0 .. of the scenario the caller allocated (scenario_alloc(frames >=
+    len(images), K >= compiled["K"])) and commits.  Raises with the image's stamp when a cell exceeds the handle's capacities."""
+    for f, cell in enumerate(compiled["images"]):
+        _check_cell_fits(batch, cell, K)
+        batch.scenario_set(f, b, cell["readings"], cell["M"], cell["slots"], cell["obs"], cell["n_drop"], skip=False)
+
+
+def stage_replay(batch, compiled, seq):
+    """the compiled images as sequence `seq` of the replay the caller allocated (replay_alloc) and commits: noise-free cells
+    that every seed assigned to the sequence expands with its own noise"""
+    for f, cell in enumerate(compiled["images"]):
+        _check_cell_fits(batch, cell, batch._replay_K)
+        batch.replay_set_cell(f, seq, cell["readings"], cell["M"], cell["slots"], cell["obs"], cell["n_drop"], skip=False)
 
 
 def write_stage_timing(path, records):

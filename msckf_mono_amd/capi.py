@@ -45,6 +45,7 @@ SYMBOLS = [
     "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
     "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
+    "msckf_hip_compile_create", "msckf_hip_compile_destroy", "msckf_hip_compile_image", "msckf_hip_compile_cell", "msckf_hip_replay_imu_sums",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -90,6 +91,9 @@ ALIGN_FIELDS = {"n": slice(0, 1), "R": slice(1, 10), "t": slice(10, 13), "cond":
 RPE_STRIDE = 4
 RPE_MAX_LAGS = 8
 RPE_FIELDS = {"n_pairs": slice(0, 1), "sum_sq_trans_err": slice(1, 2), "sum_sq_ang_err": slice(2, 3), "max_trans_err": slice(3, 4)}
+# columns of replay_imu_sums' result (csrc/replay_plan.h, ImuSum)
+IMU_SUM_STRIDE = 8
+IMU_SUM_FIELDS = {"n": slice(0, 1), "omega": slice(1, 4), "a": slice(4, 7), "dT": slice(7, 8)}
 
 
 def build():
@@ -472,6 +476,27 @@ class Batch:
         _chk(self.L.msckf_hip_replay_fault_counts(self.h, int(f0), f1, out.ctypes.data_as(C.POINTER(C.c_longlong))))
         return out
 
+    def replay_imu_sums(self, f0=0, f1=None):
+        """per trajectory the IMU samples a run over the frames [f0, f1) (default: all) would hand its propagate, summed on the
+        device as the expansion stores them: [B][8], columns IMU_SUM_FIELDS (sums and counts: ranges add)"""
+        f1 = self._replay_frames if f1 is None else int(f1)
+        out = np.zeros((self.B, IMU_SUM_STRIDE))
+        _chk(self.L.msckf_hip_replay_imu_sums(self.h, int(f0), f1, out.ctypes.data_as(_dp)))
+        return out
+
+    def replay_standstill(self, f0, f1):
+        """the stand-still initialisation of the no-ground-truth runner, per seed: every trajectory's IMU state is set from the
+        means of its own noisy samples over the frames [f0, f1) (replay_imu_sums -> asl.standstill_state -> set_imu_state).
+        Returns the states [B][29]; the caller then runs run_frames_replay(f1, ...)."""
+        from . import asl
+        sums = self.replay_imu_sums(f0, f1)
+        if not np.all(sums[:, 0] > 0):
+            raise ValueError("no IMU samples inside the stand-still interval")
+        states = np.stack([asl.standstill_state(r[1:4] / r[0], r[4:7] / r[0]) for r in sums])
+        for b in range(self.B):
+            self.set_imu_state(b, states[b])
+        return states
+
     def scenario_pin(self, f0, f1):
         """page-lock the per-frame blocks of frames [f0, f1) ahead of a streamed run (outside any timed region)"""
         _chk(self.L.msckf_hip_scenario_pin(self.h, int(f0), int(f1)))
@@ -811,6 +836,44 @@ class Batch:
         _chk(self.L.msckf_hip_profile_read_ex(self.h, ms.ctypes.data_as(_dp), cnt.ctypes.data_as(_ip), 16))
         names = ["propagate", "augment", "feature", "compress_stage1", "compress_merge", "kalman", "prune", "select", "lit_pre", "lit_gamma", "literal", "replay_expand", "replay_walk_scan"]
         return {n: (float(m), int(c)) for n, m, c in zip(names, ms, cnt)}
+
+
+class TrackCompiler:
+    """A recorded feature-id stream compiled into the cells of the frame loops (csrc/track_compile.h): host code alone, no GPU.
+    One image at a time, in the order of the recording; `image` returns the cell the frame loop takes for it."""
+
+    def __init__(self, max_cam_states, min_track_length, max_track_length):
+        self.L = lib()
+        self.c = C.c_void_p()
+        _chk(self.L.msckf_hip_compile_create(int(max_cam_states), int(min_track_length), int(max_track_length), C.byref(self.c)))
+
+    def close(self):
+        if self.c:
+            self.L.msckf_hip_compile_destroy(self.c)
+            self.c = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def image(self, cur, new):
+        """cur / new = (measurements [n][2], feature ids [n]) as update() / addFeatures() take them.  Returns the image's cell:
+        dict of M [F], slots [sum M], obs [sum M][2], ids [F] (the tracks' feature ids, in work-list order), n_drop, window
+        (camera states after the augment, before the drop) and live (tracks still followed)"""
+        um, pum = _d(np.asarray(cur[0], dtype=np.float64).reshape(-1, 2)); ui = np.ascontiguousarray(cur[1], dtype=np.uint64).reshape(-1)
+        nm, pnm = _d(np.asarray(new[0], dtype=np.float64).reshape(-1, 2)); ni = np.ascontiguousarray(new[1], dtype=np.uint64).reshape(-1)
+        if len(um) != len(ui) or len(nm) != len(ni):
+            raise ValueError("one measurement per feature id")
+        o5 = np.zeros(5, dtype=np.int32)
+        _chk(self.L.msckf_hip_compile_image(self.c, pum, ui.ctypes.data_as(_up), len(ui), pnm, ni.ctypes.data_as(_up), len(ni), o5.ctypes.data_as(_ip)))
+        F, E = int(o5[0]), int(o5[1])
+        M = np.zeros(max(F, 1), dtype=np.int32); ids = np.zeros(max(F, 1), dtype=np.uint64)
+        slots = np.zeros(max(E, 1), dtype=np.int32); obs = np.zeros((max(E, 1), 2))
+        n = _chk(self.L.msckf_hip_compile_cell(self.c, M.ctypes.data_as(_ip), slots.ctypes.data_as(_ip), obs.ctypes.data_as(_dp), ids.ctypes.data_as(_up), F, E))
+        assert n == F
+        return dict(M=M[:F], slots=slots[:E], obs=obs[:E], ids=ids[:F], n_drop=int(o5[2]), window=int(o5[3]), live=int(o5[4]))
 
 
 class MSCKF:

@@ -607,6 +607,10 @@ template <class S> void launch_map_fault_metrics(const S* rec, const int* found,
 // the model's walk table wstart[frames + 1][B][6] for all B trajectories: one workgroup per trajectory, REPLAY_SCAN_CHUNK frames
 // at a time.  rd / k: the sequence store's readings [frames][S][K][7] and counts [frames][S]; t.sigma and t.base are not read.
 void launch_replay_walk_scan(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, double* wstart, int frames, int S, int K, int B, hipStream_t st);
+// msckf_hip_replay_imu_sums: per trajectory the count, the six summed scalars and the summed dT (replay_plan.h, ImuSum: out [B][8])
+// of the IMU samples the expansion hands its propagate over the frames [f0, f1), each rounded to the handle's scalar as the
+// expansion stores it; rd / k as for the walk scan, m.wstart the walk table from row 0 (m.L == nullptr: the sigma4 model)
+void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();
 void qr_device_setup();

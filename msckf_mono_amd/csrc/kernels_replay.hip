@@ -23,7 +23,8 @@
 //
 // With a fault record (replay_plan.h, FAULTS) k_replay_expand_faults runs in its place: the same fixed items, and track items
 // instead of entry items -- a group of lanes per track drops the missed observations behind the survivors and displaces the
-// outliers.  k_replay_fault_counts counts a frame range's faults without expanding anything.
+// outliers.  k_replay_fault_counts counts a frame range's faults without expanding anything, and k_replay_imu_sums sums the IMU
+// samples a frame range would expand, per trajectory, from the same device functions (the stand-still initialisation's means).
 #include <type_traits>
 
 #include "dev_common.h"
@@ -68,6 +69,20 @@ __device__ __forceinline__ void model_w(uint64_t s_imu, int i, const double* L, 
     w[r] = a;
   }
 }
+// one walk component's increment over a sample with dT > 0, and the scalar a sample stores: (value + W(f, i)) + n, n absent when
+// dT <= 0 -- w: the component's row of w = L z (n_wg 3 .. 5, n_wa 9 .. 11 for the increment; n_g 0 .. 2, n_a 6 .. 8 for the noise).
+// Stated once for the scan, the expansion and the sums.
+__device__ __forceinline__ double model_delta(double scale, double w, double dT) {
+#pragma clang fp contract(off)
+  const double sq = sqrt(dT);
+  return (scale * w) * sq;
+}
+__device__ __forceinline__ double model_stored(double v, double W, double scale, double w, double dT) {
+#pragma clang fp contract(off)
+  v = v + W;
+  if (dT > 0.0) { const double nz = (scale * w) / sqrt(dT); v = v + nz; }
+  return v;
+}
 // P(f, n) of a cell: the sequential sum of the first n samples' increments, per component; rd: the cell's readings [K][7]
 __device__ __forceinline__ void model_prefix(const double* rd, uint64_t s_imu, const double* L, double scale, int n, double* P) {
 #pragma clang fp contract(off)
@@ -77,10 +92,9 @@ __device__ __forceinline__ void model_prefix(const double* rd, uint64_t s_imu, c
     if (!(dT > 0.0)) continue;
     double w[rp::NQ];
     model_w(s_imu, i, L, w);
-    const double sq = sqrt(dT);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const double dg = (scale * w[3 + c]) * sq, da = (scale * w[9 + c]) * sq;
+      const double dg = model_delta(scale, w[3 + c], dT), da = model_delta(scale, w[9 + c], dT);
       P[c] = P[c] + dg; P[3 + c] = P[3 + c] + da;
     }
   }
@@ -122,7 +136,7 @@ __device__ __forceinline__ void model_imu(const double* cell, S* out, const doub
       for (int i = 0; i < n; ++i) {
         W[i][lane] = start + run;
         const double dT = cell[(i0 + i) * RD_STRIDE + 6];
-        if (dT > 0.0) { const double d = (scale * w[i][r]) * sqrt(dT); run = run + d; }
+        if (dT > 0.0) { const double d = model_delta(scale, w[i][r], dT); run = run + d; }
       }
       P[lane] = run;
     }
@@ -131,11 +145,7 @@ __device__ __forceinline__ void model_imu(const double* cell, S* out, const doub
       const int i = j / rp::WALK_ROW, c = j % rp::WALK_ROW;
       const double* rd = cell + (i0 + i) * RD_STRIDE;
       double v = rd[c];
-      if (i < n) {
-        v = v + W[i][c];
-        const double dT = rd[6];
-        if (dT > 0.0) { const double nz = (scale * w[i][c < 3 ? c : 3 + c]) / sqrt(dT); v = v + nz; }   // n_g: rows 0 .. 2, n_a: rows 6 .. 8
-      }
+      if (i < n) v = model_stored(v, W[i][c], scale, w[i][c < 3 ? c : 3 + c], rd[6]);   // n_g: rows 0 .. 2, n_a: rows 6 .. 8
       out[(i0 + i) * RD_STRIDE + c] = (S)v;
     }
     __syncthreads();                                                   // the next tile overwrites z, w and W
@@ -159,6 +169,13 @@ __device__ __forceinline__ Vec2<S> entry_obs(const double* z, const double* sg, 
   return w;
 }
 
+// The sigma4 model's pair p (0 .. 2) of IMU sample i: columns 2 p, 2 p + 1 of its row r with pair 3 i + p of s_imu (replay_plan.h, NOISE)
+__device__ __forceinline__ void sigma4_pair(const double* r, const double* sg, uint64_t s_imu, int i, int p, double& v0, double& v1) {
+  const int cc = 2 * p;
+  const Pair g = box_muller(s_imu, (uint64_t)(rp::IMU_PAIRS * i + p));
+  v0 = noisy(r[cc], sg[cc < 3 ? rp::SIG_G : rp::SIG_A], g.c); v1 = noisy(r[cc + 1], sg[cc + 1 < 3 ? rp::SIG_G : rp::SIG_A], g.s);
+}
+
 // The fixed items of a trajectory, j counted from the first of them (the list at the top of the file without the entries):
 // IMU noise pairs (sigma4 model only), dT, M[t] / off[t], and n / drop / k.  with_M == false: M[t] is somebody else's (the
 // faulted form's track items store the survivors).
@@ -172,10 +189,7 @@ __device__ __forceinline__ void fixed_item(const ReplaySeqIn& q, const ReplayOut
     const double* r = q.rd + ((long)s * K + i) * RD_STRIDE;
     S* w = o.rd + ((long)b * K + i) * RD_STRIDE;
     double v0 = r[cc], v1 = r[cc + 1];
-    if (i < c.kc) {                                                    // (a skipped cell's k is IMU_SKIP: no noise; rows from k on stay zero)
-      const Pair g = box_muller(rp::imu_seed(c.seed, f), (uint64_t)j);
-      v0 = noisy(v0, c.sg[cc < 3 ? rp::SIG_G : rp::SIG_A], g.c); v1 = noisy(v1, c.sg[cc + 1 < 3 ? rp::SIG_G : rp::SIG_A], g.s);
-    }
+    if (i < c.kc) sigma4_pair(r, c.sg, rp::imu_seed(c.seed, f), i, j % rp::IMU_PAIRS, v0, v1);   // (a skipped cell's k is IMU_SKIP: no noise; rows from k on stay zero)
     w[cc] = (S)v0; w[cc + 1] = (S)v1;
   } else if (j < m0) {
     const int i = j - dt0;
@@ -334,6 +348,69 @@ __global__ __launch_bounds__(64) void k_replay_fault_counts(const int* n, const 
 void launch_replay_fault_counts(const int* n, const int* M, const int* off, const ReplayTrajIn& t, int f0, int f1, int S, int f_cap, int B, long long* out, hipStream_t st) {
   if (B <= 0) return;
   hipLaunchKernelGGL(k_replay_fault_counts, dim3((unsigned)B), dim3(64), 0, st, n, M, off, t, f0, f1, S, f_cap, out);
+}
+
+// msckf_hip_replay_imu_sums: what the expansion would hand each trajectory's propagate over the frames [f0, f1), summed --
+// one workgroup (one wavefront) per trajectory; lane l takes the frames f0 + l, f0 + l + 64, ... in ascending order and a frame's
+// samples i < k in ascending order, adds the count, the six scalars and dT of each sample as the expansion stores them (the
+// value of sigma4_pair, or of model_stored on the walk W(f, i) = Wstart(f) + P(f, i) built as model_imu builds it; rounded to
+// the handle's scalar S, widened to double) onto its own eight doubles; the lanes are combined by wave_sum.  The order of every
+// addition is fixed: the same inputs give the same bits.  Skipped cells add nothing.  No LDS, no atomics.
+// rd / kcell: the sequence store's readings [frames][S][K][7] and counts [frames][S] from frame 0; m.wstart: the walk table from
+// row 0; out [B][8] (replay_plan.h, ImuSum).
+template <class S, bool MODEL>
+__global__ __launch_bounds__(64) void k_replay_imu_sums(const double* rd, const int* kcell, ReplayTrajIn t, ReplayModelIn m, int f0, int f1, int n_seq, int K, int B, double* out) {
+#pragma clang fp contract(off)
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  double acc[rp::IMU_SUM_ROW] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int f = f0 + lane; f < f1; f += 64) {
+    const long cell = (long)f * n_seq + s;
+    const int kc = kcell[cell];                                        // (a skipped cell's k is IMU_SKIP: nothing)
+    const int k = kc < K ? kc : K;
+    const double* cr = rd + cell * K * RD_STRIDE;
+    const uint64_t s_imu = rp::imu_seed(seed, f);
+    double P[rp::WALK_ROW] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < k; ++i) {
+      const double* r = cr + i * RD_STRIDE;
+      double v[6];
+      if constexpr (MODEL) {
+        const double* L = m.L + (long)b * rp::L_SIZE;
+        const double* start = m.wstart + ((long)f * B + b) * rp::WALK_ROW;
+        const double scale = m.scale[b], dT = r[6];
+        double w[rp::NQ];
+        if (dT > 0.0) model_w(s_imu, i, L, w);
+        else for (int q = 0; q < rp::NQ; ++q) w[q] = 0.0;              // (not read: a sample with dT <= 0 gets no noise and no increment)
+#pragma unroll
+        for (int c = 0; c < rp::WALK_ROW; ++c) {
+          const double W = start[c] + P[c];
+          v[c] = model_stored(r[c], W, scale, w[c < 3 ? c : 3 + c], dT);
+          if (dT > 0.0) { const double d = model_delta(scale, w[c < 3 ? 3 + c : 6 + c], dT); P[c] = P[c] + d; }
+        }
+      } else {
+        const double* sg = t.sigma + (long)b * rp::N_SIGMA;
+#pragma unroll
+        for (int p = 0; p < rp::IMU_PAIRS; ++p) sigma4_pair(r, sg, s_imu, i, p, v[2 * p], v[2 * p + 1]);
+      }
+      acc[rp::IS_COUNT] += 1.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) acc[rp::IS_OMEGA + c] += (double)(S)v[c];
+      acc[rp::IS_DT] += (double)(S)r[6];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < rp::IMU_SUM_ROW; ++i) {
+    const double v = wave_sum(acc[i]);
+    if (lane == 0) out[(long)b * rp::IMU_SUM_ROW + i] = v;
+  }
+}
+void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st) {
+  if (B <= 0) return;
+  const bool model = m.L != nullptr;
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), 0, st, rd, k, t, m, f0, f1, S, K, B, out); };
+  if (scalar_is_float) { if (model) go(k_replay_imu_sums<float, true>); else go(k_replay_imu_sums<float, false>); }
+  else { if (model) go(k_replay_imu_sums<double, true>); else go(k_replay_imu_sums<double, false>); }
 }
 
 // The walk table of the model, wstart[frames + 1][B][6], once per assignment: workgroup b takes trajectory b.  Per chunk of

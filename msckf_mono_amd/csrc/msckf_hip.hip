@@ -41,6 +41,7 @@
 #include "replay_plan.h"
 #include "settings.h"
 #include "slice_policy.h"
+#include "track_compile.h"
 
 namespace {
 using namespace msckf;
@@ -1168,6 +1169,28 @@ struct BatchCore {
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dout);
     if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("replay_fault_counts: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // msckf_hip_replay_imu_sums: per trajectory the count, the summed omega, a and dT of the IMU samples a run over [f0, f1) would
+  // hand its propagate, out [B][8] (replay_plan.h, ImuSum), summed on the device from the sequences and the assignment alone
+  // (k_replay_imu_sums): no run, no log, nothing of the filters changes
+  int replay_imu_sums(int f0, int f1, double* out) {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.sums_refusal(f0, f1))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    if (int rc = replay_walk_table()) return rc;
+    constexpr size_t W = msckf_replay::IMU_SUM_ROW;
+    double* dout = nullptr;
+    HIPCHK(hipMalloc((void**)&dout, (size_t)B * W * sizeof(double)));
+    launch_replay_imu_sums(reinterpret_cast<const double*>(rp_dev[SEC_RD]), reinterpret_cast<const int*>(rp_dev[SEC_K]), ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base},
+                           replay_model(0), f0, f1, rp.S, rp.K(), B, esz == sizeof(float), dout, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)B * W * sizeof(double), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dout);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("replay_imu_sums: ") + hipGetErrorString(e != hipSuccess ? e : es));
     return 0;
   }
   // what map_log_fault_metrics checks before anything reaches the device: the log and its ordinals, then the replay frames
@@ -2873,6 +2896,34 @@ int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints
 int msckf_hip_replay_set_faults(msckf_hip_handle h, const double* fault4) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_faults(fault4); }
 int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* code, int cap_entries) { if (!h || !code) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, code); }
 int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_fault_counts(f0, f1, out); }
+int msckf_hip_replay_imu_sums(msckf_hip_handle h, int f0, int f1, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_imu_sums(f0, f1, out); }
+// ---- the track compiler (track_compile.h): host code alone, no handle, no device
+int msckf_hip_compile_create(int max_cam_states, int min_track_length, int max_track_length, msckf_hip_compiler* out) {
+  if (!out) return fail(-EINVAL, "null out pointer");
+  *out = nullptr;
+  if (const msckf_compile::Refusal r = msckf_compile::Compiler::create_refusal(max_cam_states, min_track_length, max_track_length); r.code) return fail(r.code, r.why);
+  *out = reinterpret_cast<msckf_hip_compiler>(new msckf_compile::Compiler(max_cam_states, min_track_length, max_track_length));
+  return 0;
+}
+int msckf_hip_compile_destroy(msckf_hip_compiler c) { delete reinterpret_cast<msckf_compile::Compiler*>(c); return 0; }
+int msckf_hip_compile_image(msckf_hip_compiler c, const double* upd_meas2, const uint64_t* upd_ids, int upd_n, const double* new_meas2, const uint64_t* new_ids, int new_n, int* out5) {
+  if (!c || !out5) return fail(-EINVAL, "null argument");
+  msckf_compile::ImageSummary s{0, 0, 0, 0, 0};
+  if (const msckf_compile::Refusal r = reinterpret_cast<msckf_compile::Compiler*>(c)->image(upd_meas2, upd_ids, upd_n, new_meas2, new_ids, new_n, s); r.code) return fail(r.code, r.why);
+  out5[0] = s.F; out5[1] = s.entries; out5[2] = s.n_drop; out5[3] = s.window; out5[4] = s.live;
+  return 0;
+}
+int msckf_hip_compile_cell(msckf_hip_compiler c, int* M, int* slots, double* obs2, uint64_t* ids, int cap_tracks, int cap_entries) {
+  if (!c) return fail(-EINVAL, "null argument");
+  const msckf_compile::Compiler& k = *reinterpret_cast<const msckf_compile::Compiler*>(c);
+  if (const msckf_compile::Refusal r = k.cell_refusal(cap_tracks, cap_entries); r.code) return fail(r.code, r.why);
+  if ((!k.wl.M.empty() && (!M || !ids)) || (!k.wl.slots.empty() && (!slots || !obs2))) return fail(-EINVAL, "null output with a work-list to store");
+  std::copy(k.wl.M.begin(), k.wl.M.end(), M);
+  std::copy(k.ids.begin(), k.ids.end(), ids);
+  std::copy(k.wl.slots.begin(), k.wl.slots.end(), slots);
+  std::copy(k.wl.obs.begin(), k.wl.obs.end(), obs2);
+  return (int)k.wl.M.size();
+}
 int msckf_hip_map_log_fault_metrics(msckf_hip_handle h, int q0, int q1, int f0, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->map_log_fault_metrics(q0, q1, f0, out); }
 int msckf_hip_sync(msckf_hip_handle h) { return H(h)->sync(); }
 int msckf_hip_profile_enable(msckf_hip_handle h, int on) { return H(h)->prof_enable(on); }

@@ -143,6 +143,11 @@ constexpr TrackFaults track_faults(uint64_t s_flt, uint64_t e0, int M, double p_
 enum FaultCount { FC_ENTRIES, FC_MISSED, FC_OUTLIERS, FC_TRACKS, FC_TRACKS_SHORTENED, FC_TRACKS_CONTAMINATED, N_FAULT_COUNT };
 enum FaultMetric { FM_RECORDS, FM_CLEAN_PASS, FM_CLEAN_REJ, FM_CONT_PASS, FM_CONT_REJ, FM_SUM_GAMMA, FM_SUM_DOF, FM_UNMATCHED, N_FAULT_METRIC };
 
+// ---- 2d. SUMS: a row of msckf_hip_replay_imu_sums, per trajectory over a frame range: the IMU samples the expansion hands the
+// trajectory's propagate (rows below the cell's k of the cells that are not skipped), each scalar as the expansion stores it --
+// rounded to the handle's scalar, widened to double -- summed in double: the count, omega, a, dT.  Sums and counts: ranges add.
+enum ImuSum { IS_COUNT = 0, IS_OMEGA = 1, IS_A = 4, IS_DT = 7, IMU_SUM_ROW = 8 };
+
 // ---- 3. the plan
 using msckf_inputs::FrameLayout;
 using msckf_inputs::Refusal;
@@ -267,6 +272,8 @@ struct Plan {
     if (!assigned) return {-EINVAL, "replay not assigned"};
     return {0, nullptr};
   }
+  // msckf_hip_replay_imu_sums reads what a run over [f0, f1) would expand: a run's refusals, in a run's order
+  Refusal sums_refusal(int f0, int f1) const { return run_refusal(f0, f1); }
   Refusal expand_refusal(int f, int b) const {
     if (const Refusal r = run_refusal(0, seq.frames); r.code) return r;
     if (f < 0 || f >= seq.frames || b < 0 || b >= B) return {-EINVAL, "replay cell out of range"};

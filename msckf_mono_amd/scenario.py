@@ -241,6 +241,31 @@ def replay_model_expand(seq_traj, frame, seed, L, scale, sigma_uv, w_start=None)
     return replay_model_cell(seq_traj.imu_for_frame(frame), seq_traj.frames[frame]["obs"], frame, seed, L, scale, sigma_uv, w_start)[:2]
 
 
+def replay_imu_sums(seq_traj_or_cells, seed, f0, f1, sigma4=None, model=None, dtype=np.float64):
+    """msckf_hip_replay_imu_sums for one trajectory: [8] = samples, sum omega (3), sum a (3), sum dT over the frames [f0, f1) of a
+    noise-free Trajectory or a list of per-frame readings [k][7] (None: a skipped cell), each sample as the expansion stores it:
+    replay_cell's rows under sigma4 = (sigma_g, sigma_a, ., .), or replay_model_cell's under model = (L, scale) on the walk of
+    replay_walk, rounded to `dtype` (the handle's scalar) and summed in double.  The order of the sum is numpy's, not the
+    device's: the two agree to the summation bound, not to the bit."""
+    cells = _replay_cells(seq_traj_or_cells)
+    if (sigma4 is None) == (model is None):
+        raise ValueError("one of sigma4 and model")
+    W = None if model is None else replay_walk(cells, seed, model[0], model[1])
+    out = np.zeros(8)
+    for f in range(int(f0), int(f1)):
+        rd = cells[f]
+        if not len(rd):
+            continue
+        if model is None:
+            rows = replay_cell(rd, np.zeros((0, 2)), f, seed, sigma4)[0]
+        else:
+            rows = replay_model_cell(rd, np.zeros((0, 2)), f, seed, model[0], model[1], (0.0, 0.0), W[f])[0]
+        rows = rows.astype(dtype).astype(np.float64)
+        out[0] += len(rows)
+        out[1:8] += rows.sum(0)
+    return out
+
+
 def replay_bias_gt(trajs, walks):
     """the true b_g, b_a at each frame-log record: [frames][B][6] = trajs[b]'s constant biases + walks[f + 1][b] (walks
     [frames + 1][B][6]: Batch.replay_walk() or the stacked replay_walk of each trajectory), to take bias errors and bias NEES
