@@ -335,6 +335,42 @@ int msckf_hip_replay_set_faults(msckf_hip_handle h, const double* fault4 /*[B][4
 /* per SEQUENCE entry of trajectory b's cell on `frame`: 0 kept, 1 outlier, 2 missed, from the same launch as
  * msckf_hip_replay_expand.  Returns the cell's entries; -E2BIG when they exceed cap_entries. */
 int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* code /*[entries]*/, int cap_entries);
+/* The camera's clock, on top of either noise model and of the faults: a constant camera-IMU time offset, per-image timestamp
+ * jitter and rolling-shutter readout, per trajectory timing4[b] = (t_d, r_y, y_0, sigma_j) -- the offset in seconds, the readout
+ * slope in seconds per unit of normalised image y (a sensor of H rows read in t_r seconds: r_y = t_r f_v / H,
+ * y_0 = (H / 2 - c_v) / f_v), the jitter in seconds; all finite, sigma_j >= 0.  A record is non-zero when t_d, r_y or sigma_j is.
+ *   image table of a sequence, built at msckf_hip_replay_commit from its cells alone.  Frames in order with T = 0 (double),
+ *     ord = 0, W = 0: a skipped cell changes nothing; any other cell adds its dT_i, i < k ascending, to T, sets ord += 1,
+ *     W += 1, records time[ord - 1] = T, frame_of[ord - 1] = f, base(f) = ord - W, then sets W -= n_drop(f).  Camera slot s of
+ *     frame f's cell is image base(f) + s: the window an empty start at frame 0 gives, always a suffix of the images.
+ *   entry l of a track has the sequence value (x_l, y_l) and image i_l = base(f) + slot_l; it was exposed at time[i_l] + delta_l,
+ *     delta_l = (t_d + r_y (y_l - y_0)) + sigma_j g(frame_of[i_l]): the difference, the product, the sum, the product sigma_j g,
+ *     the sum, each rounded in double.  g(q) is the first component of pair(mix(s_b, 2^63 + 2), q): one draw per image and seed,
+ *     shared by every observation of that image in whichever cell it surfaces (sigma_j == 0: no draw, the term is 0).
+ *   the shift uses nodes of the same track, in sequence order: M = 1 unchanged; M = 2 both entries; M >= 3 the entries l0, l0 + 1,
+ *     l0 + 2 with l0 = min(max(l - 1, 0), M - 3).  d_j = time[i_j] - time[i_l], relative to the entry's own time;
+ *     w_j = prod_{m != j} (delta_l - d_m) / prod_{m != j} (d_j - d_m), m ascending, numerator and denominator each one product
+ *     (three nodes) or one difference (two), then one division; the new value is sum_j w_j (x_j, y_j), j ascending, the first
+ *     product, then each further product added: + - x / only, each rounded in double, no contraction.  delta_l == 0 exactly:
+ *     the value itself.
+ *   the Gaussian pixel noise and the outlier ring are then added to the shifted value exactly as without timing; a missed
+ *     observation still serves its neighbours as a node; draws stay indexed by the sequence entry, so a seed's noise and faults
+ *     do not depend on its timing.  Timing moves no IMU row.
+ * With NULL, or every record zero (y_0 alone moves nothing), the expansion launched and every bit are those without timing.
+ * -EINVAL, in this order: "no replay allocated", "timing values must be finite", "jitter must not be negative"; then, only
+ * under a non-zero record (here on committed cells, and at msckf_hip_replay_commit while such a record is in force), with the
+ * sequence, frame and track named ("timing: sequence S, frame F, track T: ..."): a cell that names a camera slot >= W(f), a track
+ * whose slots do not ascend strictly, a track whose node times do not increase strictly.  A refused call leaves the previous
+ * record in force.  May be called between runs; survives msckf_hip_replay_assign, _assign_q, _set_faults and _commit;
+ * msckf_hip_replay_alloc clears it.  msckf_hip_replay_expand / _expand_ints / _expand_faults return what the timed kernel wrote. */
+int msckf_hip_replay_set_timing(msckf_hip_handle h, const double* timing4 /*[B][4], NULL: none*/);
+/* Sequence seq's image table as the last msckf_hip_replay_commit built it: time [images], frame_of [images], base [frames], each
+ * or NULL.  Returns the image count (<= frames).  -EINVAL "no replay allocated", "replay not committed", "replay cell out of
+ * range". */
+int msckf_hip_replay_image_table(msckf_hip_handle h, int seq, double* time, int* frame_of, int* base);
+/* per SEQUENCE entry of trajectory b's cell on `frame`: its delta in seconds (0 without timing), from the same launch as
+ * msckf_hip_replay_expand.  Returns the cell's entries; -E2BIG when they exceed cap_entries. */
+int msckf_hip_replay_expand_timing(msckf_hip_handle h, int frame, int b, double* delta /*[entries]*/, int cap_entries);
 /* The faults of the frames [f0, f1) per trajectory, counted on the device from the sequences, the seeds and the fault record
  * alone (no run, no log): out [B][6] = entries, missed, outliers, tracks, tracks that lost at least one observation, tracks that
  * carry at least one outlier.  Integers: they equal the twin's exactly.  Refusals as msckf_hip_run_frames_replay. */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "msckf_hip_replay_alloc", "msckf_hip_replay_set_cell", "msckf_hip_replay_assign", "msckf_hip_replay_commit", "msckf_hip_run_frames_replay", "msckf_hip_replay_expand",
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
     "msckf_hip_replay_set_faults", "msckf_hip_replay_expand_faults", "msckf_hip_replay_fault_counts", "msckf_hip_map_log_fault_metrics",
+    "msckf_hip_replay_set_timing", "msckf_hip_replay_image_table", "msckf_hip_replay_expand_timing",
     "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
     "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
@@ -467,6 +468,29 @@ class Batch:
         code = np.zeros(cap, dtype=np.int32)
         n = _chk(self.L.msckf_hip_replay_expand_faults(self.h, int(frame), int(b), code.ctypes.data_as(_ip), cap))
         return code[:n]
+
+    def replay_set_timing(self, timing4):
+        """the camera's clock (include/msckf_hip.h): per trajectory (t_d, r_y, y_0, sigma_j) -- time offset [s], readout slope
+        [s per unit of normalised image y], the row exposed at the stamp, timestamp jitter [s]; one row serves every trajectory;
+        None: no timing.  Stays through replay_assign, replay_assign_q, replay_set_faults and replay_commit."""
+        if timing4 is None:
+            _chk(self.L.msckf_hip_replay_set_timing(self.h, None))
+            return
+        tm = np.ascontiguousarray(np.broadcast_to(np.asarray(timing4, dtype=np.float64), (self.B, 4)))
+        _chk(self.L.msckf_hip_replay_set_timing(self.h, tm.ctypes.data_as(_dp)))
+
+    def replay_image_table(self, seq):
+        """sequence seq's image table as the last replay_commit built it: (time [images], frame_of [images], base [frames])"""
+        time = np.zeros(self._replay_frames); frame_of = np.zeros(self._replay_frames, dtype=np.int32); base = np.zeros(self._replay_frames, dtype=np.int32)
+        n = _chk(self.L.msckf_hip_replay_image_table(self.h, int(seq), time.ctypes.data_as(_dp), frame_of.ctypes.data_as(_ip), base.ctypes.data_as(_ip)))
+        return time[:n], frame_of[:n], base
+
+    def replay_expand_timing(self, frame, b):
+        """per sequence entry of trajectory b's cell on `frame`: its delta in seconds, from the expansion's own launch"""
+        cap = self.f_cap * self.m_cap
+        delta = np.zeros(cap)
+        n = _chk(self.L.msckf_hip_replay_expand_timing(self.h, int(frame), int(b), delta.ctypes.data_as(_dp), cap))
+        return delta[:n]
 
     def replay_fault_counts(self, f0=0, f1=None):
         """the faults of the frames [f0, f1) (default: all) per trajectory, counted on the device: int64 [B][6], columns

@@ -598,6 +598,12 @@ struct ReplayModelIn { const double* L; const double* scale; const double* wstar
 // With t.fault the faulted form runs: a group of fault_group(m_cap) lanes per track, the grid sized from f_cap tracks; code (or
 // null): per entry of the block, at base[b] + the entry's index in the sequence cell, 0 kept, 1 outlier, 2 missed.
 template <class S> void launch_replay_expand(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, int max_entries, hipStream_t st, int m_cap = 0, int* code = nullptr);
+// The timed form (replay_plan.h, TIMING): the faulted form's lane groups, each entry moved along its track to the time it was
+// exposed before noise and ring are added.  tm: the record timing4[B][4], the image tables of all sequences (time / frame_of
+// [S][stride], row s the images of sequence s) and the frame's base[S]; t.fault is not null (zeros: timing alone).  delta (or
+// null): per entry of the block, at base[b] + the entry's index in the sequence cell, its delta in seconds.
+struct ReplayTimingIn { const double* timing; const double* time; const int* frame_of; const int* base; int stride; };
+template <class S> void launch_replay_expand_timed(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, hipStream_t st, int m_cap, int* code = nullptr, double* delta = nullptr);
 // the faults of the frames [f0, f1) counted per trajectory, out[B][6] (replay_plan.h, FaultCount): n / M / off are the sequence
 // store's sections from frame 0, t.fault is not null; one workgroup per trajectory.  And the map log's records with ordinal in
 // [q0, q1) -- record ordinal q belongs to replay frame f0 + (q - q0) -- against the faults of their tracks, recomputed from

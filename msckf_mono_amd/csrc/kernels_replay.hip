@@ -25,6 +25,10 @@
 // instead of entry items -- a group of lanes per track drops the missed observations behind the survivors and displaces the
 // outliers.  k_replay_fault_counts counts a frame range's faults without expanding anything, and k_replay_imu_sums sums the IMU
 // samples a frame range would expand, per trajectory, from the same device functions (the stand-still initialisation's means).
+//
+// With a non-zero timing record (replay_plan.h, TIMING) k_replay_expand_timed runs in place of either: the faulted form's lane
+// groups, where each lane first moves its entry along the track to the time the pixel was exposed -- the stencil's neighbours come
+// from the lanes of its group -- and then goes through the same entry_obs.  The two forms above are not touched by it.
 #include <type_traits>
 
 #include "dev_common.h"
@@ -287,6 +291,143 @@ __global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand_faults(ReplaySeq
     } else fixed_item<S, MODEL>(q, o, c, it - T, f, K, f_cap, false);
   }
 }
+
+// A product that is rounded before anything is added to it, whatever the file's contraction mode (-ffp-contract=fast fuses
+// across statements and disregards the pragma): the value passes through an empty asm the compiler cannot look into.
+__device__ __forceinline__ double rounded(double p) {
+  asm volatile("" : "+v"(p));
+  return p;
+}
+// The shift of one entry along its track (replay_plan.h, TIMING): n nodes (2 or 3) with values (x[j], y[j]) and times d[j]
+// relative to the entry's own, the entry exposed dl after its image's time.  w_j = prod_{m != j} (dl - d_m) / prod_{m != j}
+// (d_j - d_m), the value sum_j w_j (x_j, y_j) with j ascending: + - x / only, each rounded in double (every product that an
+// addition takes goes through rounded()).
+__device__ __forceinline__ void timing_shift(int n, const double* d, const double* x, const double* y, double dl, double* z) {
+#pragma clang fp contract(off)
+  double w[3] = {0.0, 0.0, 0.0};
+  if (n == 2) {
+    w[0] = (dl - d[1]) / (d[0] - d[1]);
+    w[1] = (dl - d[0]) / (d[1] - d[0]);
+  } else {
+    w[0] = ((dl - d[1]) * (dl - d[2])) / ((d[0] - d[1]) * (d[0] - d[2]));
+    w[1] = ((dl - d[0]) * (dl - d[2])) / ((d[1] - d[0]) * (d[1] - d[2]));
+    w[2] = ((dl - d[0]) * (dl - d[1])) / ((d[2] - d[0]) * (d[2] - d[1]));
+  }
+  double ax = rounded(w[0] * x[0]), ay = rounded(w[0] * y[0]);
+  { const double px = rounded(w[1] * x[1]), py = rounded(w[1] * y[1]); ax = ax + px; ay = ay + py; }
+  if (n == 3) { const double px = rounded(w[2] * x[2]), py = rounded(w[2] * y[2]); ax = ax + px; ay = ay + py; }
+  z[0] = ax; z[1] = ay;
+}
+// delta_l of an entry with sequence value y on image q of the sequence (replay_plan.h, TIMING): tm4 the trajectory's record,
+// s_tim = timing_seed(s_b); sigma_j == 0: no draw
+__device__ __forceinline__ double timing_delta(const double* tm4, uint64_t s_tim, double y, int frame_of) {
+#pragma clang fp contract(off)
+  const double a = y - tm4[rp::TIM_Y0];
+  const double p = rounded(tm4[rp::TIM_RY] * a);
+  const double s = tm4[rp::TIM_TD] + p;
+  const double sj = tm4[rp::TIM_SIGMA_J];
+  const double g = sj != 0.0 ? box_muller(s_tim, (uint64_t)frame_of).c : 0.0;
+  const double j = rounded(sj * g);
+  return s + j;
+}
+
+// The timed form (replay_plan.h, TIMING): k_replay_expand_faults' items and lane groups -- one lane per entry of a track -- with
+// the entry's value moved along its track before it goes through entry_obs.  A lane loads its entry's value, its slot and the
+// time and frame of image base(f) + slot, forms its delta, and fetches the values and times of its stencil's nodes from the
+// lanes l0 .. l0 + 2 of its group (__shfl: ds_bpermute; every lane of a track wavefront is active, the lanes beyond M hold
+// zeros nobody asks for).  Missed entries serve as nodes like any other.  With p_miss = p_out = 0 it is timing alone: all
+// survive, in sequence order.  delta (null in the frame loop): per entry, at base + the entry's SEQUENCE index.
+// No LDS, no atomics, no exchange between wavefronts.
+template <class S, bool MODEL, int G>
+__global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand_timed(ReplaySeqIn q, ReplayTrajIn t, ReplayModelIn m, ReplayTimingIn tm, ReplayOut<S> o, int* code, double* delta, int f, int b0, int K, int f_cap) {
+  const int b = b0 + (int)blockIdx.y;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double* sg = t.sigma + (long)b * (MODEL ? 2 : rp::N_SIGMA);
+  const double* flt = t.fault + (long)b * rp::N_FAULT;
+  const double* tm4 = tm.timing + (long)b * rp::N_TIMING;
+  const double* times = tm.time + (long)s * tm.stride;
+  const int* frames_of = tm.frame_of + (long)s * tm.stride;
+  const int img0 = tm.base[s];                                         // camera slot 0 of the cell is this image of the sequence
+  const int* Ms = q.M + (long)s * f_cap;
+  const int* offs = q.off + (long)s * f_cap;
+  const int first = offs[0];
+  const int base = t.base[b];
+  const int kc = q.k[s];
+  if constexpr (MODEL) {
+    if (blockIdx.x == 0)
+      model_imu<S>(q.rd + (long)s * K * RD_STRIDE, o.rd + (long)b * K * RD_STRIDE, m.L + (long)b * rp::L_SIZE, m.scale[b], m.wstart + (long)b * rp::WALK_ROW, rp::imu_seed(seed, f), K, kc < K ? kc : K);
+  }
+  const ReplayCell c{s, b, kc, first, base, seed, sg, Ms, offs};
+  const double p_miss = flt[rp::FLT_P_MISS], p_out = flt[rp::FLT_P_OUT];
+  const uint64_t s_flt = rp::fault_seed(seed, f), s_obs = rp::obs_seed(seed, f), s_tim = rp::timing_seed(seed);
+  const int lane = (int)threadIdx.x & 63;
+  const int T = (f_cap * G + 63) & ~63;                                // as in k_replay_expand_faults: `it < T` is the same for a whole wavefront
+  const int end = T + fixed_items(MODEL, K, f_cap);
+  for (int it = (int)blockIdx.x * REPLAY_CHUNK + (int)threadIdx.x; it < end; it += (int)gridDim.x * REPLAY_CHUNK) {
+    if (it < T) {
+      const int tr = it / G, l = it % G;
+      const int M = tr < f_cap ? Ms[tr] : 0;                           // (M <= m_cap <= G)
+      const bool have = l < M;
+      const int e = have ? offs[tr] - first + l : 0;
+      // the entry's own value, slot and image; the host has checked slot < W(f): base(f) + slot names an image of the table
+      const int slot = have ? q.slots[(long)first + e] : 0;
+      const double vx = have ? q.obs[2 * (long)(first + e)] : 0.0, vy = have ? q.obs[2 * (long)(first + e) + 1] : 0.0;
+      const double tl = have ? times[img0 + slot] : 0.0;
+      const double dl = have ? timing_delta(tm4, s_tim, vy, frames_of[img0 + slot]) : 0.0;
+      // the stencil's nodes from the lanes of the group (every lane of the wavefront takes part)
+      const int n = rp::stencil_nodes(M), g0 = (lane & ~(G - 1)) + (have ? rp::stencil_first(l, M) : 0);
+      double nx[3], ny[3], nd[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int src = j < n ? g0 + j : lane;
+        nx[j] = __shfl(vx, src, 64); ny[j] = __shfl(vy, src, 64); nd[j] = __shfl(tl, src, 64) - tl;
+      }
+      double z[2] = {vx, vy};
+      if (have && n >= 2 && dl != 0.0) timing_shift(n, nd, nx, ny, dl, z);
+      // from here on k_replay_expand_faults, on the shifted value
+      const bool raw = have && p_miss > 0.0 && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e) < p_miss;
+      unsigned long long gm = __ballot(raw ? 1 : 0);
+      if constexpr (G < 64) gm &= ((1ull << G) - 1) << (lane & ~(G - 1));
+      if (M - __popcll(gm) < 2) gm = 0;                                // a track keeps two observations or loses none
+      const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(gm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)gm, 0u));
+      const int surv = M - __popcll(gm);
+      if (have) {
+        const bool miss = (gm >> lane) & 1;
+        const bool out = !miss && p_out > 0.0 && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 1) < p_out;
+        const long dst = (long)base + (offs[tr] - first) + (miss ? surv + below : l - below);
+        o.slots[dst] = slot;
+        *reinterpret_cast<Vec2<S>*>(o.obs + 2 * dst) = entry_obs<S, MODEL>(z, sg, s_obs, (uint64_t)e, out, out ? rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 2) : 0.0, flt);
+        if (code) code[(long)base + e] = miss ? rp::FAULT_MISSED : out ? rp::FAULT_OUTLIER : rp::FAULT_KEPT;
+        if (delta) delta[(long)base + e] = dl;
+      }
+      if (l == 0 && tr < f_cap) o.M[(long)b * f_cap + tr] = surv;
+    } else fixed_item<S, MODEL>(q, o, c, it - T, f, K, f_cap, false);
+  }
+}
+
+template <class S, bool MODEL, int G>
+static void launch_timed(const dim3& grid, hipStream_t st, const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayOut<S>& o, int* code, double* delta, int f, int b0, int K, int f_cap) {
+  hipLaunchKernelGGL((k_replay_expand_timed<S, MODEL, G>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, tm, o, code, delta, f, b0, K, f_cap);
+}
+// the faulted form's grid: f_cap tracks of G lanes, G from m_cap
+template <class S>
+void launch_replay_expand_timed(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, hipStream_t st, int m_cap, int* code, double* delta) {
+  if (nb <= 0) return;
+  const bool model = m.L != nullptr;
+  const int G = rp::fault_group(m_cap);
+  const long items = (long)((f_cap * G + 63) & ~63) + fixed_items(model, K, f_cap);
+  const dim3 grid((unsigned)((items + REPLAY_CHUNK - 1) / REPLAY_CHUNK), (unsigned)nb);
+  auto go = [&](auto mdl) {
+    constexpr bool MD = decltype(mdl)::value;
+    if (G == 16) launch_timed<S, MD, 16>(grid, st, q, t, m, tm, o, code, delta, f, b0, K, f_cap);
+    else if (G == 32) launch_timed<S, MD, 32>(grid, st, q, t, m, tm, o, code, delta, f, b0, K, f_cap);
+    else launch_timed<S, MD, 64>(grid, st, q, t, m, tm, o, code, delta, f, b0, K, f_cap);
+  };
+  if (model) go(std::true_type{}); else go(std::false_type{});
+}
+template void launch_replay_expand_timed<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayOut<float>&, int, int, int, int, int, hipStream_t, int, int*, double*);
+template void launch_replay_expand_timed<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayOut<double>&, int, int, int, int, int, hipStream_t, int, int*, double*);
 
 // max_entries: the entries of the frame's largest sequence cell (the unfaulted grid's width; a trajectory with fewer leaves its
 // lanes idle).  t.fault != nullptr: the faulted form, its grid sized from f_cap tracks of G lanes, G from m_cap.

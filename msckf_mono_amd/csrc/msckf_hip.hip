@@ -238,6 +238,10 @@ struct BatchCore {
   // the fault record fault4[B][4] (zeros while none is set; rp.faults_uploaded) and replay_expand_faults' codes, one per entry of
   // the largest expanded frame
   double* rp_fault = nullptr; int* rp_code = nullptr; size_t rp_code_count = 0;
+  // the timing record timing4[B][4] (zeros while none is set; rp.timing_uploaded), the sequences' image tables as commit built
+  // them (time / frame_of [S][frames], base [frames][S]) and replay_expand_timing's deltas, one per entry of the largest frame
+  double* rp_timing = nullptr; double* rp_img_time = nullptr; int* rp_img_frame = nullptr; int* rp_img_base = nullptr;
+  double* rp_delta = nullptr; size_t rp_delta_count = 0;
   std::vector<int> rp_cells[MAXS];
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
@@ -1064,6 +1068,7 @@ struct BatchCore {
     rp_blk_bytes = 0;
     dfree(rp_scratch); rp_scratch_bytes = 0;
     dfree(rp_fault); dfree(rp_code); rp_code_count = 0;
+    dfree(rp_timing); dfree(rp_img_time); dfree(rp_img_frame); dfree(rp_img_base); dfree(rp_delta); rp_delta_count = 0;
     rp_uploaded = false;
   }
   int replay_alloc(int n_seq, int n_frames, int K) {
@@ -1094,6 +1099,12 @@ struct BatchCore {
     for (int s = 0; s < N_SECTIONS; ++s)
       HIPCHK(hipMalloc((void**)&rp_dev[s], std::max<size_t>(s < N_FIXED ? q.fixed[s].size() : q.total() * q.lay.entry_bytes(s), 16)));
     if (int rc = upload_store(q, rp_dev)) return rc;
+    // the image tables of the timed expansion (replay_plan.h, TIMING)
+    dfree(rp_img_time); dfree(rp_img_frame); dfree(rp_img_base);
+    HIPCHK(hipMalloc((void**)&rp_img_time, rp.img_time.size() * sizeof(double))); HIPCHK(hipMalloc((void**)&rp_img_frame, rp.img_frame.size() * sizeof(int))); HIPCHK(hipMalloc((void**)&rp_img_base, rp.img_base.size() * sizeof(int)));
+    HIPCHK(hipMemcpy(rp_img_time, rp.img_time.data(), rp.img_time.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rp_img_frame, rp.img_frame.data(), rp.img_frame.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(rp_img_base, rp.img_base.data(), rp.img_base.size() * sizeof(int), hipMemcpyHostToDevice));
     rp_maxcell.assign(q.frames, 0);
     for (int f = 0; f < q.frames; ++f) for (int s = 0; s < rp.S; ++s) rp_maxcell[f] = std::max(rp_maxcell[f], (int)rp.entries(s, f));
     rp.committed = true;
@@ -1124,15 +1135,39 @@ struct BatchCore {
     rp.set_faults(fault4);
     return 0;
   }
+  // the timing record (replay_plan.h, TIMING), or null for none; may be called between runs, stays through assign, assign_q,
+  // set_faults and commit, and replay_alloc clears it.  A refused call leaves the previous record in force.
+  int replay_set_timing(const double* timing4) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.timing_refusal(timing4))) return rc;
+    rp.set_timing(timing4);
+    return 0;
+  }
+  // msckf_hip_replay_image_table: sequence seq's image table as commit built it -- time / frame_of [images], base [frames], each
+  // or null -- and the image count
+  int replay_image_table(int seq, double* time, int* frame_of, int* base) {
+    if (int rc = guard()) return rc;
+    if (rp.frames() <= 0) return fail(-EINVAL, "no replay allocated");
+    if (!rp.committed) return fail(-EINVAL, "replay not committed");
+    if (seq < 0 || seq >= rp.S) return fail(-EINVAL, "replay cell out of range");
+    const int F = rp.frames(), n = rp.img_n[seq];
+    if (time) std::copy(rp.img_time.begin() + (size_t)seq * F, rp.img_time.begin() + (size_t)seq * F + n, time);
+    if (frame_of) std::copy(rp.img_frame.begin() + (size_t)seq * F, rp.img_frame.begin() + (size_t)seq * F + n, frame_of);
+    if (base) for (int f = 0; f < F; ++f) base[f] = rp.img_base[rp.cell(f, seq)];
+    return n;
+  }
+  // the timing part of the timed expansion's arguments on frame f
+  ReplayTimingIn replay_timing(int f) const { return ReplayTimingIn{rp_timing, rp_img_time, rp_img_frame, rp_img_base + (size_t)f * rp.S, rp.frames()}; }
   // before a run or an expansion (after enter()): the bases of every frame, and with the assignment and the fault record on the device
   int replay_upload_plan() {
-    if (rp.planned && rp_uploaded && rp.faults_uploaded) return 0;
+    if (rp.planned && rp_uploaded && rp.faults_uploaded && rp.timing_uploaded) return 0;
     if (int rc = refuse(rp.index_trajectories())) return rc;
     HIPCHK(hipStreamSynchronize(st));                        // the last run's kernels have read the old ones
     if (!rp_seq_of) {
       HIPCHK(hipMalloc((void**)&rp_seq_of, (size_t)B * sizeof(int))); HIPCHK(hipMalloc((void**)&rp_seed, (size_t)B * sizeof(uint64_t)));
       HIPCHK(hipMalloc((void**)&rp_sigma, (size_t)B * msckf_replay::N_SIGMA * sizeof(double)));
       HIPCHK(hipMalloc((void**)&rp_fault, (size_t)B * msckf_replay::N_FAULT * sizeof(double)));
+      HIPCHK(hipMalloc((void**)&rp_timing, (size_t)B * msckf_replay::N_TIMING * sizeof(double)));
     }
     if (rp.base.size() != rp_base_count) { dfree(rp_base); rp_base_count = 0; HIPCHK(hipMalloc((void**)&rp_base, rp.base.size() * sizeof(int))); rp_base_count = rp.base.size(); }
     HIPCHK(hipMemcpy(rp_seq_of, rp.seq_of.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
@@ -1148,7 +1183,9 @@ struct BatchCore {
     }
     if (rp.fault.empty()) HIPCHK(hipMemset(rp_fault, 0, (size_t)B * msckf_replay::N_FAULT * sizeof(double)));
     else HIPCHK(hipMemcpy(rp_fault, rp.fault.data(), rp.fault.size() * sizeof(double), hipMemcpyHostToDevice));
-    rp_uploaded = rp.faults_uploaded = true;
+    if (rp.timing.empty()) HIPCHK(hipMemset(rp_timing, 0, (size_t)B * msckf_replay::N_TIMING * sizeof(double)));
+    else HIPCHK(hipMemcpy(rp_timing, rp.timing.data(), rp.timing.size() * sizeof(double), hipMemcpyHostToDevice));
+    rp_uploaded = rp.faults_uploaded = rp.timing_uploaded = true;
     return 0;
   }
   // msckf_hip_replay_fault_counts: the faults of the frames [f0, f1) per trajectory, out [B][6], counted on the device from the
@@ -1396,7 +1433,7 @@ struct BatchCore {
   // THE frame step of run_frames / run_frames_streamed / run_frames_replay: frame f of a call over [f0, f1) for slice s, inputs
   // in staging set `staged` of the upload ring, or resident (IN_RESIDENT), or expanded by the replay (IN_REPLAY)
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
-  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr) = 0;
+  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr) = 0;
   virtual int map_log_fault_metrics(int q0, int q1, int f0, double* out) = 0;                  // out [B][8]
   virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
   virtual void apply_settings() = 0;   // the one place where `settings` reaches the kernel argument
@@ -2098,8 +2135,15 @@ struct Batch : BatchCore {
     auto i = [&](int s) { return reinterpret_cast<const int*>(at(s)); };
     return ReplaySeqIn{reinterpret_cast<const double*>(at(SEC_RD)), i(SEC_N), i(SEC_DROP), i(SEC_K), i(SEC_M), i(SEC_OFF), i(SEC_SLOTS), reinterpret_cast<const double*>(at(SEC_OBS))};
   }
-  // (the fault record only while some trajectory has a non-zero probability: otherwise the unfaulted form is launched)
-  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B, rp.faulted ? rp_fault : nullptr}; }
+  // (the fault record only while some trajectory has a non-zero probability, or the timed form runs: otherwise the unfaulted
+  // form is launched)
+  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B, rp.faulted || rp.timed ? rp_fault : nullptr}; }
+  // THE expansion's launch, for the frame loop and the read-backs: the timed form while some timing record is non-zero
+  // (replay_plan.h, TIMING), otherwise the un-timed launch as it always was
+  void replay_launch(const ReplayOut<S>& o, int f, int b0, int nb, hipStream_t q, int* code = nullptr, double* delta = nullptr) {
+    if (rp.timed) launch_replay_expand_timed<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_timing(f), o, f, b0, nb, rp.K(), f_cap, q, m_cap, code, delta);
+    else launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b0, nb, rp.K(), f_cap, rp_maxcell[f], q, m_cap, code);
+  }
   ReplayOut<S> replay_out(unsigned char* blk, int f) const {
     using namespace inputs;
     const FrameLayout L = rp.out_layout(sizeof(S));
@@ -2116,7 +2160,7 @@ struct Batch : BatchCore {
   // slots (each pair null or not); code (or null): per SEQUENCE entry 0 kept, 1 outlier, 2 missed, from the same launch.  Under
   // faults M holds the survivors and slots / obs are in partition order.  Returns the cell's entries.  Nothing of the handle's
   // filters, inputs or logs changes.
-  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr) override {
+  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr) override {
     using namespace inputs;
     if (int rc = guard()) return rc;
     if (int rc = refuse(rp.expand_refusal(f, b))) return rc;
@@ -2132,7 +2176,14 @@ struct Batch : BatchCore {
       HIPCHK(hipMalloc((void**)&rp_scratch, need));
       rp_scratch_bytes = need;
     }
-    const bool coded = code && rp.faulted;                     // (without faults every code is 0: FAULT_KEPT)
+    const bool coded = code && (rp.faulted || rp.timed);       // (without faults every code is 0: FAULT_KEPT)
+    const bool timed = delta && rp.timed;                      // (without timing every delta is 0)
+    if (timed && rp.largest > rp_delta_count) {
+      HIPCHK(hipStreamSynchronize(st));
+      dfree(rp_delta); rp_delta_count = 0;
+      HIPCHK(hipMalloc((void**)&rp_delta, rp.largest * sizeof(double)));
+      rp_delta_count = rp.largest;
+    }
     if (coded && rp.largest > rp_code_count) {
       HIPCHK(hipStreamSynchronize(st));
       dfree(rp_code); rp_code_count = 0;
@@ -2140,7 +2191,7 @@ struct Batch : BatchCore {
       rp_code_count = rp.largest;
     }
     const ReplayOut<S> o = replay_out(rp_scratch, f);
-    launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b, 1, K, f_cap, rp_maxcell[f], st, m_cap, coded ? rp_code : nullptr);
+    replay_launch(o, f, b, 1, st, coded ? rp_code : nullptr, timed ? rp_delta : nullptr);
     HIPCHK(hipGetLastError());
     const size_t base = (size_t)rp.base[(size_t)f * B + b];
     std::vector<S> hr((size_t)K * RD_STRIDE), ho((size_t)2 * std::max(E, 1));
@@ -2150,6 +2201,8 @@ struct Batch : BatchCore {
     if (E) HIPCHK(hipMemcpyAsync(hs.data(), o.slots + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
     if (code) std::fill(code, code + E, (int)msckf_replay::FAULT_KEPT);
     if (coded && E) HIPCHK(hipMemcpyAsync(code, rp_code + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (delta) std::fill(delta, delta + E, 0.0);
+    if (timed && E) HIPCHK(hipMemcpyAsync(delta, rp_delta + base, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[0], o.n + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[1], o.drop + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[2], o.k + b, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2183,7 +2236,7 @@ struct Batch : BatchCore {
     const int* cell_k = cells.k; const int* cell_drop = cells.drop;
     const int K = replay ? rp.K() : sc.lay.K;
     // replay: the slice's trajectories of this frame's block, from the sequences (outside the frame step's own stage timers)
-    if (replay) { stage_begin(11, q); launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_out(rp_blk[hh], f), f, b0, nb, K, f_cap, rp_maxcell[f], q, m_cap); stage_end(11, q); }
+    if (replay) { stage_begin(11, q); replay_launch(replay_out(rp_blk[hh], f), f, b0, nb, q); stage_end(11, q); }
     Dev<S> v = d;
     v.P = s.flipped ? P_spare : d.P; v.ncam_defer = s.pending ? 1 : 0;
     const bool fuse = fuse_frame(f, f1);
@@ -2895,6 +2948,9 @@ int msckf_hip_replay_expand(msckf_hip_handle h, int frame, int b, double* rd, do
 int msckf_hip_replay_expand_ints(msckf_hip_handle h, int frame, int b, int* ints, int* slots, int cap_entries) { if (!h || !ints || !slots) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, ints, slots, cap_entries); }
 int msckf_hip_replay_set_faults(msckf_hip_handle h, const double* fault4) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_faults(fault4); }
 int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* code, int cap_entries) { if (!h || !code) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, code); }
+int msckf_hip_replay_set_timing(msckf_hip_handle h, const double* timing4) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_timing(timing4); }
+int msckf_hip_replay_image_table(msckf_hip_handle h, int seq, double* time, int* frame_of, int* base) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_image_table(seq, time, frame_of, base); }
+int msckf_hip_replay_expand_timing(msckf_hip_handle h, int frame, int b, double* delta, int cap_entries) { if (!h || !delta) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, nullptr, delta); }
 int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_fault_counts(f0, f1, out); }
 int msckf_hip_replay_imu_sums(msckf_hip_handle h, int f0, int f1, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_imu_sums(f0, f1, out); }
 // ---- the track compiler (track_compile.h): host code alone, no handle, no device

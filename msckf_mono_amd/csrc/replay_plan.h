@@ -11,6 +11,8 @@
 //   2. the noise      which pair of which sub-seed a value takes (NOISE and MODEL below), and chol_psd, the factor of Q_imu
 //                     and the faults on top of either model: missed observations and outliers (FAULTS below), the rule on a
 //                     track stated serially (track_faults), the lane group of the faulted expansion
+//                     and the camera's clock: time offset, jitter and rolling shutter (TIMING below), the image table of a
+//                     sequence, the stencil of the shift and its preconditions
 //   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record
 //                     of either model, per frame each trajectory's first entry in the expanded block and the block's size, the
 //                     largest expanded frame, and every refusal with its code and text
@@ -20,6 +22,8 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <string>
 #include <vector>
 
 #include "host_lists.h"
@@ -148,6 +152,39 @@ enum FaultMetric { FM_RECORDS, FM_CLEAN_PASS, FM_CLEAN_REJ, FM_CONT_PASS, FM_CON
 // rounded to the handle's scalar, widened to double -- summed in double: the count, omega, a, dT.  Sums and counts: ranges add.
 enum ImuSum { IS_COUNT = 0, IS_OMEGA = 1, IS_A = 4, IS_DT = 7, IMU_SUM_ROW = 8 };
 
+// ---- 2e. TIMING: camera time offset, per-image timestamp jitter and rolling-shutter readout (msckf_hip_replay_set_timing;
+// normative, the header, DESIGN section 4.13 and the twin state the same).  Independent of the noise model and of the faults.
+// Trajectory b has timing4[b] = (t_d, r_y, y_0, sigma_j): the offset [s], the readout slope [s per unit of normalised image y],
+// the image row exposed at the image's stamp, the jitter [s]; all finite, sigma_j >= 0.  A record is non-zero when t_d, r_y or
+// sigma_j is (y_0 alone moves nothing).
+//   image table  of a sequence, built at commit from its cells alone.  Frames in order with T = 0 (double), ord = 0, W = 0: a
+//                skipped cell changes nothing; any other cell adds its dT_i, i < k ascending, to T, sets ord += 1, W += 1,
+//                records time[ord - 1] = T, frame_of[ord - 1] = f, base(f) = ord - W, then sets W -= n_drop(f).  Camera slot s
+//                of frame f's cell is image base(f) + s: the window an empty start at frame 0 gives (a suffix of the images).
+//   exposure     entry l of a track has the sequence value (x_l, y_l) and camera image i_l = base(f) + slot_l; it was exposed at
+//                time[i_l] + delta_l, delta_l = (t_d + r_y (y_l - y_0)) + sigma_j g(frame_of[i_l]): the difference, the product,
+//                the sum, the product sigma_j g, the sum, each rounded in double.  g(q) is the first component of
+//                pair(mix(s_b, 2^63 + 2), q): one draw per image and seed, shared by every observation of that image in
+//                whichever cell it surfaces (sigma_j == 0: no draw, the term is 0).
+//   shift        along the entry's own track, nodes in sequence order: M = 1 unchanged; M = 2 both entries; M >= 3 the entries
+//                l0, l0 + 1, l0 + 2 with l0 = min(max(l - 1, 0), M - 3).  d_j = time[i_j] - time[i_l];
+//                w_j = prod_{m != j} (delta_l - d_m) / prod_{m != j} (d_j - d_m), m ascending, numerator and denominator each a
+//                product (three nodes) or a single difference (two), then one division; the new value is sum_j w_j (x_j, y_j),
+//                j ascending, the first product, then each further product added.  + - x / only, each rounded in double, no
+//                contraction.  delta_l == 0 exactly: the value itself, no arithmetic.
+//   then         the Gaussian pixel noise and the outlier ring are added to the shifted value exactly as without timing; a
+//                missed observation still serves its neighbours as a node; draws stay indexed by the sequence entry.
+//   refused      while some record is non-zero (set_timing on committed cells, commit under a non-zero record), with the
+//                sequence, frame and track named: a cell that names a slot >= W(f); a track whose slots do not ascend
+//                strictly; a track whose node times do not increase strictly.
+// With no record, or every record zero, the expansion launched is the un-timed one.
+constexpr uint64_t TIMING_STREAM = 0x8000000000000002ull;   // 2^63 + 2
+constexpr uint64_t timing_seed(uint64_t s) { return mix(s, TIMING_STREAM); }
+enum Timing { TIM_TD, TIM_RY, TIM_Y0, TIM_SIGMA_J, N_TIMING };
+// the stencil of entry l of a track of M entries: its node count and its first node
+constexpr int stencil_nodes(int M) { return M < 3 ? M : 3; }
+constexpr int stencil_first(int l, int M) { return M < 3 ? 0 : (l - 1 < 0 ? 0 : l - 1 > M - 3 ? M - 3 : l - 1); }
+
 // ---- 3. the plan
 using msckf_inputs::FrameLayout;
 using msckf_inputs::Refusal;
@@ -173,6 +210,13 @@ struct Plan {
   // the fault record (FAULTS above): [B][N_FAULT], empty: none set; faulted: some trajectory has a non-zero probability;
   // faults_uploaded: the caller's device copy is this record (set by the caller, cleared here)
   std::vector<double> fault; bool faulted = false, faults_uploaded = false;
+  // the timing record (TIMING above): [B][N_TIMING], empty: none set; timed: some trajectory's record is non-zero;
+  // timing_uploaded as faults_uploaded.  The image tables, built by commit(): per sequence img_n[s] images with
+  // img_time / img_frame [S][frames] (row s, the first img_n[s] filled) and per cell img_base / img_W [frames][S]
+  // (W: the window the cell's slots index, after the frame's own image joined it)
+  std::vector<double> timing; bool timed = false, timing_uploaded = false;
+  std::vector<double> img_time; std::vector<int> img_frame, img_base, img_W, img_n;
+  std::string timing_why;            // the text of the last timing_precondition() refusal
 
   int frames() const { return seq.frames; }
   int K() const { return seq.lay.K; }
@@ -193,6 +237,8 @@ struct Plan {
     committed = assigned = planned = walk_planned = false; model = MODEL_SIGMA4;
     seq_of.clear(); seed.clear(); sigma.clear(); L.clear(); scale.clear(); sigma_uv.clear(); base.clear(); nf.clear(); largest = 0;
     fault.clear(); faulted = faults_uploaded = false;
+    timing.clear(); timed = timing_uploaded = false;
+    img_time.clear(); img_frame.clear(); img_base.clear(); img_W.clear(); img_n.clear();
   }
   // the rules of one sequence cell, in scenario_set_cell's order: its place, the work-list rules, the drop, the cell rule, the readings
   Refusal cell_refusal(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, int n_drop, int flags, int m_cap, int n_cap) const {
@@ -216,7 +262,57 @@ struct Plan {
   // unless an expanded one does, which index_trajectories refuses)
   Refusal commit() {
     if (!seq.index()) return {-E2BIG, "a frame's sequence work-lists exceed 2^31 observations"};
+    build_image_table();
+    if (timed) if (const Refusal r = timing_precondition(); r.code) return r;
     committed = true; planned = walk_planned = false;
+    return {0, nullptr};
+  }
+  // the image table of every sequence (TIMING), a pure function of the cells
+  void build_image_table() {
+    using namespace msckf_inputs;
+    const int F = seq.frames, K_ = K();
+    img_time.assign((size_t)S * F, 0.0); img_frame.assign((size_t)S * F, 0); img_base.assign((size_t)F * S, 0); img_W.assign((size_t)F * S, 0); img_n.assign(S, 0);
+    const double* rd = reinterpret_cast<const double*>(seq.fixed[SEC_RD].data());
+    for (int s = 0; s < S; ++s) {
+      double T = 0.0;
+      int ord = 0, W = 0;
+      for (int f = 0; f < F; ++f) {
+        const size_t c = cell(f, s);
+        const int k = seq.ints(SEC_K)[c];
+        if (k != NO_IMAGE) {
+          for (int i = 0; i < k; ++i) T += rd[(c * K_ + i) * RD_ROW + 6];
+          ++ord; ++W;
+          img_time[(size_t)s * F + ord - 1] = T; img_frame[(size_t)s * F + ord - 1] = f;
+        }
+        img_base[c] = ord - W; img_W[c] = k != NO_IMAGE ? W : 0;
+        if (k != NO_IMAGE) W -= seq.ints(SEC_DROP)[c];
+      }
+      img_n[s] = ord;
+    }
+  }
+  // what the shift asks of the committed cells (TIMING, refused), in this order per sequence, frame and track
+  Refusal timing_precondition() {
+    using namespace msckf_inputs;
+    const int F = seq.frames;
+    auto refuse = [&](const char* what, int s, int f, int t) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "timing: sequence %d, frame %d, track %d: %s", s, f, t, what);
+      timing_why = buf;
+      return Refusal{-EINVAL, timing_why.c_str()};
+    };
+    for (int s = 0; s < S; ++s) for (int f = 0; f < F; ++f) {
+      const size_t c = cell(f, s);
+      const int n = seq.ints(SEC_N)[c], base_ = img_base[c], W = img_W[c];
+      const int* sl = seq.slots[c].data();
+      const double* tm = img_time.data() + (size_t)s * F;
+      for (int t = 0, o = 0; t < n; ++t) {
+        const int M = seq.ints(SEC_M)[c * f_cap + t];
+        for (int l = 0; l < M; ++l) if (sl[o + l] < 0 || sl[o + l] >= W) return refuse("a camera slot beyond the window an empty start gives", s, f, t);
+        for (int l = 1; l < M; ++l) if (sl[o + l] <= sl[o + l - 1]) return refuse("camera slots do not ascend strictly", s, f, t);
+        for (int l = 1; l < M; ++l) if (!(tm[base_ + sl[o + l]] > tm[base_ + sl[o + l - 1]])) return refuse("node times do not increase strictly", s, f, t);
+        o += M;
+      }
+    }
     return {0, nullptr};
   }
 
@@ -262,6 +358,27 @@ struct Plan {
     faulted = false;
     for (size_t b = 0; b * N_FAULT < fault.size(); ++b) faulted = faulted || fault[b * N_FAULT + FLT_P_MISS] > 0.0 || fault[b * N_FAULT + FLT_P_OUT] > 0.0;
     faults_uploaded = false;
+  }
+  // the timing record (TIMING), timing4 [B][N_TIMING] or null for none, in this order: the replay, every value finite, the
+  // jitter, and -- on committed cells under a non-zero record -- the preconditions of the shift
+  static bool nonzero_timing(const double* timing4, int B_) {
+    for (int b = 0; timing4 && b < B_; ++b) if (timing4[b * N_TIMING + TIM_TD] != 0.0 || timing4[b * N_TIMING + TIM_RY] != 0.0 || timing4[b * N_TIMING + TIM_SIGMA_J] != 0.0) return true;
+    return false;
+  }
+  Refusal timing_refusal(const double* timing4) {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    if (!timing4) return {0, nullptr};
+    for (int i = 0; i < B * N_TIMING; ++i) if (!std::isfinite(timing4[i])) return {-EINVAL, "timing values must be finite"};
+    for (int b = 0; b < B; ++b) if (timing4[b * N_TIMING + TIM_SIGMA_J] < 0.0) return {-EINVAL, "jitter must not be negative"};
+    if (committed && nonzero_timing(timing4, B)) return timing_precondition();
+    return {0, nullptr};
+  }
+  // independent of the assignment, the faults and the cells: it stays through assign, assign_q, set_faults and commit, and
+  // alloc() clears it
+  void set_timing(const double* timing4) {
+    if (timing4) timing.assign(timing4, timing4 + (size_t)B * N_TIMING); else timing.clear();
+    timed = nonzero_timing(timing.empty() ? nullptr : timing.data(), B);
+    timing_uploaded = false;
   }
 
   // -- a run

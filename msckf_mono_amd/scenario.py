@@ -362,6 +362,125 @@ def replay_model_expand_faulted(seq_traj, frame, seed, L, scale, sigma_uv, fault
     return (rd,) + _replay_faulted(frame, seed, fr["M"], fr["slots"], obs, fault4)
 
 
+# ---- the camera's clock (csrc/replay_plan.h, TIMING; include/msckf_hip.h, msckf_hip_replay_set_timing): time offset, per-image
+# jitter and rolling-shutter readout per trajectory, timing4 = (t_d, r_y, y_0, sigma_j), on top of either noise model and of the
+# faults.  Every operation below is one rounded double operation in the header's order: given the same delta the device's bits
+# are these.
+REPLAY_TIMING_STREAM = (1 << 63) + 2
+
+
+def replay_image_table(cells):
+    """the image table of a sequence: (time [images], frame_of [images], base [frames]).  cells: a noise-free Trajectory (its
+    frames drop one state once the window is full), or per frame None (a skipped cell) or (readings [k][7], n_drop).  T = 0,
+    ord = 0, W = 0; every cell that is not skipped adds its dT in order to T, then ord += 1, W += 1, time[ord - 1] = T,
+    frame_of[ord - 1] = f, base[f] = ord - W, W -= n_drop; camera slot s of frame f's cell is image base[f] + s"""
+    if hasattr(cells, "imu_for_frame"):
+        tr = cells
+        cells = [(tr.imu_for_frame(f), 1 if tr.frames[f]["Nw"] == tr.N else 0) for f in range(tr.n_frames)]
+    T, ord_, W = np.float64(0.0), 0, 0
+    time, frame_of, base = [], [], np.zeros(len(cells), dtype=np.int32)
+    for f, c in enumerate(cells):
+        if c is not None:
+            for dT in np.asarray(c[0], dtype=np.float64).reshape(-1, 7)[:, 6]:
+                T = T + dT
+            ord_ += 1
+            W += 1
+            time.append(T)
+            frame_of.append(f)
+        base[f] = ord_ - W
+        if c is not None:
+            W -= int(c[1])
+    return np.array(time, dtype=np.float64), np.array(frame_of, dtype=np.int32), base
+
+
+def replay_timing_jitter(seed, image_frames):
+    """g(q) for the frames q of some images: the first component of pair q of the sub-seed mix(seed, 2^63 + 2)"""
+    s = int(replay_mix(seed, REPLAY_TIMING_STREAM))
+    q = np.asarray(image_frames, dtype=np.uint64)
+    u1 = 1.0 - replay_uniform(s, np.uint64(2) * q)
+    u2 = replay_uniform(s, np.uint64(2) * q + np.uint64(1))
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2 * np.pi * u2)
+
+
+def replay_timing_delta(y, image_frames, seed, timing4):
+    """delta [n] of entries with sequence values y [n] on images taken at the frames image_frames [n] (frame_of[base + slot]):
+    (t_d + r_y (y - y_0)) + sigma_j g(frame); sigma_j == 0: no draw"""
+    t_d, r_y, y_0, s_j = (np.float64(x) for x in timing4)
+    y = np.asarray(y, dtype=np.float64)
+    g = replay_timing_jitter(seed, image_frames) if s_j != 0.0 else np.zeros(len(y))
+    return (t_d + r_y * (y - y_0)) + s_j * g
+
+
+def replay_timing_stencil(l, M):
+    """(first node, node count) of entry l of a track of M entries: M < 3 the whole track, else l0 = min(max(l - 1, 0), M - 3)"""
+    return (0, M) if M < 3 else (min(max(l - 1, 0), M - 3), 3)
+
+
+def replay_timing_shift(M, slots, obs, time, base_f, delta, stencil=replay_timing_stencil):
+    """the cell's coordinates [n][2] with every entry moved along its own track to time[base_f + slot] + delta: Lagrange weights
+    over the stencil's nodes, times taken relative to the entry's own; delta == 0 and tracks of one entry: the value itself"""
+    ob = np.asarray(obs, dtype=np.float64).reshape(-1, 2)
+    out = ob.copy()
+    tm = np.asarray(time, dtype=np.float64)[int(base_f) + np.asarray(slots, dtype=np.int64)] if len(ob) else np.zeros(0)
+    delta = np.asarray(delta, dtype=np.float64)
+    o = 0
+    for m in (int(x) for x in M):
+        for l in range(m):
+            dl = delta[o + l]
+            l0, n = stencil(l, m)
+            if n < 2 or dl == 0.0:
+                continue
+            d = [tm[o + l0 + j] - tm[o + l] for j in range(n)]
+            acc = None
+            for j in range(n):
+                others = [i for i in range(n) if i != j]
+                num, den = dl - d[others[0]], d[j] - d[others[0]]
+                for i in others[1:]:
+                    num, den = num * (dl - d[i]), den * (d[j] - d[i])
+                p = (num / den) * ob[o + l0 + j]
+                acc = p if acc is None else acc + p
+            out[o + l] = acc
+        o += m
+    assert o == len(ob)
+    return out
+
+
+def _replay_timed_obs(seq_traj, frame, seed, timing4, delta, table):
+    fr = seq_traj.frames[frame]
+    time, frame_of, base = replay_image_table(seq_traj) if table is None else table
+    if delta is None:
+        delta = replay_timing_delta(fr["obs"][:, 1], frame_of[base[frame] + fr["slots"]], seed, timing4) if len(fr["obs"]) else np.zeros(0)
+    return replay_timing_shift(fr["M"], fr["slots"], fr["obs"], time, base[frame], delta)
+
+
+def replay_expand_timed(seq_traj, frame, seed, sigma4, timing4, delta=None, table=None):
+    """replay_expand under the timing record: every coordinate moved along its track before the noise is added.  delta [n]: the
+    entries' deltas when they are known (the device's), else replay_timing_delta's; table: replay_image_table(seq_traj)"""
+    return replay_cell(seq_traj.imu_for_frame(frame), _replay_timed_obs(seq_traj, frame, seed, timing4, delta, table), frame, seed, sigma4)
+
+
+def replay_model_expand_timed(seq_traj, frame, seed, L, scale, sigma_uv, timing4, w_start=None, delta=None, table=None):
+    """replay_model_expand under the timing record"""
+    if w_start is None:
+        w_start = replay_walk(seq_traj, seed, L, scale)[frame]
+    obs = _replay_timed_obs(seq_traj, frame, seed, timing4, delta, table)
+    return replay_model_cell(seq_traj.imu_for_frame(frame), obs, frame, seed, L, scale, sigma_uv, w_start)[:2]
+
+
+def replay_expand_timed_faulted(seq_traj, frame, seed, sigma4, timing4, fault4, delta=None, table=None):
+    """replay_expand_timed with faults: (readings, M', slots, obs, code) in the expanded block's partition order"""
+    rd, obs = replay_expand_timed(seq_traj, frame, seed, sigma4, timing4, delta, table)
+    fr = seq_traj.frames[frame]
+    return (rd,) + _replay_faulted(frame, seed, fr["M"], fr["slots"], obs, fault4)
+
+
+def replay_model_expand_timed_faulted(seq_traj, frame, seed, L, scale, sigma_uv, timing4, fault4, w_start=None, delta=None, table=None):
+    """replay_model_expand_timed with faults: (readings, M', slots, obs, code) in the expanded block's partition order"""
+    rd, obs = replay_model_expand_timed(seq_traj, frame, seed, L, scale, sigma_uv, timing4, w_start, delta, table)
+    fr = seq_traj.frames[frame]
+    return (rd,) + _replay_faulted(frame, seed, fr["M"], fr["slots"], obs, fault4)
+
+
 def replay_fault_counts(cells_M, seed, fault4, f0=0, f1=None):
     """msckf_hip_replay_fault_counts for one trajectory: cells_M[f] the track lengths of its sequence's cell on frame f (None or
     empty: no track); int64 [6] = entries, missed, outliers, tracks, tracks that lost an observation, tracks with an outlier"""
