@@ -395,6 +395,52 @@ int msckf_hip_map_log_fault_metrics(msckf_hip_handle h, int q0, int q1, int f0, 
  * needs (mean omega = the gyro bias, mean a = the attitude against gravity and the accelerometer bias), from samples that
  * exist only on the device.  Nothing of the handle's filters, inputs or logs changes. */
 int msckf_hip_replay_imu_sums(msckf_hip_handle h, int f0, int f1, double* out /*[B][8]*/);
+/* Calibration errors of the sensors, on top of either noise model, the faults and the timing (csrc/replay_plan.h, CALIB: the
+ * arithmetic below is that file's inline functions calib_imu, calib_out and calib_cam, which the kernels compile).
+ * The IMU record imucal[b] = [31]: T_g (0 .. 8, 3 x 3 row-major), T_a (9 .. 17), G (18 .. 26, the gyro's response to specific
+ * force, rad/s per m/s^2), sat_g, sat_a (27, 28; 0: no saturation), lsb_g, lsb_a (29, 30; 0: no quantisation).  The identity
+ * record is T_g = T_a = I and everything else 0; a record is non-trivial when it differs from that.  The matrices act on the
+ * sequence's values, constant bias included: the cell holds omega + b_0 and a + b_0, and the shift (T - I) b_0 is a bias the
+ * filter estimates anyway.
+ *   sample i < k of a cell that is not skipped, v_g = cell[0:3], v_a = cell[3:6]: c_a[r] = sum_c T_a[r][c] v_a[c] and
+ *     c_g[r] = sum_c T_g[r][c] v_g[c], the first product, then each further product added, c ascending; for the gyro then
+ *     + G[r][0] v_a[0], + G[r][1] v_a[1], + G[r][2] v_a[2] in that order; every product and sum rounded in double.
+ *   c takes the place of the sequence value in the noise rule: c + sigma g under sigma4, (c + W(f, i)) + n under the Q_imu
+ *     model (no n when dT_i <= 0).  The bias walk stays an output bias: the walk table does not change.
+ *   saturation where sat > 0: x = min(max(x, -sat), sat); a component is CLIPPED when its value before the clamp lies strictly
+ *     outside [-sat, sat].  Quantisation where lsb > 0: x = lsb rint(x / lsb), the quotient rounded, rint to nearest even, then
+ *     the product.  The result is rounded once to the handle's scalar.  dT, rows from k on and skipped cells are untouched.
+ * -EINVAL, in this order: "no replay allocated", "calibration values must be finite", "saturation and quantisation must not be
+ * negative"; a refused call leaves the previous record in force.  May be called between runs; survives msckf_hip_replay_assign,
+ * _assign_q, _set_faults, _set_timing and _commit; msckf_hip_replay_alloc clears it.  msckf_hip_replay_imu_sums sums the
+ * calibrated rows: a per-seed stand-still initialisation sees the scale and g-sensitivity error as it would on a real unit. */
+int msckf_hip_replay_set_imu_calib(msckf_hip_handle h, const double* imucal /*[B][31], NULL: none*/);
+/* The camera record camcal[b] = (e_u, e_v, d_u, d_v, k1, k2, p1, p2): the residual map, in normalised coordinates, between the
+ * true camera and the calibration the front end undistorted with -- e the relative focal-length error, d the principal-point
+ * error divided by the focal length, k and p the residual radial-tangential coefficients; all finite, all zero is trivial.
+ * It applies to an entry's value (x, y): the sequence value, or what the timing shift made of it (delta keeps the sequence's y):
+ *   xx = x x, yy = y y, xy = x y, r2 = xx + yy, rad = (1 + k1 r2) + k2 (r2 r2)
+ *   xd = (x rad + (2 p1) xy) + p2 (r2 + 2 xx),  yd = (y rad + p1 (r2 + 2 yy)) + (2 p2) xy
+ *   x' = (xd + e_u xd) + d_u,                   y' = (yd + e_v yd) + d_v
+ * + - x only, each rounded in double, no contraction.  The Gaussian pixel noise and the outlier ring are then added to (x', y')
+ * exactly as before; draws stay indexed by the sequence entry, so a seed's noise and faults do not depend on its calibration;
+ * missed entries are mapped too.  -EINVAL, in this order: "no replay allocated", "calibration values must be finite".
+ * Lifetime as the IMU record's.  While neither record is non-trivial for any trajectory, the kernels launched and every bit
+ * they write are those without calibration; otherwise msckf_hip_replay_expand / _ints / _faults / _timing return what the
+ * calibrated kernel wrote. */
+int msckf_hip_replay_set_cam_calib(msckf_hip_handle h, const double* camcal /*[B][8], NULL: none*/);
+/* From the same single-trajectory launch as msckf_hip_replay_expand, each pointer or NULL: rd_cal, the noise-free calibrated c
+ * of every sample in double (rows from k on: the sequence's); clip, per sample the 6-bit mask of clipped components (bit c:
+ * column c of the row; the noise is part of the clipped value); obs_cal, the mapped noise-free (x', y') per SEQUENCE entry.
+ * Without records c and (x', y') are the sequence's (shifted) values and clip is 0.  Returns the cell's entries; -E2BIG when
+ * they exceed cap_entries. */
+int msckf_hip_replay_expand_calib(msckf_hip_handle h, int frame, int b, double* rd_cal /*[K][6]*/, int* clip /*[K]*/, double* obs_cal /*[entries][2]*/, int cap_entries);
+/* The saturation of the frames [f0, f1) per trajectory, counted on the device without a run: the stored values are recomputed
+ * from the sequences, the assignment and the IMU record.  out [B][8] = 0 samples (i < k of the non-skipped cells), 1-3 gyro
+ * x, y, z clipped, 4-6 accelerometer x, y, z clipped, 7 samples with any component clipped.  Integers; ranges add.  One
+ * wavefront per trajectory, a fixed order and a fixed tree, as msckf_hip_replay_imu_sums.  Refusals as
+ * msckf_hip_run_frames_replay.  Nothing of the handle's filters, inputs or logs changes. */
+int msckf_hip_replay_calib_counts(msckf_hip_handle h, int f0, int f1, long long* out /*[B][8]*/);
 /* ---- the track compiler: a recorded feature-id stream into the cells of the frame loops (host code, no device) -------- */
 /* The frame loops take positional work-lists per frame, (M, slots, obs2, n_drop); a recording is an id stream, the tracked and
  * the new features of every image.  Without pruneRedundantStates the bookkeeping that turns one into the other -- update(),

@@ -47,6 +47,7 @@ SYMBOLS = [
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
     "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
     "msckf_hip_compile_create", "msckf_hip_compile_destroy", "msckf_hip_compile_image", "msckf_hip_compile_cell", "msckf_hip_replay_imu_sums",
+    "msckf_hip_replay_set_imu_calib", "msckf_hip_replay_set_cam_calib", "msckf_hip_replay_expand_calib", "msckf_hip_replay_calib_counts",
 ]
 CELL_SKIP = 1   # msckf_hip_scenario_set_cell's flag bit MSCKF_HIP_CELL_SKIP
 
@@ -506,6 +507,43 @@ class Batch:
         f1 = self._replay_frames if f1 is None else int(f1)
         out = np.zeros((self.B, IMU_SUM_STRIDE))
         _chk(self.L.msckf_hip_replay_imu_sums(self.h, int(f0), f1, out.ctypes.data_as(_dp)))
+        return out
+
+    def replay_set_imu_calib(self, imucal):
+        """IMU calibration errors (include/msckf_hip.h): per trajectory the record [31] = T_g (9, row-major), T_a (9), G (9), sat_g,
+        sat_a, lsb_g, lsb_a (scenario.imu_calib_record builds one); one row serves every trajectory; None: no record.  Stays
+        through replay_assign, replay_assign_q, replay_set_faults, replay_set_timing and replay_commit."""
+        if imucal is None:
+            _chk(self.L.msckf_hip_replay_set_imu_calib(self.h, None))
+            return
+        ic = np.ascontiguousarray(np.broadcast_to(np.asarray(imucal, dtype=np.float64), (self.B, 31)))
+        _chk(self.L.msckf_hip_replay_set_imu_calib(self.h, ic.ctypes.data_as(_dp)))
+
+    def replay_set_cam_calib(self, camcal):
+        """camera calibration errors (include/msckf_hip.h): per trajectory (e_u, e_v, d_u, d_v, k1, k2, p1, p2), the residual map
+        in normalised coordinates (scenario.cam_calib_record / cam_calib_from_intrinsics build one); one row serves every
+        trajectory; None: no record.  Lifetime as replay_set_imu_calib's."""
+        if camcal is None:
+            _chk(self.L.msckf_hip_replay_set_cam_calib(self.h, None))
+            return
+        cc = np.ascontiguousarray(np.broadcast_to(np.asarray(camcal, dtype=np.float64), (self.B, 8)))
+        _chk(self.L.msckf_hip_replay_set_cam_calib(self.h, cc.ctypes.data_as(_dp)))
+
+    def replay_expand_calib(self, frame, b):
+        """from the expansion's own launch for trajectory b on `frame`: dict of rd_cal [K][6] (the noise-free calibrated samples, in
+        double), clip [K] (6-bit masks of clipped components), obs_cal [entries][2] (the mapped noise-free coordinates per
+        sequence entry)"""
+        cap = self.f_cap * self.m_cap
+        rd_cal = np.zeros((self._replay_K, 6)); clip = np.zeros(self._replay_K, dtype=np.int32); obs_cal = np.zeros((cap, 2))
+        n = _chk(self.L.msckf_hip_replay_expand_calib(self.h, int(frame), int(b), rd_cal.ctypes.data_as(_dp), clip.ctypes.data_as(_ip), obs_cal.ctypes.data_as(_dp), cap))
+        return dict(rd_cal=rd_cal, clip=clip, obs_cal=obs_cal[:n])
+
+    def replay_calib_counts(self, f0=0, f1=None):
+        """the saturation of the frames [f0, f1) (default: all) per trajectory, counted on the device without a run: int64 [B][8] =
+        samples, gyro x y z clipped, accelerometer x y z clipped, samples with any component clipped"""
+        f1 = self._replay_frames if f1 is None else int(f1)
+        out = np.zeros((self.B, 8), dtype=np.int64)
+        _chk(self.L.msckf_hip_replay_calib_counts(self.h, int(f0), f1, out.ctypes.data_as(C.POINTER(C.c_longlong))))
         return out
 
     def replay_standstill(self, f0, f1):

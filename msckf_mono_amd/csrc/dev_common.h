@@ -616,7 +616,19 @@ void launch_replay_walk_scan(const double* rd, const int* k, const ReplayTrajIn&
 // msckf_hip_replay_imu_sums: per trajectory the count, the six summed scalars and the summed dT (replay_plan.h, ImuSum: out [B][8])
 // of the IMU samples the expansion hands its propagate over the frames [f0, f1), each rounded to the handle's scalar as the
 // expansion stores it; rd / k as for the walk scan, m.wstart the walk table from row 0 (m.L == nullptr: the sigma4 model)
-void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st);
+// imucal (or null): the IMU calibration record [B][31] (replay_plan.h, CALIB): the calibrated rows are summed
+void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st, const double* imucal = nullptr);
+// The calibrated form (replay_plan.h, CALIB): the timed form's lane groups with the camera's residual map between the shift and
+// the noise, and the IMU items under the calibration rule.  c: the records imucal[B][31] and camcal[B][8] (identity / zeros
+// where none is set, never null), timed: a timing record is in force (false: tm is not read, every delta is 0), and the
+// read-back's outputs, each or null and for a launch of one trajectory (nb == 1) only: rd_cal[K][6] the noise-free calibrated
+// values, clip[K][6] 1 where the component was clipped, obs_cal[entries][2] at base[b] + the entry's index in the sequence cell.
+// t.fault is not null (zeros: no faults).
+struct ReplayCalibIn { const double* imu; const double* cam; bool timed; double* rd_cal; int* clip; double* obs_cal; };
+template <class S> void launch_replay_expand_calib(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayCalibIn& c, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, hipStream_t st, int m_cap, int* code = nullptr, double* delta = nullptr);
+// msckf_hip_replay_calib_counts: per trajectory the samples of the frames [f0, f1) and how many of them the saturation clipped,
+// out[B][8] (replay_plan.h, CalibCount), recomputed as the expansion stores them; rd / k / m as for the sums, imucal not null
+void launch_replay_calib_counts(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, const double* imucal, int f0, int f1, int S, int K, int B, long long* out, hipStream_t st);
 // one-time per-device setup of each kernel file (constant tables, dynamic-LDS limits); msckf_hip_create calls them
 void feature_device_setup();
 void qr_device_setup();

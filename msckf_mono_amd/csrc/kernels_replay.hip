@@ -29,6 +29,12 @@
 // With a non-zero timing record (replay_plan.h, TIMING) k_replay_expand_timed runs in place of either: the faulted form's lane
 // groups, where each lane first moves its entry along the track to the time the pixel was exposed -- the stencil's neighbours come
 // from the lanes of its group -- and then goes through the same entry_obs.  The two forms above are not touched by it.
+//
+// With a non-trivial calibration record (replay_plan.h, CALIB) k_replay_expand_calib runs in place of all three: the timed form's
+// lane groups with the camera's residual map between the shift and entry_obs, the IMU pair items under the calibration rule
+// (model_imu's CAL instantiation under the Q_imu model), with or without faults and timing.  k_replay_imu_sums has a CAL
+// instantiation that sums the calibrated rows, and k_replay_calib_counts counts the clipped components of a frame range from
+// the same device function (sample_stored).  The arithmetic of the records is replay_plan.h's inline functions.
 #include <type_traits>
 
 #include "dev_common.h"
@@ -112,8 +118,11 @@ __device__ __forceinline__ void model_prefix(const double* rd, uint64_t s_imu, c
 //   4. lane j stores scalar j % 6 of sample j / 6: (value + W(f, i)) + noise; rows from k on are the sequence's
 // Every sum is the normative one (replay_plan.h): who forms it changes, its order does not.
 constexpr int MODEL_TILE = 32;
-template <class S>
-__device__ __forceinline__ void model_imu(const double* cell, S* out, const double* L, double scale, const double* wstart, uint64_t s_imu, int K, int k) {
+// CAL (replay_plan.h, CALIB; the calibrated expansion's instantiation): step 4's lane forms its own component of the calibrated
+// row from the sample's six values, puts it in the value's place and passes the sum through saturation and quantisation;
+// rd_cal / clip (or null): the read-back's noise-free calibrated values and clipped components, [K][6] each.
+template <class S, bool CAL = false>
+__device__ __forceinline__ void model_imu(const double* cell, S* out, const double* L, double scale, const double* wstart, uint64_t s_imu, int K, int k, const double* ic = nullptr, double* rd_cal = nullptr, int* clip = nullptr) {
 #pragma clang fp contract(off)
   __shared__ double z[MODEL_TILE][rp::NQ], w[MODEL_TILE][rp::NQ], W[MODEL_TILE][rp::WALK_ROW], P[rp::WALK_ROW];
   const int lane = (int)threadIdx.x;
@@ -149,7 +158,16 @@ __device__ __forceinline__ void model_imu(const double* cell, S* out, const doub
       const int i = j / rp::WALK_ROW, c = j % rp::WALK_ROW;
       const double* rd = cell + (i0 + i) * RD_STRIDE;
       double v = rd[c];
-      if (i < n) v = model_stored(v, W[i][c], scale, w[i][c < 3 ? c : 3 + c], rd[6]);   // n_g: rows 0 .. 2, n_a: rows 6 .. 8
+      if constexpr (CAL) {
+        bool cl = false;
+        if (i < n) {
+          v = rp::calib_imu(ic, rd, c);
+          const double cv = v;
+          v = rp::calib_out(ic, c, model_stored(v, W[i][c], scale, w[i][c < 3 ? c : 3 + c], rd[6]), &cl);
+          if (rd_cal) rd_cal[(i0 + i) * 6 + c] = cv;
+        } else if (rd_cal) rd_cal[(i0 + i) * 6 + c] = v;
+        if (clip) clip[(i0 + i) * 6 + c] = cl ? 1 : 0;
+      } else if (i < n) v = model_stored(v, W[i][c], scale, w[i][c < 3 ? c : 3 + c], rd[6]);   // n_g: rows 0 .. 2, n_a: rows 6 .. 8
       out[(i0 + i) * RD_STRIDE + c] = (S)v;
     }
     __syncthreads();                                                   // the next tile overwrites z, w and W
@@ -429,6 +447,132 @@ void launch_replay_expand_timed(const ReplaySeqIn& q, const ReplayTrajIn& t, con
 template void launch_replay_expand_timed<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayOut<float>&, int, int, int, int, int, hipStream_t, int, int*, double*);
 template void launch_replay_expand_timed<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayOut<double>&, int, int, int, int, int, hipStream_t, int, int*, double*);
 
+// The calibrated form (replay_plan.h, CALIB): k_replay_expand_timed's items and lane groups, with the camera's residual map
+// (rp::calib_cam) between the shift and entry_obs, and the IMU items under the calibration rule -- in the sigma4 form an item
+// still owns one pair of columns of one sample and reads the sample's six values (rp::calib_imu for its two components, the
+// noise of its pair, rp::calib_out); under the Q_imu model model_imu's CAL instantiation.  It runs whenever some trajectory's
+// calibration record is non-trivial, with or without faults and timing: zero fault records mean all survive in sequence order,
+// and with c.timed false no image table is consulted and every delta is 0 exactly -- the value itself.
+// c.rd_cal / c.clip / c.obs_cal (null in the frame loop): the read-back's, for a launch of one trajectory.
+// No LDS in the track items, no atomics, no exchange between wavefronts.
+template <class S, bool MODEL, int G>
+__global__ __launch_bounds__(REPLAY_CHUNK) void k_replay_expand_calib(ReplaySeqIn q, ReplayTrajIn t, ReplayModelIn m, ReplayTimingIn tm, ReplayCalibIn cal, ReplayOut<S> o, int* code, double* delta, int f, int b0, int K, int f_cap) {
+  const int b = b0 + (int)blockIdx.y;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double* sg = t.sigma + (long)b * (MODEL ? 2 : rp::N_SIGMA);
+  const double* flt = t.fault + (long)b * rp::N_FAULT;
+  const double* ic = cal.imu + (long)b * rp::IMU_CAL;
+  const double* cc = cal.cam + (long)b * rp::CAM_CAL;
+  const bool timed = cal.timed;
+  const double* tm4 = timed ? tm.timing + (long)b * rp::N_TIMING : nullptr;
+  const double* times = timed ? tm.time + (long)s * tm.stride : nullptr;
+  const int* frames_of = timed ? tm.frame_of + (long)s * tm.stride : nullptr;
+  const int img0 = timed ? tm.base[s] : 0;
+  const int* Ms = q.M + (long)s * f_cap;
+  const int* offs = q.off + (long)s * f_cap;
+  const int first = offs[0];
+  const int base = t.base[b];
+  const int kc = q.k[s];
+  if constexpr (MODEL) {
+    if (blockIdx.x == 0)
+      model_imu<S, true>(q.rd + (long)s * K * RD_STRIDE, o.rd + (long)b * K * RD_STRIDE, m.L + (long)b * rp::L_SIZE, m.scale[b], m.wstart + (long)b * rp::WALK_ROW, rp::imu_seed(seed, f), K, kc < K ? kc : K,
+                         ic, cal.rd_cal, cal.clip);
+  }
+  const ReplayCell c{s, b, kc, first, base, seed, sg, Ms, offs};
+  const double p_miss = flt[rp::FLT_P_MISS], p_out = flt[rp::FLT_P_OUT];
+  const uint64_t s_flt = rp::fault_seed(seed, f), s_obs = rp::obs_seed(seed, f), s_tim = rp::timing_seed(seed);
+  const int lane = (int)threadIdx.x & 63;
+  const int T = (f_cap * G + 63) & ~63;                                // as in k_replay_expand_faults: `it < T` is the same for a whole wavefront
+  const int dt0 = (MODEL ? 0 : rp::IMU_PAIRS) * K;                     // the IMU pair items of the sigma4 form
+  const int end = T + fixed_items(MODEL, K, f_cap);
+  for (int it = (int)blockIdx.x * REPLAY_CHUNK + (int)threadIdx.x; it < end; it += (int)gridDim.x * REPLAY_CHUNK) {
+    if (it < T) {
+      const int tr = it / G, l = it % G;
+      const int M = tr < f_cap ? Ms[tr] : 0;                           // (M <= m_cap <= G)
+      const bool have = l < M;
+      const int e = have ? offs[tr] - first + l : 0;
+      const int slot = have ? q.slots[(long)first + e] : 0;
+      const double vx = have ? q.obs[2 * (long)(first + e)] : 0.0, vy = have ? q.obs[2 * (long)(first + e) + 1] : 0.0;
+      double z[2] = {vx, vy};
+      double dl = 0.0;
+      if (timed) {                                                     // (uniform over the launch: every lane of the wavefront takes part in the exchange)
+        const double tl = have ? times[img0 + slot] : 0.0;
+        dl = have ? timing_delta(tm4, s_tim, vy, frames_of[img0 + slot]) : 0.0;
+        const int n = rp::stencil_nodes(M), g0 = (lane & ~(G - 1)) + (have ? rp::stencil_first(l, M) : 0);
+        double nx[3], ny[3], nd[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int src = j < n ? g0 + j : lane;
+          nx[j] = __shfl(vx, src, 64); ny[j] = __shfl(vy, src, 64); nd[j] = __shfl(tl, src, 64) - tl;
+        }
+        if (have && n >= 2 && dl != 0.0) timing_shift(n, nd, nx, ny, dl, z);
+      }
+      if (have) rp::calib_cam(cc, z[0], z[1], z);                      // the camera's residual map of the (shifted) value
+      // from here on k_replay_expand_faults, on the mapped value
+      const bool raw = have && p_miss > 0.0 && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e) < p_miss;
+      unsigned long long gm = __ballot(raw ? 1 : 0);
+      if constexpr (G < 64) gm &= ((1ull << G) - 1) << (lane & ~(G - 1));
+      if (M - __popcll(gm) < 2) gm = 0;                                // a track keeps two observations or loses none
+      const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(gm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)gm, 0u));
+      const int surv = M - __popcll(gm);
+      if (have) {
+        const bool miss = (gm >> lane) & 1;
+        const bool out = !miss && p_out > 0.0 && rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 1) < p_out;
+        const long dst = (long)base + (offs[tr] - first) + (miss ? surv + below : l - below);
+        o.slots[dst] = slot;
+        *reinterpret_cast<Vec2<S>*>(o.obs + 2 * dst) = entry_obs<S, MODEL>(z, sg, s_obs, (uint64_t)e, out, out ? rp::U(s_flt, rp::FAULT_DRAWS * (uint64_t)e + 2) : 0.0, flt);
+        if (code) code[(long)base + e] = miss ? rp::FAULT_MISSED : out ? rp::FAULT_OUTLIER : rp::FAULT_KEPT;
+        if (delta) delta[(long)base + e] = dl;
+        if (cal.obs_cal) { cal.obs_cal[2 * ((long)base + e)] = z[0]; cal.obs_cal[2 * ((long)base + e) + 1] = z[1]; }
+      }
+      if (l == 0 && tr < f_cap) o.M[(long)b * f_cap + tr] = surv;
+    } else if (!MODEL && it - T < dt0) {
+      // pair p of sample i under the calibration rule: the row's six values, the two components of the pair
+      const int j = it - T, i = j / rp::IMU_PAIRS, p = j % rp::IMU_PAIRS, c0 = 2 * p;
+      const double* r = q.rd + ((long)s * K + i) * RD_STRIDE;
+      S* w = o.rd + ((long)b * K + i) * RD_STRIDE;
+      double v[2] = {r[c0], r[c0 + 1]}, cv[2] = {r[c0], r[c0 + 1]};
+      bool cl[2] = {false, false};
+      if (i < kc) {
+        double row[6];
+#pragma unroll
+        for (int x = 0; x < 6; ++x) row[x] = r[x];
+        cv[0] = rp::calib_imu(ic, row, c0); cv[1] = rp::calib_imu(ic, row, c0 + 1);
+        const Pair g = box_muller(rp::imu_seed(seed, f), (uint64_t)(rp::IMU_PAIRS * i + p));
+        v[0] = rp::calib_out(ic, c0, noisy(cv[0], sg[c0 < 3 ? rp::SIG_G : rp::SIG_A], g.c), &cl[0]);
+        v[1] = rp::calib_out(ic, c0 + 1, noisy(cv[1], sg[c0 + 1 < 3 ? rp::SIG_G : rp::SIG_A], g.s), &cl[1]);
+      }
+      w[c0] = (S)v[0]; w[c0 + 1] = (S)v[1];
+      if (cal.rd_cal) { cal.rd_cal[i * 6 + c0] = cv[0]; cal.rd_cal[i * 6 + c0 + 1] = cv[1]; }
+      if (cal.clip) { cal.clip[i * 6 + c0] = cl[0] ? 1 : 0; cal.clip[i * 6 + c0 + 1] = cl[1] ? 1 : 0; }
+    } else fixed_item<S, MODEL>(q, o, c, it - T, f, K, f_cap, false);
+  }
+}
+
+template <class S, bool MODEL, int G>
+static void launch_calib(const dim3& grid, hipStream_t st, const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayCalibIn& c, const ReplayOut<S>& o, int* code, double* delta, int f, int b0, int K, int f_cap) {
+  hipLaunchKernelGGL((k_replay_expand_calib<S, MODEL, G>), grid, dim3(REPLAY_CHUNK), 0, st, q, t, m, tm, c, o, code, delta, f, b0, K, f_cap);
+}
+// the faulted form's grid: f_cap tracks of G lanes, G from m_cap
+template <class S>
+void launch_replay_expand_calib(const ReplaySeqIn& q, const ReplayTrajIn& t, const ReplayModelIn& m, const ReplayTimingIn& tm, const ReplayCalibIn& c, const ReplayOut<S>& o, int f, int b0, int nb, int K, int f_cap, hipStream_t st, int m_cap, int* code, double* delta) {
+  if (nb <= 0) return;
+  const bool model = m.L != nullptr;
+  const int G = rp::fault_group(m_cap);
+  const long items = (long)((f_cap * G + 63) & ~63) + fixed_items(model, K, f_cap);
+  const dim3 grid((unsigned)((items + REPLAY_CHUNK - 1) / REPLAY_CHUNK), (unsigned)nb);
+  auto go = [&](auto mdl) {
+    constexpr bool MD = decltype(mdl)::value;
+    if (G == 16) launch_calib<S, MD, 16>(grid, st, q, t, m, tm, c, o, code, delta, f, b0, K, f_cap);
+    else if (G == 32) launch_calib<S, MD, 32>(grid, st, q, t, m, tm, c, o, code, delta, f, b0, K, f_cap);
+    else launch_calib<S, MD, 64>(grid, st, q, t, m, tm, c, o, code, delta, f, b0, K, f_cap);
+  };
+  if (model) go(std::true_type{}); else go(std::false_type{});
+}
+template void launch_replay_expand_calib<float>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayCalibIn&, const ReplayOut<float>&, int, int, int, int, int, hipStream_t, int, int*, double*);
+template void launch_replay_expand_calib<double>(const ReplaySeqIn&, const ReplayTrajIn&, const ReplayModelIn&, const ReplayTimingIn&, const ReplayCalibIn&, const ReplayOut<double>&, int, int, int, int, int, hipStream_t, int, int*, double*);
+
 // max_entries: the entries of the frame's largest sequence cell (the unfaulted grid's width; a trajectory with fewer leaves its
 // lanes idle).  t.fault != nullptr: the faulted form, its grid sized from f_cap tracks of G lanes, G from m_cap.
 template <class S, bool MODEL, int G>
@@ -491,6 +635,38 @@ void launch_replay_fault_counts(const int* n, const int* M, const int* off, cons
   hipLaunchKernelGGL(k_replay_fault_counts, dim3((unsigned)B), dim3(64), 0, st, n, M, off, t, f0, f1, S, f_cap, out);
 }
 
+// One sample as the expansion stores it, before the rounding to the handle's scalar: v[6] of sample i with the readings r[7] --
+// sigma4_pair's values, or model_stored's on the walk W(f, i) = start + P with P advanced past the sample as model_imu advances
+// it.  CAL (replay_plan.h, CALIB): rp::calib_imu's row in the values' place and rp::calib_out on the sums; returns the mask of
+// clipped components (0 without CAL).  Stated once for the sums and the counts.
+template <bool MODEL, bool CAL>
+__device__ __forceinline__ int sample_stored(const double* r, int i, uint64_t s_imu, const double* sg, const double* L, const double* start, double scale, const double* ic, double* P, double* v) {
+#pragma clang fp contract(off)
+  double cv[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) cv[c] = CAL ? rp::calib_imu(ic, r, c) : r[c];
+  if constexpr (MODEL) {
+    const double dT = r[6];
+    double w[rp::NQ];
+    if (dT > 0.0) model_w(s_imu, i, L, w);
+    else for (int q = 0; q < rp::NQ; ++q) w[q] = 0.0;              // (not read: a sample with dT <= 0 gets no noise and no increment)
+#pragma unroll
+    for (int c = 0; c < rp::WALK_ROW; ++c) {
+      const double W = start[c] + P[c];
+      v[c] = model_stored(cv[c], W, scale, w[c < 3 ? c : 3 + c], dT);
+      if (dT > 0.0) { const double d = model_delta(scale, w[c < 3 ? 3 + c : 6 + c], dT); P[c] = P[c] + d; }
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < rp::IMU_PAIRS; ++p) sigma4_pair(cv, sg, s_imu, i, p, v[2 * p], v[2 * p + 1]);
+  }
+  int mask = 0;
+  if constexpr (CAL) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { bool cl; v[c] = rp::calib_out(ic, c, v[c], &cl); mask |= cl ? 1 << c : 0; }
+  }
+  return mask;
+}
 // msckf_hip_replay_imu_sums: what the expansion would hand each trajectory's propagate over the frames [f0, f1), summed --
 // one workgroup (one wavefront) per trajectory; lane l takes the frames f0 + l, f0 + l + 64, ... in ascending order and a frame's
 // samples i < k in ascending order, adds the count, the six scalars and dT of each sample as the expansion stores them (the
@@ -498,13 +674,15 @@ void launch_replay_fault_counts(const int* n, const int* M, const int* off, cons
 // the handle's scalar S, widened to double) onto its own eight doubles; the lanes are combined by wave_sum.  The order of every
 // addition is fixed: the same inputs give the same bits.  Skipped cells add nothing.  No LDS, no atomics.
 // rd / kcell: the sequence store's readings [frames][S][K][7] and counts [frames][S] from frame 0; m.wstart: the walk table from
-// row 0; out [B][8] (replay_plan.h, ImuSum).
-template <class S, bool MODEL>
-__global__ __launch_bounds__(64) void k_replay_imu_sums(const double* rd, const int* kcell, ReplayTrajIn t, ReplayModelIn m, int f0, int f1, int n_seq, int K, int B, double* out) {
+// row 0; out [B][8] (replay_plan.h, ImuSum).  CAL: imucal is the IMU calibration record [B][31] and the calibrated rows are
+// summed (replay_plan.h, CALIB); without it imucal is not read.
+template <class S, bool MODEL, bool CAL>
+__global__ __launch_bounds__(64) void k_replay_imu_sums(const double* rd, const int* kcell, ReplayTrajIn t, ReplayModelIn m, const double* imucal, int f0, int f1, int n_seq, int K, int B, double* out) {
 #pragma clang fp contract(off)
   const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
   const int s = t.seq_of[b];
   const uint64_t seed = t.seed[b];
+  const double* ic = CAL ? imucal + (long)b * rp::IMU_CAL : nullptr;
   double acc[rp::IMU_SUM_ROW] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int f = f0 + lane; f < f1; f += 64) {
     const long cell = (long)f * n_seq + s;
@@ -516,24 +694,8 @@ __global__ __launch_bounds__(64) void k_replay_imu_sums(const double* rd, const 
     for (int i = 0; i < k; ++i) {
       const double* r = cr + i * RD_STRIDE;
       double v[6];
-      if constexpr (MODEL) {
-        const double* L = m.L + (long)b * rp::L_SIZE;
-        const double* start = m.wstart + ((long)f * B + b) * rp::WALK_ROW;
-        const double scale = m.scale[b], dT = r[6];
-        double w[rp::NQ];
-        if (dT > 0.0) model_w(s_imu, i, L, w);
-        else for (int q = 0; q < rp::NQ; ++q) w[q] = 0.0;              // (not read: a sample with dT <= 0 gets no noise and no increment)
-#pragma unroll
-        for (int c = 0; c < rp::WALK_ROW; ++c) {
-          const double W = start[c] + P[c];
-          v[c] = model_stored(r[c], W, scale, w[c < 3 ? c : 3 + c], dT);
-          if (dT > 0.0) { const double d = model_delta(scale, w[c < 3 ? 3 + c : 6 + c], dT); P[c] = P[c] + d; }
-        }
-      } else {
-        const double* sg = t.sigma + (long)b * rp::N_SIGMA;
-#pragma unroll
-        for (int p = 0; p < rp::IMU_PAIRS; ++p) sigma4_pair(r, sg, s_imu, i, p, v[2 * p], v[2 * p + 1]);
-      }
+      if constexpr (MODEL) sample_stored<true, CAL>(r, i, s_imu, nullptr, m.L + (long)b * rp::L_SIZE, m.wstart + ((long)f * B + b) * rp::WALK_ROW, m.scale[b], ic, P, v);
+      else sample_stored<false, CAL>(r, i, s_imu, t.sigma + (long)b * rp::N_SIGMA, nullptr, nullptr, 0.0, ic, P, v);
       acc[rp::IS_COUNT] += 1.0;
 #pragma unroll
       for (int c = 0; c < 6; ++c) acc[rp::IS_OMEGA + c] += (double)(S)v[c];
@@ -546,12 +708,58 @@ __global__ __launch_bounds__(64) void k_replay_imu_sums(const double* rd, const 
     if (lane == 0) out[(long)b * rp::IMU_SUM_ROW + i] = v;
   }
 }
-void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st) {
+void launch_replay_imu_sums(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, int f0, int f1, int S, int K, int B, bool scalar_is_float, double* out, hipStream_t st, const double* imucal) {
   if (B <= 0) return;
   const bool model = m.L != nullptr;
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), 0, st, rd, k, t, m, f0, f1, S, K, B, out); };
-  if (scalar_is_float) { if (model) go(k_replay_imu_sums<float, true>); else go(k_replay_imu_sums<float, false>); }
-  else { if (model) go(k_replay_imu_sums<double, true>); else go(k_replay_imu_sums<double, false>); }
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(64), 0, st, rd, k, t, m, imucal, f0, f1, S, K, B, out); };
+  auto pick = [&](auto cal) {
+    constexpr bool CAL = decltype(cal)::value;
+    if (scalar_is_float) { if (model) go(k_replay_imu_sums<float, true, CAL>); else go(k_replay_imu_sums<float, false, CAL>); }
+    else { if (model) go(k_replay_imu_sums<double, true, CAL>); else go(k_replay_imu_sums<double, false, CAL>); }
+  };
+  if (imucal) pick(std::true_type{}); else pick(std::false_type{});
+}
+
+// msckf_hip_replay_calib_counts: the samples of the frames [f0, f1) and the components the saturation clips, counted without
+// expanding anything -- one workgroup (one wavefront) per trajectory, lane l takes the frames f0 + l, f0 + l + 64, ... in ascending
+// order and a frame's samples i < k in ascending order, recomputes each stored value with sample_stored (what the expansion and
+// the sums use) and counts; the lanes are combined by wave_sum, a fixed tree.  Integers below 2^53 in doubles: exact.
+// out [B][8] (replay_plan.h, CalibCount).  No LDS, no atomics.
+template <bool MODEL>
+__global__ __launch_bounds__(64) void k_replay_calib_counts(const double* rd, const int* kcell, ReplayTrajIn t, ReplayModelIn m, const double* imucal, int f0, int f1, int n_seq, int K, int B, long long* out) {
+  const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int s = t.seq_of[b];
+  const uint64_t seed = t.seed[b];
+  const double* ic = imucal + (long)b * rp::IMU_CAL;
+  double cnt[rp::N_CALIB_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int f = f0 + lane; f < f1; f += 64) {
+    const long cell = (long)f * n_seq + s;
+    const int kc = kcell[cell];                                        // (a skipped cell's k is IMU_SKIP: nothing)
+    const int k = kc < K ? kc : K;
+    const double* cr = rd + cell * K * RD_STRIDE;
+    const uint64_t s_imu = rp::imu_seed(seed, f);
+    double P[rp::WALK_ROW] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < k; ++i) {
+      double v[6];
+      int mask;
+      if constexpr (MODEL) mask = sample_stored<true, true>(cr + i * RD_STRIDE, i, s_imu, nullptr, m.L + (long)b * rp::L_SIZE, m.wstart + ((long)f * B + b) * rp::WALK_ROW, m.scale[b], ic, P, v);
+      else mask = sample_stored<false, true>(cr + i * RD_STRIDE, i, s_imu, t.sigma + (long)b * rp::N_SIGMA, nullptr, nullptr, 0.0, ic, P, v);
+      cnt[rp::CCNT_SAMPLES] += 1.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) cnt[rp::CCNT_CLIP + c] += (mask >> c) & 1;
+      cnt[rp::CCNT_ANY] += mask != 0;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < rp::N_CALIB_COUNT; ++i) {
+    const double v = wave_sum(cnt[i]);
+    if (lane == 0) out[(long)b * rp::N_CALIB_COUNT + i] = (long long)v;
+  }
+}
+void launch_replay_calib_counts(const double* rd, const int* k, const ReplayTrajIn& t, const ReplayModelIn& m, const double* imucal, int f0, int f1, int S, int K, int B, long long* out, hipStream_t st) {
+  if (B <= 0) return;
+  if (m.L != nullptr) hipLaunchKernelGGL(k_replay_calib_counts<true>, dim3((unsigned)B), dim3(64), 0, st, rd, k, t, m, imucal, f0, f1, S, K, B, out);
+  else hipLaunchKernelGGL(k_replay_calib_counts<false>, dim3((unsigned)B), dim3(64), 0, st, rd, k, t, m, imucal, f0, f1, S, K, B, out);
 }
 
 // The walk table of the model, wstart[frames + 1][B][6], once per assignment: workgroup b takes trajectory b.  Per chunk of

@@ -242,6 +242,10 @@ struct BatchCore {
   // them (time / frame_of [S][frames], base [frames][S]) and replay_expand_timing's deltas, one per entry of the largest frame
   double* rp_timing = nullptr; double* rp_img_time = nullptr; int* rp_img_frame = nullptr; int* rp_img_base = nullptr;
   double* rp_delta = nullptr; size_t rp_delta_count = 0;
+  // the calibration records imucal[B][31] and camcal[B][8] (the identity and zeros while none is set; rp.calib_uploaded) and
+  // replay_expand_calib's outputs: rd_cal / clip [K][6], obs_cal one pair per entry of the largest frame
+  double* rp_imucal = nullptr; double* rp_camcal = nullptr; double* rp_rdcal = nullptr; int* rp_clip = nullptr; size_t rp_rdcal_count = 0;
+  double* rp_obscal = nullptr; size_t rp_obscal_count = 0;
   std::vector<int> rp_cells[MAXS];
   Workers workers;   // enqueue threads of the slices
   // frame log (msckf_hip_frame_log_*; kernels_log.hip): [log_cap][B][LOG_STRIDE] scalars of esz bytes, null unless enabled.  log_n
@@ -1069,6 +1073,7 @@ struct BatchCore {
     dfree(rp_scratch); rp_scratch_bytes = 0;
     dfree(rp_fault); dfree(rp_code); rp_code_count = 0;
     dfree(rp_timing); dfree(rp_img_time); dfree(rp_img_frame); dfree(rp_img_base); dfree(rp_delta); rp_delta_count = 0;
+    dfree(rp_imucal); dfree(rp_camcal); dfree(rp_rdcal); dfree(rp_clip); rp_rdcal_count = 0; dfree(rp_obscal); rp_obscal_count = 0;
     rp_uploaded = false;
   }
   int replay_alloc(int n_seq, int n_frames, int K) {
@@ -1143,6 +1148,20 @@ struct BatchCore {
     rp.set_timing(timing4);
     return 0;
   }
+  // the calibration records (replay_plan.h, CALIB), or null for none; may be called between runs, stay through assign, assign_q,
+  // set_faults, set_timing and commit, and replay_alloc clears them.  A refused call leaves the previous record in force.
+  int replay_set_imu_calib(const double* imucal) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.imu_calib_refusal(imucal))) return rc;
+    rp.set_imu_calib(imucal);
+    return 0;
+  }
+  int replay_set_cam_calib(const double* camcal) {
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.cam_calib_refusal(camcal))) return rc;
+    rp.set_cam_calib(camcal);
+    return 0;
+  }
   // msckf_hip_replay_image_table: sequence seq's image table as commit built it -- time / frame_of [images], base [frames], each
   // or null -- and the image count
   int replay_image_table(int seq, double* time, int* frame_of, int* base) {
@@ -1160,7 +1179,7 @@ struct BatchCore {
   ReplayTimingIn replay_timing(int f) const { return ReplayTimingIn{rp_timing, rp_img_time, rp_img_frame, rp_img_base + (size_t)f * rp.S, rp.frames()}; }
   // before a run or an expansion (after enter()): the bases of every frame, and with the assignment and the fault record on the device
   int replay_upload_plan() {
-    if (rp.planned && rp_uploaded && rp.faults_uploaded && rp.timing_uploaded) return 0;
+    if (rp.planned && rp_uploaded && rp.faults_uploaded && rp.timing_uploaded && rp.calib_uploaded) return 0;
     if (int rc = refuse(rp.index_trajectories())) return rc;
     HIPCHK(hipStreamSynchronize(st));                        // the last run's kernels have read the old ones
     if (!rp_seq_of) {
@@ -1168,6 +1187,8 @@ struct BatchCore {
       HIPCHK(hipMalloc((void**)&rp_sigma, (size_t)B * msckf_replay::N_SIGMA * sizeof(double)));
       HIPCHK(hipMalloc((void**)&rp_fault, (size_t)B * msckf_replay::N_FAULT * sizeof(double)));
       HIPCHK(hipMalloc((void**)&rp_timing, (size_t)B * msckf_replay::N_TIMING * sizeof(double)));
+      HIPCHK(hipMalloc((void**)&rp_imucal, (size_t)B * msckf_replay::IMU_CAL * sizeof(double)));
+      HIPCHK(hipMalloc((void**)&rp_camcal, (size_t)B * msckf_replay::CAM_CAL * sizeof(double)));
     }
     if (rp.base.size() != rp_base_count) { dfree(rp_base); rp_base_count = 0; HIPCHK(hipMalloc((void**)&rp_base, rp.base.size() * sizeof(int))); rp_base_count = rp.base.size(); }
     HIPCHK(hipMemcpy(rp_seq_of, rp.seq_of.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice));
@@ -1185,7 +1206,14 @@ struct BatchCore {
     else HIPCHK(hipMemcpy(rp_fault, rp.fault.data(), rp.fault.size() * sizeof(double), hipMemcpyHostToDevice));
     if (rp.timing.empty()) HIPCHK(hipMemset(rp_timing, 0, (size_t)B * msckf_replay::N_TIMING * sizeof(double)));
     else HIPCHK(hipMemcpy(rp_timing, rp.timing.data(), rp.timing.size() * sizeof(double), hipMemcpyHostToDevice));
-    rp_uploaded = rp.faults_uploaded = rp.timing_uploaded = true;
+    {
+      std::vector<double> ic = rp.imucal;                    // (no record: the identity)
+      if (ic.empty()) { ic.resize((size_t)B * msckf_replay::IMU_CAL); for (int b = 0; b < B; ++b) msckf_replay::imu_calib_identity(ic.data() + (size_t)b * msckf_replay::IMU_CAL); }
+      HIPCHK(hipMemcpy(rp_imucal, ic.data(), ic.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (rp.camcal.empty()) HIPCHK(hipMemset(rp_camcal, 0, (size_t)B * msckf_replay::CAM_CAL * sizeof(double)));
+    else HIPCHK(hipMemcpy(rp_camcal, rp.camcal.data(), rp.camcal.size() * sizeof(double), hipMemcpyHostToDevice));
+    rp_uploaded = rp.faults_uploaded = rp.timing_uploaded = rp.calib_uploaded = true;
     return 0;
   }
   // msckf_hip_replay_fault_counts: the faults of the frames [f0, f1) per trajectory, out [B][6], counted on the device from the
@@ -1222,12 +1250,34 @@ struct BatchCore {
     double* dout = nullptr;
     HIPCHK(hipMalloc((void**)&dout, (size_t)B * W * sizeof(double)));
     launch_replay_imu_sums(reinterpret_cast<const double*>(rp_dev[SEC_RD]), reinterpret_cast<const int*>(rp_dev[SEC_K]), ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base},
-                           replay_model(0), f0, f1, rp.S, rp.K(), B, esz == sizeof(float), dout, st);
+                           replay_model(0), f0, f1, rp.S, rp.K(), B, esz == sizeof(float), dout, st, rp.imu_calibrated ? rp_imucal : nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)B * W * sizeof(double), hipMemcpyDeviceToHost, st);
     const hipError_t es = hipStreamSynchronize(st);
     (void)hipFree(dout);
     if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("replay_imu_sums: ") + hipGetErrorString(e != hipSuccess ? e : es));
+    return 0;
+  }
+  // msckf_hip_replay_calib_counts: per trajectory the samples of the frames [f0, f1) and the components the saturation clips,
+  // out [B][8] (replay_plan.h, CalibCount), counted on the device from the sequences, the assignment and the IMU record alone
+  // (k_replay_calib_counts): no run, no log, nothing of the filters changes
+  int replay_calib_counts(int f0, int f1, long long* out) {
+    using namespace inputs;
+    if (int rc = guard()) return rc;
+    if (int rc = refuse(rp.run_refusal(f0, f1))) return rc;
+    if (int rc = enter()) return rc;
+    if (int rc = replay_upload_plan()) return rc;
+    if (int rc = replay_walk_table()) return rc;
+    constexpr size_t W = msckf_replay::N_CALIB_COUNT;
+    long long* dout = nullptr;
+    HIPCHK(hipMalloc((void**)&dout, (size_t)B * W * sizeof(long long)));
+    launch_replay_calib_counts(reinterpret_cast<const double*>(rp_dev[SEC_RD]), reinterpret_cast<const int*>(rp_dev[SEC_K]), ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base},
+                               replay_model(0), rp_imucal, f0, f1, rp.S, rp.K(), B, dout, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)B * W * sizeof(long long), hipMemcpyDeviceToHost, st);
+    const hipError_t es = hipStreamSynchronize(st);
+    (void)hipFree(dout);
+    if (e != hipSuccess || es != hipSuccess) return fail(-EIO, std::string("replay_calib_counts: ") + hipGetErrorString(e != hipSuccess ? e : es));
     return 0;
   }
   // what map_log_fault_metrics checks before anything reaches the device: the log and its ordinals, then the replay frames
@@ -1433,7 +1483,9 @@ struct BatchCore {
   // THE frame step of run_frames / run_frames_streamed / run_frames_replay: frame f of a call over [f0, f1) for slice s, inputs
   // in staging set `staged` of the upload ring, or resident (IN_RESIDENT), or expanded by the replay (IN_REPLAY)
   virtual void enqueue_frame(Slice& s, int f, int f0, int f1, int staged) = 0;
-  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr) = 0;
+  // the read-back of the calibrated expansion (msckf_hip_replay_expand_calib): each pointer or null
+  struct CalibOut { double* rd_cal; int* clip; double* obs_cal; };
+  virtual int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr, const CalibOut* co = nullptr) = 0;
   virtual int map_log_fault_metrics(int q0, int q1, int f0, double* out) = 0;                  // out [B][8]
   virtual void commit_buffer_parity(int f0, int f1) = 0;   // after the frames [f0, f1): the covariance buffer that is current becomes the handle's
   virtual void apply_settings() = 0;   // the one place where `settings` reaches the kernel argument
@@ -2137,11 +2189,16 @@ struct Batch : BatchCore {
   }
   // (the fault record only while some trajectory has a non-zero probability, or the timed form runs: otherwise the unfaulted
   // form is launched)
-  ReplayTrajIn replay_traj(int f) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B, rp.faulted || rp.timed ? rp_fault : nullptr}; }
+  ReplayTrajIn replay_traj(int f, bool calib = false) const { return ReplayTrajIn{rp_seq_of, rp_seed, rp_sigma, rp_base + (size_t)f * B, rp.faulted || rp.timed || rp.calibrated() || calib ? rp_fault : nullptr}; }
   // THE expansion's launch, for the frame loop and the read-backs: the timed form while some timing record is non-zero
   // (replay_plan.h, TIMING), otherwise the un-timed launch as it always was
-  void replay_launch(const ReplayOut<S>& o, int f, int b0, int nb, hipStream_t q, int* code = nullptr, double* delta = nullptr) {
-    if (rp.timed) launch_replay_expand_timed<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_timing(f), o, f, b0, nb, rp.K(), f_cap, q, m_cap, code, delta);
+  // calib (the read-back's outputs on the device, or null): the calibrated form -- what runs anyway while some calibration
+  // record is non-trivial (replay_plan.h, CALIB), and under trivial records writes the bits of the other forms
+  void replay_launch(const ReplayOut<S>& o, int f, int b0, int nb, hipStream_t q, int* code = nullptr, double* delta = nullptr, const ReplayCalibIn* calib = nullptr) {
+    if (rp.calibrated() || calib) {
+      const ReplayCalibIn c{rp_imucal, rp_camcal, rp.timed, calib ? calib->rd_cal : nullptr, calib ? calib->clip : nullptr, calib ? calib->obs_cal : nullptr};
+      launch_replay_expand_calib<S>(replay_seq(f), replay_traj(f, true), replay_model(f), replay_timing(f), c, o, f, b0, nb, rp.K(), f_cap, q, m_cap, code, delta);
+    } else if (rp.timed) launch_replay_expand_timed<S>(replay_seq(f), replay_traj(f), replay_model(f), replay_timing(f), o, f, b0, nb, rp.K(), f_cap, q, m_cap, code, delta);
     else launch_replay_expand<S>(replay_seq(f), replay_traj(f), replay_model(f), o, f, b0, nb, rp.K(), f_cap, rp_maxcell[f], q, m_cap, code);
   }
   ReplayOut<S> replay_out(unsigned char* blk, int f) const {
@@ -2160,7 +2217,9 @@ struct Batch : BatchCore {
   // slots (each pair null or not); code (or null): per SEQUENCE entry 0 kept, 1 outlier, 2 missed, from the same launch.  Under
   // faults M holds the survivors and slots / obs are in partition order.  Returns the cell's entries.  Nothing of the handle's
   // filters, inputs or logs changes.
-  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr) override {
+  // co (msckf_hip_replay_expand_calib): the noise-free calibrated samples rd_cal [K][6], the 6-bit masks of clipped components
+  // clip [K] and the mapped noise-free coordinates obs_cal per SEQUENCE entry, from the same launch.
+  int replay_expand(int f, int b, double* rd, double* obs, int* ints, int* slots, int cap_entries, int* code = nullptr, double* delta = nullptr, const CalibOut* co = nullptr) override {
     using namespace inputs;
     if (int rc = guard()) return rc;
     if (int rc = refuse(rp.expand_refusal(f, b))) return rc;
@@ -2176,7 +2235,7 @@ struct Batch : BatchCore {
       HIPCHK(hipMalloc((void**)&rp_scratch, need));
       rp_scratch_bytes = need;
     }
-    const bool coded = code && (rp.faulted || rp.timed);       // (without faults every code is 0: FAULT_KEPT)
+    const bool coded = code && (rp.faulted || rp.timed || rp.calibrated());   // (without faults every code is 0: FAULT_KEPT)
     const bool timed = delta && rp.timed;                      // (without timing every delta is 0)
     if (timed && rp.largest > rp_delta_count) {
       HIPCHK(hipStreamSynchronize(st));
@@ -2190,8 +2249,16 @@ struct Batch : BatchCore {
       HIPCHK(hipMalloc((void**)&rp_code, rp.largest * sizeof(int)));
       rp_code_count = rp.largest;
     }
+    if (co && ((size_t)K * 6 > rp_rdcal_count || rp.largest > rp_obscal_count)) {
+      HIPCHK(hipStreamSynchronize(st));
+      dfree(rp_rdcal); dfree(rp_clip); dfree(rp_obscal); rp_rdcal_count = rp_obscal_count = 0;
+      HIPCHK(hipMalloc((void**)&rp_rdcal, (size_t)K * 6 * sizeof(double))); HIPCHK(hipMalloc((void**)&rp_clip, (size_t)K * 6 * sizeof(int)));
+      HIPCHK(hipMalloc((void**)&rp_obscal, std::max<size_t>(rp.largest, 1) * 2 * sizeof(double)));
+      rp_rdcal_count = (size_t)K * 6; rp_obscal_count = rp.largest;
+    }
     const ReplayOut<S> o = replay_out(rp_scratch, f);
-    replay_launch(o, f, b, 1, st, coded ? rp_code : nullptr, timed ? rp_delta : nullptr);
+    const ReplayCalibIn cal{rp_imucal, rp_camcal, rp.timed, rp_rdcal, rp_clip, rp_obscal};
+    replay_launch(o, f, b, 1, st, coded ? rp_code : nullptr, timed ? rp_delta : nullptr, co ? &cal : nullptr);
     HIPCHK(hipGetLastError());
     const size_t base = (size_t)rp.base[(size_t)f * B + b];
     std::vector<S> hr((size_t)K * RD_STRIDE), ho((size_t)2 * std::max(E, 1));
@@ -2203,6 +2270,10 @@ struct Batch : BatchCore {
     if (coded && E) HIPCHK(hipMemcpyAsync(code, rp_code + base, (size_t)E * sizeof(int), hipMemcpyDeviceToHost, st));
     if (delta) std::fill(delta, delta + E, 0.0);
     if (timed && E) HIPCHK(hipMemcpyAsync(delta, rp_delta + base, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
+    std::vector<int> hclip(co ? (size_t)K * 6 : 0);
+    if (co && co->rd_cal) HIPCHK(hipMemcpyAsync(co->rd_cal, rp_rdcal, (size_t)K * 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (co && co->clip) HIPCHK(hipMemcpyAsync(hclip.data(), rp_clip, (size_t)K * 6 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (co && co->obs_cal && E) HIPCHK(hipMemcpyAsync(co->obs_cal, rp_obscal + 2 * base, (size_t)2 * E * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[0], o.n + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[1], o.drop + b, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(&hi[2], o.k + b, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2213,6 +2284,7 @@ struct Batch : BatchCore {
     if (obs) for (int i = 0; i < 2 * E; ++i) obs[i] = (double)ho[i];
     if (ints) std::copy(hi.begin(), hi.end(), ints);
     if (slots) std::copy(hs.begin(), hs.begin() + E, slots);
+    if (co && co->clip) for (int i = 0; i < K; ++i) { co->clip[i] = 0; for (int c = 0; c < 6; ++c) co->clip[i] |= hclip[(size_t)i * 6 + c] << c; }
     return E;
   }
   // THE frame step: frame f of a call over [f0, f1) for slice s, inputs in staging set `staged`, resident or the replay's --
@@ -2951,6 +3023,14 @@ int msckf_hip_replay_expand_faults(msckf_hip_handle h, int frame, int b, int* co
 int msckf_hip_replay_set_timing(msckf_hip_handle h, const double* timing4) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_timing(timing4); }
 int msckf_hip_replay_image_table(msckf_hip_handle h, int seq, double* time, int* frame_of, int* base) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_image_table(seq, time, frame_of, base); }
 int msckf_hip_replay_expand_timing(msckf_hip_handle h, int frame, int b, double* delta, int cap_entries) { if (!h || !delta) return fail(-EINVAL, "null argument"); return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, nullptr, delta); }
+int msckf_hip_replay_set_imu_calib(msckf_hip_handle h, const double* imucal) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_imu_calib(imucal); }
+int msckf_hip_replay_set_cam_calib(msckf_hip_handle h, const double* camcal) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->replay_set_cam_calib(camcal); }
+int msckf_hip_replay_expand_calib(msckf_hip_handle h, int frame, int b, double* rd_cal, int* clip, double* obs_cal, int cap_entries) {
+  if (!h) return fail(-EINVAL, "null handle");
+  const BatchCore::CalibOut co{rd_cal, clip, obs_cal};
+  return H(h)->replay_expand(frame, b, nullptr, nullptr, nullptr, nullptr, cap_entries, nullptr, nullptr, &co);
+}
+int msckf_hip_replay_calib_counts(msckf_hip_handle h, int f0, int f1, long long* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_calib_counts(f0, f1, out); }
 int msckf_hip_replay_fault_counts(msckf_hip_handle h, int f0, int f1, long long* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_fault_counts(f0, f1, out); }
 int msckf_hip_replay_imu_sums(msckf_hip_handle h, int f0, int f1, double* out) { if (!h || !out) return fail(-EINVAL, "null argument"); return H(h)->replay_imu_sums(f0, f1, out); }
 // ---- the track compiler (track_compile.h): host code alone, no handle, no device

@@ -13,6 +13,8 @@
 //                     track stated serially (track_faults), the lane group of the faulted expansion
 //                     and the camera's clock: time offset, jitter and rolling shutter (TIMING below), the image table of a
 //                     sequence, the stencil of the shift and its preconditions
+//                     and the sensors' calibration errors: IMU scale, misalignment, g-sensitivity, saturation and quantisation,
+//                     the camera's residual intrinsics (CALIB below), as inline functions the kernels compile too
 //   3. Plan           the sequence store (a ScenarioStore of S "trajectories" whose scalars are doubles), the assignment record
 //                     of either model, per frame each trajectory's first entry in the expanded block and the block's size, the
 //                     largest expanded frame, and every refusal with its code and text
@@ -185,6 +187,100 @@ enum Timing { TIM_TD, TIM_RY, TIM_Y0, TIM_SIGMA_J, N_TIMING };
 constexpr int stencil_nodes(int M) { return M < 3 ? M : 3; }
 constexpr int stencil_first(int l, int M) { return M < 3 ? 0 : (l - 1 < 0 ? 0 : l - 1 > M - 3 ? M - 3 : l - 1); }
 
+// ---- 2f. CALIB: IMU and camera calibration errors (msckf_hip_replay_set_imu_calib, msckf_hip_replay_set_cam_calib; normative,
+// the header, DESIGN section 4.13 and the twin state the same).  Independent of the noise model, the faults and the timing.
+// The arithmetic is the inline functions below: the kernels and a host program compile this text.
+//   IMU      trajectory b has imucal[b] = [31]: T_g (0 .. 8, 3 x 3 row-major), T_a (9 .. 17), G (18 .. 26, the gyro's response to
+//            specific force [rad/s per m/s^2]), sat_g, sat_a (27, 28: saturation levels, 0: none), lsb_g, lsb_a (29, 30:
+//            quantisation steps, 0: none); all finite, the last four >= 0.  The identity record is T_g = T_a = I, the rest 0; a
+//            record is non-trivial when it differs from that.
+//            The matrices act on the sequence's values, constant bias included: the cell holds omega + b_0 and a + b_0, and the
+//            shift (T - I) b_0 is a bias the filter estimates anyway.
+//   sample   i < k of a cell that is not skipped, v_g = cell[0:3], v_a = cell[3:6]:
+//              c_a[r] = sum_c T_a[r][c] v_a[c], c_g[r] = sum_c T_g[r][c] v_g[c]: the first product, then each further product
+//              added, c ascending; for the gyro then + G[r][0] v_a[0], + G[r][1] v_a[1], + G[r][2] v_a[2] in that order; every
+//              product and every sum rounded in double (calib_imu).
+//            c takes the place of the sequence value in the noise rule: c + sigma g under NOISE, (c + W(f, i)) + n under MODEL (no
+//            n when dT_i <= 0).  The bias walk stays an output bias: Wstart and k_replay_walk_scan do not change.
+//            then, per component with its sensor's sat and lsb (calib_out): where sat > 0, x = min(max(x, -sat), sat), and the
+//            component is CLIPPED when its value before the clamp lies strictly outside [-sat, sat]; where lsb > 0,
+//            x = lsb rint(x / lsb): the quotient rounded, rint to nearest even, then the product.  The result is rounded once to
+//            the handle's scalar.  dT, rows from k on and skipped cells are untouched.
+//   camera   trajectory b has camcal[b] = (e_u, e_v, d_u, d_v, k1, k2, p1, p2), all finite: the residual map, in normalised
+//            coordinates, between the true camera and the calibration the front end undistorted with -- e the relative focal
+//            length error, d the principal point error over the focal length, k and p the residual radial-tangential
+//            coefficients.  The all-zero record is trivial.
+//   entry    the map applies to an entry's value (x, y): the sequence value, or what the TIMING shift made of it (the timing
+//            delta keeps using the sequence's y).  calib_cam:
+//              xx = x x, yy = y y, xy = x y, r2 = xx + yy, rad = (1 + k1 r2) + k2 (r2 r2)
+//              xd = (x rad + (2 p1) xy) + p2 (r2 + 2 xx),  yd = (y rad + p1 (r2 + 2 yy)) + (2 p2) xy
+//              x' = (xd + e_u xd) + d_u,                   y' = (yd + e_v yd) + d_v
+//            + - x only, each rounded in double, no contraction.  The Gaussian pixel noise and the outlier ring are then added to
+//            (x', y') exactly as before; draws stay indexed by the sequence entry, so a seed's noise and faults do not depend on
+//            its calibration.  Missed entries are mapped too: every entry carries its coordinates.
+// With no record, or only trivial ones, the expansion launched is the one without calibration.
+#if defined(__HIPCC__)
+#define MSCKF_RP_HD __host__ __device__
+#else
+#define MSCKF_RP_HD
+#endif
+// a value that is rounded before anything else is done with it, whatever the translation unit's contraction mode: it passes
+// through an empty asm the compiler cannot look into (a product that goes into a sum is never fused with it)
+MSCKF_RP_HD inline double rnd(double p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(p));
+#elif defined(__x86_64__)
+  asm volatile("" : "+x"(p));
+#else
+  volatile double q = p; p = q;
+#endif
+  return p;
+}
+constexpr int IMU_CAL = 31, CAM_CAL = 8;   // scalars of the two records
+enum ImuCal { IC_TG = 0, IC_TA = 9, IC_G = 18, IC_SAT_G = 27, IC_SAT_A = 28, IC_LSB_G = 29, IC_LSB_A = 30 };
+enum CamCal { CC_EU, CC_EV, CC_DU, CC_DV, CC_K1, CC_K2, CC_P1, CC_P2 };
+// columns of msckf_hip_replay_calib_counts: samples, gyro x y z clipped, accelerometer x y z clipped, samples with any component clipped
+enum CalibCount { CCNT_SAMPLES = 0, CCNT_CLIP = 1, CCNT_ANY = 7, N_CALIB_COUNT = 8 };
+// c of column col (0 .. 2 gyro, 3 .. 5 accelerometer) of a sample with the sequence values v[6]
+MSCKF_RP_HD inline double calib_imu(const double* ic, const double* v, int col) {
+  const bool gyro = col < 3;
+  const int r = gyro ? col : col - 3;
+  const double* T = ic + (gyro ? IC_TG : IC_TA) + 3 * r;
+  const double* x = v + (gyro ? 0 : 3);
+  double a = rnd(T[0] * x[0]);
+  a = rnd(a + rnd(T[1] * x[1]));
+  a = rnd(a + rnd(T[2] * x[2]));
+  if (gyro) {
+    const double* G = ic + IC_G + 3 * r;
+    a = rnd(a + rnd(G[0] * v[3]));
+    a = rnd(a + rnd(G[1] * v[4]));
+    a = rnd(a + rnd(G[2] * v[5]));
+  }
+  return a;
+}
+// saturation and quantisation of column col's value x (noise included); *clipped: x lay strictly outside [-sat, sat]
+MSCKF_RP_HD inline double calib_out(const double* ic, int col, double x, bool* clipped) {
+  const double sat = ic[col < 3 ? IC_SAT_G : IC_SAT_A], lsb = ic[col < 3 ? IC_LSB_G : IC_LSB_A];
+  *clipped = sat > 0.0 && (x < -sat || x > sat);
+  if (sat > 0.0) { x = x > -sat ? x : -sat; x = x < sat ? x : sat; }
+  if (lsb > 0.0) x = lsb * std::rint(rnd(x / lsb));
+  return x;
+}
+// the camera's residual map of (x, y) under cc[8], out[2] (out may be where x and y came from)
+MSCKF_RP_HD inline void calib_cam(const double* cc, double x, double y, double* out) {
+  const double xx = rnd(x * x), yy = rnd(y * y), xy = rnd(x * y), r2 = rnd(xx + yy);
+  const double rad = rnd(rnd(1.0 + rnd(cc[CC_K1] * r2)) + rnd(cc[CC_K2] * rnd(r2 * r2)));
+  const double xd = rnd(rnd(rnd(x * rad) + rnd(rnd(2.0 * cc[CC_P1]) * xy)) + rnd(cc[CC_P2] * rnd(r2 + rnd(2.0 * xx))));
+  const double yd = rnd(rnd(rnd(y * rad) + rnd(cc[CC_P1] * rnd(r2 + rnd(2.0 * yy)))) + rnd(rnd(2.0 * cc[CC_P2]) * xy));
+  out[0] = rnd(xd + rnd(cc[CC_EU] * xd)) + cc[CC_DU];
+  out[1] = rnd(yd + rnd(cc[CC_EV] * yd)) + cc[CC_DV];
+}
+// the identity IMU record
+inline void imu_calib_identity(double* ic) {
+  for (int i = 0; i < IMU_CAL; ++i) ic[i] = 0.0;
+  for (int r = 0; r < 3; ++r) ic[IC_TG + 4 * r] = ic[IC_TA + 4 * r] = 1.0;
+}
+
 // ---- 3. the plan
 using msckf_inputs::FrameLayout;
 using msckf_inputs::Refusal;
@@ -217,6 +313,10 @@ struct Plan {
   std::vector<double> timing; bool timed = false, timing_uploaded = false;
   std::vector<double> img_time; std::vector<int> img_frame, img_base, img_W, img_n;
   std::string timing_why;            // the text of the last timing_precondition() refusal
+  // the calibration records (CALIB above): [B][IMU_CAL] and [B][CAM_CAL], empty: none set; imu_calibrated / cam_calibrated:
+  // some trajectory's record is non-trivial; calib_uploaded as faults_uploaded
+  std::vector<double> imucal, camcal; bool imu_calibrated = false, cam_calibrated = false, calib_uploaded = false;
+  bool calibrated() const { return imu_calibrated || cam_calibrated; }
 
   int frames() const { return seq.frames; }
   int K() const { return seq.lay.K; }
@@ -239,6 +339,7 @@ struct Plan {
     fault.clear(); faulted = faults_uploaded = false;
     timing.clear(); timed = timing_uploaded = false;
     img_time.clear(); img_frame.clear(); img_base.clear(); img_W.clear(); img_n.clear();
+    imucal.clear(); camcal.clear(); imu_calibrated = cam_calibrated = calib_uploaded = false;
   }
   // the rules of one sequence cell, in scenario_set_cell's order: its place, the work-list rules, the drop, the cell rule, the readings
   Refusal cell_refusal(int f, int s, const double* rd, int k, int F, const int* M, const int* slots, int n_drop, int flags, int m_cap, int n_cap) const {
@@ -379,6 +480,43 @@ struct Plan {
     if (timing4) timing.assign(timing4, timing4 + (size_t)B * N_TIMING); else timing.clear();
     timed = nonzero_timing(timing.empty() ? nullptr : timing.data(), B);
     timing_uploaded = false;
+  }
+  // the calibration records (CALIB), imucal [B][IMU_CAL] / camcal [B][CAM_CAL] or null for none, in this order: the replay,
+  // every value finite, and for the IMU record the saturation levels and quantisation steps
+  Refusal imu_calib_refusal(const double* ic) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    if (!ic) return {0, nullptr};
+    for (int i = 0; i < B * IMU_CAL; ++i) if (!std::isfinite(ic[i])) return {-EINVAL, "calibration values must be finite"};
+    for (int b = 0; b < B; ++b) for (int c = IC_SAT_G; c < IMU_CAL; ++c) if (ic[b * IMU_CAL + c] < 0.0) return {-EINVAL, "saturation and quantisation must not be negative"};
+    return {0, nullptr};
+  }
+  Refusal cam_calib_refusal(const double* cc) const {
+    if (seq.frames <= 0) return {-EINVAL, "no replay allocated"};
+    if (!cc) return {0, nullptr};
+    for (int i = 0; i < B * CAM_CAL; ++i) if (!std::isfinite(cc[i])) return {-EINVAL, "calibration values must be finite"};
+    return {0, nullptr};
+  }
+  static bool nontrivial_imu_calib(const double* ic, int B_) {
+    double id[IMU_CAL];
+    imu_calib_identity(id);
+    for (int b = 0; ic && b < B_; ++b) for (int i = 0; i < IMU_CAL; ++i) if (ic[b * IMU_CAL + i] != id[i]) return true;
+    return false;
+  }
+  static bool nontrivial_cam_calib(const double* cc, int B_) {
+    for (int i = 0; cc && i < B_ * CAM_CAL; ++i) if (cc[i] != 0.0) return true;
+    return false;
+  }
+  // independent of the assignment, the faults, the timing and the cells: they stay through assign, assign_q, set_faults,
+  // set_timing and commit, and alloc() clears them
+  void set_imu_calib(const double* ic) {
+    if (ic) imucal.assign(ic, ic + (size_t)B * IMU_CAL); else imucal.clear();
+    imu_calibrated = nontrivial_imu_calib(imucal.empty() ? nullptr : imucal.data(), B);
+    calib_uploaded = false;
+  }
+  void set_cam_calib(const double* cc) {
+    if (cc) camcal.assign(cc, cc + (size_t)B * CAM_CAL); else camcal.clear();
+    cam_calibrated = nontrivial_cam_calib(camcal.empty() ? nullptr : camcal.data(), B);
+    calib_uploaded = false;
   }
 
   // -- a run

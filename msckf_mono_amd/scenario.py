@@ -527,6 +527,174 @@ def replay_gate_confusion(records, cells_M, seed, fault4, q0, q1, f0):
     return out
 
 
+# ---- calibration errors (csrc/replay_plan.h, CALIB; include/msckf_hip.h, msckf_hip_replay_set_imu_calib / _set_cam_calib): per
+# trajectory an IMU record [31] = T_g, T_a, G (3 x 3 row-major each), sat_g, sat_a, lsb_g, lsb_a and a camera record
+# (e_u, e_v, d_u, d_v, k1, k2, p1, p2), on top of either noise model, the faults and the timing.  Every operation below is one
+# rounded double operation in the header's order: the device's noise-free bits are these.
+REPLAY_EXTRINSIC_STREAM = (1 << 63) + 3
+IMU_CAL, CAM_CAL = 31, 8
+
+
+def imu_calib_identity():
+    """the identity IMU record: T_g = T_a = I, everything else 0"""
+    ic = np.zeros(IMU_CAL)
+    ic[[0, 4, 8, 9, 13, 17]] = 1.0
+    return ic
+
+
+def replay_imu_calib_row(rd6, imucal):
+    """c [k][6] of samples with the sequence values rd6 [k][6] (omega, a): c_a = T_a v_a, c_g = T_g v_g then + G v_a column by
+    column -- the first product, then each further product added, every product and sum rounded"""
+    v = np.asarray(rd6, dtype=np.float64).reshape(-1, 6)
+    ic = np.asarray(imucal, dtype=np.float64)
+    Tg, Ta, G = ic[0:9].reshape(3, 3), ic[9:18].reshape(3, 3), ic[18:27].reshape(3, 3)
+    c = np.zeros_like(v)
+    for r in range(3):
+        a = Tg[r, 0] * v[:, 0]
+        a = a + Tg[r, 1] * v[:, 1]
+        a = a + Tg[r, 2] * v[:, 2]
+        a = a + G[r, 0] * v[:, 3]
+        a = a + G[r, 1] * v[:, 4]
+        a = a + G[r, 2] * v[:, 5]
+        c[:, r] = a
+        a = Ta[r, 0] * v[:, 3]
+        a = a + Ta[r, 1] * v[:, 4]
+        a = a + Ta[r, 2] * v[:, 5]
+        c[:, 3 + r] = a
+    return c
+
+
+def replay_imu_calib_out(x6, imucal):
+    """saturation and quantisation of the values x6 [k][6] (noise included): (values, clipped [k][6] bool).  sat > 0:
+    min(max(x, -sat), sat), clipped where x lay strictly outside [-sat, sat]; lsb > 0: lsb rint(x / lsb), rint to nearest even"""
+    x = np.array(x6, dtype=np.float64).reshape(-1, 6)
+    ic = np.asarray(imucal, dtype=np.float64)
+    clipped = np.zeros(x.shape, dtype=bool)
+    for cols, sat, lsb in ((slice(0, 3), ic[27], ic[29]), (slice(3, 6), ic[28], ic[30])):
+        if sat > 0.0:
+            clipped[:, cols] = (x[:, cols] < -sat) | (x[:, cols] > sat)
+            x[:, cols] = np.minimum(np.maximum(x[:, cols], -sat), sat)
+        if lsb > 0.0:
+            x[:, cols] = lsb * np.rint(x[:, cols] / lsb)
+    return x, clipped
+
+
+def replay_cam_calib(obs, camcal):
+    """the camera's residual map of the values obs [n][2] under camcal = (e_u, e_v, d_u, d_v, k1, k2, p1, p2), [n][2]"""
+    ob = np.asarray(obs, dtype=np.float64).reshape(-1, 2)
+    e_u, e_v, d_u, d_v, k1, k2, p1, p2 = (np.float64(t) for t in camcal)
+    x, y = ob[:, 0], ob[:, 1]
+    xx, yy, xy = x * x, y * y, x * y
+    r2 = xx + yy
+    rad = (1.0 + k1 * r2) + k2 * (r2 * r2)
+    xd = (x * rad + (2.0 * p1) * xy) + p2 * (r2 + 2.0 * xx)
+    yd = (y * rad + p1 * (r2 + 2.0 * yy)) + (2.0 * p2) * xy
+    return np.stack([(xd + e_u * xd) + d_u, (yd + e_v * yd) + d_v], -1)
+
+
+def replay_expand_calibrated(seq_traj, frame, seed, sigma4=None, model=None, imucal=None, camcal=None, timing4=None, fault4=None,
+                             delta=None, table=None):
+    """frame `frame` of the noise-free Trajectory seq_traj under the calibration records, composed with the timing shift (timing4,
+    or the known deltas) before and the faults (fault4) after, as replay_expand_timed / replay_expand_faulted compose them.
+    sigma4 for the white noise, or model = (L, scale, sigma_uv, w_start) for the Q_imu model.  dict of rd [K][7], rd_cal [K][6]
+    (the noise-free c), clip [K] (6-bit masks), obs_cal [n][2] (mapped, noise-free, sequence order), Mp, slots, obs (partition
+    order), code"""
+    if (sigma4 is None) == (model is None):
+        raise ValueError("one of sigma4 and model")
+    fr = seq_traj.frames[frame]
+    rd = np.array(seq_traj.imu_for_frame(frame), dtype=np.float64).reshape(-1, 7)
+    ic = imu_calib_identity() if imucal is None else np.asarray(imucal, dtype=np.float64)
+    cc = np.zeros(CAM_CAL) if camcal is None else np.asarray(camcal, dtype=np.float64)
+    obs = np.asarray(fr["obs"], dtype=np.float64).reshape(-1, 2)
+    if timing4 is not None or delta is not None:
+        obs = _replay_timed_obs(seq_traj, frame, seed, timing4, delta, table)
+    obs_cal = replay_cam_calib(obs, cc)
+    cal = rd.copy()
+    cal[:, :6] = replay_imu_calib_row(rd[:, :6], ic)
+    if model is None:
+        out, nobs = replay_cell(cal, obs_cal, frame, seed, sigma4)
+    else:
+        L, scale, sigma_uv, w_start = model
+        if w_start is None:
+            w_start = replay_walk(seq_traj, seed, L, scale)[frame]
+        out, nobs = replay_model_cell(cal, obs_cal, frame, seed, L, scale, sigma_uv, w_start)[:2]
+    out[:, :6], clipped = replay_imu_calib_out(out[:, :6], ic)
+    clip = (clipped.astype(np.int32) << np.arange(6, dtype=np.int32)).sum(1).astype(np.int32)
+    Mp, slots, fobs, code = _replay_faulted(frame, seed, fr["M"], fr["slots"], nobs, np.zeros(4) if fault4 is None else fault4)
+    return dict(rd=out, rd_cal=cal[:, :6], clip=clip, obs_cal=obs_cal, Mp=Mp, slots=slots, obs=fobs, code=code)
+
+
+def replay_calib_counts(seq_traj_or_cells, seed, imucal, f0, f1, sigma4=None, model=None):
+    """msckf_hip_replay_calib_counts for one trajectory: int64 [8] = samples, gyro x y z clipped, accelerometer x y z clipped,
+    samples with any component clipped, over the frames [f0, f1) of a noise-free Trajectory or a list of per-frame readings
+    [k][7] (None: a skipped cell); sigma4 = (sigma_g, sigma_a, ., .) or model = (L, scale)"""
+    cells = _replay_cells(seq_traj_or_cells)
+    if (sigma4 is None) == (model is None):
+        raise ValueError("one of sigma4 and model")
+    ic = imu_calib_identity() if imucal is None else np.asarray(imucal, dtype=np.float64)
+    W = None if model is None else replay_walk(cells, seed, model[0], model[1])
+    out = np.zeros(8, dtype=np.int64)
+    for f in range(int(f0), int(f1)):
+        rd = cells[f]
+        if not len(rd):
+            continue
+        cal = rd.copy()
+        cal[:, :6] = replay_imu_calib_row(rd[:, :6], ic)
+        if model is None:
+            rows = replay_cell(cal, np.zeros((0, 2)), f, seed, sigma4)[0]
+        else:
+            rows = replay_model_cell(cal, np.zeros((0, 2)), f, seed, model[0], model[1], (0.0, 0.0), W[f])[0]
+        clipped = replay_imu_calib_out(rows[:, :6], ic)[1]
+        out[0] += len(rows)
+        out[1:7] += clipped.sum(0)
+        out[7] += int(clipped.any(1).sum())
+    return out
+
+
+def _small_matrix(scale, misalign):
+    """diag(1 + scale) + the off-diagonal misalignment [6] = (xy, xz, yx, yz, zx, zy): row r picks up misalign * axis c"""
+    T = np.diag(1.0 + np.broadcast_to(np.asarray(scale, dtype=np.float64), (3,)))
+    m = np.broadcast_to(np.asarray(misalign, dtype=np.float64), (6,))
+    T[0, 1], T[0, 2], T[1, 0], T[1, 2], T[2, 0], T[2, 1] = m
+    return T
+
+
+def imu_calib_record(scale_g=0.0, misalign_g=0.0, scale_a=0.0, misalign_a=0.0, g_sens=0.0, sat_g=0.0, sat_a=0.0, lsb_g=0.0, lsb_a=0.0):
+    """an IMU record [31]: T = diag(1 + scale) + misalignment (scale a scalar or [3]; misalign a scalar or [6] = the off-diagonal
+    entries xy, xz, yx, yz, zx, zy [rad]), G = g_sens (a scalar for every entry, or 3 x 3) [rad/s per m/s^2], saturation levels
+    and quantisation steps (0: none)"""
+    G = np.broadcast_to(np.asarray(g_sens, dtype=np.float64), (3, 3)) if np.ndim(g_sens) == 0 else np.asarray(g_sens, dtype=np.float64).reshape(3, 3)
+    return np.concatenate([_small_matrix(scale_g, misalign_g).ravel(), _small_matrix(scale_a, misalign_a).ravel(), np.ravel(G),
+                           [float(sat_g), float(sat_a), float(lsb_g), float(lsb_a)]])
+
+
+def cam_calib_record(e_u=0.0, e_v=0.0, d_u=0.0, d_v=0.0, k1=0.0, k2=0.0, p1=0.0, p2=0.0):
+    """a camera record [8]: relative focal-length errors, principal-point errors over the focal length, residual radtan coefficients"""
+    return np.array([e_u, e_v, d_u, d_v, k1, k2, p1, p2], dtype=np.float64)
+
+
+def cam_calib_from_intrinsics(true, assumed):
+    """the first-order record of a camera that IS `true` and is undistorted with `assumed`, each (f_u, f_v, c_u, c_v, k1, k2, p1,
+    p2) of a pinhole-radtan model: e = f_true / f_assumed - 1, d = (c_true - c_assumed) / f_assumed, and the coefficient
+    differences.  Exact to first order in the perturbation around an assumed calibration without distortion; around one with
+    distortion delta the residual also has a cross term of the order perturbation x delta"""
+    t, a = np.asarray(true, dtype=np.float64), np.asarray(assumed, dtype=np.float64)
+    return np.array([t[0] / a[0] - 1.0, t[1] / a[1] - 1.0, (t[2] - a[2]) / a[0], (t[3] - a[3]) / a[1], t[4] - a[4], t[5] - a[5], t[6] - a[6], t[7] - a[7]])
+
+
+def perturbed_cam12(cam12, seed, sigma_rot, sigma_trans):
+    """a trajectory's own camera-IMU extrinsic error, for initialize (which takes the camera block per trajectory: no kernel is
+    involved): cam12 = (c_u, c_v, f_u, f_v, b, q_CI [4], p_C_I [3]) with q_CI <- update_quat(sigma_rot n[0:3]) q_CI and
+    p_C_I += sigma_trans n[3:6], n the pairs 0 .. 2 of the sub-seed mix(seed, 2^63 + 3) (2^63 .. 2^63 + 2 are taken by the
+    initial error, the faults and the timing)"""
+    out = np.array(cam12, dtype=np.float64)
+    n = replay_pairs(int(replay_mix(seed, REPLAY_EXTRINSIC_STREAM)), 3).reshape(6)
+    q = quat_mul(update_quat(float(sigma_rot) * n[0:3]), out[5:9])
+    out[5:9] = q / np.linalg.norm(q)
+    out[9:12] = out[9:12] + float(sigma_trans) * n[3:6]
+    return out
+
+
 def rot_to_quat(R):
     """Rotation matrix -> (w,x,y,z) such that Eigen's toRotationMatrix() gives R back."""
     t = np.trace(R)
