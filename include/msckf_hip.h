@@ -176,8 +176,8 @@ int msckf_hip_get_error_flags(msckf_hip_handle h, int b, int* flags);
 int msckf_hip_last_tracks(msckf_hip_handle h, int b, double* out8, int cap);
 int msckf_hip_last_deltax(msckf_hip_handle h, int b, double* dx, int cap);
 /* per track of the last marginalize, what the feature kernels stored for the information-form route (-ENOTSUP on handles without
- * it or with an f16 Jacobian): first[t] = first | last << 8 camera slot of the track; Hx[t][m_cap][12] the whitened 2 x 6
- * Jacobian block of every observation; rw[t][m_cap][2] the whitened residuals; Bh[t][3][6 n_cap + 1] the three rows of B^ (the
+ * it; an f16 Jacobian is read as stored and widened, so Hx holds exact binary16 values): first[t] = first | last << 8 camera slot
+ * of the track; Hx[t][m_cap][12] the whitened 2 x 6 Jacobian block of every observation; rw[t][m_cap][2] the whitened residuals; Bh[t][3][6 n_cap + 1] the three rows of B^ (the
  * window's camera columns, c in column 6 n_cam).  Entries beyond a track's observations, and columns of B^ outside its slot
  * range, are whatever the buffers held.  Returns the number of tracks (at most cap). */
 int msckf_hip_last_track_blocks(msckf_hip_handle h, int b, int* first, double* Hx, double* rw, double* Bh, int cap);

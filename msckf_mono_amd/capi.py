@@ -313,7 +313,9 @@ class Batch:
 
     def last_track_blocks(self, b):
         """per track of the last marginalize, as the feature kernels stored it for the information form: dict of first [F], last [F]
-        (camera slots), Hx [F][m_cap][2][6], rw [F][m_cap][2], B [F][3][6 n_cap + 1] (stale where a track has no observation / slot)"""
+        (camera slots), Hx [F][m_cap][2][6], rw [F][m_cap][2], B [F][3][6 n_cap + 1] (stale where a track has no observation / slot).
+        On an F16H handle Hx is the stored fp16 blocks, widened: every entry is exactly a binary16 value.  -ENOTSUP only on handles
+        without the information form."""
         F, m, nc = self.f_cap, self.m_cap, 6 * self.n_cap + 1
         first, Hx, rw, Bh = np.zeros(F, np.int32), np.zeros((F, m, 2, 6)), np.zeros((F, m, 2)), np.zeros((F, 3, nc))
         n = _chk(self.L.msckf_hip_last_track_blocks(self.h, int(b), first.ctypes.data_as(_ip), Hx.ctypes.data_as(_dp), rw.ctypes.data_as(_dp),

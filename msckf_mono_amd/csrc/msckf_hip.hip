@@ -2129,20 +2129,22 @@ struct Batch : BatchCore {
   // outside its slot range are whatever the buffers held): first [F], Hx [F][m_cap][12], rw [F][m_cap][2], Bh [F][3][6 n_cap + 1]
   int track_blocks(int b, int* first, double* Hx, double* rw, double* Bh, int cap) override {
     if (int rc = enter_traj(b)) return rc;
-    if (!d.trk_B || !d.trk_Hx || !d.trk_rw) return fail(-ENOTSUP, "the per-track blocks exist on the information-form route with an f32 / f64 Jacobian only");
+    if (!d.trk_B || !(d.h16 ? (const void*)d.trk_Hx16 : (const void*)d.trk_Hx) || !d.trk_rw) return fail(-ENOTSUP, "the per-track blocks exist on the information-form route only");
     int tmp[STAT_STRIDE];
     if (const int rc = read_back(tmp, d.stats + (size_t)b * STAT_STRIDE, sizeof(tmp))) return rc;
     const int F = tmp[STAT_NTRACKS];
     if (F > cap) return fail(-E2BIG, "output buffer too small");
     if (!F) return 0;
     const size_t tb = (size_t)b * f_cap, nh = (size_t)F * m_cap * 12, nr = (size_t)F * 2 * m_cap, ldR = (size_t)d.ldR, nB = (size_t)F * 3 * ldR, nc = 6 * (size_t)n_cap + 1;
-    std::vector<S> hx(nh), r(nr); std::vector<double> bb(nB);
+    std::vector<S> hx(d.h16 ? 0 : nh), r(nr); std::vector<__half> hx16(d.h16 ? nh : 0); std::vector<double> bb(nB);
     HIPCHK(hipMemcpyAsync(first, d.trk_first + tb, F * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(hx.data(), d.trk_Hx + tb * m_cap * 12, nh * sizeof(S), hipMemcpyDeviceToHost, st));
+    if (d.h16) HIPCHK(hipMemcpyAsync(hx16.data(), d.trk_Hx16 + tb * m_cap * 12, nh * sizeof(__half), hipMemcpyDeviceToHost, st));   // as stored: fp16, widened below
+    else HIPCHK(hipMemcpyAsync(hx.data(), d.trk_Hx + tb * m_cap * 12, nh * sizeof(S), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(r.data(), d.trk_rw + tb * 2 * m_cap, nr * sizeof(S), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(bb.data(), d.trk_B + tb * 3 * ldR, nB * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (size_t i = 0; i < nh; ++i) Hx[i] = (double)hx[i];
+    if (d.h16) for (size_t i = 0; i < nh; ++i) Hx[i] = (double)__half2float(hx16[i]);
+    else for (size_t i = 0; i < nh; ++i) Hx[i] = (double)hx[i];
     for (size_t i = 0; i < nr; ++i) rw[i] = (double)r[i];
     for (size_t q = 0; q < (size_t)F * 3; ++q) for (size_t c = 0; c < nc; ++c) Bh[q * nc + c] = bb[q * ldR + c];
     return F;

@@ -415,3 +415,34 @@ def mutate(win, track, which):
     else:
         raise ValueError(which)
     return t
+
+
+# ------------------------------------------------------------------------------------------------------------ the early-accept line
+# Tracks on both sides of the early-accept rule of msckf_hip_set_gate_early_accept, ub = |r_o|^2 / sigma^2 < 0.5 * threshold: per
+# length class LINE_SUBS landmarks (`spread` slots, a landmark and unit noise of their own), each at the two noise sizes where the
+# double twin of tests/h16_lab.py puts ub / (0.5 * threshold) at 0.98 and at 1.02 -- found by bisection on the CPU (ub grows with
+# the square of the noise); tests/test_feature_inputs.py asserts that they land there.  A float kernel's ub differs by ~1e-5: both
+# sides are far outside the 1e-3 band in which either report is accepted.
+LINE_LENGTHS = (2, 3, 16, 30, 31, 62)
+LINE_TARGETS = (0.98, 1.02)
+LINE_SUBS = 2
+LINE_TOL = 1e-4                       # how close to its target a line case's ratio is (asserted on the CPU)
+LINE_NOISE_PX = {(2, 0, 0.98): 7.22122573, (2, 0, 1.02): 7.36258755, (2, 1, 0.98): 1.29741525, (2, 1, 1.02): 1.32307730,
+                 (3, 0, 0.98): 3.01268468, (3, 0, 1.02): 3.06830646, (3, 1, 0.98): 2.19028855, (3, 1, 1.02): 2.23419040,
+                 (16, 0, 0.98): 2.91333937, (16, 0, 1.02): 2.97334564, (16, 1, 0.98): 2.78549022, (16, 1, 1.02): 2.84155778,
+                 (30, 0, 0.98): 2.75003289, (30, 0, 1.02): 2.80535436, (30, 1, 0.98): 3.09777572, (30, 1, 1.02): 3.16013138,
+                 (31, 0, 0.98): 2.85974972, (31, 0, 1.02): 2.91741167, (31, 1, 0.98): 3.08037391, (31, 1, 1.02): 3.14223710,
+                 (62, 0, 0.98): 2.70816967, (62, 0, 1.02): 2.76285612, (62, 1, 0.98): 3.06557625, (62, 1, 1.02): 3.12725493}
+
+
+def line_case(win, L, sub, target):
+    rng = sc.SplitMix64(0x11AE0000 + 1009 * L + 7 * int(sub))
+    lm = _landmarks(win, rng, 1)
+    noise = rng.normal(N_WIN * 2).reshape(N_WIN, 2)
+    return make_track(win, lm[0], noise, "spread", L, LINE_NOISE_PX[(L, sub, target)], kind="line")
+
+
+def line_cases(po, m_cap=N_WIN):
+    """the line cases of at most m_cap observations, the 0.98 and the 1.02 case of a landmark next to each other"""
+    win = window(po)
+    return [line_case(win, L, sub, tg) for L in LINE_LENGTHS if L <= m_cap for sub in range(LINE_SUBS) for tg in LINE_TARGETS]

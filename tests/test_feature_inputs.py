@@ -148,3 +148,25 @@ def test_mutants_and_one_track_update_at_every_edge_length(po, win, L):
         if m == "drop_last" and L > 2:                  # (L = 2: the mutant is motion-rejected, no update at all)
             em = FL.update_errors(out[2], out[3], dx, dP)
             assert em[0] >= 10 * FL.ONE_TRACK_FLOAT_FACTOR * e32[0] and em[1] >= 10 * FL.ONE_TRACK_FLOAT_FACTOR * e32[1], (L, em, e32)
+
+
+def test_early_accept_line_cases_land_on_both_sides_of_the_line(po, win):
+    """feature_lab.line_cases: per length class and landmark one track whose |r_o|^2 / sigma^2 is 0.98 of half its chi-square
+    threshold and one at 1.02 (the double twin of tests/h16_lab.py, which the double oracle agrees with on gamma and the
+    decision); both have a Jacobian and pass the gate, the second one by the real statistic: gamma <= ub = 0.51 x threshold."""
+    import h16_lab as HL
+    cases = FL.line_cases(po)
+    assert len(cases) == len(FL.LINE_LENGTHS) * FL.LINE_SUBS * len(FL.LINE_TARGETS)
+    infos = HL.line_reference(po)
+    rows, _ = FL.run_oracle(win, po.F64, cases)
+    k = 0
+    for L in FL.LINE_LENGTHS:
+        for sub in range(FL.LINE_SUBS):
+            for tg in FL.LINE_TARGETS:
+                t, i = cases[k], infos[k]
+                assert t.L == L and t.kind == "line" and i["own"] is not None and i["thresh"] == FL.chi2_threshold(L)
+                ratio = i["ub"] / (0.5 * i["thresh"])
+                assert abs(ratio - tg) <= FL.LINE_TOL, (L, sub, tg, ratio)
+                assert list(rows[k, :3]) == [1, 1, 1] and abs(rows[k, 4] - i["gamma"]) <= 1e-9 * i["gamma"], (L, sub, tg, rows[k], i["gamma"])
+                assert i["gamma"] < 0.52 * i["thresh"]
+                k += 1

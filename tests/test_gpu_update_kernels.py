@@ -20,8 +20,8 @@ silently empty a case.  The settings are read when the handle is created, so the
 Found while writing this suite: the one-launch update fits windows of at most 12 cameras (routes::small_limit(84) = 72 columns),
 not the 14 the setting asks for; 13 and 14 cameras take the chain.  Hence 12 among the sizes, and `mixed` from n_cap 14 on.
 
-Out of scope: the fp16-Jacobian dtype (an envelope of its own), the early-accept bound, tracks longer than 30 (the feature routes:
-tests/test_gpu_feature_kernels.py); the anisotropic and literal routes and aniso_mode == 1 are tests/test_gpu_literal_kernels.py's.
+Out of scope: the fp16-Jacobian dtype (tests/test_gpu_h16_kernels.py holds it to a given-H twin on these windows), the early-accept
+bound (tests/test_gpu_gate_early.py), tracks longer than 30 (the feature routes: tests/test_gpu_feature_kernels.py); the anisotropic and literal routes and aniso_mode == 1 are tests/test_gpu_literal_kernels.py's.
 The `tsqr` variant below holds the Householder TSQR route on THESE lists only (every track from slot 0, all or none passing, at
 most 720 rows); everything else about that route -- every k_qr_update instantiation, the chunk counts, staggered first slots,
 compactions with holes, blind cameras, stacks deeper than the pipeline and longer than the progress ring, the route taken by
