@@ -689,9 +689,18 @@ int msckf_hip_set_feature_overlap(msckf_hip_handle h, int on);
  * frame, and every frame of a double handle, takes order 0: propagate + augmentState, per-track kernel, selection.
  * Bit-identical results either way.  -EINVAL for any other value.
  * msckf_hip_get_frame_order_count: how many frames took order 1 since the handle was created, counted once per slice
- * (msckf_hip_set_streams) and frame. */
+ * (msckf_hip_set_streams) and frame.
+ * msckf_hip_set_frame_order_chol (on by default; it acts under order 1 only): "order 2".  Where a frame that takes order 1 runs
+ * the kernel chain with a one-level Gram Cholesky (information form, windows up to 31 cameras; no trajectory of the slice in the
+ * one-launch update of short windows, none of the batch on the literal anisotropic route) the selection keeps a launch of its own
+ * and propagate + augmentState run inside the Gram Cholesky's launch, on compute units the factorization leaves idle -- off the
+ * frame's latency chain altogether.  A frame that cannot takes order 1 as described above.  Bit-identical results either way.
+ * (A switch of its own and not a value 2 of msckf_hip_set_frame_order, which keeps refusing every value but 0 and 1.)
+ * msckf_hip_get_frame_order_chol_count: those of msckf_hip_get_frame_order_count's frames that took order 2. */
 int msckf_hip_set_frame_order(msckf_hip_handle h, int order);
 int msckf_hip_get_frame_order_count(msckf_hip_handle h, long long* count);
+int msckf_hip_set_frame_order_chol(msckf_hip_handle h, int on);
+int msckf_hip_get_frame_order_chol_count(msckf_hip_handle h, long long* count);
 /* Anisotropic pixel noise, u_var_prime != v_var_prime (see the header comment): mode 0 (default) the reference's
  * R_o_j = A_j^T R_j A_j / HouseholderQR in column order / R_n = Q_1^T R_o Q_1 on the device (msckf.h:423-431, 1343-1366;
  * f64: the Householder sweep for its decisions, the result as a projection onto range(Q_1), kernels_literal.hip), handed to the

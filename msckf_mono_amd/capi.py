@@ -43,7 +43,7 @@ SYMBOLS = [
     "msckf_hip_replay_expand_ints", "msckf_hip_replay_assign_q", "msckf_hip_replay_walk", "msckf_hip_last_track_blocks",
     "msckf_hip_replay_set_faults", "msckf_hip_replay_expand_faults", "msckf_hip_replay_fault_counts", "msckf_hip_map_log_fault_metrics",
     "msckf_hip_replay_set_timing", "msckf_hip_replay_image_table", "msckf_hip_replay_expand_timing",
-    "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count",
+    "msckf_hip_set_frame_order", "msckf_hip_get_frame_order_count", "msckf_hip_set_frame_order_chol", "msckf_hip_get_frame_order_chol_count",
     "msckf_hip_truth_set", "msckf_hip_nees_log_enable", "msckf_hip_nees_log_reset", "msckf_hip_nees_log_count", "msckf_hip_nees_log_read", "msckf_hip_nees_log_ensemble",
     "msckf_hip_frame_log_align", "msckf_hip_frame_log_rpe", "msckf_hip_traj_align", "msckf_hip_traj_rpe",
     "msckf_hip_compile_create", "msckf_hip_compile_destroy", "msckf_hip_compile_image", "msckf_hip_compile_cell", "msckf_hip_replay_imu_sums",
@@ -616,10 +616,21 @@ class Batch:
         frames that allow it, 0 propagate first on every frame; same bits either way."""
         _chk(self.L.msckf_hip_set_frame_order(self.h, int(order)))
 
+    def set_frame_order_chol(self, on):
+        """under order 1 (on by default): propagate + augmentState inside the Gram Cholesky's launch on the frames that allow it,
+        the selection in a launch of its own -- "order 2"; off: order 1 as it is described above; same bits either way."""
+        _chk(self.L.msckf_hip_set_frame_order_chol(self.h, 1 if on else 0))
+
     def frame_order_count(self):
         """frames (one count per slice and frame) that took order 1 since the handle was created"""
         n = C.c_longlong(0)
         _chk(self.L.msckf_hip_get_frame_order_count(self.h, C.byref(n)))
+        return n.value
+
+    def frame_order_chol_count(self):
+        """those of frame_order_count's frames that took order 2"""
+        n = C.c_longlong(0)
+        _chk(self.L.msckf_hip_get_frame_order_chol_count(self.h, C.byref(n)))
         return n.value
 
     def set_gate_early_accept(self, on):

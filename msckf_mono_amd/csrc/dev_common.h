@@ -174,6 +174,14 @@ template <class S> __device__ __forceinline__ bool other_route(const Dev<S>& d, 
   return d.small_split != 0 && (6 * ncam <= d.small_split) != small_kernel;
 }
 
+// Window size of trajectory b as the launches of its update see it.  A kernel of the update that runs BEFORE the frame's
+// augmentState has ended (ncam_bias: the early k_feature; the selection and block-diagonal roles of k_propagate's HEAD instance,
+// in whose launch another workgroup commits and increments ncam; and on the frame step's order 2 the selection, k_gram and the
+// Gram Cholesky, whose launch holds that workgroup) takes it from ncam_upd, "the size after the next augment", which the
+// previous frame's prune left and nothing writes before this frame's own prune.
+template <class S>
+__device__ __forceinline__ int update_ncam(const Dev<S>& d, int b) { return d.ncam_bias ? d.ncam_upd[b] : d.ncam[b]; }
+
 // first observation of track t of the launch's i-th trajectory in trk_slots / trk_obs
 template <class S> __device__ __forceinline__ long wl_first(const Dev<S>& d, int i, int t) {
   return d.trk_off ? (long)d.trk_off[(long)i * d.wl_stride_f + t] : (long)i * d.wl_stride_o + (long)t * d.m_cap;
@@ -541,6 +549,8 @@ template <class S> void launch_select(const Dev<S>& d, int b0, int nb, hipStream
 template <class S> void launch_select_diag(const Dev<S>& d, int b0, int nb, hipStream_t st);   // k_select + block-diagonal part of Lam^ in one launch
 // launch_select_diag's workgroups and launch_propagate's (then_augment, qroute 0 | 2) in ONE launch (k_propagate's HEAD instance, kernels_state.hip; float only)
 template <class S> void launch_frame_head(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, int qroute, const int* cnt);
+// launch_gram's phase 2 at one Cholesky level and launch_propagate's workgroups (then_augment, qroute 0 | 2) in ONE launch (k_propagate's CHOL instances, kernels_state.hip; float only)
+template <class S> void launch_chol_gram_propagate(const Dev<S>& d, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, int qroute, const int* cnt);
 // phase: 0 = stage 1 + merges, 1 = stage 1 only (chunk-local QR updates), 2 = merge tree only
 template <class S> void launch_compress(const Dev<S>& d, int b0, int nb, hipStream_t st, int phase);
 // phase: 0 = both, 1 = Gram accumulation only, 2 = Cholesky only, 3 = SYRK only (the block-diagonal part came with launch_select_diag)

@@ -69,6 +69,45 @@ inline FrameOrderRefusal frame_order(int setting, int overlap_feature, size_t sc
   return feature_ahead(nb, ncam, maxslot, k, skip_mark, n_cap, first_frame, prof);
 }
 
+// ---------------------------------------------------------------- order 2: propagate + augmentState inside the Gram Cholesky's launch
+// The frame still enqueues k_feature first; the selection keeps a launch of its own (k_select_diag), k_gram follows, and
+// propagate + augmentState ride in the one-level Gram Cholesky's launch, one workgroup per trajectory beside the factorization's
+// (k_propagate's CHOL instances, kernels_state.hip).  The selection, k_gram and the Cholesky take the window size from ncam_upd.
+// Nothing reads what propagate + augmentState write before the PHt product, the launch behind.
+// why a slice's frame that could take it keeps order 1 (or 0); FC_TAKEN: it does not
+enum FrameOrderCholRefusal {
+  FC_TAKEN = 0,
+  FC_SETTING,      // the handle asks for order 0 (msckf_hip_set_frame_order) or switched the form off (msckf_hip_set_frame_order_chol)
+  FC_ORDER1,       // order 1 is not taken (frame_order names the reason): nothing has run k_feature ahead of augmentState
+  FC_LEVELS,       // the compression is not the information form with a ONE-level Cholesky (TSQR, or two levels beyond 192 columns:
+                   // its first level is followed by k_trsm_rows, and only the CH_GRAM instances have the joint form)
+  FC_SMALL,        // some trajectory of the slice's frame has its update in k_update_small: no Cholesky launch to ride in
+                   // (SMALL_ONLY), or one that leaves the small trajectories' workgroups at once (SMALL_AND_CHAIN)
+  FC_LITERAL       // a trajectory of the batch is on the literal anisotropic route: its launches sit between k_gram and the Cholesky
+};
+inline const char* frame_order_chol_text(FrameOrderCholRefusal r) {
+  switch (r) {
+    case FC_TAKEN: return "in_cholesky";
+    case FC_SETTING: return "setting";
+    case FC_ORDER1: return "order1_refused";
+    case FC_LEVELS: return "chol_levels";
+    case FC_SMALL: return "small_update";
+    case FC_LITERAL: return "literal";
+  }
+  return "?";
+}
+// Does the slice's frame take order 2?  setting: the handle's effective order (FrameSettings::effective: 2 asks for it, the default); order1: frame_order's answer for the
+// same frame; info, chol_levels: routes::compress_route's; chain_only: routes::small_route's kind is CHAIN_ONLY for the slice's
+// frame; n_lit: trajectories of the batch on the literal anisotropic route.
+inline FrameOrderCholRefusal frame_order_chol(int setting, FrameOrderRefusal order1, bool info, int chol_levels, bool chain_only, int n_lit) {
+  if (setting < 2) return FC_SETTING;
+  if (order1 != FO_TAKEN) return FC_ORDER1;
+  if (!info || chol_levels != 1) return FC_LEVELS;
+  if (!chain_only) return FC_SMALL;
+  if (n_lit > 0) return FC_LITERAL;
+  return FC_TAKEN;
+}
+
 }  // namespace routes
 }  // namespace msckf
 #endif

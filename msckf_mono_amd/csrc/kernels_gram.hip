@@ -53,7 +53,8 @@ __global__ __launch_bounds__(512) void k_gram(Dev<S> d, int b0, int nb, int npai
   if (!xcd_item(nb, npairs, bi, bxi)) return;
   const int b = b0 + bi, grp = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6;
   const int* st = d.stats + (long)b * STAT_STRIDE;
-  const int mrows_ = st[STAT_MROWS], P = st[STAT_PASSED], N = d.ncam[b];   // independent scalar loads, one wait
+  // (window size through update_ncam: on the frame step's order 2 this launch runs before the frame's augmentState, frame_order.h)
+  const int mrows_ = st[STAT_MROWS], P = st[STAT_PASSED], N = update_ncam(d, b);   // independent scalar loads, one wait
   if (mrows_ == 0 || other_route(d, N, false)) return;
   const int n = 6 * N, ldL = d.ldR, f_cap = d.f_cap, m_cap = d.m_cap;
   const int* order = d.trk_order + (long)b * f_cap;

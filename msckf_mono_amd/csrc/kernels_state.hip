@@ -13,6 +13,7 @@
 // computes the unused determinant of msckf.h:176.
 #include "dev_common.h"
 #include "select_diag.h"
+#include "chol_mfma.h"
 
 namespace msckf {
 
@@ -186,12 +187,40 @@ __global__ __launch_bounds__(256) void k_augment(Dev<S> d, int b0, const int* cn
 //   imu[b], P, cam[b][ncam]   propagate / augmentState W; selection and sums read none of them (k_feature, the launch before,
 //                read IG of imu, the P blocks and the camera states below the newest slot)
 //   Dg, row_start, trk_order  sums W / selection W; propagate neither
-// nb, ndiag: read by a HEAD launch only.
-template <class S, bool AUGMENT, int QM, bool HEAD = false>
-__global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K, const int* cnt, int nb, int ndiag) {
+// nb, ndiag: read by a HEAD launch only (nb by a CHOL launch too).
+//
+// CHOL (k_propagate<float, true, QM, false, 4 | 8 | 12>, launch_chol_gram_propagate): the frame step's order 2
+// (routes::frame_order_chol, frame_order.h).  k_feature, the selection's own launch (k_select_diag) and k_gram have run in front
+// of this launch, all three with the window size from ncam_upd, and nothing reads what propagate + augmentState write before the
+// PHt product, the launch behind this one.  The launch is ONE grid of 2 nb workgroups of 1 024 threads: workgroups x < nb are
+// the one-level Gram Cholesky of CHOL column blocks (chol_mfma_body, chol_mfma.h: the body k_chol_mfma<double, float, CHOL, 0,
+// CH_GRAM, 1> runs) -- the chain, first in the grid --, workgroup nb + i is propagate + augmentState of the launch's i-th trajectory.
+// The Cholesky keeps one workgroup per compute unit whatever runs beside it, so the propagate workgroups go to other compute units
+// and end while the factorization's pivot chains are under way.  The propagate body is still 256 threads wide: the other twelve
+// wavefronts of its workgroup are parked -- their tid is PARKED, which fails every range test and ends every strided loop of the
+// body at once, so they store nothing and only meet the barriers (no barrier is left to wavefronts that have ended).
+// Words of trajectory b that both roles of a CHOL launch touch or that one writes and the other could be thought to read:
+//   ncam[b]      propagate W (deferred commit, augmentState's increment); the Cholesky takes the window size from
+//                ncam_upd[b] (update_ncam, d.ncam_bias = 1 in this launch, as in the selection's and k_gram's launches in front)
+//   ncam_upd[b]  R by both; written by the previous and by this frame's prune only
+//   stats[b]     Cholesky R STAT_MROWS (the selection's), W STAT_RROWS; augmentState ORs STAT_ERR only for a full window, which
+//                the host keeps on order 1 (and that on order 0); propagate none
+//   n_resid[b], nres_upd[b]   neither (the selection's launch has ended)
+//   imu[b], P, cam[b][N - 1]  propagate / augmentState W; the Cholesky reads Lam^, Dg and writes Rbuf (T_H, r_n), k_gram in front
+//                read trk_B, trk_order, row_start, stats -- none of them the filter's state: the first reader of imu, P and the
+//                newest camera state is the PHt product
+//   Lam, Dg, Rbuf             Cholesky R / R / W; propagate none
+// So no reader of the launch meets a writer of it.
+template <class S, bool AUGMENT, int QM, bool HEAD = false, int CHOL = 0>
+__global__ __launch_bounds__(CHOL ? 1024 : 256) void k_propagate(Dev<S> d, int b0, const S* readings, long rd_stride, int K, const int* cnt, int nb, int ndiag) {
   if (HEAD && (int)blockIdx.x <= ndiag) { select_diag_body<S>(d, b0, nb, ndiag, (int)blockIdx.x, (int)blockIdx.y); return; }
-  const int b = b0 + (HEAD ? blockIdx.y : blockIdx.x), tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (cnt) K = cnt[HEAD ? blockIdx.y : blockIdx.x];
+  if constexpr (CHOL != 0) {
+    if ((int)blockIdx.x < nb) { chol_mfma_body<double, S, CHOL, 0, CH_GRAM, 1, true>(d, b0, nb, (int)blockIdx.x); return; }
+  }
+  constexpr int PARKED = 1 << 20;   // tid of a CHOL launch's wavefronts 4 .. 15: beyond every range the body tests
+  const int bix = CHOL ? (int)blockIdx.x - nb : (HEAD ? blockIdx.y : blockIdx.x);
+  const int b = b0 + bix, tid = (CHOL && threadIdx.x >= 256) ? PARKED : (int)threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (cnt) K = cnt[bix];
   constexpr bool FULLQ = QM == 2;
   if (QM != 0 && (d.qf[(long)b * QF_STRIDE + QF_FLAG] != S(0)) != FULLQ) return;   // the other instantiation's trajectory
   __builtin_amdgcn_s_setprio(3);   // latency-bound chain: win instruction arbitration against co-resident throughput waves of the other slice
@@ -227,7 +256,7 @@ __global__ __launch_bounds__(256) void k_propagate(Dev<S> d, int b0, const S* re
   // columns each, B-operand layout of the 16x16x4 MFMA) now, so that the loads fly under the whole chain
   constexpr int PIC_T = 6;   // 4 waves x 6 tiles x 16 columns >= 6 * 63
   S pic[PIC_T][4];
-  {
+  {   // (a CHOL launch's parked wavefronts load too, from the clamped addresses: a branch around these loads cost the Cholesky's side of the 12-block instance 73 spilled registers)
     const int g = lane >> 4, c = lane & 15;
 #pragma unroll
     for (int t = 0; t < PIC_T; ++t) {
@@ -648,6 +677,23 @@ void launch_frame_head(const Dev<S>& d, int b0, int nb, const S* readings, long 
     else hipLaunchKernelGGL((k_propagate<S, true, 2, true>), grid, dim3(256), lds, st, d, b0, readings, rd_stride, K, cnt, nb, ndiag);
   }
 }
+// The frame step's order 2: the one-level Gram Cholesky (what launch_gram's phase 2 launches) and propagate + augmentState in
+// ONE launch, k_propagate's CHOL instances.  d.ncam_bias = 1 and d.compress are the caller's; the caller has asked
+// routes::frame_order_chol (float handle, one-level Cholesky, qroute 0 or 2).
+template <class S>
+void launch_chol_gram_propagate(const Dev<S>& din, int b0, int nb, const S* readings, long rd_stride, int K, hipStream_t st, int qroute, const int* cnt) {
+  if (nb <= 0) return;
+  if constexpr (sizeof(S) == 4) {
+    Dev<S> d = din;
+    const routes::CompressRoute r = routes::compress_route(d.compress, d.ldR, d.Mp != nullptr, d.lam_part > 0, din.gram_parts);
+    d.gram_parts = r.gram_parts;   // (as launch_gram hands it to the Cholesky)
+    const size_t lds = (size_t)6 * d.ld * sizeof(S);
+    dispatch_int<4, 8, 12>(r.nb_a, [&](auto NB) {
+      if (qroute == 0) hipLaunchKernelGGL((k_propagate<S, true, 0, false, NB()>), dim3(2 * nb), dim3(1024), lds, st, d, b0, readings, rd_stride, K, cnt, nb, 0);
+      else hipLaunchKernelGGL((k_propagate<S, true, 2, false, NB()>), dim3(2 * nb), dim3(1024), lds, st, d, b0, readings, rd_stride, K, cnt, nb, 0);
+    });
+  }
+}
 template <class S>
 void launch_augment(const Dev<S>& d, int b0, int nb, hipStream_t st, const int* cnt) {
   if (nb <= 0) return;
@@ -669,6 +715,8 @@ template void launch_propagate<float>(const Dev<float>&, int, int, const float*,
 template void launch_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, bool, int, const int*);
 template void launch_frame_head<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, int, const int*);
 template void launch_frame_head<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, int, const int*);
+template void launch_chol_gram_propagate<float>(const Dev<float>&, int, int, const float*, long, int, hipStream_t, int, const int*);
+template void launch_chol_gram_propagate<double>(const Dev<double>&, int, int, const double*, long, int, hipStream_t, int, const int*);
 template void launch_augment<float>(const Dev<float>&, int, int, hipStream_t, const int*);
 template void launch_augment<double>(const Dev<double>&, int, int, hipStream_t, const int*);
 template void launch_prune<float>(const Dev<float>&, int, int, hipStream_t, const int*, int);

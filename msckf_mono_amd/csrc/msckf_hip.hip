@@ -172,7 +172,9 @@ struct BatchCore {
   // frames of a slice (one count per slice and frame) that took the feature-first order (routes::frame_order) since the handle
   // was created; the slices' enqueue threads count concurrently
   std::atomic<long long> n_feature_first{0};
-  int small_limit = 0;       // settings.small_update as far as it fits k_update_small at this handle's dtype and f_cap (apply_settings): the per-trajectory limit launch_update routes by
+  // ... and those of them that took order 2, propagate + augmentState inside the Gram Cholesky's launch (routes::frame_order_chol)
+  std::atomic<long long> n_in_cholesky{0};
+  int small_limit = 0;      // settings.small_update as far as it fits k_update_small at this handle's dtype and f_cap (apply_settings): the per-trajectory limit launch_update routes by
   bool info_form = false;    // the information form's buffers exist (Dev::trk_B; set by the typed half's create)
   std::vector<double> h_uv;  // [B][2] u_var', v_var' as initialize() got them
   std::vector<char> h_imu_ok;   // [B] the typed half's host copy of the IMU state is current (see Batch<S>::h_imu)
@@ -1395,6 +1397,7 @@ struct BatchCore {
     frame_settings.order = order;
     return 0;
   }
+  int set_frame_order_chol(int on) { frame_settings.in_cholesky = on ? 1 : 0; return 0; }
   int set_compression(int route) {
     if (route < -1 || route > 3) return fail(-EINVAL, "route: -1 default, 0 Householder TSQR, 1..3 information form (blocked matrix-core Cholesky; 1 and 2 named retired factorizations)");
     if (route >= 1 && !info_form) return fail(-ENOTSUP, "information form not available for this window size (6 n_cap + 1 > 384 or f_cap > 1024)");
@@ -1882,17 +1885,35 @@ struct Batch : BatchCore {
   // bits are the trajectory's own (tests/test_gpu_ragged.py holds it: 5 .. 14 cameras alone and beside each other).
   // cell_k (run_frames: the frame's sample counts from b0 on): a skipped cell has no augmentState ahead.
   // select_done (the frame step's feature-first order): k_propagate's HEAD instance has run the selection and the block-diagonal sums already.
-  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr, bool select_done = false) {
+  // ride (the frame step's order 2, routes::frame_order_chol: k_feature has run, the range is CHAIN_ONLY on the one-level
+  // information form, no literal trajectory): the frame's propagate + augmentState, not launched yet, go into the Gram Cholesky's
+  // launch (launch_chol_gram_propagate); the selection, k_gram and that launch take the window size from ncam_upd.
+  struct CholRide { const S* rd; long rd_stride; int K; int q_route; const int* cnt; int ncam_defer; };
+  // the one-launch update's say on a range (routes::small_route) with the handle's own arguments: launch_update and the frame order ask
+  routes::SmallRoute range_small_route(int compress, int b0, int nb, int ncam_ahead, const int* cell_k) const {
+    return routes::small_route(nb, [&](int i) { return routes::window_cols(h_ncam[b0 + i], ncam_ahead, cell_k && cell_k[i] == IMU_SKIP, n_cap); },
+                               small_limit, compress, n_lit, d.joseph, f_cap, sizeof(S), update_small_granted());
+  }
+  void launch_update(const Dev<S>& vin, int b0, int nb, hipStream_t q, bool feature_done = false, int ncam_ahead = 0, const int* cell_k = nullptr, bool select_done = false,
+                     const CholRide* ride = nullptr) {
     invalidate_imu(b0, nb);            // the update corrects the IMU state on the device (msckf.h:1376-1383)
     Dev<S> v = vin;
     v.compress = update_compress();
     if (!feature_done) { stage_begin(2, q); launch_feature<S>(v, b0, nb, q); stage_end(2, q); }
     // information form: k_select and the block-diagonal reduction share a launch (both only read k_feature's outputs)
     const routes::CompressRoute cr = routes::compress_route(v.compress, d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts);
+    if (ride) {
+      Dev<S> v2 = v; v2.ncam_bias = 1;
+      launch_select_diag<S>(v2, b0, nb, q);
+      launch_gram<S>(v2, b0, nb, q, 3);
+      v2.ncam_defer = ride->ncam_defer;
+      launch_chol_gram_propagate<S>(v2, b0, nb, ride->rd, ride->rd_stride, ride->K, q, ride->q_route, ride->cnt);
+      launch_kalman<S>(v, b0, nb, q);
+      return;
+    }
     if (!select_done) { stage_begin(7, q); if (cr.select_diag) launch_select_diag<S>(v, b0, nb, q); else launch_select<S>(v, b0, nb, q); stage_end(7, q); }
     // short windows (single filters, BASELINE configs[1]): everything after the selection in ONE launch (k_update_small)
-    const routes::SmallRoute sr = routes::small_route(nb, [&](int i) { return routes::window_cols(h_ncam[b0 + i], ncam_ahead, cell_k && cell_k[i] == IMU_SKIP, n_cap); },
-                                                      small_limit, v.compress, n_lit, d.joseph, f_cap, sizeof(S), update_small_granted());
+    const routes::SmallRoute sr = range_small_route(v.compress, b0, nb, ncam_ahead, cell_k);
     if (sr.kind != routes::CHAIN_ONLY) {
       v.small_split = sr.small_split;
       stage_begin(5, q); launch_update_small<S>(v, b0, nb, q, sr); stage_end(5, q);
@@ -2320,19 +2341,26 @@ struct Batch : BatchCore {
     // not have ended with a prune -- nor beside a skipped cell, which gets no camera state: ncam_upd would be one too many)
     const int q_route = qroute(b0, nb);
     const bool select_diag = routes::compress_route(update_compress(), d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts).select_diag;
-    const bool feature_first = routes::frame_order(frame_settings.order, settings.overlap_feature, sizeof(S), select_diag, q_route, nb, h_ncam.data() + b0,
-                                                   cells.maxslot + b0, cell_k + b0, IMU_SKIP, n_cap, f == f0, prof) == routes::FO_TAKEN;
+    const routes::CompressRoute c_route = routes::compress_route(update_compress(), d.ldR, d.Mp != nullptr, d.lam_part > 0, d.gram_parts);
+    const routes::FrameOrderRefusal order1 = routes::frame_order(frame_settings.order, settings.overlap_feature, sizeof(S), select_diag, q_route, nb, h_ncam.data() + b0,
+                                                                 cells.maxslot + b0, cell_k + b0, IMU_SKIP, n_cap, f == f0, prof);
+    const bool feature_first = order1 == routes::FO_TAKEN;
+    // order 2 (frame_order.h): propagate + augmentState wait for the Gram Cholesky's launch, the selection keeps its own
+    const bool in_cholesky = routes::frame_order_chol(frame_settings.effective(), order1, c_route.info, c_route.chol_levels,
+                                                      range_small_route(update_compress(), b0, nb, 1, cell_k + b0).kind == routes::CHAIN_ONLY, n_lit) == routes::FC_TAKEN;
     const bool early = may_overlap && settings.overlap_feature &&
                        routes::feature_ahead(nb, h_ncam.data() + b0, cells.maxslot + b0, cell_k + b0, IMU_SKIP, n_cap, f == f0, prof) == routes::FO_TAKEN;
     if (feature_first) {
       // feature-first order, on the slice's own stream: k_feature from what the previous frame's prune left (window size from ncam_upd),
-      // then the selection's workgroups and propagate + augmentState side by side in one launch (k_propagate's HEAD instance), then the rest of the update
+      // then the selection's workgroups and propagate + augmentState side by side in one launch (k_propagate's HEAD instance), then the rest of the update;
+      // order 2 launches k_feature alone here, the rest in launch_update
       StageRange r("msckf_marginalize(features)+imu_prop+msckf_augment_state");
       Dev<S> v2 = v; v2.ncam_bias = 1;
       v2.compress = update_compress();
       launch_feature<S>(v2, b0, nb, q);
-      launch_frame_head<S>(v2, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, q_route, in.k);
+      if (!in_cholesky) launch_frame_head<S>(v2, b0, nb, in.rd, (long)K * RD_STRIDE, K, q, q_route, in.k);
       n_feature_first.fetch_add(1, std::memory_order_relaxed);
+      if (in_cholesky) n_in_cholesky.fetch_add(1, std::memory_order_relaxed);
     }
     if (early) {
       (void)hipEventRecord(ev_fa[hh], q);
@@ -2349,9 +2377,10 @@ struct Batch : BatchCore {
       if (prof) { stage_begin(1, q); launch_augment<S>(v, b0, nb, q, in.k); stage_end(1, q); }
     }
     if (early) (void)hipStreamWaitEvent(q, ev_fb[hh], 0);
+    const CholRide ride{in.rd, (long)K * RD_STRIDE, K, q_route, in.k, v.ncam_defer};
     v.ncam_defer = 0;
     if (fuse) { v.Pout = s.flipped ? d.P : P_spare; v.fuse_drop = in.drop; }
-    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early || feature_first, 1, cell_k + b0, feature_first); }
+    { StageRange r(fuse ? "msckf_marginalize+msckf_prune_empty_states" : "msckf_marginalize"); launch_update(v, b0, nb, q, early || feature_first, 1, cell_k + b0, feature_first, in_cholesky ? &ride : nullptr); }
     if (fuse) s.flipped = !s.flipped;
     else {
       // pruned-state log: the states this frame drops, as the update left them (v.P: in place), with frame ordinal
@@ -3081,6 +3110,12 @@ int msckf_hip_set_frame_order(msckf_hip_handle h, int order) { if (!h) return fa
 int msckf_hip_get_frame_order_count(msckf_hip_handle h, long long* count) {
   if (!h || !count) return fail(-EINVAL, "null handle or null count");
   *count = H(h)->n_feature_first.load(std::memory_order_relaxed);
+  return 0;
+}
+int msckf_hip_set_frame_order_chol(msckf_hip_handle h, int on) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_frame_order_chol(on); }
+int msckf_hip_get_frame_order_chol_count(msckf_hip_handle h, long long* count) {
+  if (!h || !count) return fail(-EINVAL, "null handle or null count");
+  *count = H(h)->n_in_cholesky.load(std::memory_order_relaxed);
   return 0;
 }
 int msckf_hip_set_covariance_update(msckf_hip_handle h, int form) { if (!h) return fail(-EINVAL, "null handle"); return H(h)->set_cov_update(form); }

@@ -7,12 +7,7 @@
 
 namespace msckf {
 
-// Window size of trajectory b as the launches of its update see it.  A kernel of the update that runs BEFORE the frame's
-// augmentState (ncam_bias: the early k_feature, and the selection and block-diagonal roles of k_propagate's HEAD instance, in whose launch
-// another workgroup commits and increments ncam) takes it from ncam_upd, "the size after the next augment", which the
-// previous frame's prune left and nothing writes before this frame's own prune.
-template <class S>
-__device__ __forceinline__ int update_ncam(const Dev<S>& d, int b) { return d.ncam_bias ? d.ncam_upd[b] : d.ncam[b]; }
+// (update_ncam, the window size as the launches of an update see it: dev_common.h)
 
 // One wavefront per trajectory: resolves the order-dependent part of marginalize (:352-399) -- checkMotion is
 // skipped while fewer than 4 tracks have ever been residualized (Q4, msckf.h:354) -- and lays the gated-in

@@ -87,7 +87,11 @@ inline void Settings::take_over(const Settings& o) {
 // which kernels run (same bits either way).
 struct FrameSettings {
   int order = 1;   // 1: k_feature first, then selection and propagate + augmentState in one launch, on the frames that allow it; 0: propagate first on every frame
-  void take_over(const FrameSettings& o) { order = o.order; }
+  // msckf_hip_set_frame_order_chol, under order 1: on the frames that allow it (routes::frame_order_chol) the selection keeps its
+  // own launch and propagate + augmentState run inside the Gram Cholesky's launch -- "order 2"; 0: order 1 as it was
+  int in_cholesky = 1;
+  int effective() const { return order ? (in_cholesky ? 2 : 1) : 0; }   // the order routes::frame_order_chol is asked with
+  void take_over(const FrameSettings& o) { order = o.order; in_cholesky = o.in_cholesky; }
 };
 
 // the environment's say on a new handle's settings; false: a value was refused, err says which
