@@ -166,7 +166,22 @@ int msckf_hip_set_num_residualized(msckf_hip_handle h, int b, long long n);
  * S = T_H P T_H^T + R_n (msckf.h:1369) met a non-positive pivot since the flags were last cleared -- the covariance lost
  * positive definiteness (the pivot is clamped and the run continues; the reference's explicit S.inverse() would return
  * garbage silently).  (No kernel waits for another workgroup without a fall-back: the in-place prune is one workgroup per
- * trajectory, the gain solve's shared product is re-formed locally when a sibling does not show up.) */
+ * trajectory, the gain solve's shared product is re-formed locally when a sibling does not show up.)
+ *
+ * The non-positive pivot report, stated once (held by tests/test_gpu_pivot_report.py at every factorization of S):
+ *   - the flag is per trajectory and sticky until msckf_hip_clear_error_flags, and it is raised by every covariance-update form
+ *     (0, 1, 2), every compression route (the literal anisotropic route has no factorization of S of its own, neither a Cholesky
+ *     nor the reference's explicit inverse: it leaves its information matrix where k_gram leaves H_o^T H_o and the same kernels
+ *     factor S from there) and both dtypes;
+ *   - the other trajectories of the launch, of the frame range and of the handle are unaffected, bit for bit;
+ *   - the failed trajectory's state and covariance are undefined from the failed update on, until they are overwritten
+ *     (set_covariance, set_imu_state, set_cam_pose) or the trajectory is re-initialised; its counts and per-track results of that
+ *     update are still the update's own;
+ *   - the handle is otherwise reusable after msckf_hip_clear_error_flags: no scratch buffer carries anything of the failure
+ *     into a later update, of that trajectory or of another.
+ * The per-track gate factors N_j = H_x,j P H_x,j^T + R_j of the track's unprojected Jacobian; a track whose N_j is not positive
+ * definite is gate-rejected (where the reference, which factors the projected A_j^T N_j A_j, may pass it) and raises no flag
+ * of its own; such a P is no covariance, and the factorization of the joint S reports it in the same update. */
 int msckf_hip_last_stats(msckf_hip_handle h, int b, int* out7);
 int msckf_hip_clear_error_flags(msckf_hip_handle h, int b);
 /* the sticky flags themselves, without turning them into a return code: bit 0 capacity overflow (-EOVERFLOW above), bit 1

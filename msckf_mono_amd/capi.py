@@ -304,6 +304,11 @@ class Batch:
         _chk(self.L.msckf_hip_copy_state(self.h, other.h))
 
     def error_flags(self, b):
+        """the trajectory's sticky device-side flags: bit 0 (1) camera-state capacity exceeded, bit 1 (2) a factorization of
+        S = T_H P T_H^T + R_n met a non-positive pivot.  The pivot contract (include/msckf_hip.h, msckf_hip_last_stats): the flag is per
+        trajectory, sticky until clear_error_flags, and raised by every covariance-update form, compression route and dtype; the
+        other trajectories are unaffected bit for bit; the failed trajectory's state and covariance are undefined until they are
+        overwritten or the trajectory is re-initialised; the handle is otherwise reusable after clear_error_flags."""
         f = C.c_int(0)
         _chk(self.L.msckf_hip_get_error_flags(self.h, int(b), C.byref(f)))
         return int(f.value)
@@ -570,6 +575,7 @@ class Batch:
         _chk(self.L.msckf_hip_set_upload_ring(self.h, int(depth), int(mode)))
 
     def clear_error_flags(self, b):
+        """clears trajectory b's sticky flags (error_flags has the contract); a state the failure left undefined stays as it is"""
         _chk(self.L.msckf_hip_clear_error_flags(self.h, int(b)))
 
     def sync(self):
